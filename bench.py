@@ -8,14 +8,18 @@ decoder + fused head/CE) at 512x512, 151 classes, bf16 compute, batch 32 per GPU
 
 A "step" is one full iteration of the reference's train loop (engine.py:78-104) on one synthetic batch that is
 already resident in HBM: zero_grad -> forward -> CE -> backward (-> gradient all-reduce) -> optimizer step.
-Rank 0 prints ONE JSON line (see the driver contract in the task statement) including
+Rank 0 prints ONE JSON line: images/s (`value`) and `ms_per_step` of the --steps timed steps.  A plain run does nothing
+else; --full adds
   roofline     — the dominant kernel (bf16 MFMA NT GEMM): algorithmic FLOPs / HIP-event-timed duration of
                  every launch of it inside the timed steps, against the 2.5 PFLOP/s dense bf16 peak;
   cpu_baseline — the CPU oracle's train step timed on this box's host cores on a bounded sample.
+--dump-outputs DIR writes what the last timed step hands its caller (loss, a fixed sample of the updated parameters and
+of their gradients) as float32 .npy files; inputs and initial weights are seeded, so runs with the same arguments compare.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -188,6 +192,27 @@ def profile_reference(args):
     return json.loads(ROOFLINE_REF.read_text())
 
 
+DUMP_SAMPLE = 1 << 22   # positions of the parameter arena written by --dump-outputs: 2 x 16 MB of float32
+
+
+def dump_outputs(out_dir, loss, arena):
+    """--dump-outputs: what one timed step hands its caller, after the last one — the loss, and the model's updated parameters
+    and their gradients (the flat fp32 buffers of ParamArena).  At the headline size the arena holds ~158 M values, so a fixed
+    sample of DUMP_SAMPLE sorted positions drawn from seed 0 is written; it depends on the arena's size only."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = arena.numel
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(arena.flat.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "params_sample": arena.flat[idx], "grads_sample": arena.grad[idx]}
+    for name, t in arrays.items():
+        np.save(out_dir / f"{name}.npy", t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -199,7 +224,12 @@ def main():
                     "14 = ViT-L/14 (configs[3]: use --in-size 640)")
     ap.add_argument("--text-len", type=int, default=16)
     ap.add_argument("--optimizer", default="sgd")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline leg (HIP-event pairs around the dominant "
+                         "kernel on every 4th timed step, figures of profiles/roofline_ref.json) and the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's loss and a fixed sample "
+                    "of the updated parameters and gradients to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-baseline leg")
     ap.add_argument("--cpu-images", type=int, default=4, help="CPU-baseline batch (SURVEY.md §8d: 4)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps after one warm-up (SURVEY.md §8d: >= 3)")
     ap.add_argument("--graph", action="store_true", help="replay the step as one hipGraph (single GPU, SGD, no dropout): the text-tower fork / join and the "
@@ -210,6 +240,8 @@ def main():
                          "--backend, GradReducer attached (3-layer weight-gradient groups, bucketed all_reduce enqueues on RCCL's "
                          "stream, event waits) — to price the DP path itself; the JSON line says config.dp_path_forced")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -296,13 +328,14 @@ def main():
     for _ in range(args.warmup):
         loss = ts.step(inputs, labels)
     sync()
-    timer = GemmTimer()
+    timer = GemmTimer() if args.full else None
     if use_graph:
-        # events cannot be recorded inside a replayed graph: the roofline leg times one eager step instead
-        with timer:
-            timer.steps_sampled = 1
-            loss = ts.step(inputs, labels)
-            sync()
+        if timer is not None:
+            # events cannot be recorded inside a replayed graph: the roofline leg times one eager step instead
+            with timer:
+                timer.steps_sampled = 1
+                loss = ts.step(inputs, labels)
+                sync()
         run = ts.capture(inputs, labels)
         sync()
         t0 = time.perf_counter()
@@ -313,25 +346,26 @@ def main():
         timed_steps = 1
     else:
         t0 = time.perf_counter()
-        with timer:  # every gemm_nt launch of the timed steps is bracketed by HIP events on its launch stream
+        # --full: every gemm_nt launch of the sampled timed steps is bracketed by HIP events on its launch stream
+        with timer if timer is not None else contextlib.nullcontext():
             for i in range(args.steps):
-                timer.active = (i % SAMPLE_EVERY == 0)
-                timer.steps_sampled += timer.active
+                if timer is not None:
+                    timer.active = (i % SAMPLE_EVERY == 0)
+                    timer.steps_sampled += timer.active
                 loss = ts.step(inputs, labels)
             sync()
         dt = time.perf_counter() - t0
-        timed_steps = timer.steps_sampled
-    gsum = timer.summary()
+        timed_steps = timer.steps_sampled if timer is not None else 0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, ts.arena)
 
     if rank == 0:
         n_img = args.batch * world * args.steps
-        achieved = gsum["flops"] / gsum["seconds"] / 1e12 if gsum["seconds"] > 0 else 0.0
-        ref = profile_reference(args)
         out = {
             "metric": f"training-step images/sec ({in_size}x{in_size}, ADE20K-150)", "value": n_img / dt, "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -344,27 +378,31 @@ def main():
                                              "enqueues per step"} if forced_dp else {})},
             "final_loss": loss_val,
             **({"diagnostic": "LC2IS_BENCH_CACHED_TEXT: the text tower is skipped — NOT a benchmark result"} if diag_cached_text else {}),
-            "roofline": {"bound": "mfma", "kernel": "large-tile LDS-DMA NT GEMM family: gemm_nt_pp_kernel<*> (persistent ping-pong 256x256), gemm_nt_w384_kernel (256x384, N = 768), gemm_nt_dma_kernel<256,256,2,4,*> (every launch of each 4th timed step)",
-                         "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_BF16_TFLOPS, "traffic": ref.get("dominant_kernel_hbm_bytes_per_launch"),
-                         "traffic_source": (f"profiles/roofline_ref.json: {ref.get('dominant_kernel_hbm_source')}"
-                                            if ref.get("dominant_kernel_hbm_bytes_per_launch") else None),
-                         # the quantity the north_star target is stated in: whole step (live) and ViT encoder (rocprofv3)
-                         "step_frac": (STEP_GF_PER_IMG * 1e9 * (n_img / dt) / world / 1e12 / PEAK_BF16_TFLOPS
-                                       if args.patch == 16 and args.in_size == 512 else None),
-                         # rocprof counter evidence for the dominant kernel family (north_star: "rocprof-evidenced MFMA utilisation")
-                         "mfma_busy_frac": ref.get("dominant_kernel_mfma_busy_frac"), "clock_ghz": ref.get("dominant_kernel_clock_ghz"),
-                         "counter_source": ref.get("dominant_kernel_counter_source"),
-                         "encoder_frac": ref.get("encoder_frac"),
-                         "encoder_kernel_ms_per_step": ref.get("encoder_kernel_ms_per_step"),
-                         "bandwidth_kernels": [dict(kernel=b["kernel"], achieved_gbs=round(b["achieved_gbs"], 1), peak_gbs=8000.0,
-                                                    avg_us=round(b["avg_us"], 1)) for b in ref.get("bandwidth_kernels", [])],
-                         "profile_source": (f"profiles/roofline_ref.json @ {ref.get('commit')} ({ref.get('source')})" if ref else None),
-                         "launches_per_step": gsum["launches"] / timed_steps, "hip_graph": use_graph,
-                         "event_timed_steps": timed_steps,
-                         "avg_launch_us": gsum["seconds"] / max(gsum["launches"], 1) * 1e6,
-                         "gemm_nt_time_share": gsum["seconds"] / timed_steps / (dt / args.steps)},
         }
+        if args.full:
+            gsum = timer.summary()
+            achieved = gsum["flops"] / gsum["seconds"] / 1e12 if gsum["seconds"] > 0 else 0.0
+            ref = profile_reference(args)
+            out["roofline"] = {"bound": "mfma", "kernel": "large-tile LDS-DMA NT GEMM family: gemm_nt_pp_kernel<*> (persistent ping-pong 256x256), gemm_nt_w384_kernel (256x384, N = 768), gemm_nt_dma_kernel<256,256,2,4,*> (every launch of each 4th timed step)",
+                               "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": achieved / PEAK_BF16_TFLOPS, "traffic": ref.get("dominant_kernel_hbm_bytes_per_launch"),
+                               "traffic_source": (f"profiles/roofline_ref.json: {ref.get('dominant_kernel_hbm_source')}"
+                                                  if ref.get("dominant_kernel_hbm_bytes_per_launch") else None),
+                               # the quantity the north_star target is stated in: whole step (live) and ViT encoder (rocprofv3)
+                               "step_frac": (STEP_GF_PER_IMG * 1e9 * (n_img / dt) / world / 1e12 / PEAK_BF16_TFLOPS
+                                             if args.patch == 16 and args.in_size == 512 else None),
+                               # rocprof counter evidence for the dominant kernel family (north_star: "rocprof-evidenced MFMA utilisation")
+                               "mfma_busy_frac": ref.get("dominant_kernel_mfma_busy_frac"), "clock_ghz": ref.get("dominant_kernel_clock_ghz"),
+                               "counter_source": ref.get("dominant_kernel_counter_source"),
+                               "encoder_frac": ref.get("encoder_frac"),
+                               "encoder_kernel_ms_per_step": ref.get("encoder_kernel_ms_per_step"),
+                               "bandwidth_kernels": [dict(kernel=b["kernel"], achieved_gbs=round(b["achieved_gbs"], 1), peak_gbs=8000.0,
+                                                          avg_us=round(b["avg_us"], 1)) for b in ref.get("bandwidth_kernels", [])],
+                               "profile_source": (f"profiles/roofline_ref.json @ {ref.get('commit')} ({ref.get('source')})" if ref else None),
+                               "launches_per_step": gsum["launches"] / timed_steps, "hip_graph": use_graph,
+                               "event_timed_steps": timed_steps,
+                               "avg_launch_us": gsum["seconds"] / max(gsum["launches"], 1) * 1e6,
+                               "gemm_nt_time_share": gsum["seconds"] / timed_steps / (dt / args.steps)}
         if rccl_log is not None and rccl_log.exists():   # what RCCL chose (first lines that name an algorithm / channel count)
             try:
                 picks = [ln.split("NCCL INFO", 1)[-1].strip() for ln in rccl_log.read_text(errors="replace").splitlines()
@@ -372,7 +410,7 @@ def main():
                 out["config"]["rccl"] = picks[:6]
             except OSError:
                 pass
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline leg belongs to the N=1 line only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline leg belongs to the N=1 line only
             try:
                 if args.patch != 16:
                     raise RuntimeError("cpu_baseline is defined for the headline ViT-B/16 workload only")
