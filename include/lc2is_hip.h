@@ -386,11 +386,11 @@ int lc2is_crop_lut(const void* src_u8, int H, int W, int C, int top, int left, i
 
 /* ---- remaining losses (model/loss.py) and the parity metric (metrics.py) on channels-last scores ----------
  * rows_ce: softmax-CE over the K contiguous classes of each of M rows: loss_sum[0] += sum of per-row losses,
- *   lse[M] (optional), dx (optional) (+)= grad_scale * (softmax - onehot).  ContrastiveLoss.loss_visual
- *   (model/loss.py:59) — also usable for any [M,K] logits.
+ *   lse[M] (optional), dx (optional) (+)= grad_scale * (softmax - onehot).  A row whose label lies outside [0, K)
+ *   adds nothing to loss_sum or dx.  ContrastiveLoss.loss_visual (model/loss.py:59) — also usable for any [M,K] logits.
  * cols_ce: ContrastiveLoss.loss_textual (model/loss.py:58): x viewed [B,H,W,K], log-softmax over H (dim 1 — what
  *   nn.CrossEntropyLoss does with the reference's one-hot float targets), loss_sum[0] += sum over (b,w,k) columns;
- *   dx += grad_scale * d/dx. */
+ *   dx += grad_scale * d/dx; labels outside [0, K) match no class. */
 int lc2is_rows_ce(const float* x, const int64_t* labels, float* lse, float* loss_sum, float* dx, float grad_scale,
                   int M, int K, int accumulate_dx, lc2is_stream_t stream);
 int lc2is_cols_ce(const float* x, const int64_t* labels, float* loss_sum, float* dx, float grad_scale, int B, int H,

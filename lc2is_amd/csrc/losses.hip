@@ -27,13 +27,14 @@ __global__ __launch_bounds__(256) void rows_ce_kernel(const float* __restrict__ 
     for (int c = lane; c < K; c += 64) s += __expf(xr[c] - m);
     s = wave_sum(s);
     const float lse = m + __logf(s);
-    const int lab = (int)labels[row];
+    const int64_t lab = labels[row];
+    const bool counted = lab >= 0 && lab < K;   // a label outside [0, K) adds nothing to the loss or to dx (never read xr[lab])
     if (lse_out && lane == 0) lse_out[row] = lse;
-    lacc += lse - xr[lab];
+    if (counted) lacc += lse - xr[lab];
     if (dx) {
       float* dr = dx + (size_t)row * K;
       for (int c = lane; c < K; c += 64) {
-        const float g = gscale * (__expf(xr[c] - lse) - (c == lab ? 1.f : 0.f));
+        const float g = counted ? gscale * (__expf(xr[c] - lse) - (c == lab ? 1.f : 0.f)) : 0.f;
         dr[c] = accumulate_dx ? dr[c] + g : g;
       }
     }

@@ -5,6 +5,8 @@ Both take NCHW fp32 logits and int64 labels like the reference; reduction is 'me
 """
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import nn
 
@@ -114,9 +116,15 @@ class ContrastiveLoss(nn.Module):
 
     def forward(self, outputs: torch.Tensor, labels: torch.Tensor):
         require_cuda(outputs, "outputs")
-        H = int(round(outputs.shape[1] ** 0.5))
+        HW = outputs.shape[1]
+        H = math.isqrt(HW)
+        if H * H != HW:
+            raise ValueError(f"ContrastiveLoss: {HW} pixels do not form a square map (the reference's rearrange raises)")
         if outputs.shape[2] != 151:
             raise ValueError("ContrastiveLoss: the reference hard-codes num_classes=151 (model/loss.py:55)")
+        # F.one_hot(labels, 151) in the reference raises for any label outside [0, 151); one host sync, as there
+        if labels.dtype != torch.int64 or ((labels < 0) | (labels >= 151)).any().item():
+            raise RuntimeError("ContrastiveLoss: labels must be int64 class indices in [0, 151)")
         return _ContrastiveFn.apply(outputs, labels, H)
 
 

@@ -60,6 +60,18 @@ def relative_position_index(ws: int) -> torch.Tensor:
     return rel.sum(-1).view(-1)
 
 
+def relative_position_csr(ws: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of ``relative_position_index`` (init-time host code): for every table row t, the (query, key) pairs that
+    read it.  Returns int32 (offsets [T+1], pair ids [ws^4]) — the pairs of row t are ids[offsets[t]:offsets[t+1]], in
+    ascending order — the CSR index ops.swin_bias_table_grad sums in."""
+    T = (2 * ws - 1) ** 2
+    host = relative_position_index(ws)
+    order = torch.sort(host, stable=True).indices                   # pairs grouped by t, ascending pair id inside
+    offs = torch.zeros(T + 1, dtype=torch.int64)
+    offs[1:] = torch.cumsum(torch.bincount(host, minlength=T), 0)
+    return offs.to(torch.int32), order.to(torch.int32)
+
+
 # ---- parameter tree under the reference's / transformers' names ---------------------------------------------------
 class _RelBias(nn.Module):
     def __init__(self, nH: int, ws: int):
@@ -235,13 +247,7 @@ class SwinTransformer(HipModule):
         if idx is None or idx.device != dev:      # built once: no host-to-device copy per refresh (hipGraph-capturable)
             idx = self._rel_idx = relative_position_index(ws).to(dev)
         if self._onehot is None or self._onehot[0].device != dev:
-            # inverse of the index (init-time host code): for every table row t, the (query, key) pairs that read it
-            T = (2 * ws - 1) ** 2
-            host = relative_position_index(ws)
-            order = torch.sort(host, stable=True).indices                   # pairs grouped by t, ascending pair id inside
-            offs = torch.zeros(T + 1, dtype=torch.int64)
-            offs[1:] = torch.cumsum(torch.bincount(host, minlength=T), 0)
-            self._onehot = (offs.to(torch.int32).to(dev), order.to(torch.int32).to(dev))
+            self._onehot = tuple(t.to(dev) for t in relative_position_csr(ws))
         for st, ss in zip(self._stages(), self._sh["stages"]):
             for b, s in zip(st.blocks, ss["blocks"]):
                 t = b.attention.relative_position_bias.relative_position_bias_table.detach()

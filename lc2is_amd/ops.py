@@ -835,9 +835,20 @@ def sr_scatter_add(src16, dst32, B: int, h: int, w: int):
     _lib.check(_fn("lc2is_sr_scatter_add_f32")(_ptr(src16), _ptr(dst32), B, h, w, Cc, _stream()), "sr_scatter_add")
 
 
+def _labels(labels, n: int, name: str):
+    _chk(labels, torch.int64, "labels", None)
+    if not labels.is_contiguous() or labels.numel() != n:
+        raise RuntimeError(f"lc2is_amd.{name}: labels must be contiguous int64 with {n} elements, got {tuple(labels.shape)}")
+
+
 def rows_ce(x, labels, *, loss_sum=None, dx=None, grad_scale: float = 1.0, accumulate_dx: bool = False, want_lse=False):
+    """Softmax-CE over the K classes of each row of x [M,K]; a label outside [0, K) adds nothing to loss_sum or dx."""
     _dense(x, torch.float32, "x")
     M, K = x.shape
+    _labels(labels, M, "rows_ce")
+    _dense(dx, torch.float32, "dx")
+    if dx is not None and dx.shape != x.shape:
+        raise RuntimeError("lc2is_amd.rows_ce: dx must match x")
     lse = torch.empty((M,), dtype=torch.float32, device=x.device) if want_lse else None
     _lib.check(_fn("lc2is_rows_ce")(_ptr(x), _ptr(labels), _ptr(lse), _ptr(loss_sum), _ptr(dx), grad_scale, M, K,
                                     int(accumulate_dx), _stream()), "rows_ce")
@@ -846,6 +857,12 @@ def rows_ce(x, labels, *, loss_sum=None, dx=None, grad_scale: float = 1.0, accum
 
 def cols_ce(x, labels, B: int, H: int, W: int, K: int, loss_sum, dx=None, grad_scale: float = 1.0):
     _dense(x, torch.float32, "x")
+    if x.numel() != B * H * W * K or x.shape[1] != K:
+        raise RuntimeError(f"lc2is_amd.cols_ce: x {tuple(x.shape)} is not [B*H*W, K] for B={B} H={H} W={W} K={K}")
+    _labels(labels, B * H * W, "cols_ce")
+    _dense(dx, torch.float32, "dx")
+    if dx is not None and dx.shape != x.shape:
+        raise RuntimeError("lc2is_amd.cols_ce: dx must match x")
     _lib.check(_fn("lc2is_cols_ce")(_ptr(x), _ptr(labels), _ptr(loss_sum), _ptr(dx), grad_scale, B, H, W, K, _stream()),
                "cols_ce")
 
@@ -875,6 +892,8 @@ def npair_bwd(x, x_pos, x_neg, dres):
 def miou_counts(scores_hi, labels_lo, S: int):
     _chk(scores_hi, torch.float32, "scores_hi", 4); _chk(labels_lo, torch.int64, "labels", 3)
     B, K, H, W = scores_hi.shape
+    if S <= 0 or H % S or W % S or tuple(labels_lo.shape) != (B, H // S, W // S):
+        raise RuntimeError(f"lc2is_amd.miou_counts: labels {tuple(labels_lo.shape)} do not match scores {tuple(scores_hi.shape)} / {S}")
     counts = torch.zeros((B, 3, K), dtype=torch.int32, device=scores_hi.device)
     _lib.check(_fn("lc2is_miou_counts")(_ptr(scores_hi.contiguous()), _ptr(labels_lo.contiguous()), _ptr(counts), B, K, H,
                                         W, S, _stream()), "miou_counts")

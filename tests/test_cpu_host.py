@@ -188,3 +188,19 @@ def test_product_path_has_no_library_math():
                 hits.append((str(f.relative_to(root)), code.strip()))
     # the one allowed use: pos_emebedding_interpolate's separable bicubic resize of the 14x14 position table at load time
     assert len(hits) == 1 and hits[0][0] == "nn/clip.py" and "yi,ijc,xj->yxc" in hits[0][1], hits
+
+
+def test_swin_relative_position_csr_inverts_the_index():
+    """The CSR index swin_bias_table_grad sums in: row t lists exactly the (query, key) pairs whose relative_position_index
+    is t, in ascending order, and every pair appears once."""
+    from lc2is_amd.nn.swin import relative_position_csr, relative_position_index
+    for ws in (2, 7, 12):
+        idx = relative_position_index(ws)
+        offs, ids = relative_position_csr(ws)
+        T = (2 * ws - 1) ** 2
+        assert offs.dtype == ids.dtype == torch.int32 and offs.shape == (T + 1,) and ids.shape == (ws ** 4,)
+        assert offs[0] == 0 and offs[-1] == ws ** 4 and bool((offs[1:] >= offs[:-1]).all())
+        assert torch.equal(ids.sort().values, torch.arange(ws ** 4, dtype=torch.int32))
+        for t in range(T):
+            row = ids[offs[t]:offs[t + 1]].long()
+            assert torch.equal(row, torch.nonzero(idx == t).flatten()), (ws, t)

@@ -211,6 +211,25 @@ def test_contrastive_npair_losses_vs_reference(dev):
         assert _rel(a.grad, b.grad) < 1e-4
 
 
+def test_contrastive_loss_refuses_what_the_reference_refuses(dev):
+    """The reference's F.one_hot(labels, 151) raises for a label outside [0, 151) (-100 included) and its rearrange raises
+    when HW is not a square; the HIP module raises too instead of returning a silently wrong loss."""
+    import lc2is_amd.nn as N
+    loss = N.ContrastiveLoss()
+    out = torch.randn(2, 64, 151, device=dev)
+    labels = torch.randint(0, 151, (2, 8, 8), device=dev)
+    assert torch.isfinite(loss(out, labels)[0])
+    for bad in (-100, -1, 151, 255):
+        lb = labels.clone()
+        lb[1, 7, 7] = bad
+        with pytest.raises(RuntimeError, match=r"\[0, 151\)"):
+            loss(out, lb)
+    with pytest.raises(RuntimeError):
+        loss(out, labels.to(torch.int32))
+    with pytest.raises(ValueError, match="square"):
+        loss(torch.randn(2, 60, 151, device=dev), torch.randint(0, 151, (2, 6, 10), device=dev))
+
+
 def test_device_miou_vs_oracle(dev):
     """metrics.compute_mIOU needs torchmetrics (absent): checked against the oracle's restatement (parity unpinned)."""
     from lc2is_amd.metrics import compute_mIOU
