@@ -306,6 +306,17 @@ int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int64_t* labels
                            float* scores_hi, float* loss_sum, int B, int h, int w, int C, int S, int mode,
                            long ignore_index, float grad_scale, void* workspace, size_t workspace_bytes,
                            lc2is_stream_t stream);
+/* lc2is_head_upsample_ce with F.cross_entropy's class weights and label smoothing (S in {4, 8, 16}):
+ * class_weight: device fp32 [C] or NULL (all ones); label_smoothing eps in [0, 1] (else LC2IS_ERR_SHAPE).  With w, W = sum_c w_c,
+ *   loss_sum[0] = sum_i (1-eps) w_y (lse - z_y) + (eps/C) (W lse - sum_c w_c z_c), loss_sum[1] = sum_i w_y (the weighted count of
+ *   the mean), dscores_lo = grad_scale * U^T (((1-eps) w_y + eps W/C) softmax - (1-eps) w_y onehot - (eps/C) w).
+ * NULL weights with eps = 0 (or no loss_sum) is exactly lc2is_head_upsample_ce; other S with options: LC2IS_ERR_UNSUPPORTED.
+ * replaces: nn.CrossEntropyLoss(weight=w, label_smoothing=eps) at engine.py:94 and AuxiliaryLoss(weight, label_smoothing)
+ *   (model/loss.py:14-21), fused as above. */
+int lc2is_head_upsample_ce_opts(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                float* scores_hi, float* loss_sum, int B, int h, int w, int C, int S, int mode,
+                                long ignore_index, float grad_scale, const float* class_weight, float label_smoothing,
+                                void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
 /* Transposed upsample (autograd of F.interpolate) for the unfused path: dhi NCHW fp32 [B,C,h*S,w*S] ->
  * dlo channels-last fp32 [B,h,w,ld] (columns >= C untouched). */
 int lc2is_upsample_bwd_nchw(const float* dhi, float* dlo, int ld, int B, int h, int w, int C, int S, int mode,
@@ -317,6 +328,19 @@ int lc2is_ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, fl
 int lc2is_ce_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_scale_dev,
                       float grad_scale, float* dlogits, int B, int C, long HW, long ignore_index,
                       lc2is_stream_t stream);
+/* The same with class weights (device fp32 [C] or NULL), label smoothing eps in [0, 1] and reduction="none": the per-pixel
+ * terms of lc2is_head_upsample_ce_opts.  Forward: loss_sum[0] = sum of the per-pixel losses, loss_sum[1] = sum of w_y (the
+ * caller clears both), loss_px (optional, [B,HW]) = per-pixel loss, 0 where not counted.  Backward: dlogits = grad_scale *
+ * (*grad_scale_dev) * grad_px[i] (grad_px optional, [B,HW]; NULL = 1) * dloss_i/dlogits.
+ * replaces: nn.CrossEntropyLoss(weight, reduction, label_smoothing) (torch: nn/modules/loss.py CrossEntropyLoss.forward) and its
+ *   autograd, on materialised NCHW logits. */
+int lc2is_ce_nchw_fwd_opts(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px,
+                           int B, int C, long HW, long ignore_index, const float* class_weight, float label_smoothing,
+                           lc2is_stream_t stream);
+int lc2is_ce_nchw_bwd_opts(const float* logits, const int64_t* labels, const float* lse, const float* grad_scale_dev,
+                           float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW,
+                           long ignore_index, const float* class_weight, float label_smoothing,
+                           lc2is_stream_t stream);
 
 /* ---- multi-scale decoder glue (BASELINE config 5; all channels-last token tensors [B, h*w, C]) --------
  * bilinear xS upsample (align_corners=False) forward / backward.

@@ -77,6 +77,9 @@ struct HeadArgs {
   float* ws_loss;                // [blocks][2] loss / count partials
   float* ws_dlo;                 // [blocks][F4 * F4][cq] footprint mirrors
   int cq;                        // channels per slab cell: C rounded up to 4
+  // class weights / label smoothing (group kernels with OPT = true only)
+  const float* cw;               // [C] class weights (device) or null = all ones
+  float eps;                     // label smoothing in [0, 1]
 };
 
 __device__ __forceinline__ void lds_add(float* p, float v) {
@@ -233,6 +236,11 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_ce_kernel(HeadArgs p) {
 // The label's logit (for the loss) is 16 x NT*NT scalars per unit: LDS reads with one (pixel, cell quad) per lane; its one-hot
 // is subtracted from dlogits in the accumulator layout.
 // Bilinear's clamp of the source coordinate at 0 (torch) equals clamping the tap indices because the two clamped taps coincide.
+// OPT = true: class weights w and label smoothing eps (F.cross_entropy's weight / label_smoothing), W = sum_c w_c:
+//   loss_i  = (1 - eps) w_y (lse - z_y) + (eps / C) (W lse - sum_c w_c z_c),   count_i = w_y
+//   dz_k    = ((1 - eps) w_y + eps W / C) p_k - (1 - eps) w_y [k == y] - (eps / C) w_k
+// The weights sit in LDS behind the labels (zero past C); sum_c w_c z_c is one more 16-lane row sum, taken before exp overwrites
+// the logits.  OPT = false is the plain CE of the default call, untouched (its register count carries the headline step).
 template <int MODE, int S> __device__ __forceinline__ float tap_w(int ph, int k) {
   const float t = ((float)ph + 0.5f) * (1.f / (float)S);
   if constexpr (MODE == LC2IS_INTERP_BICUBIC)
@@ -255,7 +263,7 @@ __device__ __forceinline__ float row16_sum(float v) {
 
 constexpr int head_grp_footprint(int mode, int S) { return HT / S + (mode == LC2IS_INTERP_BICUBIC ? 4 : 2) - 1; }
 
-template <int MODE, int TN, int S>
+template <int MODE, int TN, int S, bool OPT>
 __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_kernel(HeadArgs p) {
   constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;   // taps per axis
   constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;  // first tap = a - OFF
@@ -277,6 +285,7 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
   float* s_lo = (float*)smem;
   float* s_dlo = s_lo + F4 * F4 * CS;
   int* s_lab = (int*)(s_dlo + F4 * F4 * CS);     // [16][16] pixels of the tile: -2 outside the image, -1 not counted, else label
+  float* s_w = (float*)(s_lab + HT * HT);        // OPT: [CMAX] class weights, zero past C
   const int fsize = F4 * F4 * Cp;
   for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
     const int cell = i / Cp, c = i % Cp;
@@ -299,7 +308,16 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
     }
     s_lab[tid] = code;
   }
+  if constexpr (OPT) {
+    if (tid < CMAX) s_w[tid] = tid < p.C ? (p.cw ? p.cw[tid] : 1.f) : 0.f;
+  }
   __syncthreads();
+  float a1 = 0.f, ac = 0.f, aw = 0.f;   // OPT: 1 - eps, eps / C, eps W / C
+  if constexpr (OPT) {
+    a1 = 1.f - p.eps;
+    ac = p.eps / (float)p.C;
+    aw = ac * wave_sum(s_w[lane] + s_w[lane + 64] + s_w[lane + 128]);
+  }
 
   const int m = lane & 15, kq = lane >> 4;
   const float NEG = -__builtin_inff();
@@ -374,18 +392,38 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
         // the label's logit: this lane owns pixel m x cells {4q + kq}
         const int lab_m = s_lab[(S * gy + py_m) * 16 + S * gx + px_m];
         if (lab_m >= 0) {
+          if constexpr (OPT) {
+            float zl = 0.f;
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) loss_acc -= Af[q] * s_lo[gbase + cell_off[q] + lab_m];
+            for (int q = 0; q < NQ; ++q) zl += Af[q] * s_lo[gbase + cell_off[q] + lab_m];
+            loss_acc -= a1 * s_w[lab_m] * zl;
+          } else {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) loss_acc -= Af[q] * s_lo[gbase + cell_off[q] + lab_m];
+          }
         }
         // softmax over the channels of four pixels at once
         float mx[4] = {NEG, NEG, NEG, NEG}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+        float wz[4] = {0.f, 0.f, 0.f, 0.f};   // OPT: sum_c w_c z_c
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
           if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C
             if (16 * t + m >= p.C) acc[t] = f32x4_t{NEG, NEG, NEG, NEG};
           }
+          if constexpr (OPT) {
+            const float wk = s_w[16 * t + m];   // 0 past C (and there the logit is -inf)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wz[r] += wk != 0.f ? wk * acc[t][r] : 0.f;
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], acc[t][r]);
+        }
+        if constexpr (OPT) {   // the smoothing's -(eps/C) sum_c w_c z_c, before exp overwrites the logits
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            wz[r] = row16_sum(wz[r]);
+            if (lab4[r] >= 0 && m == 0) loss_acc -= ac * wz[r];
+          }
         }
         float mxl[4];   // -max * log2(e): exp(x - max) = exp2(fma(x, log2(e), mxl))
 #pragma unroll
@@ -400,15 +438,30 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
           }
         float inv[4];
         int dl[4];   // label - lane's channel offset: the one-hot sits in tile t where dl == 16 t
+        float oh[4];            // OPT: one-hot coefficient gscale (1 - eps) w_y
+        unsigned cmask = 0u;    // OPT: bit r = pixel r counted
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           sum[r] = row16_sum(sum[r]);
           const bool counted = lab4[r] >= 0;
-          inv[r] = counted ? p.gscale / sum[r] : 0.f;
-          dl[r] = counted ? lab4[r] - m : -1;
-          if (counted && m == 0) {
-            loss_acc += mx[r] + __logf(sum[r]);
-            cnt_acc += 1.f;
+          if constexpr (OPT) {
+            const float wy = counted ? s_w[counted ? lab4[r] : 0] : 0.f;
+            const float cy = a1 * wy, cs = cy + aw;
+            inv[r] = counted ? p.gscale * cs / sum[r] : 0.f;
+            dl[r] = counted ? lab4[r] - m : -1;
+            oh[r] = p.gscale * cy;
+            cmask |= counted ? (1u << r) : 0u;
+            if (counted && m == 0) {
+              loss_acc += cs * (mx[r] + __logf(sum[r]));
+              cnt_acc += wy;
+            }
+          } else {
+            inv[r] = counted ? p.gscale / sum[r] : 0.f;
+            dl[r] = counted ? lab4[r] - m : -1;
+            if (counted && m == 0) {
+              loss_acc += mx[r] + __logf(sum[r]);
+              cnt_acc += 1.f;
+            }
           }
         }
         if (p.dlo) {
@@ -416,8 +469,15 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
 #pragma unroll
           for (int t = 0; t < TN; ++t) {
             f32x4_t gv;
+            if constexpr (OPT) {
+              const float sk = p.gscale * ac * s_w[16 * t + m];   // smoothing term of channel 16 t + m
 #pragma unroll
-            for (int r = 0; r < 4; ++r) gv[r] = acc[t][r] * inv[r] - (dl[r] == 16 * t ? p.gscale : 0.f);
+              for (int r = 0; r < 4; ++r)
+                gv[r] = acc[t][r] * inv[r] - (dl[r] == 16 * t ? oh[r] : 0.f) - ((cmask >> r) & 1u ? sk : 0.f);
+            } else {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) gv[r] = acc[t][r] * inv[r] - (dl[r] == 16 * t ? p.gscale : 0.f);
+            }
             f32x4_t d = {0.f, 0.f, 0.f, 0.f};
             if constexpr (SUMD) d = dsum[t];
 #pragma unroll
@@ -529,43 +589,73 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadArgs p, int nblk_m
 
 // ---- generic pieces for the drop-in (unfused) path -----------------------------------------------------
 // softmax cross-entropy over NCHW fp32 logits: per-pixel lse + loss; backward writes dlogits NCHW.
+// OPT = true: class weights cw (null = ones), label smoothing eps, per-pixel losses loss_px (null = none; 0 where not counted) and
+// (backward) a per-pixel upstream gradient grad_px — the formulas of head_ce_grp_kernel's OPT variant.
+struct CeOpts { const float* cw; float eps; float* loss_px; const float* grad_px; };
+
+template <bool OPT>
 __global__ __launch_bounds__(256) void ce_nchw_fwd_kernel(const float* __restrict__ logits,
                                                            const int64_t* __restrict__ labels, float* lse,
                                                            float* loss_sum, int B, int C, size_t HW,
-                                                           long ignore_index) {
+                                                           long ignore_index, CeOpts o) {
   const size_t total = (size_t)B * HW;
   float lacc = 0.f, cacc = 0.f;
+  float wsum = 0.f;   // OPT: W = sum_c w_c
+  if constexpr (OPT) {
+    if (o.cw) { for (int c = 0; c < C; ++c) wsum += o.cw[c]; } else wsum = (float)C;
+  }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t b = i / HW, px = i % HW;
     const float* base = logits + b * C * HW + px;
     float m = -__builtin_inff();
     for (int c = 0; c < C; ++c) m = fmaxf(m, base[(size_t)c * HW]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += __expf(base[(size_t)c * HW] - m);
+    float s = 0.f, wz = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float z = base[(size_t)c * HW];
+      s += __expf(z - m);
+      if constexpr (OPT) wz += (o.cw ? o.cw[c] : 1.f) * z;
+    }
     const float l = m + __logf(s);
     if (lse) lse[i] = l;
     const long lab = (long)labels[i];
-    if (lab != ignore_index && lab >= 0 && lab < C) {
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    if constexpr (OPT) {
+      float li = 0.f;
+      if (counted) {
+        const float wy = o.cw ? o.cw[lab] : 1.f;
+        li = (1.f - o.eps) * wy * (l - base[(size_t)lab * HW]) + (o.eps / (float)C) * (wsum * l - wz);
+        lacc += li;
+        cacc += wy;
+      }
+      if (o.loss_px) o.loss_px[i] = li;
+    } else if (counted) {
       lacc += l - base[(size_t)lab * HW];
       cacc += 1.f;
     }
   }
   lacc = wave_sum(lacc);
   cacc = wave_sum(cacc);
-  if ((threadIdx.x & 63) == 0 && cacc > 0.f) {
+  if ((threadIdx.x & 63) == 0 && (OPT ? lacc != 0.f || cacc != 0.f : cacc > 0.f)) {
     atomicAdd(loss_sum, lacc);
     atomicAdd(loss_sum + 1, cacc);
   }
 }
 
+template <bool OPT>
 __global__ __launch_bounds__(256) void ce_nchw_bwd_kernel(const float* __restrict__ logits,
                                                            const int64_t* __restrict__ labels,
                                                            const float* __restrict__ lse,
                                                            const float* __restrict__ gscale_dev, float gscale,
                                                            float* dlogits, int B, int C, size_t HW,
-                                                           long ignore_index) {
+                                                           long ignore_index, CeOpts o) {
   const size_t total = (size_t)B * HW;
   const float gs = gscale * (gscale_dev ? *gscale_dev : 1.f);
+  float aw = 0.f;   // OPT: eps W / C
+  if constexpr (OPT) {
+    float wsum = 0.f;
+    if (o.cw) { for (int c = 0; c < C; ++c) wsum += o.cw[c]; } else wsum = (float)C;
+    aw = o.eps * wsum / (float)C;
+  }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t b = i / HW, px = i % HW;
     const float* base = logits + b * C * HW + px;
@@ -573,10 +663,26 @@ __global__ __launch_bounds__(256) void ce_nchw_bwd_kernel(const float* __restric
     const long lab = (long)labels[i];
     const bool counted = lab != ignore_index && lab >= 0 && lab < C;
     const float l = lse[i];
-    for (int c = 0; c < C; ++c) {
-      float g = 0.f;
-      if (counted) g = gs * (__expf(base[(size_t)c * HW] - l) - (c == lab ? 1.f : 0.f));
-      dbase[(size_t)c * HW] = g;
+    if constexpr (OPT) {
+      float cy = 0.f, cs = 0.f, g0 = 0.f;
+      if (counted) {
+        g0 = gs * (o.grad_px ? o.grad_px[i] : 1.f);
+        cy = (1.f - o.eps) * (o.cw ? o.cw[lab] : 1.f);
+        cs = cy + aw;
+      }
+      const float ac = o.eps / (float)C;
+      for (int c = 0; c < C; ++c) {
+        float g = 0.f;
+        if (counted)
+          g = g0 * (cs * __expf(base[(size_t)c * HW] - l) - (c == lab ? cy : 0.f) - ac * (o.cw ? o.cw[c] : 1.f));
+        dbase[(size_t)c * HW] = g;
+      }
+    } else {
+      for (int c = 0; c < C; ++c) {
+        float g = 0.f;
+        if (counted) g = gs * (__expf(base[(size_t)c * HW] - l) - (c == lab ? 1.f : 0.f));
+        dbase[(size_t)c * HW] = g;
+      }
     }
   }
 }
@@ -654,10 +760,11 @@ extern "C" size_t lc2is_head_upsample_ce_workspace_bytes(int B, int h, int w, in
   return g.loss_bytes + g.dlo_bytes;
 }
 
-extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
-                                      float* scores_hi, float* loss_sum, int B, int h, int w, int C, int S,
-                                      int mode, long ignore_index, float grad_scale, void* workspace,
-                                      size_t workspace_bytes, lc2is_stream_t stream_) {
+namespace {
+int head_upsample_ce(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo, float* scores_hi,
+                     float* loss_sum, int B, int h, int w, int C, int S, int mode, long ignore_index, float grad_scale,
+                     const float* class_weight, float label_smoothing, void* workspace, size_t workspace_bytes,
+                     lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!scores_lo) return LC2IS_ERR_NULL;
   if (!scores_hi && !loss_sum) return LC2IS_ERR_NULL;
@@ -666,9 +773,13 @@ extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int6
   if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || ld < C || ld > CMAX || ld % 64) return LC2IS_ERR_SHAPE;
   if (S < 4 || (HT % S != 0 && S % HT != 0)) return LC2IS_ERR_UNSUPPORTED;
   if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return LC2IS_ERR_UNSUPPORTED;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return LC2IS_ERR_SHAPE;
+  // weights / smoothing only shape the loss: a scores-only call runs the plain kernel; the atomic path (S >= 32) has no such variant
+  const bool opt = loss_sum && (class_weight || label_smoothing != 0.f);
+  if (opt && !(S == 4 || S == 8 || S == 16)) return LC2IS_ERR_UNSUPPORTED;
   const int H = h * S, W = w * S;
   HeadArgs a{scores_lo, ld, labels, dscores_lo, scores_hi, loss_sum, B, h, w, H, W, C, S, mode, ignore_index,
-             grad_scale, nullptr, nullptr, 0};
+             grad_scale, nullptr, nullptr, 0, class_weight, label_smoothing};
   const int lds_bytes = 2 * FMAX * FMAX * ld * (int)sizeof(float);
   static DevOnce attr_set;
   if (attr_set.need()) {
@@ -686,23 +797,29 @@ extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int6
     const int tn = nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12));
     const HeadGrpPlan gp = head_grp_plan(B, h, w, C, S, mode, dscores_lo != nullptr);
     const int f4 = gp.f4, t4 = gp.t4;
-    const int lds4 = 2 * f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int);
+    const int lds4 = 2 * f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +
+                     (opt ? CMAX * (int)sizeof(float) : 0);
     if (loss_sum) {   // loss / gradient leave through per-block partials and slabs: a workspace is part of the call
       if (!workspace || ((size_t)workspace & 15) || workspace_bytes < gp.loss_bytes + gp.dlo_bytes) return LC2IS_ERR_WORKSPACE;
       a.ws_loss = (float*)workspace;
       a.ws_dlo = dscores_lo ? (float*)((char*)workspace + gp.loss_bytes) : nullptr;
       a.cq = gp.cq;
     }
-#define LC2IS_HEAD_GRP(MODE_, TN_, S_)                                                                                       \
+#define LC2IS_HEAD_GRP1(MODE_, TN_, S_, OPT_)                                                                                \
   do {                                                                                                                      \
     static DevOnce attr;                                                                                               \
     if (attr.need()) {                                                                                                            \
-      if (hipFuncSetAttribute((const void*)head_ce_grp_kernel<MODE_, TN_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                              2 * 7 * 7 * (CMAX + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int)) != hipSuccess) \
+      if (hipFuncSetAttribute((const void*)head_ce_grp_kernel<MODE_, TN_, S_, OPT_>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                              2 * 7 * 7 * (CMAX + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +             \
+                                  (OPT_ ? CMAX * (int)sizeof(float) : 0)) != hipSuccess)                                    \
         return LC2IS_ERR_LAUNCH;                                                                                            \
       attr.done();                                                                                                          \
     }                                                                                                                       \
-    hipLaunchKernelGGL((head_ce_grp_kernel<MODE_, TN_, S_>), dim3(B * t4), dim3(HEAD_THREADS), lds4, stream, a);            \
+    hipLaunchKernelGGL((head_ce_grp_kernel<MODE_, TN_, S_, OPT_>), dim3(B * t4), dim3(HEAD_THREADS), lds4, stream, a);      \
+  } while (0)
+#define LC2IS_HEAD_GRP(MODE_, TN_, S_)                                                                                       \
+  do {                                                                                                                      \
+    if (opt) LC2IS_HEAD_GRP1(MODE_, TN_, S_, true); else LC2IS_HEAD_GRP1(MODE_, TN_, S_, false);                             \
   } while (0)
 #define LC2IS_HEAD_GRP_TN(MODE_, S_)                                                                                         \
   do {                                                                                                                      \
@@ -718,6 +835,7 @@ extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int6
 #undef LC2IS_HEAD_GRP_S
 #undef LC2IS_HEAD_GRP_TN
 #undef LC2IS_HEAD_GRP
+#undef LC2IS_HEAD_GRP1
     int rc = lc2is_check_launch();
     if (rc || !loss_sum) return rc;
     // second launch: fixed-order sums of the slabs (one wave per low-res cell) and of the loss partials
@@ -739,27 +857,84 @@ extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int6
   return lc2is_check_launch();
 }
 
-extern "C" int lc2is_ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, int B,
-                                 int C, long HW, long ignore_index, lc2is_stream_t stream_) {
+int ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px, int B, int C,
+                long HW, long ignore_index, const float* class_weight, float label_smoothing, lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || !labels || !loss_sum) return LC2IS_ERR_NULL;
   if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return LC2IS_ERR_SHAPE;
   size_t g = ((size_t)B * HW + 255) / 256;
   if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(ce_nchw_fwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, loss_sum, B, C,
-                     (size_t)HW, ignore_index);
+  const CeOpts o{class_weight, label_smoothing, loss_px, nullptr};
+  if (class_weight || label_smoothing != 0.f || loss_px)
+    hipLaunchKernelGGL(ce_nchw_fwd_kernel<true>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, loss_sum, B, C,
+                       (size_t)HW, ignore_index, o);
+  else
+    hipLaunchKernelGGL(ce_nchw_fwd_kernel<false>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, loss_sum, B, C,
+                       (size_t)HW, ignore_index, o);
   return lc2is_check_launch();
+}
+
+int ce_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_scale_dev, float grad_scale,
+                const float* grad_px, float* dlogits, int B, int C, long HW, long ignore_index, const float* class_weight,
+                float label_smoothing, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !lse || !dlogits) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return LC2IS_ERR_SHAPE;
+  size_t g = ((size_t)B * HW + 255) / 256;
+  if (g > 8192) g = 8192;
+  const CeOpts o{class_weight, label_smoothing, nullptr, grad_px};
+  if (class_weight || label_smoothing != 0.f || grad_px)
+    hipLaunchKernelGGL(ce_nchw_bwd_kernel<true>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, grad_scale_dev,
+                       grad_scale, dlogits, B, C, (size_t)HW, ignore_index, o);
+  else
+    hipLaunchKernelGGL(ce_nchw_bwd_kernel<false>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, grad_scale_dev,
+                       grad_scale, dlogits, B, C, (size_t)HW, ignore_index, o);
+  return lc2is_check_launch();
+}
+}  // namespace
+
+extern "C" int lc2is_head_upsample_ce(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                      float* scores_hi, float* loss_sum, int B, int h, int w, int C, int S,
+                                      int mode, long ignore_index, float grad_scale, void* workspace,
+                                      size_t workspace_bytes, lc2is_stream_t stream) {
+  return head_upsample_ce(scores_lo, ld, labels, dscores_lo, scores_hi, loss_sum, B, h, w, C, S, mode, ignore_index,
+                          grad_scale, nullptr, 0.f, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lc2is_head_upsample_ce_opts(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                           float* scores_hi, float* loss_sum, int B, int h, int w, int C, int S,
+                                           int mode, long ignore_index, float grad_scale, const float* class_weight,
+                                           float label_smoothing, void* workspace, size_t workspace_bytes,
+                                           lc2is_stream_t stream) {
+  return head_upsample_ce(scores_lo, ld, labels, dscores_lo, scores_hi, loss_sum, B, h, w, C, S, mode, ignore_index,
+                          grad_scale, class_weight, label_smoothing, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lc2is_ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, int B,
+                                 int C, long HW, long ignore_index, lc2is_stream_t stream) {
+  return ce_nchw_fwd(logits, labels, lse, loss_sum, nullptr, B, C, HW, ignore_index, nullptr, 0.f, stream);
+}
+
+extern "C" int lc2is_ce_nchw_fwd_opts(const float* logits, const int64_t* labels, float* lse, float* loss_sum,
+                                      float* loss_px, int B, int C, long HW, long ignore_index,
+                                      const float* class_weight, float label_smoothing, lc2is_stream_t stream) {
+  return ce_nchw_fwd(logits, labels, lse, loss_sum, loss_px, B, C, HW, ignore_index, class_weight, label_smoothing,
+                     stream);
 }
 
 extern "C" int lc2is_ce_nchw_bwd(const float* logits, const int64_t* labels, const float* lse,
                                  const float* grad_scale_dev, float grad_scale, float* dlogits, int B, int C,
-                                 long HW, long ignore_index, lc2is_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!logits || !labels || !lse || !dlogits) return LC2IS_ERR_NULL;
-  if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
-  size_t g = ((size_t)B * HW + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(ce_nchw_bwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, grad_scale_dev,
-                     grad_scale, dlogits, B, C, (size_t)HW, ignore_index);
-  return lc2is_check_launch();
+                                 long HW, long ignore_index, lc2is_stream_t stream) {
+  return ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale, nullptr, dlogits, B, C, HW, ignore_index, nullptr,
+                     0.f, stream);
+}
+
+extern "C" int lc2is_ce_nchw_bwd_opts(const float* logits, const int64_t* labels, const float* lse,
+                                      const float* grad_scale_dev, float grad_scale, const float* grad_px,
+                                      float* dlogits, int B, int C, long HW, long ignore_index,
+                                      const float* class_weight, float label_smoothing, lc2is_stream_t stream) {
+  return ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale, grad_px, dlogits, B, C, HW, ignore_index,
+                     class_weight, label_smoothing, stream);
 }

@@ -24,7 +24,7 @@ from .base import assign_rng_names, require_cuda
 from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import FTNDecoder
-from .model import TextToPatch
+from .model import TextToPatch, fused_loss_options
 from .score import KPAD, ScoreMapTail, _scores_bwd, _scores_lo
 from .swin import SWIN_B, SwinArch, SwinTransformer
 
@@ -67,10 +67,14 @@ class PromptFTN(nn.Module):
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         return None, self.tail(visual_embeddings, text_embeddings)                                # model.py:204-214
 
-    def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
-        """``nn.CrossEntropyLoss()(forward(inputs)[1], labels)`` (engine.py:94) without materialising the [B,K,512,512] map."""
+    def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
+                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+        """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
+        materialising the [B,K,512,512] map ('mean' or 'sum')."""
+        fused_loss_options(weight, label_smoothing, reduction)   # (refused before the towers run)
         visual_embeddings, text_embeddings = self._embeddings(inputs)
-        return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index)
+        return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
+                              label_smoothing=label_smoothing, reduction=reduction)
 
 
 class _ScoreGridFn(torch.autograd.Function):

@@ -1,7 +1,8 @@
 """Losses of the hot path on MI355X — drop-ins for ``nn.CrossEntropyLoss()`` as used by the reference
 (evaluate.py:68, engine.py:82,94,150) and for ``model/loss.py``'s ``AuxiliaryLoss``.
 
-Both take NCHW fp32 logits and int64 labels like the reference; reduction is 'mean' over non-ignored pixels.
+Both take NCHW fp32 logits and int64 labels like the reference, and nn.CrossEntropyLoss's class weights, label smoothing and
+reductions ('mean' = sum of the per-pixel losses over the sum of the counted pixels' class weights, as torch).
 """
 from __future__ import annotations
 
@@ -9,6 +10,7 @@ import math
 
 import torch
 from torch import nn
+from torch.nn.modules.loss import _Reduction
 
 from .. import ops
 from .base import require_cuda
@@ -30,47 +32,91 @@ class _CEFn(torch.autograd.Function):
         return ops.ce_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index), None, None
 
 
+class _CEOptsFn(torch.autograd.Function):
+    """Class weights / label smoothing / 'sum' / 'none' (the default configuration stays on _CEFn)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, label_smoothing, reduction):
+        lg = logits.float().contiguous()
+        lb = labels.contiguous()
+        kw = dict(class_weight=weight, label_smoothing=label_smoothing)
+        loss2, lse, *lpx = ops.ce_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
+        ctx.saved = (lg, lb, lse, loss2, ignore_index, kw, reduction)
+        if reduction == "none":
+            return lpx[0]
+        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lb, lse, loss2, ignore_index, kw, reduction = ctx.saved
+        if reduction == "none":
+            d = ops.ce_nchw_bwd(lg, lb, lse, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
+        else:   # device scalar: upstream gradient (over the weighted count for 'mean')
+            scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
+            d = ops.ce_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index, **kw)
+        return d, None, None, None, None, None
+
+
 class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss() for [B,C,H,W] logits / [B,H,W] labels on the HIP path (mean reduction)."""
+    """nn.CrossEntropyLoss for [B,C,H,W] logits / [B,H,W] labels on the HIP path: class weights (registered as the buffer
+    ``weight`` like torch's), ``reduction`` 'mean' / 'sum' / 'none', ``label_smoothing``, legacy ``size_average`` / ``reduce``."""
 
     def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None, reduction: str = "mean",
                  label_smoothing: float = 0.0) -> None:
         super().__init__()
-        if weight is not None or reduction != "mean" or label_smoothing != 0.0:
-            raise NotImplementedError("lc2is_amd CrossEntropyLoss: only the reference's default configuration "
-                                      "(no class weights, mean reduction, no label smoothing) is implemented")
+        if size_average is not None or reduce is not None:
+            reduction = _Reduction.legacy_get_string(size_average, reduce)
+        if reduction not in ("mean", "sum", "none"):   # (torch raises at the first forward)
+            raise ValueError(f"{reduction} is not a valid value for reduction")
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+        self.register_buffer("weight", weight)
+        self.weight: torch.Tensor | None
         self.ignore_index = ignore_index
+        self.reduction = reduction
+        self.label_smoothing = label_smoothing
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         require_cuda(input, "logits")
         if input.dim() != 4 or target.dim() != 3:
             raise ValueError("lc2is_amd CrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
-        return _CEFn.apply(input, target, self.ignore_index)
+        if self.weight is None and self.label_smoothing == 0.0 and self.reduction == "mean":
+            return _CEFn.apply(input, target, self.ignore_index)
+        return _CEOptsFn.apply(input, target, self.ignore_index, self.weight, self.label_smoothing, self.reduction)
 
 
 class _AuxFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inp, target, ignore_index, S):
+    def forward(ctx, inp, target, ignore_index, S, weight, label_smoothing, reduction):
         B, K, h, w = inp.shape
         ld = (K + 63) // 64 * 64
         lo = torch.zeros(B * h * w, ld, dtype=torch.float32, device=inp.device)
         lo[:, :K] = inp.float().permute(0, 2, 3, 1).reshape(B * h * w, K)
         n = float(B * h * S * w * S)
         loss2, dlo, _ = ops.head_upsample_ce(lo, target.contiguous(), B, h, w, K, S, ops.INTERP_BILINEAR,
-                                             want_grad=True, ignore_index=ignore_index, grad_scale=1.0 / n)
-        ctx.saved = (dlo, loss2, n, (B, K, h, w))
-        return loss2[0] / loss2[1]
+                                             want_grad=True, ignore_index=ignore_index, grad_scale=1.0 / n,
+                                             class_weight=weight, label_smoothing=label_smoothing)
+        ctx.saved = (dlo, loss2, n, (B, K, h, w), reduction)
+        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
 
     @staticmethod
     def backward(ctx, g):
-        dlo, loss2, n, (B, K, h, w) = ctx.saved
-        d = dlo[:, :K].reshape(B, h, w, K).permute(0, 3, 1, 2) * (g * n / loss2[1])
-        return d.contiguous(), None, None, None
+        dlo, loss2, n, (B, K, h, w), reduction = ctx.saved
+        d = dlo[:, :K].reshape(B, h, w, K).permute(0, 3, 1, 2) * (g * n / loss2[1] if reduction == "mean" else g * n)
+        return d.contiguous(), None, None, None, None, None, None
 
 
 class AuxiliaryLoss(CrossEntropyLoss):
     """Drop-in for model/loss.py:12-21: bilinear-resize the low-resolution score map to the label size, then
-    cross-entropy — one fused HIP pass (the resized map is never materialised)."""
+    cross-entropy — one fused HIP pass (the resized map is never materialised).  Class weights, label smoothing and the
+    'mean' / 'sum' reductions; 'none' would materialise the per-pixel map the fusion exists to avoid."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None, reduction: str = "mean",
+                 label_smoothing: float = 0.0) -> None:
+        super().__init__(weight, size_average, ignore_index, reduce, reduction, label_smoothing)
+        if self.reduction == "none":
+            raise NotImplementedError("lc2is_amd AuxiliaryLoss: reduction='none' is not implemented on the fused "
+                                      "resize + cross-entropy path (use 'mean' or 'sum')")
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         require_cuda(input, "input")
@@ -78,7 +124,7 @@ class AuxiliaryLoss(CrossEntropyLoss):
         h = input.shape[-1]
         if input.shape[-2] != h or H != W or H % h or (H // h) not in (4, 8, 16) or input.shape[1] > 192:
             raise NotImplementedError("lc2is_amd AuxiliaryLoss: square maps, integer scale 4/8/16, <= 192 classes")
-        return _AuxFn.apply(input, target, self.ignore_index, H // h)
+        return _AuxFn.apply(input, target, self.ignore_index, H // h, self.weight, self.label_smoothing, self.reduction)
 
 
 class _ContrastiveFn(torch.autograd.Function):

@@ -73,12 +73,35 @@ class TextToPatch(HipModule):
 
 
 # ----------------------------------------------------------------------------------------------------------
+def fused_loss_options(weight, label_smoothing: float, reduction: str):
+    """(weight, label_smoothing, reduction) for a fused CE head, or None for the default configuration."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    if reduction == "none":
+        raise NotImplementedError("lc2is_amd: the fused cross-entropy heads reduce to a scalar ('mean' or 'sum'); "
+                                  "reduction='none' needs the materialised logits (forward + CrossEntropyLoss)")
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+    if weight is None and label_smoothing == 0.0 and reduction == "mean":
+        return None
+    return weight, float(label_smoothing), reduction
+
+
+def _reduce(loss2, reduction: str, save: bool):
+    """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
+    gives torch's NaN mean and a zero gradient, with no host sync."""
+    if reduction == "sum":
+        return loss2[0], None
+    inv = loss2[1].masked_fill(loss2[1] == 0, 1.0).reciprocal() if save else None
+    return loss2[0] / loss2[1], inv
+
+
 class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -86,7 +109,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None
+        return ddec, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -143,7 +166,7 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -156,10 +179,17 @@ class BaseModelWithText(HipModule):
         # the kernel writes the gradient of the SUM of the per-pixel losses and counts the pixels it kept (labels that are
         # negative, == ignore_index or >= K are skipped, head.hip); the 1/count of nn.CrossEntropyLoss's mean is folded
         # into the upstream-gradient multiply of _head_bwd, from the device-side count (no host sync, no label pass)
-        loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
-                                             want_grad=save, ignore_index=ignore_index, grad_scale=1.0)
-        loss = loss2[0] / loss2[1]
-        inv_count = (1.0 / loss2[1].clamp_min(1.0)) if save else None
+        if loss_opts is None:
+            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
+                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0)
+            loss = loss2[0] / loss2[1]
+            inv_count = (1.0 / loss2[1].clamp_min(1.0)) if save else None
+        else:   # class weights / label smoothing: loss2[1] is the weighted count sum_i w_{y_i}; 'sum' drops the division
+            weight, label_smoothing, reduction = loss_opts
+            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
+                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
+                                                 class_weight=weight, label_smoothing=label_smoothing)
+            loss, inv_count = _reduce(loss2, reduction, save)
         return loss, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=inv_count)
                       if save else None)
 
@@ -169,7 +199,11 @@ class BaseModelWithText(HipModule):
         psh, sh = pp._sh, self._sh
         if saved["fused"] is not None:
             ds = saved["fused"]   # d(sum of pixel losses)/d(scores); gout: scalar upstream gradient of the mean loss
-            ds16 = ops.cast_bf16(ds * (saved["inv_count"] if gout is None else gout * saved["inv_count"]))
+            inv = saved["inv_count"]   # None: reduction='sum'
+            if inv is None:
+                ds16 = ops.cast_bf16(ds if gout is None else ds * gout)
+            else:
+                ds16 = ops.cast_bf16(ds * (inv if gout is None else gout * inv))
         else:
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, KPAD)
             ds16 = ops.cast_bf16(ds)
@@ -232,12 +266,15 @@ class BaseModelWithText(HipModule):
         logits = _HeadFn.apply(dec_v, self.class_prototypes, self, None, save, -100)
         return dict(outputs=logits)
 
-    def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
-        """Mean cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with
-        the head; never materialises the fp32 logits."""
+    def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
+                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+        """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
+        materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
+        nn.CrossEntropyLoss."""
+        opts = fused_loss_options(weight, label_smoothing, reduction)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts)
 
     @torch.no_grad()
     def forward_tuple(self, inputs: dict):

@@ -17,6 +17,7 @@ from torch import nn
 
 from .. import ops
 from .base import require_cuda
+from .model import _reduce, fused_loss_options
 
 KPAD = 192
 
@@ -58,7 +59,7 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -68,6 +69,16 @@ class _ScoreFn(torch.autograd.Function):
                                             want_loss=False)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
             return hi
+        if loss_opts is not None:   # class weights / label smoothing / 'sum' (loss2[1] = sum_i w_{y_i})
+            weight, label_smoothing, reduction = loss_opts
+            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
+                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
+                                                 class_weight=weight, label_smoothing=label_smoothing)
+            loss, inv = _reduce(loss2, reduction, save)
+            if inv is not None:
+                dlo.mul_(inv)
+            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
+            return loss
         n = float(B * h * scale * h * scale)
         loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
                                              want_grad=save, ignore_index=ignore_index, grad_scale=1.0 / n)
@@ -85,7 +96,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None
+        return dv, dt, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -102,7 +113,9 @@ class ScoreMapTail(nn.Module):
         return _ScoreFn.apply(visual_embeddings, text_embeddings, None, self.scale_factor, -100, save)
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
-             ignore_index: int = -100) -> torch.Tensor:
+             ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+        """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss."""
+        opts = fused_loss_options(weight, label_smoothing, reduction)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
-        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save)
+        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts)

@@ -61,6 +61,9 @@ _ARGTYPES = {
     "lc2is_head_upsample_ce": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _Z, _P],
     "lc2is_ce_nchw_fwd": [_P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P],
     "lc2is_ce_nchw_bwd": [_P, _P, _P, _P, _F, _P, _I, _I, C.c_long, C.c_long, _P],
+    "lc2is_head_upsample_ce_opts": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _F, _P, _Z, _P],
+    "lc2is_ce_nchw_fwd_opts": [_P, _P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
+    "lc2is_ce_nchw_bwd_opts": [_P, _P, _P, _P, _F, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
     "lc2is_upsample_bwd_nchw": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -696,11 +699,29 @@ def adamw_step(params, grads, m, v, lr, beta1, beta2, eps, weight_decay, step, g
                                        beta2, eps, weight_decay, int(step), grad_scale, _stream()), "adamw_step")
 
 
+def _ce_options(class_weight, label_smoothing: float, C: int, dev):
+    """Validate F.cross_entropy's weight / label_smoothing for a C-class call; True when either is set."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise RuntimeError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+    if class_weight is None:
+        return label_smoothing != 0.0
+    if class_weight.dim() != 1 or class_weight.numel() != C:   # torch's message (aten LossNLL.cpp)
+        raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight "
+                           f"tensor of shape: {list(class_weight.shape)}")
+    _chk(class_weight, torch.float32, "class_weight", 1)
+    if class_weight.device != dev:
+        raise RuntimeError(f"lc2is_amd: class_weight must be on {dev}, got {class_weight.device}")
+    return True
+
+
 def head_upsample_ce(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
                      want_grad: bool = False, want_scores: bool = False, want_loss: bool = True,
-                     ignore_index: int = -100, grad_scale: float = 1.0):
-    """scores_lo fp32 [B*h*w, ld].  Returns (loss_sum[2] or None, dscores_lo or None, scores_hi NCHW or None)."""
+                     ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None, label_smoothing: float = 0.0):
+    """scores_lo fp32 [B*h*w, ld].  Returns (loss_sum[2] or None, dscores_lo or None, scores_hi NCHW or None).
+    class_weight (fp32 [C] on the device) / label_smoothing: F.cross_entropy's options (S = 4 / 8 / 16); loss_sum[1] is then
+    the weighted count sum_i w_{y_i}, the denominator of the mean."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    opts = _ce_options(class_weight, label_smoothing, C, scores_lo.device) and want_loss
     if not scores_lo.is_contiguous():
         raise RuntimeError("lc2is_amd.head_upsample_ce: scores_lo must be contiguous")
     ld = scores_lo.shape[1]
@@ -715,29 +736,55 @@ def head_upsample_ce(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, 
     dlo = alloc(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
     hi = torch.empty((B, C, h * S, w * S), dtype=torch.float32, device=dev) if want_scores else None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None   # (per call: the slabs live until the second launch, in stream order)
-    rc = _fn("lc2is_head_upsample_ce")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(hi), _ptr(loss), B, h,
-                                       w, C, S, mode, ignore_index, grad_scale, _ptr(ws), nbytes, _stream())
+    if opts:
+        rc = _fn("lc2is_head_upsample_ce_opts")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(hi), _ptr(loss), B, h,
+                                                w, C, S, mode, ignore_index, grad_scale, _ptr(class_weight),
+                                                label_smoothing, _ptr(ws), nbytes, _stream())
+    else:
+        rc = _fn("lc2is_head_upsample_ce")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(hi), _ptr(loss), B, h,
+                                           w, C, S, mode, ignore_index, grad_scale, _ptr(ws), nbytes, _stream())
     _lib.check(rc, f"head_upsample_ce B={B} h={h} w={w} C={C} S={S}")
     return loss, dlo, hi
 
 
-def ce_nchw_fwd(logits, labels, ignore_index: int = -100):
+def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, label_smoothing: float = 0.0,
+                per_pixel: bool = False):
+    """Returns (loss_sum[2], lse [B,H,W]) — loss_sum = (sum of per-pixel losses, sum of w_y over the counted pixels) — and,
+    with per_pixel=True, a third tensor: the per-pixel losses [B,H,W] (reduction="none"; 0 where not counted)."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     if not logits.is_contiguous() or not labels.is_contiguous():
         raise RuntimeError("lc2is_amd.ce_nchw_fwd: logits/labels must be contiguous")
     B, Cc, H, W = logits.shape
+    opts = _ce_options(class_weight, label_smoothing, Cc, logits.device)
     lse = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
     loss = torch.zeros(2, dtype=torch.float32, device=logits.device)
-    _lib.check(_fn("lc2is_ce_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), B, Cc, H * W,
-                                        ignore_index, _stream()), "ce_nchw_fwd")
-    return loss, lse
+    if not (opts or per_pixel):
+        _lib.check(_fn("lc2is_ce_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), B, Cc, H * W,
+                                            ignore_index, _stream()), "ce_nchw_fwd")
+        return loss, lse
+    lpx = torch.empty((B, H, W), dtype=torch.float32, device=logits.device) if per_pixel else None
+    _lib.check(_fn("lc2is_ce_nchw_fwd_opts")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W,
+                                             ignore_index, _ptr(class_weight), label_smoothing, _stream()), "ce_nchw_fwd")
+    return (loss, lse, lpx) if per_pixel else (loss, lse)
 
 
-def ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float, ignore_index: int = -100):
+def ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float, ignore_index: int = -100, *, class_weight=None,
+                label_smoothing: float = 0.0, grad_px=None):
+    """dlogits = grad_scale * grad_scale_dev * grad_px (per pixel, [B,H,W] fp32, optional) * dloss_i/dlogits."""
     B, Cc, H, W = logits.shape
+    opts = _ce_options(class_weight, label_smoothing, Cc, logits.device)
     d = torch.empty_like(logits)
-    _lib.check(_fn("lc2is_ce_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
-                                        _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_nchw_bwd")
+    if not (opts or grad_px is not None):
+        _lib.check(_fn("lc2is_ce_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
+                                            _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_nchw_bwd")
+        return d
+    if grad_px is not None:
+        _chk(grad_px, torch.float32, "grad_px", 3)
+        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
+            raise RuntimeError(f"lc2is_amd.ce_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    _lib.check(_fn("lc2is_ce_nchw_bwd_opts")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
+                                             _ptr(grad_px), _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight),
+                                             label_smoothing, _stream()), "ce_nchw_bwd")
     return d
 
 

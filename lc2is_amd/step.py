@@ -3,7 +3,7 @@
 One call to :meth:`TrainStep.step` is one iteration of the reference's hot loop:
     optimizer.zero_grad()                                   engine.py:78
     outputs_dict = model(inputs)                            engine.py:93
-    loss = criterion(outputs_dict["outputs"], labels)       engine.py:94     (mean CE; fused with the head here)
+    loss = criterion(outputs_dict["outputs"], labels)       engine.py:94     (CE; fused with the head here)
     loss.backward()                                         engine.py:100    (+ NEW: DP gradient all-reduce)
     optimizer.step()                                        engine.py:101
 and returns the loss as a DEVICE tensor (the reference's per-step ``.item()`` sync, engine.py:108, is left to
@@ -13,6 +13,9 @@ MI355X layout: all parameters and gradients live in one flat fp32 arena (``Param
 a single fused HIP launch and the data-parallel reduction is over one contiguous buffer, issued per module
 (head, decoder, vision, text) as soon as that module's backward has run, on RCCL's own stream, overlapping
 the remaining backward (``lc2is_amd.dp.GradReducer``).
+
+``criterion``: an ``lc2is_amd.nn.CrossEntropyLoss`` (or ``torch.nn.CrossEntropyLoss``) whose ``ignore_index``, ``weight``,
+``label_smoothing`` and ``reduction`` ('mean' / 'sum') configure the fused head; default: ``CrossEntropyLoss()``.
 """
 from __future__ import annotations
 
@@ -28,7 +31,21 @@ from .nn.base import HipModule, ParamArena
 class TrainStep:
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = 1e-5, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
-                 ignore_index: int = -100) -> None:
+                 ignore_index: int | None = None, criterion: nn.Module | None = None) -> None:
+        # (criterion checks first: nothing is built or allocated for a step that cannot run)
+        self._loss_opts = False
+        if criterion is not None:
+            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss
+            if not isinstance(criterion, (CrossEntropyLoss, nn.CrossEntropyLoss)) or isinstance(criterion, AuxiliaryLoss):
+                raise TypeError("TrainStep: criterion must be a CrossEntropyLoss (lc2is_amd.nn or torch.nn)")
+            if ignore_index is not None and ignore_index != -100:
+                raise ValueError("TrainStep: give ignore_index through the criterion, not as a TrainStep argument too")
+            if criterion.reduction == "none":
+                raise ValueError("TrainStep: a training step needs a scalar loss; criterion reduction='none' cannot train")
+            ignore_index = criterion.ignore_index
+            self._loss_opts = (criterion.weight is not None or criterion.label_smoothing != 0.0
+                               or criterion.reduction != "mean")
+        self.criterion = criterion
         self.model = model
         self.arena = ParamArena(model)
         self.kind = optimizer.lower()
@@ -41,7 +58,7 @@ class TrainStep:
             self.m, self.v = torch.zeros_like(self.arena.flat), torch.zeros_like(self.arena.flat)
         self.t = 0
         self.reducer = reducer
-        self.ignore_index = ignore_index
+        self.ignore_index = -100 if ignore_index is None else ignore_index
         self._hip_modules = [m for m in model.modules() if isinstance(m, HipModule)]
         if reducer is not None:
             reducer.attach(model, self.arena)
@@ -52,7 +69,12 @@ class TrainStep:
         arena.zero_grad(set_to_none=True)
         if self.reducer is not None:
             self.reducer.begin_step()
-        loss = self.model.forward_loss(inputs, labels, self.ignore_index)
+        if self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
+            c = self.criterion
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
+                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction)
+        else:
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index)
         loss.backward()
         live = arena.finalize_grads()
         gscale = 1.0
