@@ -341,6 +341,14 @@ int lc2is_ce_nchw_bwd_opts(const float* logits, const int64_t* labels, const flo
                            float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW,
                            long ignore_index, const float* class_weight, float label_smoothing,
                            lc2is_stream_t stream);
+/* lc2is_ce_nchw_fwd_opts with ordered sums (class_weight NULL, label_smoothing 0 and loss_px NULL: lc2is_ce_nchw_fwd): every
+ * block writes its (loss, count) partial to the workspace, lc2is_ce_nchw_fwd_workspace_bytes(B, HW) bytes, and a second launch
+ * sums them in a fixed order into loss_sum (overwritten, no clearing), so the sums are the same bits every run.  The two entry
+ * points above add into loss_sum with float atomics, whose arrival order changes the last bits from run to run. */
+size_t lc2is_ce_nchw_fwd_workspace_bytes(int B, long HW);
+int lc2is_ce_nchw_fwd_ordered(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px,
+                              int B, int C, long HW, long ignore_index, const float* class_weight, float label_smoothing,
+                              void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
 
 /* ---- multi-scale decoder glue (BASELINE config 5; all channels-last token tensors [B, h*w, C]) --------
  * bilinear xS upsample (align_corners=False) forward / backward.

@@ -593,10 +593,12 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadArgs p, int nblk_m
 // (backward) a per-pixel upstream gradient grad_px — the formulas of head_ce_grp_kernel's OPT variant.
 struct CeOpts { const float* cw; float eps; float* loss_px; const float* grad_px; };
 
-template <bool OPT>
+// ORDERED: out = per-block (loss, count) partials [gridDim.x][2], summed in a fixed order by ce_nchw_finish_kernel (the same bits
+// every run).  Otherwise out = loss_sum, added into with float atomics (the workspace-less lc2is_ce_nchw_fwd / _opts entry points).
+template <bool OPT, bool ORDERED>
 __global__ __launch_bounds__(256) void ce_nchw_fwd_kernel(const float* __restrict__ logits,
                                                            const int64_t* __restrict__ labels, float* lse,
-                                                           float* loss_sum, int B, int C, size_t HW,
+                                                           float* out, int B, int C, size_t HW,
                                                            long ignore_index, CeOpts o) {
   const size_t total = (size_t)B * HW;
   float lacc = 0.f, cacc = 0.f;
@@ -635,10 +637,38 @@ __global__ __launch_bounds__(256) void ce_nchw_fwd_kernel(const float* __restric
   }
   lacc = wave_sum(lacc);
   cacc = wave_sum(cacc);
-  if ((threadIdx.x & 63) == 0 && (OPT ? lacc != 0.f || cacc != 0.f : cacc > 0.f)) {
-    atomicAdd(loss_sum, lacc);
-    atomicAdd(loss_sum + 1, cacc);
+  if constexpr (ORDERED) {
+    __shared__ float red[2][4];
+    if ((threadIdx.x & 63) == 0) {
+      red[0][threadIdx.x >> 6] = lacc;
+      red[1][threadIdx.x >> 6] = cacc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2)
+      out[2 * blockIdx.x + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  } else if ((threadIdx.x & 63) == 0 && (OPT ? lacc != 0.f || cacc != 0.f : cacc > 0.f)) {
+    atomicAdd(out, lacc);
+    atomicAdd(out + 1, cacc);
   }
+}
+
+// loss_sum[0..1] = the sums of ce_nchw_fwd_kernel's nblk block partials, in a fixed order (one block; overwrites loss_sum)
+__global__ __launch_bounds__(256) void ce_nchw_finish_kernel(const float* __restrict__ part, int nblk, float* loss_sum) {
+  float l = 0.f, c = 0.f;
+  for (int k = threadIdx.x; k < nblk; k += 256) {
+    l += part[2 * k];
+    c += part[2 * k + 1];
+  }
+  l = wave_sum(l);
+  c = wave_sum(c);
+  __shared__ float red[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = l;
+    red[1][threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    loss_sum[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
 template <bool OPT>
@@ -857,21 +887,37 @@ int head_upsample_ce(const float* scores_lo, int ld, const int64_t* labels, floa
   return lc2is_check_launch();
 }
 
+size_t ce_nchw_fwd_grid(int B, long HW) {
+  size_t g = ((size_t)B * HW + 255) / 256;
+  return g > 8192 ? 8192 : g;
+}
+
+// workspace != NULL: ordered sums, loss_sum overwritten; NULL: float atomics into loss_sum, which the caller clears
 int ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px, int B, int C,
-                long HW, long ignore_index, const float* class_weight, float label_smoothing, lc2is_stream_t stream_) {
+                long HW, long ignore_index, const float* class_weight, float label_smoothing, void* workspace,
+                size_t workspace_bytes, lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || !labels || !loss_sum) return LC2IS_ERR_NULL;
   if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
   if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return LC2IS_ERR_SHAPE;
-  size_t g = ((size_t)B * HW + 255) / 256;
-  if (g > 8192) g = 8192;
+  const size_t g = ce_nchw_fwd_grid(B, HW);
+  const bool ordered = workspace != nullptr;
+  if (ordered && workspace_bytes < 2 * sizeof(float) * g) return LC2IS_ERR_WORKSPACE;
+  float* out = ordered ? (float*)workspace : loss_sum;
   const CeOpts o{class_weight, label_smoothing, loss_px, nullptr};
-  if (class_weight || label_smoothing != 0.f || loss_px)
-    hipLaunchKernelGGL(ce_nchw_fwd_kernel<true>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, loss_sum, B, C,
-                       (size_t)HW, ignore_index, o);
-  else
-    hipLaunchKernelGGL(ce_nchw_fwd_kernel<false>, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, loss_sum, B, C,
-                       (size_t)HW, ignore_index, o);
+  const bool opt = class_weight || label_smoothing != 0.f || loss_px;
+#define LC2IS_CE_FWD(OPT_, ORD_) \
+  hipLaunchKernelGGL((ce_nchw_fwd_kernel<OPT_, ORD_>), dim3((int)g), dim3(256), 0, stream, logits, labels, lse, out, B, C, \
+                     (size_t)HW, ignore_index, o)
+  if (ordered) {
+    if (opt) LC2IS_CE_FWD(true, true); else LC2IS_CE_FWD(false, true);
+  } else {
+    if (opt) LC2IS_CE_FWD(true, false); else LC2IS_CE_FWD(false, false);
+  }
+#undef LC2IS_CE_FWD
+  int rc = lc2is_check_launch();
+  if (rc || !ordered) return rc;
+  hipLaunchKernelGGL(ce_nchw_finish_kernel, dim3(1), dim3(256), 0, stream, out, (int)g, loss_sum);
   return lc2is_check_launch();
 }
 
@@ -914,14 +960,27 @@ extern "C" int lc2is_head_upsample_ce_opts(const float* scores_lo, int ld, const
 
 extern "C" int lc2is_ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, int B,
                                  int C, long HW, long ignore_index, lc2is_stream_t stream) {
-  return ce_nchw_fwd(logits, labels, lse, loss_sum, nullptr, B, C, HW, ignore_index, nullptr, 0.f, stream);
+  return ce_nchw_fwd(logits, labels, lse, loss_sum, nullptr, B, C, HW, ignore_index, nullptr, 0.f, nullptr, 0, stream);
 }
 
 extern "C" int lc2is_ce_nchw_fwd_opts(const float* logits, const int64_t* labels, float* lse, float* loss_sum,
                                       float* loss_px, int B, int C, long HW, long ignore_index,
                                       const float* class_weight, float label_smoothing, lc2is_stream_t stream) {
   return ce_nchw_fwd(logits, labels, lse, loss_sum, loss_px, B, C, HW, ignore_index, class_weight, label_smoothing,
-                     stream);
+                     nullptr, 0, stream);
+}
+
+extern "C" size_t lc2is_ce_nchw_fwd_workspace_bytes(int B, long HW) {
+  return B > 0 && HW > 0 ? 2 * sizeof(float) * ce_nchw_fwd_grid(B, HW) : 0;
+}
+
+extern "C" int lc2is_ce_nchw_fwd_ordered(const float* logits, const int64_t* labels, float* lse, float* loss_sum,
+                                         float* loss_px, int B, int C, long HW, long ignore_index,
+                                         const float* class_weight, float label_smoothing, void* workspace,
+                                         size_t workspace_bytes, lc2is_stream_t stream) {
+  if (!workspace) return LC2IS_ERR_NULL;
+  return ce_nchw_fwd(logits, labels, lse, loss_sum, loss_px, B, C, HW, ignore_index, class_weight, label_smoothing,
+                     workspace, workspace_bytes, stream);
 }
 
 extern "C" int lc2is_ce_nchw_bwd(const float* logits, const int64_t* labels, const float* lse,

@@ -63,6 +63,8 @@ _ARGTYPES = {
     "lc2is_ce_nchw_bwd": [_P, _P, _P, _P, _F, _P, _I, _I, C.c_long, C.c_long, _P],
     "lc2is_head_upsample_ce_opts": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _F, _P, _Z, _P],
     "lc2is_ce_nchw_fwd_opts": [_P, _P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
+    "lc2is_ce_nchw_fwd_workspace_bytes": [_I, C.c_long],
+    "lc2is_ce_nchw_fwd_ordered": [_P, _P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P, _Z, _P],
     "lc2is_ce_nchw_bwd_opts": [_P, _P, _P, _P, _F, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
     "lc2is_upsample_bwd_nchw": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -755,16 +757,15 @@ def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, 
     if not logits.is_contiguous() or not labels.is_contiguous():
         raise RuntimeError("lc2is_amd.ce_nchw_fwd: logits/labels must be contiguous")
     B, Cc, H, W = logits.shape
-    opts = _ce_options(class_weight, label_smoothing, Cc, logits.device)
+    _ce_options(class_weight, label_smoothing, Cc, logits.device)   # (validation; the C side picks the kernel variant)
     lse = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
-    loss = torch.zeros(2, dtype=torch.float32, device=logits.device)
-    if not (opts or per_pixel):
-        _lib.check(_fn("lc2is_ce_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), B, Cc, H * W,
-                                            ignore_index, _stream()), "ce_nchw_fwd")
-        return loss, lse
+    loss = torch.empty(2, dtype=torch.float32, device=logits.device)   # overwritten: block partials summed in a fixed order
+    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)   # (per call, like head_upsample_ce's slabs)
     lpx = torch.empty((B, H, W), dtype=torch.float32, device=logits.device) if per_pixel else None
-    _lib.check(_fn("lc2is_ce_nchw_fwd_opts")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W,
-                                             ignore_index, _ptr(class_weight), label_smoothing, _stream()), "ce_nchw_fwd")
+    _lib.check(_fn("lc2is_ce_nchw_fwd_ordered")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W,
+                                                ignore_index, _ptr(class_weight), label_smoothing, _ptr(ws), nbytes,
+                                                _stream()), "ce_nchw_fwd")
     return (loss, lse, lpx) if per_pixel else (loss, lse)
 
 
