@@ -438,6 +438,29 @@ int lc2is_npair_bwd(const float* x, const float* x_pos, const float* x_neg, cons
 int lc2is_miou_counts(const float* scores_hi, const int64_t* labels_lo, int* counts, int B, int K, int H, int W, int S,
                       lc2is_stream_t stream);
 
+/* ---- original-size prediction and mIoU --------------------------------------------------------------------------------
+ * Per image b of a batch: bicubic resize of scores[b] (channels-last fp32 [N,h,w,ld], K valid channels, ld % 4 == 0, ld >= K,
+ * 16-byte aligned) to its own size H_b x W_b (any size >= 1: torch's upsample_bicubic2d with align_corners=False and an explicit
+ * size: scale h / H, A = -0.75, taps clamped), then the argmax over the K channels (exact ties: the lowest index) — without
+ * forming the [K,H,W] score map.
+ *   desc: DEVICE int64 [N][4] = {H_b, W_b, first pixel of image b in pred / gt, first tile of image b}; the images are packed
+ *     row-major one after the other (total_px pixels), image b has ceil(H_b/16) * ceil(W_b/16) tiles of LC2IS_RESIZE_TILE^2
+ *     pixels, first tiles ascending from 0 (n_tiles in all).  A descriptor that does not fit total_px / n_tiles is not followed.
+ *   pred (optional): uint8 [total_px], the argmax.
+ *   counts (optional): int32 [N][3][K] = {intersection, predicted, labelled} per class, OVERWRITTEN (no clearing): every pixel
+ *     counts in "predicted", "labelled" and "intersection" only where 0 <= gt < K (lc2is_miou_counts' rule).  Needs gt (packed
+ *     like pred; gt_bytes = 1: uint8, 4: int32, 8: int64) and workspace (>= lc2is_resize_argmax_workspace_bytes(n_tiles, K)
+ *     = n_tiles * 3 * K * 4 bytes: per-tile counts, summed per image in a fixed order by a second launch; no atomics, bitwise
+ *     reproducible).
+ * K > 192 or another gt_bytes: LC2IS_ERR_UNSUPPORTED.
+ * replaces: metrics.py:61-79 (compute_gt_mIOU: F.interpolate(size=) + Softmax2d + JaccardIndex) and metrics.py:35-42,137-143
+ *   (prepare_for_gt_metrics / original_size_interpolate, then argmax). */
+#define LC2IS_RESIZE_TILE 16
+size_t lc2is_resize_argmax_workspace_bytes(long n_tiles, int K);
+int lc2is_resize_argmax(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc, long n_tiles,
+                        long total_px, const void* gt, int gt_bytes, uint8_t* pred, int* counts, void* workspace,
+                        size_t workspace_bytes, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

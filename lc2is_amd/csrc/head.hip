@@ -23,6 +23,7 @@
 //  * other S (multiples of 16 from 32): head_ce_kernel — each wave walks 64 output pixels with the 64 lanes spread over CHANNELS (3 per lane, C <= 192),
 //    wave reductions for the softmax, ds_add_f32 for the gradient scatter.
 #include "common.h"
+#include "interp.h"
 #include "lc2is_hip.h"
 
 namespace {
@@ -32,37 +33,6 @@ constexpr int FMAX = 8;       // max footprint edge for S >= 4 (16/S + 4 bicubic
 constexpr int HEAD_THREADS = 512;
 constexpr int CMAX = 192;
 constexpr int HEAD_PAD = 4;     // floats added to a footprint cell's LDS stride in the S = 4 kernel
-
-__device__ __forceinline__ float cubic1(float x) { return ((1.25f * x - 2.25f) * x) * x + 1.f; }          // A=-0.75
-__device__ __forceinline__ float cubic2(float x) { return ((-0.75f * x + 3.75f) * x - 6.f) * x + 3.f; }
-
-// taps of one output coordinate: up to 4 (index, weight) pairs, indices clamped to [0, n-1]
-struct Taps { int idx[4]; float w[4]; };
-
-__device__ __forceinline__ Taps make_taps(int dst, float inv_scale, int n_in, int mode) {
-  Taps t;
-  if (mode == LC2IS_INTERP_BICUBIC) {
-    const float src = inv_scale * ((float)dst + 0.5f) - 0.5f;
-    const float fl = floorf(src);
-    const float tt = src - fl;
-    const int i0 = (int)fl;
-    t.w[0] = cubic2(tt + 1.f); t.w[1] = cubic1(tt); t.w[2] = cubic1(1.f - tt); t.w[3] = cubic2(2.f - tt);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int ii = i0 - 1 + k;
-      t.idx[k] = ii < 0 ? 0 : (ii > n_in - 1 ? n_in - 1 : ii);
-    }
-  } else {  // bilinear, align_corners=False
-    float src = inv_scale * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    const int i0 = (int)src;
-    const int i1 = i0 < n_in - 1 ? i0 + 1 : i0;
-    const float l1 = src - (float)i0;
-    t.idx[0] = i0; t.w[0] = 1.f - l1; t.idx[1] = i1; t.w[1] = l1;
-    t.idx[2] = i0; t.w[2] = 0.f; t.idx[3] = i0; t.w[3] = 0.f;
-  }
-  return t;
-}
 
 struct HeadArgs {
   const float* lo; int ld;       // [B, h, w, ld] scores, C valid channels

@@ -4,6 +4,8 @@ metrics.py:45-58,82-102).
 
     ev = Evaluator(model, eval_loader, criterion, aux_criterion=None, compute_metrics=segmentation_metrics)
     metrics = ev.evaluate()        # {"eval_loss": ..., ["eval_aux_loss": ...], "eval_mIOU_label": ...}
+    ev = Evaluator(..., gt_from_metas=lambda metas: [m["gt"] for m in metas])
+    metrics = ev.evaluate()        # ... and "eval_mIOU_gt": the mIoU at each image's original size (compute_gt_mIOU)
 
 Semantics kept from the reference:
   * ``model.eval()``; per batch ``inputs, metas = data``; ``labels = inputs.pop("label")``; ``torch.no_grad()`` forward;
@@ -28,19 +30,24 @@ from torch import nn
 from . import metrics as _metrics
 
 
-def segmentation_metrics(outputs: torch.Tensor, labels: torch.Tensor, n_clas: int = 151, ignore_index: int | None = 0,
-                         **_unused) -> dict:
-    """metrics.segmentation_metrics (metrics.py:45-58), label-size branch: ``dict(mIOU_label=...)``.  The ground-truth-size
-    branch (``compute_gt_mIOU``) needs the original images' label maps, which ``eval_loop`` never supplies in the reference
-    either (engine.py:166; SURVEY.md §2 staleness)."""
-    return _metrics.compute_mIOU(outputs=outputs, labels=labels, n_cls=n_clas, ignore_index=ignore_index)
+def segmentation_metrics(outputs: torch.Tensor, labels: torch.Tensor, gt_list=None, sizes=None, n_clas: int = 151,
+                         ignore_index: int | None = 0, **_unused) -> dict:
+    """metrics.segmentation_metrics (metrics.py:45-58): ``dict(mIOU_label=...)``, and ``mIOU_gt`` (``compute_gt_mIOU`` at each
+    image's original size) when the original images' label maps ``gt_list`` are given — ``eval_loop`` supplies them only with
+    ``Evaluator(gt_from_metas=...)``, as the reference's never does (engine.py:166; SURVEY.md §2 staleness).  ``sizes``: the
+    (H, W) of each image, None = the gt maps' shapes."""
+    m = _metrics.compute_mIOU(outputs=outputs, labels=labels, n_cls=n_clas, ignore_index=ignore_index)
+    if gt_list is not None:
+        m.update(_metrics.compute_gt_mIOU(outputs=outputs, gt_list=gt_list, sizes=sizes, n_cls=n_clas, ignore_index=ignore_index))
+    return m
 
 
 class Evaluator:
     """``Engine``'s evaluation half with the same constructor argument names (engine.py:15-21)."""
 
     def __init__(self, model: nn.Module, eval_loader: Iterable, criterion: nn.Module, aux_criterion: nn.Module | None = None,
-                 compute_metrics: Callable | None = segmentation_metrics, device="cuda", keep_outputs: bool = False) -> None:
+                 compute_metrics: Callable | None = segmentation_metrics, device="cuda", keep_outputs: bool = False,
+                 gt_from_metas: Callable | None = None) -> None:
         self.model = model
         self.eval_loader = eval_loader
         self.criterion = criterion
@@ -52,6 +59,10 @@ class Evaluator:
         # for the cat) over the 2000-image ADE20K validation split at 128 x 128.  ``keep_outputs=True`` (or a custom
         # ``compute_metrics``, whose contract is ``compute_metrics(outputs=..., labels=...)``) restores the concatenation.
         self.keep_outputs = keep_outputs or (compute_metrics is not None and compute_metrics is not segmentation_metrics)
+        # ``gt_from_metas(metas) -> list of label maps [H_i, W_i]`` (the original images' annotations of one batch): adds
+        # ``eval_mIOU_gt``, accumulated per image like ``per_image_mIOU``, or, when the outputs are kept, passed on to
+        # ``compute_metrics`` as ``gt_list`` and ``sizes`` (the reference's metric signature).
+        self.gt_from_metas = gt_from_metas
         self.model.to(self.device)
 
     def evaluate(self) -> dict:
@@ -59,6 +70,8 @@ class Evaluator:
         if self.compute_metrics is not None:
             if "per_image_mIOU" in eval_outputs:
                 m = dict(mIOU_label=float(eval_outputs["per_image_mIOU"].mean().item()))
+                if "per_image_mIOU_gt" in eval_outputs:
+                    m["mIOU_gt"] = float(eval_outputs["per_image_mIOU_gt"].mean().item())
             else:
                 m = self.compute_metrics(**eval_outputs)
             eval_metrics = {**eval_metrics, **{"eval_" + k: v for k, v in m.items()}}
@@ -67,9 +80,9 @@ class Evaluator:
     def eval_loop(self) -> tuple[dict, dict]:
         self.model.eval()
         losses: dict[str, list[torch.Tensor]] = {}
-        outs, labs = [], []
+        outs, labs, gts, gt_outs = [], [], [], []
         for data in self.eval_loader:
-            inputs, _metas = data
+            inputs, metas = data
             inputs = {k: v.to(self.device, non_blocking=True) for k, v in inputs.items()}
             labels = inputs.pop("label")
             with torch.no_grad():
@@ -79,14 +92,23 @@ class Evaluator:
                     step["eval_aux_loss"] = self.aux_criterion(outputs_dict["low_score_map"], labels) * 0.4
             for k, v in step.items():
                 losses.setdefault(k, []).append(v.detach().float().reshape(()))
+            gt = None if self.gt_from_metas is None else list(self.gt_from_metas(metas))
             if self.keep_outputs or self.compute_metrics is None:
                 outs.append(outputs_dict["outputs"])
                 labs.append(labels)
+                if gt is not None:
+                    gts.extend(gt)
             else:
                 outs.append(_metrics.per_image_mIOU(outputs_dict["outputs"], labels))
+                if gt is not None:
+                    gt_outs.append(_metrics.per_image_gt_mIOU(outputs_dict["outputs"], gt))
         eval_metrics = {k: float(torch.stack(v).mean().item()) for k, v in losses.items()}
         if self.keep_outputs or self.compute_metrics is None:
             eval_outputs = dict(outputs=torch.cat(outs), labels=torch.cat(labs))
+            if self.gt_from_metas is not None:
+                eval_outputs.update(gt_list=gts, sizes=torch.tensor([tuple(g.shape) for g in gts], dtype=torch.int64).view(-1, 2))
         else:
             eval_outputs = dict(per_image_mIOU=torch.cat(outs))
+            if self.gt_from_metas is not None:
+                eval_outputs["per_image_mIOU_gt"] = torch.cat(gt_outs)
         return eval_metrics, eval_outputs

@@ -78,6 +78,8 @@ _ARGTYPES = {
     "lc2is_cols_ce": [_P, _P, _P, _P, _F, _I, _I, _I, _I, _P],
     "lc2is_npair": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_miou_counts": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "lc2is_resize_argmax_workspace_bytes": [_L, _I],
+    "lc2is_resize_argmax": [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _I, _P, _P, _P, _Z, _P],
     "lc2is_npair_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_gemm_tn_grouped_workspace_bytes": [_P, _I],
     "lc2is_gemm_tn_grouped": [_P, _I, _P, _Z, _P],
@@ -946,6 +948,86 @@ def miou_counts(scores_hi, labels_lo, S: int):
     _lib.check(_fn("lc2is_miou_counts")(_ptr(scores_hi.contiguous()), _ptr(labels_lo.contiguous()), _ptr(counts), B, K, H,
                                         W, S, _stream()), "miou_counts")
     return counts
+
+
+RESIZE_TILE, RESIZE_KMAX = 16, 192      # LC2IS_RESIZE_TILE; the largest class count of lc2is_resize_argmax
+_GT_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def resize_sizes(N: int, sizes, gt=None) -> list[tuple[int, int]]:
+    """N (H, W) pairs as ints from a sequence or an [N, 2] tensor (None: the shapes of the N gt maps).  ValueError when they
+    disagree with N or with the gt maps' shapes."""
+    if gt is not None and len(gt) != N:
+        raise ValueError(f"lc2is_amd: {len(gt)} gt maps for {N} images")
+    if sizes is None:
+        if gt is None:
+            raise ValueError("lc2is_amd: sizes are needed when no gt maps are given")
+        sizes = [tuple(g.shape) for g in gt]
+    hw = [tuple(int(v) for v in s) for s in (sizes.tolist() if torch.is_tensor(sizes) else sizes)]
+    if len(hw) != N or any(len(s) != 2 or s[0] < 1 or s[1] < 1 for s in hw):
+        raise ValueError(f"lc2is_amd: sizes must be {N} (H, W) pairs of positive ints, got {hw}")
+    if gt is not None:
+        bad = [i for i, (g, s) in enumerate(zip(gt, hw)) if tuple(g.shape) != s]
+        if bad:
+            raise ValueError(f"lc2is_amd: gt maps {bad} do not have the shapes given by sizes "
+                             f"({[tuple(gt[i].shape) for i in bad]} vs {[hw[i] for i in bad]})")
+    return hw
+
+
+def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
+    """Per image, F.interpolate(scores[i:i+1], size=sizes[i], mode="bicubic", align_corners=False) and the argmax over the classes
+    (exact ties: the lowest index), fused: the [K, H, W] score map is never formed (lc2is_resize_argmax).
+    scores: the model's NCHW [N, K, h, w] logits on the GPU (any float dtype; the channels-last fp32 copy is made here), K <= 192.
+    sizes: N (H, W) pairs (sequence or [N, 2] tensor) or None (the gt maps' shapes).  gt: None or N label maps [H_i, W_i]
+    (uint8 / int32 / int64, host or device).
+    Returns (pred, counts): pred a list of uint8 [H_i, W_i] (views of one packed buffer) or None (want_pred=False);
+    counts int32 [N, 3, K] = {intersection, predicted, labelled} (labelled: 0 <= gt < K) when gt is given, else None."""
+    if scores.dim() != 4:
+        raise RuntimeError(f"lc2is_amd.resize_argmax: scores must be NCHW [N, K, h, w], got shape {tuple(scores.shape)}")
+    N, K, h, w = scores.shape
+    if not 1 <= K <= RESIZE_KMAX:
+        raise RuntimeError(f"lc2is_amd.resize_argmax: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    hw = resize_sizes(N, sizes, gt)
+    if gt is not None:
+        dts = {g.dtype for g in gt}
+        if not dts <= set(_GT_BYTES):
+            raise RuntimeError(f"lc2is_amd.resize_argmax: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
+    if not want_pred and gt is None:
+        raise ValueError("lc2is_amd.resize_argmax: nothing to compute (want_pred=False and no gt)")
+    if not scores.is_cuda:
+        raise RuntimeError("lc2is_amd.resize_argmax: scores must be a CUDA(HIP) tensor; there is no CPU path")
+    dev = scores.device
+    ld = (K + 3) // 4 * 4
+    lo = torch.empty((N, h, w, ld), dtype=torch.float32, device=dev)
+    lo[..., :K] = scores.permute(0, 2, 3, 1)
+    if ld > K:
+        lo[..., K:] = 0
+    T = RESIZE_TILE
+    tiles = [-(-H // T) * -(-W // T) for H, W in hw]
+    px = [H * W for H, W in hw]
+    first_px = [sum(px[:i]) for i in range(N)]
+    first_tile = [sum(tiles[:i]) for i in range(N)]
+    n_tiles, total_px = sum(tiles), sum(px)
+    desc = torch.tensor([[H, W, p0, t0] for (H, W), p0, t0 in zip(hw, first_px, first_tile)], dtype=torch.int64).to(dev)
+    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
+    counts = g = ws = None
+    nbytes = 0
+    if gt is not None:
+        dt = dts.pop() if len(dts) == 1 else torch.int64
+        flat = [x.reshape(-1) for x in gt]
+        if all(not x.is_cuda for x in flat):
+            g = torch.cat([x.to(dt) for x in flat]).to(dev)          # one host -> device copy
+        else:
+            g = torch.cat([x.to(dev, dt) for x in flat])
+        counts = torch.empty((N, 3, K), dtype=torch.int32, device=dev)
+        nbytes = _fn("lc2is_resize_argmax_workspace_bytes")(n_tiles, K)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)     # per-tile counts (per call: live until the second launch)
+    rc = _fn("lc2is_resize_argmax")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g),
+                                    _GT_BYTES[g.dtype] if g is not None else 0, _ptr(pred), _ptr(counts), _ptr(ws), nbytes,
+                                    _stream())
+    _lib.check(rc, f"resize_argmax N={N} K={K} h={h} w={w}")
+    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
+    return preds, counts
 
 
 # ---- Swin backbone ----------------------------------------------------------------------------------------------
