@@ -461,6 +461,57 @@ int lc2is_resize_argmax(const float* scores, int ld, int N, int h, int w, int K,
                         long total_px, const void* gt, int gt_bytes, uint8_t* pred, int* counts, void* workspace,
                         size_t workspace_bytes, lc2is_stream_t stream);
 
+/* ---- the device-held optimizer path (optim.hip) -----------------------------------------------------------------------
+ * The scalars of an optimizer step that change from call to call live in this block in DEVICE memory (48 bytes, 4-byte
+ * aligned, all zero before the first step), so a step needs no host value that differs between calls and can be replayed
+ * from a captured graph.  Only lc2is_optim_ctrl_update writes it: plain vector stores from one lane of its one block. */
+typedef struct {
+  int32_t calls;    /* iterations seen: indexes the lr table (the reference advances its scheduler every iteration)        */
+  int32_t applied;  /* updates actually applied: AdamW's t                                                                 */
+  int32_t skipped;  /* steps skipped for a non-finite gradient so far                                                      */
+  int32_t finite;   /* this step: 1 = every gradient element was finite (exponent bits, not the sum)                       */
+  float grad_norm;  /* this step: global L2 norm of grad_scale * g; +inf where the fp32 sum of squares overflowed          */
+  float clip_coef;  /* this step: min(1, max_norm / (grad_norm + 1e-6)); exactly 1 for max_norm = +inf                     */
+  float lr;         /* this step: lr_table[min(calls before this step, table_len - 1)]                                     */
+  float bc1, bc2;   /* this step: 1 - beta1^applied, 1 - beta2^applied (kept from the last applied step on a skip)         */
+  float grad_mul;   /* this step: grad_scale * clip_coef, what the _ctrl optimizers multiply g by                          */
+  int32_t apply;    /* this step: 1 = the _ctrl optimizers update; 0 = they return before touching memory                  */
+  int32_t reserved;
+} lc2is_optim_ctrl;
+
+/* Pass 1 over the flat gradient: per-block fp32 partial sums of squares and per-block "saw an inf or NaN" flags (from the
+ * exponent bits: exact, whatever the sum does).  n % 4 == 0, grads 16-byte aligned.  The grid is a function of n alone:
+ * lc2is_grad_sumsq_blocks(n) = min(4096, ceil(n / 1024)) blocks of 256 lanes, grid-stride, 16 bytes per lane, one fp32
+ * accumulator per lane in ascending index order, then a fixed 8-level tree per block.  workspace (4-byte aligned,
+ * >= lc2is_grad_sumsq_workspace_bytes(n) = 8 * blocks) receives fp32 partials[blocks] followed by uint32 flags[blocks].
+ * No atomics: bitwise reproducible.  Plain cached loads (the optimizer reads the buffer next).
+ * replaces: the gradient inspection of GradScaler.step (engine.py:89-91, `scaler.step(optimizer)` skips on inf / NaN) and the
+ *   norm of torch.nn.utils.clip_grad_norm_ (the reference does not clip). */
+int lc2is_grad_sumsq_blocks(size_t n);
+size_t lc2is_grad_sumsq_workspace_bytes(size_t n);
+int lc2is_grad_sumsq(const float* grads, size_t n, void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+
+/* One small launch between pass 1 and the optimizer.  Sums partials[0:nparts] in fp64 in index order (256 consecutive runs,
+ * run sums added in index order), ORs the flags, and writes into *ctrl:
+ *   grad_norm = grad_scale * sqrt(sum), clip_coef (max_norm > 0; +inf = no clipping), finite,
+ *   lr = lr_table[min(calls, table_len - 1)] (DEVICE fp32 table: entry i is the rate of call i + 1, the last one is held), calls += 1,
+ *   then if finite or !skip_nonfinite: apply = 1, applied += 1, bc1 / bc2 = 1 - beta^applied; else apply = 0, skipped += 1.
+ * replaces: lr_scheduler.step() at engine.py:103-104 (the host tabulates the scheduler), GradScaler's skip decision
+ *   (engine.py:89-91), clip_grad_norm_'s coefficient, and the host-side bias corrections of lc2is_adamw_step. */
+int lc2is_optim_ctrl_update(lc2is_optim_ctrl* ctrl, const float* partials, const unsigned int* flags, int nparts,
+                            const float* lr_table, int table_len, float grad_scale, float max_norm, int skip_nonfinite,
+                            float beta1, float beta2, lc2is_stream_t stream);
+
+/* lc2is_sgd_step / lc2is_adamw_step with lr, bc1, bc2 and the gradient multiplier (grad_scale * clip_coef) read from *ctrl;
+ * with ctrl->apply == 0 they return before touching params or any state buffer.  The same expressions: with clip_coef == 1 and
+ * a constant table lc2is_sgd_step_ctrl gives the bits of lc2is_sgd_step.  reverse != 0 walks the arena from its end.
+ * replaces: optimizer.step() at engine.py:101 as `scaler.step(optimizer)` runs it (engine.py:89-91). */
+int lc2is_sgd_step_ctrl(float* params, const float* grads, float* momentum_buf, size_t n, const lc2is_optim_ctrl* ctrl,
+                        float momentum, float weight_decay, int reverse, lc2is_stream_t stream);
+int lc2is_adamw_step_ctrl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
+                          const lc2is_optim_ctrl* ctrl, float beta1, float beta2, float eps, float weight_decay,
+                          int reverse, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,12 @@ _ARGTYPES = {
     "lc2is_rows_copy_f32": [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_sgd_step": [_P, _P, _P, _Z, _F, _F, _F, _F, _P],
     "lc2is_adamw_step": [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _I, _F, _P],
+    "lc2is_grad_sumsq_blocks": [_Z],
+    "lc2is_grad_sumsq_workspace_bytes": [_Z],
+    "lc2is_grad_sumsq": [_P, _Z, _P, _Z, _P],
+    "lc2is_optim_ctrl_update": [_P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P],
+    "lc2is_sgd_step_ctrl": [_P, _P, _P, _Z, _P, _F, _F, _I, _P],
+    "lc2is_adamw_step_ctrl": [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _I, _P],
     "lc2is_head_upsample_ce_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
     "lc2is_head_upsample_ce": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _Z, _P],
     "lc2is_ce_nchw_fwd": [_P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P],
@@ -701,6 +707,68 @@ def adamw_step(params, grads, m, v, lr, beta1, beta2, eps, weight_decay, step, g
     _chk(params, torch.float32, "params", 1); _chk(grads, torch.float32, "grads", 1)
     _lib.check(_fn("lc2is_adamw_step")(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), lr, beta1,
                                        beta2, eps, weight_decay, int(step), grad_scale, _stream()), "adamw_step")
+
+
+# ---- the device-held optimizer path: the lc2is_optim_ctrl block as an int32 [OPTIM_CTRL_WORDS] tensor (floats through .view) ----
+OPTIM_CTRL_WORDS = 12
+(CTRL_CALLS, CTRL_APPLIED, CTRL_SKIPPED, CTRL_FINITE, CTRL_GRAD_NORM, CTRL_CLIP_COEF, CTRL_LR, CTRL_BC1, CTRL_BC2, CTRL_GRAD_MUL,
+ CTRL_APPLY) = range(11)
+
+
+def _chk_ctrl(ctrl):
+    _chk(ctrl, torch.int32, "ctrl", 1)
+    if ctrl.numel() != OPTIM_CTRL_WORDS:
+        raise RuntimeError(f"lc2is_amd: ctrl must be an int32 [{OPTIM_CTRL_WORDS}] control block (lc2is_optim_ctrl)")
+
+
+def _chk_same_numel(name, params, *others):
+    for t in others:
+        if t is not None:
+            _chk(t, torch.float32, name + " buffer", 1)
+            if t.numel() != params.numel():
+                raise RuntimeError(f"lc2is_amd.{name}: every buffer must have params' {params.numel()} elements, got {t.numel()}")
+
+
+def grad_sumsq(grads):
+    """Pass 1 of the device-held optimizer path over a flat fp32 gradient (numel % 4 == 0): returns (partials fp32 [blocks],
+    flags int32 [blocks]) — per-block sums of squares and "saw an inf / NaN" flags — as views of the stream's workspace, valid
+    until the next grad_sumsq on this stream.  Fixed grid and summation order: bitwise reproducible."""
+    _chk(grads, torch.float32, "grads", 1)
+    n = grads.numel()
+    nb = _fn("lc2is_grad_sumsq_blocks")(n)
+    if nb <= 0:
+        raise RuntimeError(f"lc2is_amd.grad_sumsq: numel must be a positive multiple of 4, got {n}")
+    need = _fn("lc2is_grad_sumsq_workspace_bytes")(n)
+    ws = workspace(need, grads.device, "grad_sumsq")
+    _lib.check(_fn("lc2is_grad_sumsq")(_ptr(grads), n, _ptr(ws), ws.numel(), _stream()), "grad_sumsq")
+    return ws[:4 * nb].view(torch.float32), ws[4 * nb:8 * nb].view(torch.int32)
+
+
+def optim_ctrl_update(ctrl, partials, flags, lr_table, *, grad_scale=1.0, max_norm=float("inf"), skip_nonfinite=False,
+                      beta1=0.0, beta2=0.0):
+    """The one small launch between grad_sumsq and a _ctrl optimizer: global norm, clip coefficient, finite verdict, this call's
+    rate from the DEVICE fp32 ``lr_table``, counters and AdamW bias corrections, all written into ``ctrl`` on the device."""
+    _chk_ctrl(ctrl); _chk(partials, torch.float32, "partials", 1); _chk(flags, torch.int32, "flags", 1)
+    _chk(lr_table, torch.float32, "lr_table", 1)
+    if flags.numel() != partials.numel() or not partials.is_contiguous() or not flags.is_contiguous():
+        raise RuntimeError("lc2is_amd.optim_ctrl_update: partials and flags must be contiguous and of one length")
+    if lr_table.numel() < 1 or not lr_table.is_contiguous():
+        raise RuntimeError("lc2is_amd.optim_ctrl_update: lr_table must be a non-empty contiguous fp32 tensor")
+    _lib.check(_fn("lc2is_optim_ctrl_update")(_ptr(ctrl), _ptr(partials), _ptr(flags), partials.numel(), _ptr(lr_table),
+                                              lr_table.numel(), grad_scale, max_norm, int(bool(skip_nonfinite)), beta1, beta2,
+                                              _stream()), "optim_ctrl_update")
+
+
+def sgd_step_ctrl(params, grads, momentum_buf, ctrl, momentum=0.0, weight_decay=0.0, reverse=False):
+    _chk(params, torch.float32, "params", 1); _chk_same_numel("sgd_step_ctrl", params, grads, momentum_buf); _chk_ctrl(ctrl)
+    _lib.check(_fn("lc2is_sgd_step_ctrl")(_ptr(params), _ptr(grads), _ptr(momentum_buf), params.numel(), _ptr(ctrl), momentum,
+                                          weight_decay, int(bool(reverse)), _stream()), "sgd_step_ctrl")
+
+
+def adamw_step_ctrl(params, grads, m, v, ctrl, beta1, beta2, eps, weight_decay, reverse=False):
+    _chk(params, torch.float32, "params", 1); _chk_same_numel("adamw_step_ctrl", params, grads, m, v); _chk_ctrl(ctrl)
+    _lib.check(_fn("lc2is_adamw_step_ctrl")(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), _ptr(ctrl), beta1,
+                                            beta2, eps, weight_decay, int(bool(reverse)), _stream()), "adamw_step_ctrl")
 
 
 def _ce_options(class_weight, label_smoothing: float, C: int, dev):

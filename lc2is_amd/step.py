@@ -16,6 +16,15 @@ the remaining backward (``lc2is_amd.dp.GradReducer``).
 
 ``criterion``: an ``lc2is_amd.nn.CrossEntropyLoss`` (or ``torch.nn.CrossEntropyLoss``) whose ``ignore_index``, ``weight``,
 ``label_smoothing`` and ``reduction`` ('mean' / 'sum') configure the fused head; default: ``CrossEntropyLoss()``.
+
+The device-held path (opt-in: any of ``lr_schedule``, ``max_grad_norm``, ``skip_nonfinite``, ``device_state``) adds what the
+reference's loop has around ``optimizer.step()``:
+    scaler.step(optimizer)    skips on inf / NaN gradients        engine.py:89-91   -> ``skip_nonfinite``
+    lr_scheduler.step()       after every iteration               engine.py:103-104 -> ``lr_schedule`` (a device table)
+plus global gradient-norm clipping (``torch.nn.utils.clip_grad_norm_``; the reference does not clip).  The learning rate, the
+AdamW bias corrections, the clip coefficient and the skip verdict then live in a control block on the device (``ops.grad_sumsq``
+-> ``ops.optim_ctrl_update`` -> ``ops.sgd_step_ctrl`` / ``ops.adamw_step_ctrl``): no host sync, and a captured step advances its
+schedule — and AdamW's ``t`` — across replays.
 """
 from __future__ import annotations
 
@@ -28,11 +37,64 @@ from . import ops
 from .nn.base import HipModule, ParamArena
 
 
+_DEFAULT_LR = 1e-5
+
+
+def lr_table_from_torch(make_scheduler, base_lr: float, steps: int) -> torch.Tensor:
+    """Tabulate a real ``torch.optim.lr_scheduler`` for ``TrainStep(lr_schedule=...)``: ``make_scheduler(optimizer)`` is run on a
+    dummy CPU optimizer whose lr is ``base_lr``, and entry i is the rate in force at iteration i in ``Engine``'s order —
+    ``optimizer.step()`` first, ``lr_scheduler.step()`` after (engine.py:101-104).  Returns an fp32 [steps] CPU tensor."""
+    if steps < 1:
+        raise ValueError("lr_table_from_torch: steps must be >= 1")
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=base_lr)
+    sched = make_scheduler(opt)
+    rates = []
+    for i in range(steps):
+        rates.append(opt.param_groups[0]["lr"])
+        if i + 1 < steps:   # (the rate after the last iteration is never used; OneCycleLR refuses the step past its total)
+            opt.step()
+            sched.step()
+    return torch.tensor(rates, dtype=torch.float64).to(torch.float32)
+
+
+def _lr_table(lr_schedule, schedule_steps, lr) -> torch.Tensor:
+    """The host-side fp32 table of a ``lr_schedule`` argument (validated; nothing touches the device)."""
+    if lr_schedule is None:
+        if schedule_steps is not None:
+            raise ValueError("TrainStep: schedule_steps needs a callable lr_schedule")
+        return torch.tensor([lr], dtype=torch.float64).to(torch.float32)
+    if callable(lr_schedule):
+        if schedule_steps is None or int(schedule_steps) < 1:
+            raise ValueError("TrainStep: a callable lr_schedule needs schedule_steps=N >= 1 (the table is tabulated on the host)")
+        table = torch.tensor([float(lr_schedule(i)) for i in range(int(schedule_steps))], dtype=torch.float64)
+    else:
+        if schedule_steps is not None:
+            raise ValueError("TrainStep: schedule_steps goes with a callable lr_schedule, not with a table")
+        table = torch.as_tensor(lr_schedule).detach().to("cpu", torch.float64)
+        if table.dim() != 1:
+            raise ValueError("TrainStep: lr_schedule must be a 1-D sequence or tensor of rates")
+    if table.numel() == 0:
+        raise ValueError("TrainStep: lr_schedule is empty")
+    if not bool(torch.isfinite(table).all()) or bool((table < 0).any()):
+        raise ValueError("TrainStep: lr_schedule must hold finite, non-negative rates")
+    table = table.to(torch.float32)
+    if lr != _DEFAULT_LR and torch.tensor(lr, dtype=torch.float64).to(torch.float32) != table[0]:
+        raise ValueError(f"TrainStep: lr={lr} conflicts with lr_schedule, which starts at {float(table[0])}; give the rates "
+                         "through lr_schedule alone")
+    return table
+
+
 class TrainStep:
-    def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = 1e-5, momentum: float = 0.0,
+    def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
-                 ignore_index: int | None = None, criterion: nn.Module | None = None) -> None:
-        # (criterion checks first: nothing is built or allocated for a step that cannot run)
+                 ignore_index: int | None = None, criterion: nn.Module | None = None, lr_schedule=None,
+                 schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
+                 device_state: bool = False) -> None:
+        # (argument checks first: nothing is built or allocated for a step that cannot run)
+        device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"TrainStep: max_grad_norm must be > 0 (or None / inf for no clipping), got {max_grad_norm}")
+        table = _lr_table(lr_schedule, schedule_steps, lr) if (device_path or schedule_steps is not None) else None
         self._loss_opts = False
         if criterion is not None:
             from .nn.loss import AuxiliaryLoss, CrossEntropyLoss
@@ -63,6 +125,43 @@ class TrainStep:
         if reducer is not None:
             reducer.attach(model, self.arena)
         self._dev = dev
+        # the device-held path: control block (lc2is_optim_ctrl) + lr table on the device; None = today's path, untouched
+        self._ctrl = None
+        if device_path:
+            self._ctrl = torch.zeros(ops.OPTIM_CTRL_WORDS, dtype=torch.int32, device=dev)
+            self._ctrl_f = self._ctrl.view(torch.float32)
+            self.lr_table = table.to(dev)
+            self.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
+            self.skip_nonfinite = bool(skip_nonfinite)
+            self.reverse_walk = False   # the _ctrl optimizer walks the arena from its end (same bits): tools/optim_ctrl_cost.py's A/B
+
+    # -- views of the control block: device tensors, no sync unless the caller asks (.item()) --------------------------------
+    def _ctrl_view(self, word: int, as_float: bool) -> torch.Tensor:
+        if self._ctrl is None:
+            raise RuntimeError("TrainStep: this accessor needs the device-held path (lr_schedule / max_grad_norm / "
+                               "skip_nonfinite / device_state=True)")
+        return (self._ctrl_f if as_float else self._ctrl)[word]
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """Global L2 norm of the last step's gradient (after the 1/world scaling, before clipping)."""
+        return self._ctrl_view(ops.CTRL_GRAD_NORM, True)
+
+    @property
+    def last_clip_coef(self) -> torch.Tensor:
+        return self._ctrl_view(ops.CTRL_CLIP_COEF, True)
+
+    @property
+    def last_lr(self) -> torch.Tensor:
+        return self._ctrl_view(ops.CTRL_LR, True)
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        return self._ctrl_view(ops.CTRL_SKIPPED, False)
+
+    @property
+    def applied_steps(self) -> torch.Tensor:
+        return self._ctrl_view(ops.CTRL_APPLIED, False)
 
     def step(self, inputs: dict, labels: torch.Tensor) -> torch.Tensor:
         arena = self.arena
@@ -86,6 +185,25 @@ class TrainStep:
         # then, like torch.optim (which skips parameters whose grad is None), only the live segments are updated so that
         # frozen / unreached parameters stay bit-identical.
         segs = [(0, arena.numel)] if (self.weight_decay == 0.0 or live == [(0, arena.numel)]) else live
+        if self._ctrl is not None:
+            # Pass 1 runs over the WHOLE arena: finalize_grads has zeroed the segments that got no gradient and the alignment
+            # padding is never written (zero since allocation), so the sum is clip_grad_norm_'s over the parameters that have
+            # a gradient.  Under a reducer every rank runs these deterministic kernels on the same all-reduced bytes with the
+            # same 1/world: all ranks reach the same clip and skip decision without another collective.
+            ctrl = self._ctrl
+            b1, b2 = self.betas if self.kind == "adamw" else (0.0, 0.0)
+            partials, flags = ops.grad_sumsq(arena.grad)
+            ops.optim_ctrl_update(ctrl, partials, flags, self.lr_table, grad_scale=gscale, max_norm=self.max_grad_norm,
+                                  skip_nonfinite=self.skip_nonfinite, beta1=b1, beta2=b2)
+            for lo, hi in segs:
+                sl = slice(lo, hi)
+                if self.kind == "sgd":
+                    ops.sgd_step_ctrl(arena.flat[sl], arena.grad[sl], None if self.mom is None else self.mom[sl], ctrl,
+                                      self.momentum, self.weight_decay, reverse=self.reverse_walk)
+                else:
+                    ops.adamw_step_ctrl(arena.flat[sl], arena.grad[sl], self.m[sl], self.v[sl], ctrl, self.betas[0],
+                                        self.betas[1], self.eps, self.weight_decay, reverse=self.reverse_walk)
+            segs = []
         for lo, hi in segs:
             sl = slice(lo, hi)
             if self.kind == "sgd":
@@ -105,10 +223,12 @@ class TrainStep:
         static buffers and launches the graph (one host call per step instead of ~800 kernel launches).  ``warmup`` REAL
         steps on ``inputs`` run before the capture (lazy initialisation must not happen inside it); the captured step itself
         is only recorded.
+        On the device-held path the learning-rate table index, AdamW's t and the skip counters are device state that the
+        captured kernels advance: a schedule moves across replays and AdamW can be captured.
         Single-process only (the RCCL reduction is not captured)."""
         if self.reducer is not None:
             raise RuntimeError("TrainStep.capture: graph capture is only wired for single-GPU steps")
-        if self.kind == "adamw":   # (checked BEFORE anything runs or is captured)
+        if self.kind == "adamw" and self._ctrl is None:   # (checked BEFORE anything runs or is captured)
             raise RuntimeError("TrainStep.capture: AdamW bias correction is step-dependent; capture supports SGD")
         if hasattr(self.model, "overlap_text") and os.environ.get("LC2IS_GRAPH_OVERLAP", "1") == "0":
             self.model.overlap_text = False   # LC2IS_GRAPH_OVERLAP=0: one captured stream (default: the text-tower fork / join is captured too)
