@@ -512,6 +512,29 @@ int lc2is_adamw_step_ctrl(float* params, const float* grads, float* exp_avg, flo
                           const lc2is_optim_ctrl* ctrl, float beta1, float beta2, float eps, float weight_decay,
                           int reverse, lc2is_stream_t stream);
 
+/* Parameter groups: the _ctrl optimizers in ONE launch over the whole arena with a learning-rate factor and a weight decay per
+ * group.  The arena is cut into granules of LC2IS_GROUP_GRANULE = 64 elements (every parameter of ParamArena starts on one);
+ * granule_group (DEVICE, n / 64 bytes) names the group of each granule, groups (DEVICE, ngroups entries) holds the constants.
+ * Per element: lr = ctrl->lr * lr_scale (one fp32 multiplication), weight_decay the group's, everything else - grad_mul, bc1,
+ * bc2, apply, reverse - as lc2is_sgd_step_ctrl / lc2is_adamw_step_ctrl, expression for expression: a range updated here has the
+ * bits the _ctrl entry gives on that range with ctrl->lr set to the product.  A granule whose id is >= ngroups - 255 is the
+ * reserved spelling - is SKIPPED: nothing of it is loaded or stored (torch.optim leaving a parameter without a gradient alone).
+ * n % 64 == 0, 1 <= ngroups <= LC2IS_MAX_PARAM_GROUPS = 255, buffers 16-byte aligned.  No atomics; independent of the grid.
+ * replaces: optimizer.step() at engine.py:101 for an optimizer built with torch.optim param_groups. */
+#define LC2IS_GROUP_GRANULE 64
+#define LC2IS_MAX_PARAM_GROUPS 255
+#define LC2IS_GROUP_SKIP 255
+typedef struct {
+  float lr_scale;     /* multiplies ctrl->lr; 0 = the group's parameters keep their bits (moments / momentum still advance) */
+  float weight_decay; /* in place of the weight_decay argument of the _ctrl entries                                        */
+} lc2is_param_group;
+int lc2is_sgd_step_groups(float* params, const float* grads, float* momentum_buf, size_t n, const lc2is_optim_ctrl* ctrl,
+                          const uint8_t* granule_group, const lc2is_param_group* groups, int ngroups, float momentum,
+                          int reverse, lc2is_stream_t stream);
+int lc2is_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
+                            const lc2is_optim_ctrl* ctrl, const uint8_t* granule_group, const lc2is_param_group* groups,
+                            int ngroups, float beta1, float beta2, float eps, int reverse, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,84 @@ __global__ __launch_bounds__(256) void adamw_ctrl_kernel(float* p, const float* 
   }
 }
 
+// Parameter groups: sgd_ctrl_kernel / adamw_ctrl_kernel, expression for expression, with lr = ctrl->lr * group.lr_scale (one fp32
+// multiplication) and wd = group.weight_decay, the group being that of the 64-element granule the lane's float4 lies in
+// (gmap: one byte per granule; float4 i lies in granule i >> 4, so 16 consecutive lanes share a byte).  The group table
+// (<= 255 entries of 8 bytes) is staged in LDS once per block.  An id that names no table entry - 255 is the reserved one - makes
+// the 16 lanes of the granule skip it: no load, no store.
+__device__ __forceinline__ void stage_groups(float2* tab, const lc2is_param_group* __restrict__ groups, int ngroups) {
+  if ((int)threadIdx.x < ngroups) {
+    const lc2is_param_group e = groups[threadIdx.x];
+    tab[threadIdx.x] = make_float2(e.lr_scale, e.weight_decay);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void sgd_groups_kernel(float* p, const float* __restrict__ g, float* mom, size_t n4,
+                                                          const lc2is_optim_ctrl* __restrict__ ctrl,
+                                                          const uint8_t* __restrict__ gmap,
+                                                          const lc2is_param_group* __restrict__ groups, int ngroups,
+                                                          float momentum, int reverse) {
+  __shared__ float2 tab[256];
+  if (!ctrl->apply) return;   // (uniform over the grid: no lane is left waiting at the barrier below)
+  stage_groups(tab, groups, ngroups);
+  const float lr0 = ctrl->lr, gscale = ctrl->grad_mul;
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (size_t)gridDim.x * 256) {
+    const size_t i = reverse ? n4 - 1 - j : j;
+    const unsigned gid = gmap[i >> 4];
+    if (gid >= (unsigned)ngroups) continue;
+    const float2 grp = tab[gid];
+    const float lr = lr0 * grp.x, wd = grp.y;
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float d[4] = {gv.x * gscale + wd * pv.x, gv.y * gscale + wd * pv.y, gv.z * gscale + wd * pv.z,
+                  gv.w * gscale + wd * pv.w};
+    if (mom) {
+      float4 mv = reinterpret_cast<float4*>(mom)[i];
+      mv.x = momentum * mv.x + d[0]; mv.y = momentum * mv.y + d[1];
+      mv.z = momentum * mv.z + d[2]; mv.w = momentum * mv.w + d[3];
+      reinterpret_cast<float4*>(mom)[i] = mv;
+      d[0] = mv.x; d[1] = mv.y; d[2] = mv.z; d[3] = mv.w;
+    }
+    pv.x -= lr * d[0]; pv.y -= lr * d[1]; pv.z -= lr * d[2]; pv.w -= lr * d[3];
+    reinterpret_cast<float4*>(p)[i] = pv;
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float* __restrict__ g, float* m, float* v, size_t n4,
+                                                            const lc2is_optim_ctrl* __restrict__ ctrl,
+                                                            const uint8_t* __restrict__ gmap,
+                                                            const lc2is_param_group* __restrict__ groups, int ngroups,
+                                                            float b1, float b2, float eps, int reverse) {
+  __shared__ float2 tab[256];
+  if (!ctrl->apply) return;
+  stage_groups(tab, groups, ngroups);
+  const float lr0 = ctrl->lr, gscale = ctrl->grad_mul, bc1 = ctrl->bc1, bc2 = ctrl->bc2;
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (size_t)gridDim.x * 256) {
+    const size_t i = reverse ? n4 - 1 - j : j;
+    const unsigned gid = gmap[i >> 4];
+    if (gid >= (unsigned)ngroups) continue;
+    const float2 grp = tab[gid];
+    const float lr = lr0 * grp.x, wd = grp.y;
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gg = gp[k] * gscale;
+      pp[k] *= (1.f - lr * wd);
+      mp[k] = b1 * mp[k] + (1.f - b1) * gg;
+      vp[k] = b2 * vp[k] + (1.f - b2) * gg * gg;
+      const float denom = sqrtf(vp[k]) / sqrtf(bc2) + eps;
+      pp[k] -= (lr / bc1) * (mp[k] / denom);
+    }
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+
 inline int ew_grid(size_t work_items) {
   size_t g = (work_items + 255) / 256;
   if (g > 4096) g = 4096;
@@ -228,5 +306,35 @@ extern "C" int lc2is_adamw_step_ctrl(float* params, const float* grads, float* e
   if (n == 0 || n % 4) return LC2IS_ERR_SHAPE;
   hipLaunchKernelGGL(adamw_ctrl_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq,
                      n / 4, ctrl, beta1, beta2, eps, weight_decay, reverse);
+  return lc2is_check_launch();
+}
+
+// The granule map holds n / 64 bytes, so n must be whole granules.  16-byte alignment (one float4 per lane) is what is enforced;
+// the arena gives 256, which puts every granule on a 256-byte line of its own.
+extern "C" int lc2is_sgd_step_groups(float* params, const float* grads, float* momentum_buf, size_t n,
+                                     const lc2is_optim_ctrl* ctrl, const uint8_t* granule_group,
+                                     const lc2is_param_group* groups, int ngroups, float momentum, int reverse,
+                                     lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!params || !grads || !ctrl || !granule_group || !groups) return LC2IS_ERR_NULL;
+  if (n == 0 || n % LC2IS_GROUP_GRANULE || ngroups < 1 || ngroups > LC2IS_MAX_PARAM_GROUPS || !aligned16(params) ||
+      !aligned16(grads) || !aligned16(momentum_buf))
+    return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(sgd_groups_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, params, grads, momentum_buf, n / 4, ctrl,
+                     granule_group, groups, ngroups, momentum, reverse);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
+                                       const lc2is_optim_ctrl* ctrl, const uint8_t* granule_group,
+                                       const lc2is_param_group* groups, int ngroups, float beta1, float beta2, float eps,
+                                       int reverse, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !ctrl || !granule_group || !groups) return LC2IS_ERR_NULL;
+  if (n == 0 || n % LC2IS_GROUP_GRANULE || ngroups < 1 || ngroups > LC2IS_MAX_PARAM_GROUPS || !aligned16(params) ||
+      !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq))
+    return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, n / 4,
+                     ctrl, granule_group, groups, ngroups, beta1, beta2, eps, reverse);
   return lc2is_check_launch();
 }

@@ -297,6 +297,33 @@ def vec_grad(p: nn.Parameter | None):
     return grad_buf(p)
 
 
+GROUP_SKIP = 255   # granule id of a parameter the grouped optimizers leave alone (ops.GROUP_SKIP)
+
+
+def granule_group_map(offsets, sizes, group_ids, dead=(), align: int = 64, ngroups: int | None = None) -> torch.Tensor:
+    """The host side of ``ops.sgd_step_groups`` / ``ops.adamw_step_groups``: one uint8 per ``align``-element granule of an arena laid
+    out as ``ParamArena`` lays it out (parameter k starts at ``offsets[k]``, a multiple of ``align``, and owns whole granules, its
+    alignment padding included).  Every granule of parameter k carries ``group_ids[k]``; parameters whose index is in ``dead``
+    (no gradient this step) carry GROUP_SKIP.  Ids must name a table entry (0 <= id < ngroups <= 255): the kernels would skip a
+    granule with any other id silently.  A pure function of its arguments; returns a CPU tensor of ``total / align`` bytes."""
+    if not (len(offsets) == len(sizes) == len(group_ids)) or not len(offsets):
+        raise ValueError("granule_group_map: offsets, sizes and group_ids must be non-empty and of one length")
+    top = GROUP_SKIP if ngroups is None else int(ngroups)
+    if not 1 <= top <= GROUP_SKIP:
+        raise ValueError(f"granule_group_map: ngroups must be 1..{GROUP_SKIP}, got {ngroups}")
+    dead = set(dead)
+    ids, counts, at = [], [], 0
+    for k, (o, n, g) in enumerate(zip(offsets, sizes, group_ids)):
+        if o != at or o % align or n < 1:
+            raise ValueError(f"granule_group_map: parameter {k} at offset {o} (size {n}) does not continue an aligned layout at {at}")
+        if not 0 <= int(g) < top:
+            raise ValueError(f"granule_group_map: parameter {k} has group id {g}; ids are 0..{top - 1}")
+        ids.append(GROUP_SKIP if k in dead else int(g))
+        counts.append((n + align - 1) // align)
+        at = o + counts[-1] * align
+    return torch.repeat_interleave(torch.tensor(ids, dtype=torch.uint8), torch.tensor(counts, dtype=torch.int64))
+
+
 class ParamArena:
     """Flat fp32 storage for all parameters (and their gradients) of a model: one fused optimizer launch,
     one contiguous all-reduce payload, 256-byte aligned views.  Build AFTER moving the model to the GPU."""
@@ -332,6 +359,27 @@ class ParamArena:
                 p.grad = None
                 self.ranges[id(p)] = (o, o + n)
         self.numel = total
+        self.dead = ()          # indices (into self.params) of the parameters finalize_grads found without a gradient
+        self._group_ids = None
+        self._group_maps = {}   # dead set -> device map; the few sets a run sees stay resident (nothing in flight is ever freed)
+
+    def set_groups(self, group_ids, ngroups: int):
+        """group_ids[k]: the parameter group of self.params[k] (see granule_group_map)."""
+        granule_group_map(self.offsets, [p.numel() for p in self.params], group_ids, ngroups=ngroups)   # validates
+        self._group_ids, self._ngroups, self._group_maps = [int(g) for g in group_ids], int(ngroups), {}
+
+    def group_map(self) -> torch.Tensor:
+        """The device granule map for the dead set of the last finalize_grads.  Built and uploaded once per distinct set; under
+        stream capture a set that no warm-up step has seen is an error (the upload cannot be part of a captured step)."""
+        m = self._group_maps.get(self.dead)
+        if m is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ParamArena.group_map: the set of parameters without a gradient seen while capturing differs "
+                                   "from every warm-up step's; the granule map cannot be uploaded inside a captured step")
+            host = granule_group_map(self.offsets, [p.numel() for p in self.params], self._group_ids, self.dead, self.ALIGN,
+                                     self._ngroups)
+            m = self._group_maps[self.dead] = host.to(self.flat.device)
+        return m
 
     def attach_grads(self):
         for p in self.params:
@@ -352,10 +400,11 @@ class ParamArena:
         gradient so the flat buffer is fully defined for the all-reduce.  Returns the LIVE segments [(lo, hi)] of the
         arena (maximal runs of parameters that did receive a gradient, alignment padding included): torch.optim skips
         parameters whose grad is None, so an optimizer with weight decay must only touch these."""
-        live, run = [], None
-        for p, o in zip(self.params, self.offsets):
+        live, run, dead = [], None, []
+        for k, (p, o) in enumerate(zip(self.params, self.offsets)):
             end = o + (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
             if p.grad is None:
+                dead.append(k)
                 p._lc2is_grad.zero_()
                 p.grad = p._lc2is_grad
                 if run is not None:
@@ -365,6 +414,7 @@ class ParamArena:
                 run = (run[0], end) if run is not None else (o, end)
         if run is not None:
             live.append(run)
+        self.dead = tuple(dead)
         return live
 
     def module_range(self, module: nn.Module):

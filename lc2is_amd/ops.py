@@ -63,6 +63,8 @@ _ARGTYPES = {
     "lc2is_optim_ctrl_update": [_P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P],
     "lc2is_sgd_step_ctrl": [_P, _P, _P, _Z, _P, _F, _F, _I, _P],
     "lc2is_adamw_step_ctrl": [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _I, _P],
+    "lc2is_sgd_step_groups": [_P, _P, _P, _Z, _P, _P, _P, _I, _F, _I, _P],
+    "lc2is_adamw_step_groups": [_P, _P, _P, _P, _Z, _P, _P, _P, _I, _F, _F, _F, _I, _P],
     "lc2is_head_upsample_ce_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
     "lc2is_head_upsample_ce": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _Z, _P],
     "lc2is_ce_nchw_fwd": [_P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P],
@@ -769,6 +771,45 @@ def adamw_step_ctrl(params, grads, m, v, ctrl, beta1, beta2, eps, weight_decay, 
     _chk(params, torch.float32, "params", 1); _chk_same_numel("adamw_step_ctrl", params, grads, m, v); _chk_ctrl(ctrl)
     _lib.check(_fn("lc2is_adamw_step_ctrl")(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), _ptr(ctrl), beta1,
                                             beta2, eps, weight_decay, int(bool(reverse)), _stream()), "adamw_step_ctrl")
+
+
+# ---- parameter groups: one launch over the arena, a learning-rate factor and a weight decay per 64-element granule ----
+GROUP_GRANULE, MAX_PARAM_GROUPS, GROUP_SKIP = 64, 255, 255
+
+
+def _chk_groups(name, params, granule_group, groups):
+    _chk(granule_group, torch.uint8, "granule_group", 1); _chk(groups, torch.float32, "groups", 2)
+    if granule_group is None or groups is None:
+        raise RuntimeError(f"lc2is_amd.{name}: granule_group and groups are required")
+    n = params.numel()
+    if n == 0 or n % GROUP_GRANULE:
+        raise RuntimeError(f"lc2is_amd.{name}: numel must be a positive multiple of {GROUP_GRANULE}, got {n}")
+    if not params.is_contiguous() or not granule_group.is_contiguous() or granule_group.numel() != n // GROUP_GRANULE:
+        raise RuntimeError(f"lc2is_amd.{name}: granule_group must be a contiguous uint8 [{n // GROUP_GRANULE}] map (one id per "
+                           f"{GROUP_GRANULE} elements), got {tuple(granule_group.shape)}")
+    if not groups.is_contiguous() or groups.shape[1] != 2 or not 1 <= groups.shape[0] <= MAX_PARAM_GROUPS:
+        raise RuntimeError(f"lc2is_amd.{name}: groups must be a contiguous fp32 [ngroups, 2] table of (lr_scale, weight_decay), "
+                           f"1 <= ngroups <= {MAX_PARAM_GROUPS}, got {tuple(groups.shape)}")
+
+
+def sgd_step_groups(params, grads, momentum_buf, ctrl, granule_group, groups, momentum=0.0, reverse=False):
+    """sgd_step_ctrl in one launch over the whole arena with per-group constants: ``granule_group`` (uint8 [numel / 64]) names the
+    group of each 64-element granule (GROUP_SKIP = 255: the granule is neither read nor written), ``groups`` (fp32 [ngroups, 2])
+    holds (lr_scale, weight_decay); the rate of a group is ctrl's lr * lr_scale."""
+    _chk(params, torch.float32, "params", 1); _chk_same_numel("sgd_step_groups", params, grads, momentum_buf); _chk_ctrl(ctrl)
+    _chk_groups("sgd_step_groups", params, granule_group, groups)
+    _lib.check(_fn("lc2is_sgd_step_groups")(_ptr(params), _ptr(grads), _ptr(momentum_buf), params.numel(), _ptr(ctrl),
+                                            _ptr(granule_group), _ptr(groups), groups.shape[0], momentum, int(bool(reverse)),
+                                            _stream()), "sgd_step_groups")
+
+
+def adamw_step_groups(params, grads, m, v, ctrl, granule_group, groups, beta1, beta2, eps, reverse=False):
+    """adamw_step_ctrl in one launch over the whole arena with per-group (lr_scale, weight_decay): see sgd_step_groups."""
+    _chk(params, torch.float32, "params", 1); _chk_same_numel("adamw_step_groups", params, grads, m, v); _chk_ctrl(ctrl)
+    _chk_groups("adamw_step_groups", params, granule_group, groups)
+    _lib.check(_fn("lc2is_adamw_step_groups")(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), _ptr(ctrl),
+                                              _ptr(granule_group), _ptr(groups), groups.shape[0], beta1, beta2, eps,
+                                              int(bool(reverse)), _stream()), "adamw_step_groups")
 
 
 def _ce_options(class_weight, label_smoothing: float, C: int, dev):

@@ -28,7 +28,9 @@ schedule — and AdamW's ``t`` — across replays.
 """
 from __future__ import annotations
 
+import math
 import os
+import re
 
 import torch
 from torch import nn
@@ -43,7 +45,10 @@ _DEFAULT_LR = 1e-5
 def lr_table_from_torch(make_scheduler, base_lr: float, steps: int) -> torch.Tensor:
     """Tabulate a real ``torch.optim.lr_scheduler`` for ``TrainStep(lr_schedule=...)``: ``make_scheduler(optimizer)`` is run on a
     dummy CPU optimizer whose lr is ``base_lr``, and entry i is the rate in force at iteration i in ``Engine``'s order —
-    ``optimizer.step()`` first, ``lr_scheduler.step()`` after (engine.py:101-104).  Returns an fp32 [steps] CPU tensor."""
+    ``optimizer.step()`` first, ``lr_scheduler.step()`` after (engine.py:101-104).  Returns an fp32 [steps] CPU tensor.
+    Only ``param_groups[0]`` is tabulated: with ``TrainStep(param_groups=...)`` every group follows this one table times its constant
+    ``lr_scale``, so per-group schedules that are not a common factor of one another (a non-zero ``eta_min``, per-group warm-ups)
+    are not representable."""
     if steps < 1:
         raise ValueError("lr_table_from_torch: steps must be >= 1")
     opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=base_lr)
@@ -84,14 +89,139 @@ def _lr_table(lr_schedule, schedule_steps, lr) -> torch.Tensor:
     return table
 
 
+_GROUP_KEYS = {"params", "lr_scale", "weight_decay"}
+_MAX_GROUPS = ops.MAX_PARAM_GROUPS
+
+
+def _resolve_param_groups(model: nn.Module, param_groups, weight_decay: float):
+    """Validate a ``param_groups`` argument against ``model`` (host only; nothing is built).  Returns (groups, group_of) where
+    groups is a list of dict(names, numel, lr_scale, weight_decay) — an implicit last group holding the parameters named in none —
+    and group_of maps id(parameter) to its group index."""
+    named, seen = [], set()
+    for name, prm in model.named_parameters():
+        if id(prm) not in seen:
+            seen.add(id(prm))
+            named.append((name, prm))
+    by_name, name_of = dict(named), {id(prm): name for name, prm in named}
+    if isinstance(param_groups, dict) or not hasattr(param_groups, "__iter__"):
+        raise ValueError("TrainStep: param_groups must be a sequence of dicts")
+    param_groups = list(param_groups)
+    if not param_groups:
+        raise ValueError("TrainStep: param_groups is empty (use None for no groups)")
+    if len(param_groups) > _MAX_GROUPS:
+        raise ValueError(f"TrainStep: {len(param_groups)} param_groups; more than {_MAX_GROUPS} groups are not supported")
+    groups, group_of = [], {}
+    for gi, g in enumerate(param_groups):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError(f"TrainStep: param_groups[{gi}] must be a dict with a 'params' entry")
+        unknown = set(g) - _GROUP_KEYS
+        if unknown:
+            raise ValueError(f"TrainStep: param_groups[{gi}] has unknown keys {sorted(unknown)} (known: {sorted(_GROUP_KEYS)})")
+        lr_scale, wd = float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", weight_decay))
+        for key, val in (("lr_scale", lr_scale), ("weight_decay", wd)):
+            if not math.isfinite(val) or val < 0.0:
+                raise ValueError(f"TrainStep: param_groups[{gi}] {key} must be finite and >= 0, got {val}")
+        members = g["params"]
+        members = [members] if isinstance(members, (str, torch.Tensor)) else list(members)
+        if not members:
+            raise ValueError(f"TrainStep: param_groups[{gi}] has empty params")
+        names = []
+        for m in members:
+            if isinstance(m, str):
+                if m not in by_name:
+                    raise ValueError(f"TrainStep: param_groups[{gi}]: '{m}' is not a parameter of the model")
+                prm = by_name[m]
+            elif isinstance(m, torch.Tensor) and id(m) in name_of:
+                prm = m
+            else:
+                what = f"a tensor of shape {tuple(m.shape)}" if isinstance(m, torch.Tensor) else repr(m)
+                raise ValueError(f"TrainStep: param_groups[{gi}]: {what} is not a parameter of the model")
+            if id(prm) in group_of:
+                raise ValueError(f"TrainStep: parameter '{name_of[id(prm)]}' is in two groups (param_groups[{group_of[id(prm)]}] "
+                                 f"and param_groups[{gi}])" if group_of[id(prm)] != gi else
+                                 f"TrainStep: parameter '{name_of[id(prm)]}' is listed twice in param_groups[{gi}]")
+            group_of[id(prm)] = gi
+            names.append(name_of[id(prm)])
+        groups.append(dict(names=tuple(names), numel=sum(by_name[n].numel() for n in names), lr_scale=lr_scale, weight_decay=wd))
+    rest = [name for name, prm in named if id(prm) not in group_of]
+    if rest:
+        if len(groups) + 1 > _MAX_GROUPS:
+            raise ValueError(f"TrainStep: {len(groups)} param_groups plus the implicit group of the {len(rest)} parameters named in "
+                             f"none; more than {_MAX_GROUPS} groups are not supported")
+        for n in rest:
+            group_of[id(by_name[n])] = len(groups)
+        groups.append(dict(names=tuple(rest), numel=sum(by_name[n].numel() for n in rest), lr_scale=1.0,
+                           weight_decay=float(weight_decay)))
+    return groups, group_of
+
+
+_TOWER_LAYER = re.compile(r"^(.*)\.encoder\.layers\.(\d+)\.")
+
+
+def make_param_groups(model: nn.Module, *, weight_decay: float, no_decay=True, lr_scales=None, layer_decay=None) -> list:
+    """The usual fine-tuning recipes as a ``TrainStep(param_groups=...)`` list, from parameter NAMES alone (any nn.Module, no GPU).
+      no_decay=True   every 1-D parameter (biases, LayerNorm gains / biases, class_embedding) and every parameter whose name ends
+                      in position_embedding.weight or token_embedding.weight gets weight_decay 0; a tuple adds name substrings
+                      (("class_prototypes",)); False decays everything
+      lr_scales       {name prefix: factor}; the longest matching prefix wins, default 1
+      layer_decay=d   in a tower whose names match <prefix>.encoder.layers.<i>. with L layers: layer i gets d ** (L - i), what
+                      precedes the layers (<prefix>.embeddings.*, <prefix>.pre_layrnorm.*) d ** (L + 1), the rest of the tower 1,
+                      multiplied into the prefix factor
+    Parameters with the same (lr_scale, weight_decay) share a group."""
+    extra = tuple(no_decay) if isinstance(no_decay, (tuple, list)) else ()
+    lr_scales = dict(lr_scales or {})
+    named, seen = [], set()
+    for name, prm in model.named_parameters():
+        if id(prm) not in seen:
+            seen.add(id(prm))
+            named.append((name, prm))
+    depth = {}
+    for name, _ in named:
+        m = _TOWER_LAYER.match(name)
+        if m:
+            depth[m.group(1)] = max(depth.get(m.group(1), 0), int(m.group(2)) + 1)
+    merged = {}
+    for name, prm in named:
+        wd = float(weight_decay)
+        if no_decay and (prm.dim() == 1 or name.endswith(("position_embedding.weight", "token_embedding.weight"))
+                         or any(sub in name for sub in extra)):
+            wd = 0.0
+        scale, best = 1.0, -1
+        for prefix, f in lr_scales.items():
+            if name.startswith(prefix) and len(prefix) > best:
+                scale, best = float(f), len(prefix)
+        if layer_decay is not None:
+            m = _TOWER_LAYER.match(name)
+            if m:
+                scale *= float(layer_decay) ** (depth[m.group(1)] - int(m.group(2)))
+            else:
+                for tower, L in depth.items():
+                    if name.startswith((tower + ".embeddings.", tower + ".pre_layrnorm.")):
+                        scale *= float(layer_decay) ** (L + 1)
+        merged.setdefault((scale, wd), []).append(name)
+    return [dict(params=names, lr_scale=scale, weight_decay=wd) for (scale, wd), names in merged.items()]
+
+
 class TrainStep:
+    """``param_groups`` (keyword-only; selects the device-held path): a sequence of dicts ``{"params": parameters or their names in
+    model.named_parameters(), "lr_scale": 1.0, "weight_decay": <TrainStep's weight_decay>}``.  Group g trains at
+    ``fp32(lr_table[i]) * fp32(lr_scale_g)`` with its own decay, in ONE optimizer launch per step whatever the groups are; clipping
+    stays global and ``skip_nonfinite`` all-or-nothing.  Parameters named in no group form an implicit last group (lr_scale 1,
+    TrainStep's weight_decay) — unlike ``torch.optim``, which would not train them: a tower that must not move is
+    ``requires_grad=False``, or a group with ``lr_scale`` 0 (which, like torch at lr = 0, still advances AdamW's moments and SGD's
+    momentum buffer and leaves the parameter bits unchanged).  ``make_param_groups`` writes the usual recipes."""
+
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
                  ignore_index: int | None = None, criterion: nn.Module | None = None, lr_schedule=None,
                  schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
-                 device_state: bool = False) -> None:
+                 device_state: bool = False, param_groups=None) -> None:
         # (argument checks first: nothing is built or allocated for a step that cannot run)
-        device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None)
+        device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None
+                           or param_groups is not None)
+        groups = None
+        if param_groups is not None:
+            groups, group_of = _resolve_param_groups(model, param_groups, weight_decay)
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"TrainStep: max_grad_norm must be > 0 (or None / inf for no clipping), got {max_grad_norm}")
         table = _lr_table(lr_schedule, schedule_steps, lr) if (device_path or schedule_steps is not None) else None
@@ -134,6 +264,11 @@ class TrainStep:
             self.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
             self.skip_nonfinite = bool(skip_nonfinite)
             self.reverse_walk = False   # the _ctrl optimizer walks the arena from its end (same bits): tools/optim_ctrl_cost.py's A/B
+        # parameter groups: the constants in a small device table, the granule map in the arena (rebuilt when the dead set changes)
+        self._groups = groups
+        if groups is not None:
+            self.arena.set_groups([group_of[id(p)] for p in self.arena.params], len(groups))
+            self._group_table = torch.tensor([[g["lr_scale"], g["weight_decay"]] for g in groups], dtype=torch.float32).to(dev)
 
     # -- views of the control block: device tensors, no sync unless the caller asks (.item()) --------------------------------
     def _ctrl_view(self, word: int, as_float: bool) -> torch.Tensor:
@@ -162,6 +297,11 @@ class TrainStep:
     @property
     def applied_steps(self) -> torch.Tensor:
         return self._ctrl_view(ops.CTRL_APPLIED, False)
+
+    @property
+    def param_groups(self):
+        """Per group: parameter names, element count, lr_scale, weight_decay (the implicit group last); None without groups."""
+        return None if self._groups is None else tuple(dict(g) for g in self._groups)
 
     def step(self, inputs: dict, labels: torch.Tensor) -> torch.Tensor:
         arena = self.arena
@@ -195,6 +335,16 @@ class TrainStep:
             partials, flags = ops.grad_sumsq(arena.grad)
             ops.optim_ctrl_update(ctrl, partials, flags, self.lr_table, grad_scale=gscale, max_norm=self.max_grad_norm,
                                   skip_nonfinite=self.skip_nonfinite, beta1=b1, beta2=b2)
+            if self._groups is not None:
+                # one launch over the whole arena: parameters without a gradient carry the skip id in the map
+                gmap = arena.group_map()
+                if self.kind == "sgd":
+                    ops.sgd_step_groups(arena.flat, arena.grad, self.mom, ctrl, gmap, self._group_table, self.momentum,
+                                        reverse=self.reverse_walk)
+                else:
+                    ops.adamw_step_groups(arena.flat, arena.grad, self.m, self.v, ctrl, gmap, self._group_table, self.betas[0],
+                                          self.betas[1], self.eps, reverse=self.reverse_walk)
+                segs = []
             for lo, hi in segs:
                 sl = slice(lo, hi)
                 if self.kind == "sgd":
