@@ -535,6 +535,78 @@ int lc2is_adamw_step_groups(float* params, const float* grads, float* exp_avg, f
                             const lc2is_optim_ctrl* ctrl, const uint8_t* granule_group, const lc2is_param_group* groups,
                             int ngroups, float beta1, float beta2, float eps, int reverse, lc2is_stream_t stream);
 
+/* ---- train-time augmentation on the device: random rescale + crop + horizontal flip + photometric jitter, one launch per batch ----
+ * replaces: the `transform` hook of the training dataset (data/dataset.py:144-149: one random transform applied to the image and
+ *   to the label under a shared RNG state), which the reference leaves to the host.  Here the decoded uint8 pixels live on the
+ *   device (an image pool), and two launches cut a whole augmented batch into the pixel_values / label tensors of the step.
+ * Image pool: one packed uint8 buffer of HWC pixels, one of HW labels, and a descriptor per image.  The 8 bytes that follow the last
+ *   pixel of an image must be readable (img_off + 3*H*W + 5 <= img_bytes): a tap is fetched as one unaligned 8-byte read. */
+typedef struct {
+  int64_t img_off;  /* byte offset of the image's first pixel in the image buffer */
+  int64_t lab_off;  /* byte offset of the label map in the label buffer           */
+  int32_t H, W;     /* 1 .. LC2IS_AUG_MAX_SIDE                                    */
+} lc2is_aug_image;
+#define LC2IS_AUG_MAX_SIDE 4096
+#define LC2IS_AUG_MAX_RESIZED 262143 /* nh, nw <= this: (2 * n + 1) * 4096 fits int32                                           */
+#define LC2IS_AUG_PARAM_WORDS 20     /* one row of the parameter table, 32-bit words:                                          */
+#define LC2IS_AUG_NH 0               /*   int32 nh, nw: the size the image is resized to                                       */
+#define LC2IS_AUG_NW 1
+#define LC2IS_AUG_TOP 2              /*   int32 top, left: the crop's origin in the resized image                              */
+#define LC2IS_AUG_LEFT 3
+#define LC2IS_AUG_FLIP 4             /*   int32 flip: 1 = mirrored left-right                                                  */
+#define LC2IS_AUG_M 5                /*   fp32 M[3][3] row-major and fp32 o[3]: rgb' = clamp(M rgb + o, 0, 255) on the 0..255 scale */
+#define LC2IS_AUG_O 14               /*   words 17..19: 0                                                                      */
+typedef struct {
+  uint32_t seed_lo, seed_hi;      /* the 64-bit seed                                                                           */
+  int32_t crop_size, base_size;   /* S; the short edge is resized to base_size * ratio                                         */
+  int32_t ratio_lo1024, ratio_hi1024; /* the ratio's range in 1/1024 units (512, 2048 = 0.5 .. 2.0), lo <= hi                  */
+  uint32_t flip_thr;              /* round(p * 2^24): flip iff u24 < flip_thr                                                  */
+  uint32_t photo_thr[4];          /* the same for brightness, contrast, saturation, hue; all 0 = identity colour               */
+  float brightness_delta;         /* b in [-delta, delta], added on the 0..255 scale                                           */
+  float contrast_lo, contrast_hi; /* c: every channel is multiplied by c                                                      */
+  float saturation_lo, saturation_hi; /* s: rgb' = s rgb + (1 - s) grey, grey = 0.299 r + 0.587 g + 0.114 b                    */
+  float hue_delta;                /* h in [-delta, delta] RADIANS: rotation about the grey axis (1, 1, 1)                      */
+} lc2is_aug_config;
+typedef struct {
+  float mean[3], inv_std[3];      /* out_c = (v * (1/255) - mean_c) * inv_std_c, inv_std_c = 1 / std_c rounded to fp32 once    */
+} lc2is_aug_norm;
+
+/* aug_params_kernel, one thread per sample b < B: reads slot = slots[b] (the image's row in `desc`), key = keys ? keys[b] : slot (the
+ * DATASET index the random numbers are drawn for; it differs from the slot only when the pool holds a transient batch), *epoch,
+ * desc[slot].(H, W), and writes row b of params [B][LC2IS_AUG_PARAM_WORDS].  Every random number is a pure function of
+ * (seed, *epoch, key, draw number k):  h = mix32(lo32(key) + seed_lo); h = mix32(h ^ (hi32(key) + seed_hi));
+ * h = mix32(h ^ (epoch * 0x9E3779B9 + 0x85EBCA6B));  u24(k) = mix32(h + k * 0x9E3779B9) >> 8  (mix32 = lowbias32, uint32 wrap-around),
+ * so an image gets the same augmentation in an epoch whatever its batch, position, rank or batch size, and a captured launch draws
+ * new parameters on replay once the DEVICE arrays slots / keys / epoch hold new values.  Draws, integers in integer arithmetic only:
+ *   k=0  r = ratio_lo1024 + ((u24 * (ratio_hi1024 - ratio_lo1024 + 1)) >> 24);  t = (base_size * r + 512) >> 10;  s = min(H, W);
+ *        nh = min(max(1, (2*H*t + s) / (2*s)), LC2IS_AUG_MAX_RESIZED), nw the same with W
+ *   k=1  top = (u24 * (max(nh - S, 0) + 1)) >> 24      k=2  left the same with nw      k=3  flip = u24 < flip_thr
+ *   k=4,6,8,10  step on iff u24 < photo_thr[0..3];  k=5,7,9,11  its value lo + (hi - lo) * (u24 * 2^-24) in fp32
+ * Colour: M = I, o = 0, then for each step that is on, in this order: brightness o += b; contrast M, o *= c; saturation
+ * (M, o) = A (M, o) with A = s I + (1 - s) 1 w^T; hue (M, o) = R (M, o) with R the rotation by h about (1, 1, 1) / sqrt(3).  ONE
+ * clamp to [0, 255] follows in aug_apply, none between the steps.  slot outside [0, n_images) or H, W outside
+ * 1..LC2IS_AUG_MAX_SIDE: the row is all zeros, which aug_apply renders as padding.  No atomics. */
+int lc2is_aug_params(const int64_t* slots, const int64_t* keys, int B, const int32_t* epoch, const lc2is_aug_image* desc,
+                     long n_images, const lc2is_aug_config* cfg /* HOST */, int32_t* params, lc2is_stream_t stream);
+
+/* aug_apply_kernel, ONE launch for the batch: grid.y = B samples, grid.x = image blocks followed by label blocks (256 lanes; an
+ * image lane makes 4 consecutive output x of all 3 channels: three 16-byte write-back stores, patchify reads the tensor next).
+ * out_img fp32 [B][3][S][S] (16-byte aligned), out_lab int64 [B][L][L]; S % 4 == 0, S % L == 0, q = S / L, S <= 4096, B <= 65535.
+ * Output pixel (i, j) looks at resized-image pixel yr = top + i, xr = left + (flip ? S-1-j : j).  Outside [0,nh) x [0,nw) the image
+ * value is 0.0 (the mean colour after normalisation) and the label is pad_label.  Inside, exact in int32:
+ *   ny = clamp((2*yr+1)*H - nh, 0, 2*nh*(H-1)); y0 = ny / (2*nh); fy = float(ny - y0*2*nh) / float(2*nh); y1 = min(y0+1, H-1);
+ *   the same for x; a = lerp(lerp(p00, p01, fx), lerp(p10, p11, fx), fy) per channel in fp32 (lerp(a, b, f) = a + f * (b - a));
+ *   v = clamp(M a + o, 0, 255); out_c = (v * (1/255) - mean_c) * inv_std_c.
+ *   = F.interpolate(size=(nh, nw), mode="bilinear", align_corners=False) + zero pad + crop + flip + colour + normalise.
+ * Label cell (i, j) is the label at output pixel (i*q + q/2, j*q + q/2): source ys = ((2*yr+1)*H) / (2*nh), xs likewise
+ *   (mode="nearest-exact"), passed through as int64.
+ * A sample whose slot, descriptor (sides, offsets against img_bytes / lab_bytes) or nh / nw is out of range is rendered as padding:
+ * nothing outside the two buffers is read whatever the tables hold.  No atomics, no LDS; bitwise reproducible. */
+int lc2is_aug_apply(const uint8_t* img, size_t img_bytes, const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc,
+                    long n_images, const int64_t* slots, const int32_t* params, int B, int S, int L,
+                    const lc2is_aug_norm* norm /* HOST */, long pad_label, float* out_img, int64_t* out_lab,
+                    lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

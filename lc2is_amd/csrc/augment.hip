@@ -1,0 +1,284 @@
+// Train-time augmentation on the device (the `transform` hook of data/dataset.py:144-149, which the reference
+// leaves to the host): random rescale + crop + horizontal flip + photometric jitter of a whole batch, cut from a pool of decoded
+// uint8 images that lives in HBM straight into the step's pixel_values [B,3,S,S] fp32 and label [B,L,L] int64.
+//   * aug_params_kernel: one thread per sample draws the sample's parameters from a counter-based RNG keyed by
+//     (seed, epoch, dataset index, draw number) and folds the photometric steps into one 3x3 matrix + offset.
+//   * aug_apply_kernel: one launch for the batch, images and labels together (label cells are extra blocks of the same grid).
+//     HBM-bound by its 3 * 16-byte stores per lane; the source taps are unaligned 8-byte reads (two neighbouring HWC pixels) that
+//     neighbouring lanes take from neighbouring bytes.  Source coordinates are exact integers: the quotient of at most 4096 comes
+//     from one fp32 multiply by a reciprocal and an integer correction instead of hipcc's ~35-instruction udiv.
+// The exact definition is in include/lc2is_hip.h; tests/augment_ref.py restates it in numpy (integers bit for bit).
+#include "common.h"
+#include "lc2is_hip.h"
+
+namespace {
+
+constexpr int AUG_P = LC2IS_AUG_PARAM_WORDS;
+constexpr unsigned AUG_GOLD = 0x9E3779B9u;
+
+__device__ __forceinline__ unsigned aug_key(unsigned seed_lo, unsigned seed_hi, int epoch, long long key) {
+  unsigned h = mix32((unsigned)key + seed_lo);
+  h = mix32(h ^ ((unsigned)((unsigned long long)key >> 32) + seed_hi));
+  return mix32(h ^ ((unsigned)epoch * AUG_GOLD + 0x85EBCA6Bu));
+}
+__device__ __forceinline__ unsigned aug_u24(unsigned h, unsigned k) { return mix32(h + k * AUG_GOLD) >> 8; }
+__device__ __forceinline__ float aug_range(unsigned u24, float lo, float hi) {
+  return lo + (hi - lo) * ((float)u24 * (1.0f / 16777216.0f));
+}
+
+// (M, o) = A (M, o)
+__device__ __forceinline__ void aug_left_mul(const float (&A)[9], float (&M)[9], float (&o)[3]) {
+  float N[9], p[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) N[3 * r + c] = A[3 * r] * M[c] + A[3 * r + 1] * M[3 + c] + A[3 * r + 2] * M[6 + c];
+    p[r] = A[3 * r] * o[0] + A[3 * r + 1] * o[1] + A[3 * r + 2] * o[2];
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) M[e] = N[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) o[e] = p[e];
+}
+
+__global__ __launch_bounds__(64) void aug_params_kernel(const int64_t* __restrict__ slots, const int64_t* __restrict__ keys, int B,
+                                                         const int32_t* __restrict__ epoch, const lc2is_aug_image* __restrict__ desc,
+                                                         long n_images, const lc2is_aug_config cfg, int32_t* __restrict__ params) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  int32_t* row = params + (size_t)b * AUG_P;
+  const long long slot = slots[b];
+  int H = 0, W = 0;
+  if (slot >= 0 && slot < n_images) { H = desc[slot].H; W = desc[slot].W; }
+  if (H < 1 || W < 1 || H > LC2IS_AUG_MAX_SIDE || W > LC2IS_AUG_MAX_SIDE) {
+#pragma unroll
+    for (int e = 0; e < AUG_P; ++e) row[e] = 0;
+    return;
+  }
+  const unsigned h = aug_key(cfg.seed_lo, cfg.seed_hi, *epoch, keys ? (long long)keys[b] : slot);
+  const int S = cfg.crop_size;
+  // integers in integer arithmetic only (64-bit products of a 24-bit uniform)
+  const long long r = cfg.ratio_lo1024 +
+                      (long long)(((unsigned long long)aug_u24(h, 0) * (unsigned long long)(cfg.ratio_hi1024 - cfg.ratio_lo1024 + 1)) >> 24);
+  const long long t = ((long long)cfg.base_size * r + 512) >> 10;
+  const long long s = H < W ? H : W;
+  long long nh = (2 * (long long)H * t + s) / (2 * s), nw = (2 * (long long)W * t + s) / (2 * s);
+  nh = nh < 1 ? 1 : (nh > LC2IS_AUG_MAX_RESIZED ? LC2IS_AUG_MAX_RESIZED : nh);
+  nw = nw < 1 ? 1 : (nw > LC2IS_AUG_MAX_RESIZED ? LC2IS_AUG_MAX_RESIZED : nw);
+  const long long fh = nh > S ? nh - S : 0, fw = nw > S ? nw - S : 0;
+  row[LC2IS_AUG_NH] = (int)nh;
+  row[LC2IS_AUG_NW] = (int)nw;
+  row[LC2IS_AUG_TOP] = (int)(((unsigned long long)aug_u24(h, 1) * (unsigned long long)(fh + 1)) >> 24);
+  row[LC2IS_AUG_LEFT] = (int)(((unsigned long long)aug_u24(h, 2) * (unsigned long long)(fw + 1)) >> 24);
+  row[LC2IS_AUG_FLIP] = aug_u24(h, 3) < cfg.flip_thr ? 1 : 0;
+
+  // photometric steps folded into rgb' = M rgb + o (0..255 scale); one clamp, in aug_apply
+  float M[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, o[3] = {0.f, 0.f, 0.f};
+  if (aug_u24(h, 4) < cfg.photo_thr[0]) {
+    const float d = aug_range(aug_u24(h, 5), -cfg.brightness_delta, cfg.brightness_delta);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) o[e] += d;
+  }
+  if (aug_u24(h, 6) < cfg.photo_thr[1]) {
+    const float c = aug_range(aug_u24(h, 7), cfg.contrast_lo, cfg.contrast_hi);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) M[e] *= c;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) o[e] *= c;
+  }
+  if (aug_u24(h, 8) < cfg.photo_thr[2]) {
+    const float sa = aug_range(aug_u24(h, 9), cfg.saturation_lo, cfg.saturation_hi);
+    const float g0 = (1.f - sa) * 0.299f, g1 = (1.f - sa) * 0.587f, g2 = (1.f - sa) * 0.114f;
+    const float A[9] = {sa + g0, g1, g2, g0, sa + g1, g2, g0, g1, sa + g2};
+    aug_left_mul(A, M, o);
+  }
+  if (aug_u24(h, 10) < cfg.photo_thr[3]) {
+    const float a = aug_range(aug_u24(h, 11), -cfg.hue_delta, cfg.hue_delta);
+    const float cs = cosf(a), sn = sinf(a);
+    const float d = cs + (1.f - cs) * (1.f / 3.f), p = (1.f - cs) * (1.f / 3.f), q = sn * 0.57735026918962576f;
+    const float A[9] = {d, p - q, p + q, p + q, d, p - q, p - q, p + q, d};
+    aug_left_mul(A, M, o);
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) row[LC2IS_AUG_M + e] = __builtin_bit_cast(int, M[e]);
+#pragma unroll
+  for (int e = 0; e < 3; ++e) row[LC2IS_AUG_O + e] = __builtin_bit_cast(int, o[e]);
+#pragma unroll
+  for (int e = LC2IS_AUG_O + 3; e < AUG_P; ++e) row[e] = 0;
+}
+
+// n / d and the remainder for 0 <= n < 2^31, 1 <= d < 2^24, n / d <= 4096, rcp_d = v_rcp_f32(d) (1 ulp): the fp32 estimate is off
+// by less than 4097 * 2^-22 < 1, so its floor is the quotient or one next to it and one integer correction makes it exact.
+__device__ __forceinline__ int aug_div(int n, int d, float rcp_d, int& rem) {
+  int q = (int)((float)n * rcp_d);
+  int r = (int)((unsigned)n - (unsigned)q * (unsigned)d);
+  if (r < 0) { q -= 1; r += d; }
+  else if (r >= d) { q += 1; r -= d; }
+  rem = r;
+  return q;
+}
+__device__ __forceinline__ int aug_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct AugSample {   // block-uniform: one sample per blockIdx.y
+  bool valid;
+  int H, W, nh, nw, top, left, flip;
+  long long img_off, lab_off;
+};
+__device__ __forceinline__ AugSample aug_sample(const lc2is_aug_image* __restrict__ desc, long n_images,
+                                                const int64_t* __restrict__ slots, const int32_t* __restrict__ prow,
+                                                size_t img_bytes, size_t lab_bytes) {
+  AugSample s;
+  const long long slot = slots[blockIdx.y];
+  s.valid = slot >= 0 && slot < n_images;
+  const lc2is_aug_image d = s.valid ? desc[slot] : lc2is_aug_image{0, 0, 0, 0};
+  s.H = d.H; s.W = d.W; s.img_off = d.img_off; s.lab_off = d.lab_off;
+  s.nh = prow[LC2IS_AUG_NH]; s.nw = prow[LC2IS_AUG_NW];
+  s.top = prow[LC2IS_AUG_TOP]; s.left = prow[LC2IS_AUG_LEFT]; s.flip = prow[LC2IS_AUG_FLIP];
+  s.valid = s.valid && s.H >= 1 && s.W >= 1 && s.H <= LC2IS_AUG_MAX_SIDE && s.W <= LC2IS_AUG_MAX_SIDE && s.nh >= 1 && s.nw >= 1 &&
+            s.nh <= LC2IS_AUG_MAX_RESIZED && s.nw <= LC2IS_AUG_MAX_RESIZED && s.img_off >= 0 && s.lab_off >= 0 &&
+            (unsigned long long)s.img_off + (unsigned long long)s.H * s.W * 3 + 5 <= img_bytes &&
+            (unsigned long long)s.lab_off + (unsigned long long)s.H * s.W <= lab_bytes;
+  return s;
+}
+
+__device__ __forceinline__ i32x2_t aug_load8(const unsigned char* p) {   // unaligned: one global_load_dwordx2
+  i32x2_t v;
+  __builtin_memcpy(&v, p, 8);
+  return v;
+}
+__device__ __forceinline__ float aug_byte(i32x2_t v, int k) {   // byte k of the 8 (k constant after unrolling)
+  return (float)(((unsigned)(k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 0xffu);
+}
+
+__global__ __launch_bounds__(256) void aug_apply_kernel(const unsigned char* __restrict__ img, size_t img_bytes,
+                                                         const unsigned char* __restrict__ lab, size_t lab_bytes,
+                                                         const lc2is_aug_image* __restrict__ desc, long n_images,
+                                                         const int64_t* __restrict__ slots, const int32_t* __restrict__ params,
+                                                         int S, int L, int img_blocks, const lc2is_aug_norm norm, long pad_label,
+                                                         float* __restrict__ out_img, int64_t* __restrict__ out_lab) {
+  const int b = blockIdx.y;
+  const int32_t* prow = params + (size_t)b * AUG_P;
+  const AugSample s = aug_sample(desc, n_images, slots, prow, img_bytes, lab_bytes);
+  const int dy = 2 * s.nh, dx = 2 * s.nw;
+  const float rdy = __builtin_amdgcn_rcpf((float)dy), rdx = __builtin_amdgcn_rcpf((float)dx);
+
+  if ((int)blockIdx.x >= img_blocks) {   // ---- label cells ----
+    const int cell = ((int)blockIdx.x - img_blocks) * 256 + threadIdx.x;
+    if (cell >= L * L) return;
+    int cj;
+    const int ci = aug_div(cell, L, __builtin_amdgcn_rcpf((float)L), cj);
+    const int q = S / L;
+    const int i = ci * q + (q >> 1), j = cj * q + (q >> 1);
+    const int yr = (int)((unsigned)s.top + (unsigned)i), xr = (int)((unsigned)s.left + (unsigned)(s.flip ? S - 1 - j : j));
+    long v = pad_label;
+    if (s.valid && (unsigned)yr < (unsigned)s.nh && (unsigned)xr < (unsigned)s.nw) {
+      int rem;
+      const int ys = aug_div((2 * yr + 1) * s.H, dy, rdy, rem), xs = aug_div((2 * xr + 1) * s.W, dx, rdx, rem);
+      v = lab[s.lab_off + (long long)ys * s.W + xs];
+    }
+    out_lab[((size_t)b * L + ci) * L + cj] = v;
+    return;
+  }
+
+  // ---- image: 4 consecutive output x per lane, all 3 channels ----
+  const int W4 = S >> 2;
+  const int p = (int)blockIdx.x * 256 + threadIdx.x;
+  if (p >= S * W4) return;
+  int jq;
+  const int i = aug_div(p, W4, __builtin_amdgcn_rcpf((float)W4), jq);
+  const int j0 = jq * 4;
+  float* dst = out_img + ((size_t)b * 3 * S + i) * S + j0;
+  const size_t plane = (size_t)S * S;
+  const int yr = (int)((unsigned)s.top + (unsigned)i);
+  const bool row_in = s.valid && (unsigned)yr < (unsigned)s.nh;
+  if (!__builtin_amdgcn_ballot_w64(row_in)) {   // the whole wave is padding (wave-uniform branch)
+    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane) = z;
+    return;
+  }
+  // s.valid holds from here on (it is block-uniform and part of row_in); every coordinate is clamped into the image, so the reads
+  // are in bounds also for the lanes that turn out to be padding
+  const int H = s.H, W = s.W;
+  int ry;
+  const int ny = aug_clampi((2 * aug_clampi(yr, 0, s.nh - 1) + 1) * H - s.nh, 0, dy * (H - 1));
+  const int y0 = aug_div(ny, dy, rdy, ry);
+  const int y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+  const float fy = (float)ry * rdy;
+  const unsigned char* base = img + s.img_off;
+  const unsigned char* r0 = base + (size_t)y0 * W * 3;
+  const unsigned char* r1 = base + (size_t)y1 * W * 3;
+
+  i32x2_t t0[4], t1[4];
+  float fx[4];
+  bool in[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = j0 + k;
+    const int xr = (int)((unsigned)s.left + (unsigned)(s.flip ? S - 1 - j : j));
+    in[k] = row_in && (unsigned)xr < (unsigned)s.nw;
+    int rx;
+    const int nx = aug_clampi((2 * aug_clampi(xr, 0, s.nw - 1) + 1) * W - s.nw, 0, dx * (W - 1));
+    const int x0 = aug_div(nx, dx, rdx, rx);
+    fx[k] = (float)rx * rdx;   // 0 at x0 == W - 1, where the second pixel of the read lies past the row and has no weight
+    t0[k] = aug_load8(r0 + 3 * x0);
+    t1[k] = aug_load8(r1 + 3 * x0);
+  }
+  float M[9], o[3];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) M[e] = __builtin_bit_cast(float, prow[LC2IS_AUG_M + e]);
+#pragma unroll
+  for (int e = 0; e < 3; ++e) o[e] = __builtin_bit_cast(float, prow[LC2IS_AUG_O + e]);
+
+  f32x4_t out[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float a[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float p00 = aug_byte(t0[k], c), p01 = aug_byte(t0[k], 3 + c), p10 = aug_byte(t1[k], c), p11 = aug_byte(t1[k], 3 + c);
+      const float h0 = p00 + fx[k] * (p01 - p00), h1 = p10 + fx[k] * (p11 - p10);
+      a[c] = h0 + fy * (h1 - h0);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v = M[3 * c] * a[0] + M[3 * c + 1] * a[1] + M[3 * c + 2] * a[2] + o[c];
+      v = fminf(fmaxf(v, 0.f), 255.f);
+      v = (v * (1.0f / 255.0f) - norm.mean[c]) * norm.inv_std[c];
+      out[c][k] = in[k] ? v : 0.f;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane) = out[c];   // plain (write-back) stores: patchify reads them next
+}
+
+}  // namespace
+
+extern "C" int lc2is_aug_params(const int64_t* slots, const int64_t* keys, int B, const int32_t* epoch, const lc2is_aug_image* desc,
+                                long n_images, const lc2is_aug_config* cfg, int32_t* params, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!slots || !epoch || !desc || !cfg || !params) return LC2IS_ERR_NULL;
+  if (B <= 0 || n_images <= 0 || cfg->crop_size <= 0 || cfg->crop_size > LC2IS_AUG_MAX_SIDE || cfg->base_size <= 0 ||
+      cfg->base_size > 65536 || cfg->ratio_lo1024 < 1 || cfg->ratio_hi1024 < cfg->ratio_lo1024 || cfg->ratio_hi1024 > (1 << 20) ||
+      cfg->flip_thr > (1u << 24))
+    return LC2IS_ERR_SHAPE;
+  for (int e = 0; e < 4; ++e)
+    if (cfg->photo_thr[e] > (1u << 24)) return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(aug_params_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, slots, keys, B, epoch, desc, n_images, *cfg, params);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_aug_apply(const uint8_t* img, size_t img_bytes, const uint8_t* lab, size_t lab_bytes,
+                               const lc2is_aug_image* desc, long n_images, const int64_t* slots, const int32_t* params, int B, int S,
+                               int L, const lc2is_aug_norm* norm, long pad_label, float* out_img, int64_t* out_lab,
+                               lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!img || !lab || !desc || !slots || !params || !norm || !out_img || !out_lab) return LC2IS_ERR_NULL;
+  if (B <= 0 || B > 65535 || n_images <= 0 || S <= 0 || S > LC2IS_AUG_MAX_SIDE || (S & 3) || L <= 0 || S % L ||
+      ((uintptr_t)out_img & 15) || ((uintptr_t)out_lab & 7) || ((uintptr_t)params & 3) || ((uintptr_t)desc & 7))
+    return LC2IS_ERR_SHAPE;
+  const int img_blocks = (S * (S >> 2) + 255) / 256, lab_blocks = (L * L + 255) / 256;
+  hipLaunchKernelGGL(aug_apply_kernel, dim3(img_blocks + lab_blocks, B), dim3(256), 0, stream, img, img_bytes, lab, lab_bytes, desc,
+                     n_images, slots, params, S, L, img_blocks, *norm, pad_label, out_img, out_lab);
+  return lc2is_check_launch();
+}

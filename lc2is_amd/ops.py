@@ -98,6 +98,8 @@ _ARGTYPES = {
     "lc2is_resample_u8": [_P, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],
     "lc2is_gather2d_u8": [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P],
     "lc2is_crop_lut": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "lc2is_aug_params": [_P, _P, _I, _P, _P, _L, _P, _P, _P],
+    "lc2is_aug_apply": [_P, _Z, _P, _Z, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -1270,6 +1272,78 @@ def crop_lut(src: torch.Tensor, top: int, left: int, S: int, *, lut_f32: torch.T
                                _ptr(lut_i64), _ptr(out_i64 if lut_i64 is not None else None), _stream())
     _lib.check(rc, f"crop_lut {H}x{W} crop {S}@({top},{left})")
     return out_f32, out_i64
+
+
+# ---- train-time augmentation (device image pool) -------------------------------------------------------------------
+AUG_PARAM_WORDS, AUG_MAX_SIDE = 20, 4096      # LC2IS_AUG_PARAM_WORDS, LC2IS_AUG_MAX_SIDE
+AUG_NH, AUG_NW, AUG_TOP, AUG_LEFT, AUG_FLIP, AUG_M, AUG_O = 0, 1, 2, 3, 4, 5, 14
+
+
+class AugConfig(C.Structure):
+    """lc2is_aug_config (include/lc2is_hip.h): host struct, passed by value into aug_params_kernel."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("crop_size", C.c_int32), ("base_size", C.c_int32),
+                ("ratio_lo1024", C.c_int32), ("ratio_hi1024", C.c_int32), ("flip_thr", C.c_uint32), ("photo_thr", C.c_uint32 * 4),
+                ("brightness_delta", C.c_float), ("contrast_lo", C.c_float), ("contrast_hi", C.c_float),
+                ("saturation_lo", C.c_float), ("saturation_hi", C.c_float), ("hue_delta", C.c_float)]
+
+
+class AugNorm(C.Structure):
+    """lc2is_aug_norm: out_c = (v / 255 - mean_c) * inv_std_c."""
+    _fields_ = [("mean", C.c_float * 3), ("inv_std", C.c_float * 3)]
+
+
+def _aug_tables(desc, slots, name):
+    _chk(desc, torch.int64, "desc"); _chk(slots, torch.int64, "indices", 1)
+    if desc.shape[1] != 3 or not desc.is_contiguous() or desc.shape[0] < 1 or slots.numel() < 1:
+        raise RuntimeError(f"lc2is_amd.{name}: desc must be a contiguous int64 [n_images, 3] table (img_off, lab_off, H | W << 32) "
+                           "and indices non-empty")
+
+
+def aug_params(slots: torch.Tensor, epoch: torch.Tensor, desc: torch.Tensor, cfg: AugConfig, *, keys: torch.Tensor | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Draw one row of augmentation parameters per sample (lc2is_aug_params): int32 [B, AUG_PARAM_WORDS] = nh, nw, top, left, flip,
+    fp32 colour matrix M[3][3] and offset o[3] (bit patterns; view the tensor as float32 to read them).  slots int64 [B]: rows of
+    desc; keys int64 [B] or None: the dataset indices the random numbers are a function of (None: the slots); epoch: DEVICE int32
+    scalar.  Nothing but device memory decides the result, so a captured call draws again on replay."""
+    _aug_tables(desc, slots, "aug_params")
+    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
+    B = slots.numel()
+    if epoch.numel() != 1 or (keys is not None and keys.numel() != B):
+        raise RuntimeError("lc2is_amd.aug_params: epoch must hold one int32 and keys one int64 per sample")
+    if out is None:
+        out = torch.empty((B, AUG_PARAM_WORDS), dtype=torch.int32, device=slots.device)
+    _chk(out, torch.int32, "out")
+    if tuple(out.shape) != (B, AUG_PARAM_WORDS) or not out.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.aug_params: out must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    rc = _fn("lc2is_aug_params")(_ptr(slots), _ptr(keys), B, _ptr(epoch), _ptr(desc), desc.shape[0], C.addressof(cfg), _ptr(out),
+                                 _stream())
+    _lib.check(rc, f"aug_params B={B}")
+    return out
+
+
+def aug_apply(img: torch.Tensor, lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, params: torch.Tensor, S: int, L: int,
+              norm: AugNorm, *, pad_label: int = 0, out_img: torch.Tensor | None = None, out_lab: torch.Tensor | None = None):
+    """One launch for the batch (lc2is_aug_apply): bilinear resize to (nh, nw) + zero pad + S x S crop + flip + colour + normalise of
+    the pool's uint8 HWC pixels -> fp32 [B, 3, S, S], and the nearest-exact labels of the same geometry at the centres of the
+    (S / L)^2 cells -> int64 [B, L, L].  img / lab: the pool's packed uint8 buffers; desc / slots as in aug_params; params its table."""
+    _aug_tables(desc, slots, "aug_apply")
+    _chk(img, torch.uint8, "img", 1); _chk(lab, torch.uint8, "lab", 1); _chk(params, torch.int32, "params")
+    B = slots.numel()
+    if tuple(params.shape) != (B, AUG_PARAM_WORDS) or not params.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.aug_apply: params must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    if S < 1 or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
+        raise ValueError(f"lc2is_amd.aug_apply: crop size {S} must be a multiple of 4 and of the label size {L}, at most {AUG_MAX_SIDE}")
+    if out_img is None:
+        out_img = torch.empty((B, 3, S, S), dtype=torch.float32, device=img.device)
+    if out_lab is None:
+        out_lab = torch.empty((B, L, L), dtype=torch.int64, device=img.device)
+    _chk(out_img, torch.float32, "out_img", 4); _chk(out_lab, torch.int64, "out_lab", 3)
+    if tuple(out_img.shape) != (B, 3, S, S) or tuple(out_lab.shape) != (B, L, L) or not (out_img.is_contiguous() and out_lab.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.aug_apply: outputs must be contiguous [{B}, 3, {S}, {S}] fp32 and [{B}, {L}, {L}] int64")
+    rc = _fn("lc2is_aug_apply")(_ptr(img), img.numel(), _ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), _ptr(params),
+                                B, S, L, C.addressof(norm), int(pad_label), _ptr(out_img), _ptr(out_lab), _stream())
+    _lib.check(rc, f"aug_apply B={B} S={S} L={L}")
+    return out_img, out_lab
 
 
 def set_cu_budget(ncu: int) -> None:
