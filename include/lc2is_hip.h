@@ -535,6 +535,27 @@ int lc2is_adamw_step_groups(float* params, const float* grads, float* exp_avg, f
                             const lc2is_optim_ctrl* ctrl, const uint8_t* granule_group, const lc2is_param_group* groups,
                             int ngroups, float beta1, float beta2, float eps, int reverse, lc2is_stream_t stream);
 
+/* Weight EMA held on the device, following the control block: with ctrl->apply == 0 (a skipped step), or ctrl->applied % every
+ * != 0, the launch returns before touching memory; otherwise, per element, ema += w * (params - ema), one fma on the difference.
+ *   w = one_minus_decay: 1 - decay formed in fp64 ON THE HOST and rounded once (1.f - 0.9999f would be off by 3e-4 relative);
+ *   warmup != 0: the j-th EMA update (j = applied / every, 1-based) takes max(w, 9 / (10 + j)), i.e. TF's decay
+ *     min(decay, (1 + j) / (10 + j)), formed in fp64 and rounded once.
+ * An element whose bits equal the parameter's keeps its bits exactly (+-0, denormals, infinities and NaN payloads included): the
+ * EMA of parameters that never move, and of the arena's alignment padding, stays bit-identical to them.
+ * n % 4 == 0, n > 0, both buffers 16-byte aligned, 0 < one_minus_decay <= 1, every >= 1 (else LC2IS_ERR_SHAPE).  Same grid and
+ * walk (reverse != 0: from the end; the same bits) as lc2is_sgd_step_ctrl.  No atomics, element-wise: bitwise reproducible.
+ * replaces: nothing in the reference, which keeps no averaged weights; stands in for torch.optim.swa_utils.AveragedModel with
+ *   get_ema_multi_avg_fn (a second model and a torch._foreach_lerp_ over every parameter tensor per step) / timm's ModelEmaV3. */
+int lc2is_ema_update_ctrl(float* ema, const float* params, size_t n, const lc2is_optim_ctrl* ctrl, float one_minus_decay,
+                          int warmup, int every, int reverse, lc2is_stream_t stream);
+
+/* Exchanges the contents of two fp32 buffers of n elements in place, bit for bit (NaN payloads and -0.0 survive).  n % 4 == 0,
+ * n > 0, both 16-byte aligned, the ranges disjoint (else LC2IS_ERR_SHAPE).  Evaluating with the EMA weights is "swap, evaluate,
+ * swap back": every pointer - parameter views, a captured graph's arguments - stays where it was, and nothing is allocated.
+ * replaces: nothing in the reference; stands in for the store() / copy_to() / restore() of EMA helpers (torch._foreach_copy_ three
+ *   times through a temporary of the model's size), or evaluating torch.optim.swa_utils.AveragedModel.module, a second model. */
+int lc2is_swap_f32(float* a, float* b, size_t n, lc2is_stream_t stream);
+
 /* ---- train-time augmentation on the device: random rescale + crop + horizontal flip + photometric jitter, one launch per batch ----
  * replaces: the `transform` hook of the training dataset (data/dataset.py:144-149: one random transform applied to the image and
  *   to the label under a shared RNG state), which the reference leaves to the host.  Here the decoded uint8 pixels live on the

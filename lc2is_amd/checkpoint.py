@@ -8,6 +8,10 @@
   94-96, 126-127) — a network fetch.  :func:`load_pretrained_dir` fills the same towers from a LOCAL directory in the
   hub layout (``model.safetensors`` or ``pytorch_model.bin``), nothing is downloaded.
 
+* The reference cannot resume a run: its file holds the model alone.  :func:`save_train_state` / :func:`load_train_state` write
+  and read what a ``TrainStep`` holds besides the model (``step-N.train.pt``: optimizer moments, the device control block, the
+  EMA) and the averaged model in the reference's own format (``step-N.ema.pt``), next to an untouched ``step-N.pt``.
+
 Every file is read with loaders that execute nothing from it (safetensors, ``torch.load(weights_only=True)``).
 """
 from __future__ import annotations
@@ -104,6 +108,30 @@ def load_checkpoint(model: nn.Module, path: str | Path, strict: bool = True):
         if hasattr(m, "invalidate_shadows"):
             m.invalidate_shadows()
     return result
+
+
+def save_train_state(ts, out_dir: str | Path, train_step: int, write: bool | None = None) -> Path:
+    """``<out_dir>/checkpoints/step-<N>.train.pt`` holding ``ts.state_dict()`` and, when the step keeps an EMA,
+    ``step-<N>.ema.pt`` holding ``ts.ema_state_dict()`` (a plain model state dict: the reference loads it).  :func:`save_checkpoint`'s
+    conventions: no collective, no barrier; the replicas hold the same bytes, so only rank 0 writes (``write`` overrides).
+    Resume: ``load_checkpoint(model, step-N.pt)``, ``ts = TrainStep(model, <the same arguments>)``,
+    ``load_train_state(ts, step-N.train.pt)``."""
+    _, rank, _ = _dist()
+    d = Path(out_dir) / "checkpoints"
+    f = d / f"step-{train_step}.train.pt"
+    d.mkdir(parents=True, exist_ok=True)
+    if write if write is not None else rank == 0:
+        torch.save(ts.state_dict(), f)
+        if ts.ema is not None:
+            torch.save(ts.ema_state_dict(), d / f"step-{train_step}.ema.pt")
+    return f
+
+
+def load_train_state(ts, path: str | Path) -> None:
+    """Read a ``step-N.train.pt`` (``weights_only=True``: nothing in it is executed) into a ``TrainStep`` built with the arguments of
+    the run that wrote it: a mismatch raises ``ValueError`` and changes nothing; otherwise the state is copied in place."""
+    sd = torch.load(Path(path), map_location="cpu", weights_only=True)
+    ts.load_state_dict(sd)
 
 
 def _hub_file(directory: Path) -> Path:

@@ -4,6 +4,7 @@
 //   - grad_sumsq:        pass 1 over the flat gradient arena: one fp32 sum-of-squares partial and one non-finite flag per block
 //   - optim_ctrl_update: one block: global norm, clip coefficient, verdict, lr table look-up, counters, bias corrections
 //   - sgd / adamw _ctrl: sgd_kernel / adamw_kernel of misc.hip, expression for expression, scalars read from the block
+//   - ema_ctrl / swap:   the weight EMA that follows the block's verdict and counter, and the in-place exchange that evaluates it
 // Every reduction has a fixed order and there is no read-modify-write atomic: results are bitwise reproducible.
 #include "common.h"
 #include "lc2is_hip.h"
@@ -243,6 +244,45 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float
   }
 }
 
+// Exponential moving average of the parameters, held next to them: e += w * (p - e), evaluated as one fma on the difference
+// (torch's lerp form for small weights).  Geometry and early return of sgd_ctrl_kernel.  An element whose bits already equal the
+// parameter's keeps them through a select, not through arithmetic: -0 + w * 0 is +0, inf - inf is a NaN, and a NaN would come
+// back with another payload.  That is what keeps the EMA of frozen / unreached parameters and of the alignment padding
+// bit-identical to the arena without a granule map.
+// The weight: `w` as the host rounded it from 1 - decay in fp64; under warm-up max(w, 9 / (10 + j)) for the j-th EMA update
+// (TF's decay = min(decay, (1 + j) / (10 + j))), from wave-uniform values in fp64, rounded once.
+// Plain cached loads (the optimizer has just written p) and plain stores; no atomics, no LDS, no scratch.
+__device__ __forceinline__ float ema_lerp(float e, float p, float w) {
+  const float r = fmaf(w, p - e, e);
+  return __float_as_uint(p) == __float_as_uint(e) ? e : r;
+}
+
+__global__ __launch_bounds__(256) void ema_ctrl_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n4,
+                                                        const lc2is_optim_ctrl* __restrict__ ctrl, float w, int warmup,
+                                                        int every, int reverse) {
+  if (!ctrl->apply) return;
+  const int u = ctrl->applied;
+  if (u % every != 0) return;
+  if (warmup) w = fmaxf(w, (float)(9.0 / (10.0 + (double)(u / every))));
+  for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += (size_t)gridDim.x * 256) {
+    const size_t i = reverse ? n4 - 1 - j : j;
+    float4 ev = reinterpret_cast<float4*>(e)[i];
+    const float4 pv = reinterpret_cast<const float4*>(p)[i];
+    ev.x = ema_lerp(ev.x, pv.x, w); ev.y = ema_lerp(ev.y, pv.y, w);
+    ev.z = ema_lerp(ev.z, pv.z, w); ev.w = ema_lerp(ev.w, pv.w, w);
+    reinterpret_cast<float4*>(e)[i] = ev;
+  }
+}
+
+// In-place exchange of two equal-length, non-overlapping buffers, 16 bytes per lane, as integers: every bit pattern survives.
+__global__ __launch_bounds__(256) void swap_f32_kernel(uint4* __restrict__ a, uint4* __restrict__ b, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const uint4 av = a[i], bv = b[i];
+    a[i] = bv;
+    b[i] = av;
+  }
+}
+
 inline int ew_grid(size_t work_items) {
   size_t g = (work_items + 255) / 256;
   if (g > 4096) g = 4096;
@@ -336,5 +376,28 @@ extern "C" int lc2is_adamw_step_groups(float* params, const float* grads, float*
     return LC2IS_ERR_SHAPE;
   hipLaunchKernelGGL(adamw_groups_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, n / 4,
                      ctrl, granule_group, groups, ngroups, beta1, beta2, eps, reverse);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_ema_update_ctrl(float* ema, const float* params, size_t n, const lc2is_optim_ctrl* ctrl,
+                                     float one_minus_decay, int warmup, int every, int reverse, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ema || !params || !ctrl) return LC2IS_ERR_NULL;
+  if (n == 0 || n % 4 || !aligned16(ema) || !aligned16(params) || ((uintptr_t)ctrl & 3u) ||
+      !(one_minus_decay > 0.f && one_minus_decay <= 1.f) || every < 1)
+    return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(ema_ctrl_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, ema, params, n / 4, ctrl, one_minus_decay,
+                     warmup, every, reverse);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_swap_f32(float* a, float* b, size_t n, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!a || !b) return LC2IS_ERR_NULL;
+  if (n == 0 || n % 4 || !aligned16(a) || !aligned16(b)) return LC2IS_ERR_SHAPE;
+  const uintptr_t lo = (uintptr_t)(a < b ? a : b), hi = (uintptr_t)(a < b ? b : a);
+  if (hi - lo < n * sizeof(float)) return LC2IS_ERR_SHAPE;   // the two ranges overlap (a == b included)
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, stream, reinterpret_cast<uint4*>(a),
+                     reinterpret_cast<uint4*>(b), n / 4);
   return lc2is_check_launch();
 }

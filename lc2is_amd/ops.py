@@ -65,6 +65,8 @@ _ARGTYPES = {
     "lc2is_adamw_step_ctrl": [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _I, _P],
     "lc2is_sgd_step_groups": [_P, _P, _P, _Z, _P, _P, _P, _I, _F, _I, _P],
     "lc2is_adamw_step_groups": [_P, _P, _P, _P, _Z, _P, _P, _P, _I, _F, _F, _F, _I, _P],
+    "lc2is_ema_update_ctrl": [_P, _P, _Z, _P, _F, _I, _I, _I, _P],
+    "lc2is_swap_f32": [_P, _P, _Z, _P],
     "lc2is_head_upsample_ce_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
     "lc2is_head_upsample_ce": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _F, _P, _Z, _P],
     "lc2is_ce_nchw_fwd": [_P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P],
@@ -812,6 +814,27 @@ def adamw_step_groups(params, grads, m, v, ctrl, granule_group, groups, beta1, b
     _lib.check(_fn("lc2is_adamw_step_groups")(_ptr(params), _ptr(grads), _ptr(m), _ptr(v), params.numel(), _ptr(ctrl),
                                               _ptr(granule_group), _ptr(groups), groups.shape[0], beta1, beta2, eps,
                                               int(bool(reverse)), _stream()), "adamw_step_groups")
+
+
+# ---- weight EMA on the device: follows the control block's verdict and counter; evaluated through an in-place exchange ----
+def ema_update_ctrl(ema, params, ctrl, one_minus_decay, warmup=False, every=1, reverse=False):
+    """ema += w * (params - ema) over two flat fp32 buffers of one length, unless ``ctrl`` says this step was skipped or
+    ``applied % every != 0`` (then nothing is read or written).  ``one_minus_decay``: 1 - decay, formed in fp64 by the caller (it is
+    rounded to fp32 once, here); ``warmup``: the j-th update takes max(w, 9 / (10 + j)).  Elements equal to the parameter bit for
+    bit keep their bits."""
+    _chk(ema, torch.float32, "ema", 1); _chk_same_numel("ema_update_ctrl", ema, params); _chk_ctrl(ctrl)
+    if params is None:
+        raise RuntimeError("lc2is_amd.ema_update_ctrl: params is required")
+    _lib.check(_fn("lc2is_ema_update_ctrl")(_ptr(ema), _ptr(params), ema.numel(), _ptr(ctrl), float(one_minus_decay),
+                                            int(bool(warmup)), int(every), int(bool(reverse)), _stream()), "ema_update_ctrl")
+
+
+def swap_f32(a, b):
+    """Exchange the contents of two equal-length, non-overlapping flat fp32 buffers in place, bit for bit."""
+    _chk(a, torch.float32, "a", 1); _chk_same_numel("swap_f32", a, b)
+    if b is None:
+        raise RuntimeError("lc2is_amd.swap_f32: b is required")
+    _lib.check(_fn("lc2is_swap_f32")(_ptr(a), _ptr(b), a.numel(), _stream()), "swap_f32")
 
 
 def _ce_options(class_weight, label_smoothing: float, C: int, dev):

@@ -25,9 +25,15 @@ plus global gradient-norm clipping (``torch.nn.utils.clip_grad_norm_``; the refe
 AdamW bias corrections, the clip coefficient and the skip verdict then live in a control block on the device (``ops.grad_sumsq``
 -> ``ops.optim_ctrl_update`` -> ``ops.sgd_step_ctrl`` / ``ops.adamw_step_ctrl``): no host sync, and a captured step advances its
 schedule — and AdamW's ``t`` — across replays.
+
+``ema_decay`` (device-held path too) keeps an exponential moving average of the parameters in a second flat buffer, updated by one
+launch after the optimizer's that follows the control block (a skipped step leaves it alone; it is captured with the step);
+``ema_weights()`` evaluates with it by exchanging the two buffers in place.  ``state_dict()`` / ``load_state_dict()`` hold
+everything a step reads besides the model and the batch, so a stopped run continues bit for bit (``checkpoint.save_train_state``).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import re
@@ -155,6 +161,87 @@ def _resolve_param_groups(model: nn.Module, param_groups, weight_decay: float):
     return groups, group_of
 
 
+def _f32(x: float) -> float:
+    """x rounded once to fp32, as a Python float."""
+    return float(torch.tensor(float(x), dtype=torch.float64).to(torch.float32))
+
+
+def ema_weight_at(j: int, decay: float, warmup: bool = False) -> float:
+    """The host mirror of ``ops.ema_update_ctrl``'s weight for the j-th EMA update (1-based): fp32(1 - decay) with the difference
+    formed in fp64, and under warm-up the larger of that and fp32(9 / (10 + j)) — TF's decay ``min(decay, (1 + j) / (10 + j))``."""
+    w = _f32(1.0 - float(decay))
+    return max(w, _f32(9.0 / (10.0 + int(j)))) if warmup else w
+
+
+def _check_ema_args(ema_decay, ema_warmup, ema_every) -> None:
+    if isinstance(ema_every, bool) or not isinstance(ema_every, int) or ema_every < 1:
+        raise ValueError(f"TrainStep: ema_every must be an integer >= 1, got {ema_every!r}")
+    if ema_decay is None:
+        if ema_warmup or ema_every != 1:
+            raise ValueError("TrainStep: ema_warmup / ema_every need ema_decay")
+        return
+    if not 0.0 <= float(ema_decay) < 1.0:   # (a NaN fails both comparisons)
+        raise ValueError(f"TrainStep: ema_decay must satisfy 0 <= ema_decay < 1, got {ema_decay}")
+
+
+def check_train_state(saved: dict, live: dict) -> None:
+    """Compare the ``meta`` of a saved ``TrainStep.state_dict()`` with that of the live object (pure host function: dicts of
+    strings, numbers and lists).  Raises ``ValueError`` naming the first difference; returns None when the state fits."""
+    def fail(what):
+        raise ValueError(f"TrainStep.load_state_dict: {what}")
+
+    if saved.get("optimizer") != live["optimizer"]:
+        fail(f"saved optimizer is '{saved.get('optimizer')}', this TrainStep runs '{live['optimizer']}'")
+    se, le = saved.get("ema"), live["ema"]
+    if se is not None and le is None:
+        fail("EMA saved but not configured (give the TrainStep the run's ema_decay)")
+    if se is None and le is not None:
+        fail("EMA configured but not in the saved state")
+    sh, lh = saved.get("hyper", {}), live["hyper"]
+    for k in lh:
+        if sh.get(k) != lh[k]:
+            fail(f"optimizer hyper-parameter {k}: saved {sh.get(k)!r}, this TrainStep has {lh[k]!r}")
+    if bool(saved.get("device_path")) != bool(live["device_path"]):
+        fail("saved state is from the " + ("device-held" if saved.get("device_path") else "host-scalar") + " path, this TrainStep "
+             "runs the " + ("device-held" if live["device_path"] else "host-scalar") + " one (lr_schedule / max_grad_norm / "
+             "skip_nonfinite / device_state / param_groups / ema_decay select it)")
+    sl, ll = saved.get("layout", {}), live["layout"]
+    s_at = {n: (o, c) for n, o, c in zip(sl.get("names", []), sl.get("offsets", []), sl.get("numels", []))}
+    for n, o, c in zip(ll["names"], ll["offsets"], ll["numels"]):
+        if n not in s_at:
+            fail(f"parameter '{n}' is missing from the saved state")
+        if s_at[n][1] != c:
+            fail(f"parameter '{n}' has {c} elements, the saved state {s_at[n][1]}")
+        if s_at[n][0] != o:
+            fail(f"parameter '{n}' lies at arena offset {o}, in the saved state at {s_at[n][0]}")
+    extra = [n for n in sl.get("names", []) if n not in set(ll["names"])]
+    if extra:
+        fail(f"parameter '{extra[0]}' of the saved state is missing from the model")
+    if sl.get("total") != ll["total"]:
+        fail(f"arena of {ll['total']} elements, the saved state has {sl.get('total')}")
+    sg, lg = saved.get("groups"), live["groups"]
+    if (sg is None) != (lg is None):
+        fail("param_groups " + ("saved but not configured" if lg is None else "configured but not in the saved state"))
+    if lg is not None:
+        if sg["table"] != lg["table"]:
+            fail(f"another group recipe: saved (lr_scale, weight_decay) table {sg['table']}, this TrainStep has {lg['table']}")
+        for n, a, b in zip(ll["names"], sg["ids"], lg["ids"]):
+            if a != b:
+                fail(f"another group assignment: parameter '{n}' was in group {a}, is in group {b}")
+    st, lt = saved.get("lr_table"), live["lr_table"]
+    if st != lt:
+        if st is None or lt is None or len(st) != len(lt):
+            fail(f"another lr table: saved {None if st is None else len(st)} entries, this TrainStep has "
+                 f"{None if lt is None else len(lt)}")
+        i = next(k for k, (a, b) in enumerate(zip(st, lt)) if a != b)
+        fail(f"another lr table: entry {i} is {lt[i]!r}, saved {st[i]!r}")
+    if saved.get("clip") != live["clip"]:
+        fail(f"(max_grad_norm, skip_nonfinite) saved as {saved.get('clip')}, this TrainStep has {live['clip']}")
+    if se != le:
+        k = next(k for k in le if se.get(k) != le[k])
+        fail(f"EMA setting {k}: saved {se.get(k)!r}, this TrainStep has {le[k]!r}")
+
+
 _TOWER_LAYER = re.compile(r"^(.*)\.encoder\.layers\.(\d+)\.")
 
 
@@ -209,16 +296,24 @@ class TrainStep:
     stays global and ``skip_nonfinite`` all-or-nothing.  Parameters named in no group form an implicit last group (lr_scale 1,
     TrainStep's weight_decay) — unlike ``torch.optim``, which would not train them: a tower that must not move is
     ``requires_grad=False``, or a group with ``lr_scale`` 0 (which, like torch at lr = 0, still advances AdamW's moments and SGD's
-    momentum buffer and leaves the parameter bits unchanged).  ``make_param_groups`` writes the usual recipes."""
+    momentum buffer and leaves the parameter bits unchanged).  ``make_param_groups`` writes the usual recipes.
+
+    ``ema_decay`` (keyword-only; selects the device-held path): ``ts.ema``, a flat fp32 buffer laid out like ``arena.flat`` and
+    initialised from it, takes ``ema += (1 - ema_decay) * (p - ema)`` after every APPLIED optimizer update (every ``ema_every``-th
+    one; with ``ema_warmup`` the j-th EMA update uses the decay ``min(ema_decay, (1 + j) / (10 + j))``).  One launch over the arena,
+    captured with the step.  ``ema_state_dict()`` is the averaged model, ``with ts.ema_weights():`` evaluates with it in place,
+    ``reset_ema()`` restarts it from the current parameters (after loading weights into the model)."""
 
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
                  ignore_index: int | None = None, criterion: nn.Module | None = None, lr_schedule=None,
                  schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
-                 device_state: bool = False, param_groups=None) -> None:
+                 device_state: bool = False, param_groups=None, ema_decay: float | None = None, ema_warmup: bool = False,
+                 ema_every: int = 1) -> None:
         # (argument checks first: nothing is built or allocated for a step that cannot run)
+        _check_ema_args(ema_decay, ema_warmup, ema_every)
         device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None
-                           or param_groups is not None)
+                           or param_groups is not None or ema_decay is not None)
         groups = None
         if param_groups is not None:
             groups, group_of = _resolve_param_groups(model, param_groups, weight_decay)
@@ -269,6 +364,16 @@ class TrainStep:
         if groups is not None:
             self.arena.set_groups([group_of[id(p)] for p in self.arena.params], len(groups))
             self._group_table = torch.tensor([[g["lr_scale"], g["weight_decay"]] for g in groups], dtype=torch.float32).to(dev)
+        # weight EMA: a second arena-shaped buffer; None = no launch is added to the step
+        self.ema, self._ema_swapped = None, False
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup, self.ema_every = bool(ema_warmup), int(ema_every)
+        if ema_decay is not None:
+            self._ema_w = 1.0 - self.ema_decay   # fp64 here; rounded to fp32 once, at the C boundary
+            # walk the arena from its end (the same bits): the optimizer has just finished there, so the tail of p is the part
+            # still cache-warm; 401 against 415 us per launch, faster in both repetitions of profiles/ema_cost.txt
+            self.ema_reverse_walk = True
+            self.ema = self.arena.flat.clone()
 
     # -- views of the control block: device tensors, no sync unless the caller asks (.item()) --------------------------------
     def _ctrl_view(self, word: int, as_float: bool) -> torch.Tensor:
@@ -303,7 +408,121 @@ class TrainStep:
         """Per group: parameter names, element count, lr_scale, weight_decay (the implicit group last); None without groups."""
         return None if self._groups is None else tuple(dict(g) for g in self._groups)
 
+    # -- weight EMA --------------------------------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if self.ema is None:
+            raise RuntimeError(f"TrainStep.{what}: this TrainStep keeps no EMA (ema_decay=None)")
+
+    def reset_ema(self) -> None:
+        """Restart the EMA from the current parameters (after weights were loaded into the model)."""
+        self._need_ema("reset_ema")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.reset_ema: not inside ema_weights()")
+        self.ema.copy_(self.arena.flat)
+
+    def ema_state_dict(self) -> dict:
+        """``model.state_dict()``'s keys and shapes on the CPU, parameters taken from the EMA buffer and buffers from the model:
+        loads with ``strict=True`` into a fresh drop-in model, or into the reference."""
+        self._need_ema("ema_state_dict")
+        avg = self.arena.flat if self._ema_swapped else self.ema   # inside ema_weights() the two have changed places
+        params = dict(self.model.named_parameters(remove_duplicate=False))
+        out = {}
+        for k, v in self.model.state_dict().items():
+            r = self.arena.ranges.get(id(params[k])) if k in params else None
+            out[k] = (v.detach() if r is None else avg[r[0]:r[1]].view(v.shape)).to("cpu", copy=True)
+        return out
+
+    def _exchange_ema(self) -> None:
+        ops.swap_f32(self.arena.flat, self.ema)
+        for m in self._hip_modules:
+            m.invalidate_shadows()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model's parameters ARE the EMA: ``arena.flat`` and ``ts.ema`` exchange their contents in place (one
+        launch, no host sync, nothing allocated; every parameter view and every captured pointer stays valid) and the bf16 weight
+        shadows are rebuilt on the next forward.  On exit — also when the body raises — they change back.  ``step()`` and a
+        captured replay raise inside the block; so does entering it twice."""
+        self._need_ema("ema_weights")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.ema_weights: already inside ema_weights()")
+        self._exchange_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange_ema()
+            self._ema_swapped = False
+
+    # -- everything a step reads besides the model and the batch ---------------------------------------------------------------
+    def _state_meta(self) -> dict:
+        arena = self.arena
+        name_of = {}
+        for name, prm in self.model.named_parameters():
+            name_of.setdefault(id(prm), name)
+        hyper = dict(lr=float(self.lr), momentum=float(self.momentum), weight_decay=float(self.weight_decay),
+                     betas=[float(b) for b in self.betas], eps=float(self.eps))
+        meta = dict(optimizer=self.kind, hyper=hyper, device_path=self._ctrl is not None,
+                    layout=dict(names=[name_of[id(p)] for p in arena.params], offsets=[int(o) for o in arena.offsets],
+                                numels=[int(p.numel()) for p in arena.params], total=int(arena.numel)),
+                    groups=None, lr_table=None, clip=None, ema=None)
+        if self._ctrl is not None:
+            meta["lr_table"] = [float(x) for x in self.lr_table.cpu().tolist()]
+            meta["clip"] = [float(self.max_grad_norm), bool(self.skip_nonfinite)]
+        if self._groups is not None:
+            meta["groups"] = dict(table=[[_f32(g["lr_scale"]), _f32(g["weight_decay"])] for g in self._groups],
+                                  ids=[int(g) for g in arena._group_ids])
+        if self.ema is not None:
+            meta["ema"] = dict(decay=self.ema_decay, warmup=self.ema_warmup, every=self.ema_every)
+        return meta
+
+    def _state_buffers(self) -> dict:
+        bufs = {}
+        if self.mom is not None:
+            bufs["mom"] = self.mom
+        if self.kind == "adamw":
+            bufs["m"], bufs["v"] = self.m, self.v
+        if self._ctrl is not None:
+            bufs["ctrl"] = self._ctrl
+        if self.ema is not None:
+            bufs["ema"] = self.ema
+        return bufs
+
+    def state_dict(self) -> dict:
+        """Optimizer kind and hyper-parameters, ``t``, the momentum buffer or AdamW's moments, the control block and lr table, the
+        group table and ids, the EMA and its settings, and the arena's layout (names, offsets, sizes).  CPU tensors, numbers,
+        strings, lists and dicts only: the file loads with ``torch.load(weights_only=True)``."""
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.state_dict: not inside ema_weights()")
+        sd = {"format": 1, "meta": self._state_meta(), "t": int(self.t)}
+        for k, b in self._state_buffers().items():
+            sd[k] = b.detach().to("cpu", copy=True)
+        if self._ctrl is not None:
+            sd["lr_table"] = self.lr_table.detach().to("cpu", copy=True)
+        if self._groups is not None:
+            sd["group_table"] = self._group_table.detach().to("cpu", copy=True)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Check ``sd`` against this object (``check_train_state``: ValueError naming the first difference, nothing changed), then
+        copy IN PLACE into the existing device buffers: no pointer changes, a step captured before the load stays valid."""
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.load_state_dict: not inside ema_weights()")
+        if not isinstance(sd, dict) or "meta" not in sd or "t" not in sd:
+            raise ValueError("TrainStep.load_state_dict: not a TrainStep.state_dict()")
+        check_train_state(sd["meta"], self._state_meta())
+        bufs = self._state_buffers()
+        for k, b in bufs.items():
+            src = sd.get(k)
+            if not isinstance(src, torch.Tensor) or src.dtype != b.dtype or src.shape != b.shape:
+                raise ValueError(f"TrainStep.load_state_dict: '{k}' must be a {b.dtype} tensor of shape {tuple(b.shape)}")
+        for k, b in bufs.items():
+            b.copy_(sd[k])
+        self.t = int(sd["t"])
+
     def step(self, inputs: dict, labels: torch.Tensor) -> torch.Tensor:
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.step: inside ema_weights() the parameters are the EMA; leave the block before training")
         arena = self.arena
         arena.zero_grad(set_to_none=True)
         if self.reducer is not None:
@@ -362,6 +581,9 @@ class TrainStep:
             else:
                 ops.adamw_step(arena.flat[sl], arena.grad[sl], self.m[sl], self.v[sl], self.lr, self.betas[0],
                                self.betas[1], self.eps, self.weight_decay, self.t, gscale)
+        if self.ema is not None:   # after the optimizer: reads the verdict and the counter this step's optim_ctrl_update wrote
+            ops.ema_update_ctrl(self.ema, arena.flat, self._ctrl, self._ema_w, warmup=self.ema_warmup, every=self.ema_every,
+                                reverse=self.ema_reverse_walk)
         for m in self._hip_modules:
             m.invalidate_shadows()
         return loss.detach()
@@ -374,10 +596,12 @@ class TrainStep:
         steps on ``inputs`` run before the capture (lazy initialisation must not happen inside it); the captured step itself
         is only recorded.
         On the device-held path the learning-rate table index, AdamW's t and the skip counters are device state that the
-        captured kernels advance: a schedule moves across replays and AdamW can be captured.
+        captured kernels advance: a schedule moves across replays and AdamW can be captured; so is the EMA launch.
         Single-process only (the RCCL reduction is not captured)."""
         if self.reducer is not None:
             raise RuntimeError("TrainStep.capture: graph capture is only wired for single-GPU steps")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.capture: inside ema_weights() the parameters are the EMA; leave the block before training")
         if self.kind == "adamw" and self._ctrl is None:   # (checked BEFORE anything runs or is captured)
             raise RuntimeError("TrainStep.capture: AdamW bias correction is step-dependent; capture supports SGD")
         if hasattr(self.model, "overlap_text") and os.environ.get("LC2IS_GRAPH_OVERLAP", "1") == "0":
@@ -408,6 +632,9 @@ class TrainStep:
         self.t = t_before   # capture records the step; nothing ran
 
         def replay(new_inputs: dict, new_labels: torch.Tensor) -> torch.Tensor:
+            if self._ema_swapped:
+                raise RuntimeError("TrainStep replay: inside ema_weights() the parameters are the EMA; leave the block before "
+                                   "training")
             for k, v in new_inputs.items():
                 if v is not static_in[k]:
                     static_in[k].copy_(v, non_blocking=True)
