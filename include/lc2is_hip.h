@@ -628,6 +628,45 @@ int lc2is_aug_apply(const uint8_t* img, size_t img_bytes, const uint8_t* lab, si
                     const lc2is_aug_norm* norm /* HOST */, long pad_label, float* out_img, int64_t* out_lab,
                     lc2is_stream_t stream);
 
+/* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
+ * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
+ * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with
+ * loss_thresh = fp32(-log(thresh)) formed in fp64 by the caller; a valid pixel is KEPT iff l_i > L_eff (IEEE, strict: the pivot
+ * and its ties are dropped).  labels_out = label where kept, ignore_index elsewhere; the OHEM loss is the existing criterion on
+ * labels_out.
+ * replaces: mmseg's OHEMPixelSampler with a threshold / HRNet's OhemCrossEntropy (softmax, gather, sort, p < max(p_sorted[k],
+ *   thresh)) — torch.sort / topk over every pixel of the batch.
+ *
+ * lc2is_head_upsample_px: the forward half of lc2is_head_upsample_ce alone, S in {4, 8, 16} (else LC2IS_ERR_UNSUPPORTED): the same
+ * upsample products and softmax, one launch, no workspace, no gradient; loss_px fp32 [B,H,W] (16-byte aligned) receives l_i, 0
+ * where the pixel is not valid.  Bitwise reproducible.
+ * replaces: F.interpolate + F.cross_entropy(reduction="none") in front of the sampler. */
+int lc2is_head_upsample_px(const float* scores_lo, int ld, const int64_t* labels, float* loss_px, int B, int h, int w, int C,
+                           int S, int mode, long ignore_index, lc2is_stream_t stream);
+
+/* The 24-byte block lc2is_ohem_select writes.  n_valid = 0: k = -1, L = +inf (nothing exceeds the pivot of an empty set). */
+typedef struct {
+  int64_t n_valid;   /* valid pixels                                                  */
+  int64_t k;         /* min(min_kept_total, n_valid - 1)                              */
+  float L;           /* the valid loss of rank k, descending                          */
+  float L_eff;       /* fminf(L, loss_thresh): kept iff l_i > L_eff                   */
+} lc2is_ohem_info;
+
+/* Exact k-th largest on the device and the relabelling, over n = B*H*W values (1 <= n < 2^31), no host read, capturable.
+ * Most-significant-digit radix select, four 8-bit digits of the monotone uint32 image of the fp32 bits (sign-flipped; a NaN of
+ * either sign orders above +inf; -0 below +0).  Pass 0 reads loss_px + labels and writes the keys (0 = not valid) to the
+ * workspace; every pass counts the digit histogram of the keys that match the prefix found so far — 8 wave ballots of the digit
+ * bits, lane j combines them into the counts of bins 4j..4j+3 in registers — and a one-block launch sums the blocks' rows and
+ * picks the digit; the last launch writes labels_out and *info.  NO read-modify-write atomics, LDS included; the counts are
+ * integers: the same bytes every run.  loss_px, labels, labels_out, workspace: 16-byte aligned (else LC2IS_ERR_SHAPE);
+ * workspace >= lc2is_ohem_select_workspace_bytes(n) = 4 n + a fixed 0.5 MB of histogram rows (a pure host function; 0 for a
+ * refused n).  loss_thresh >= 0, min_kept_total >= 0, C >= 1 (else LC2IS_ERR_SHAPE).  info: lc2is_ohem_info on the device.
+ * replaces: the sort / topk of the samplers named above. */
+size_t lc2is_ohem_select_workspace_bytes(long n);
+int lc2is_ohem_select(const float* loss_px, const int64_t* labels, int64_t* labels_out, long n, int C, long ignore_index,
+                      float loss_thresh, long min_kept_total, void* info, void* workspace, size_t workspace_bytes,
+                      lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -503,6 +503,131 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_grp_ke
   }
 }
 
+// ---- per-pixel loss of the same head, forward only (the input of the OHEM selection, ohem.hip) ----
+// head_ce_grp_kernel's tiles, groups, units and forward product Wm x lo, and its softmax in the accumulator layout; nothing of its
+// backward: no gradient mirror in LDS, no slabs, no partials, no finish launch.  loss_px[b, Y, X] = lse - z_y in fp32 (plain CE: class
+// weights and label smoothing never enter the selection), 0 where the pixel is not counted.  The label's logit is still in the
+// accumulators when the maximum is taken: it is the element of tile t in the lane with dl[r] == 16 t, and one more 16-lane row sum of
+// that select brings it to every lane of the row.  Lane m == 0 of a row then holds the losses of four consecutive pixels of one
+// image row: one 16-byte store (S = 4: tiles start at X = -2 mod 4, the store is 8-byte aligned; a quad that crosses the image
+// edge leaves pixel by pixel).  A kernel of its own, so that the instantiations of head_ce_grp_kernel compile to what they were.
+typedef float __attribute__((ext_vector_type(4), aligned(4))) f32x4_u_t;
+
+template <int MODE, int TN, int S>
+__global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_px_grp_kernel(HeadArgs p, float* __restrict__ loss_px) {
+  constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;
+  constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;
+  constexpr int G = HT / S;
+  constexpr int F4 = G + NT - 1;
+  constexpr int NQ = NT * NT / 4;
+  constexpr int UPG = S * S / 16;
+  static_assert(S == 4 || S == 8 || S == 16, "group kernel: S x S pixel groups inside a 16 x 16 tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles_x = (p.W + S / 2 + HT - 1) / HT, tiles_y = (p.H + S / 2 + HT - 1) / HT;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int tyi = (blockIdx.x / tiles_x) % tiles_y, txi = blockIdx.x % tiles_x;
+  const int a0 = G * tyi - 1, b0 = G * txi - 1;
+  const int Y0 = S * a0 + S / 2, X0 = S * b0 + S / 2;
+  const int Cp = p.ld;
+  const int CS = Cp + HEAD_PAD;
+  float* s_lo = (float*)smem;
+  int* s_lab = (int*)(s_lo + F4 * F4 * CS);      // [16][16] pixels of the tile: -2 outside the image, -1 not counted, else label
+  const int fsize = F4 * F4 * Cp;
+  for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
+    const int cell = i / Cp, c = i % Cp;
+    int ry = a0 - OFF + cell / F4, rx = b0 - OFF + cell % F4;
+    ry = ry < 0 ? 0 : (ry > p.h - 1 ? p.h - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > p.w - 1 ? p.w - 1 : rx);
+    *reinterpret_cast<float4*>(s_lo + cell * CS + c) =
+        *reinterpret_cast<const float4*>(p.lo + (((size_t)b * p.h + ry) * p.w + rx) * p.ld + c);
+  }
+  if (tid < HT * HT) {
+    const int Y = Y0 + (tid >> 4), X = X0 + (tid & 15);
+    int code = -2;
+    if (Y >= 0 && X >= 0 && Y < p.H && X < p.W) {
+      code = -1;
+      const int64_t lab64 = p.labels[((size_t)b * p.H + Y) * p.W + X];
+      if (lab64 != (int64_t)p.ignore_index && lab64 >= 0 && lab64 < p.C) code = (int)lab64;
+    }
+    s_lab[tid] = code;
+  }
+  __syncthreads();
+
+  const int m = lane & 15, kq = lane >> 4;
+  const float NEG = -__builtin_inff();
+  constexpr float LOG2E = 1.4426950408889634f;
+  int cell_off[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
+
+#pragma unroll 1
+  for (int g2 = 0; g2 < 2; ++g2) {
+    const int u = 2 * wid + g2, gi = u / UPG, rt = u % UPG, gy = gi / G, gx = gi % G;
+    const int Yb = Y0 + S * gy, Xb = X0 + S * gx;
+    const int prow = rt * (16 / S);
+    const bool active = !(Yb + prow >= p.H || Xb >= p.W || Yb + prow + 16 / S - 1 < 0 || Xb + S - 1 < 0);  // wave-uniform
+    if (!active) continue;
+    const int gbase = (gy * F4 + gx) * CS;
+    const int py_m = prow + m / S, px_m = m % S;
+    float Af[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + kq) / NT) * tap_w<MODE, S>(px_m, (4 * q + kq) % NT);
+    f32x4_t acc[TN];
+#pragma unroll
+    for (int t = 0; t < TN; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const float* bp = s_lo + gbase + cell_off[q] + m;
+      float bv[TN];
+#pragma unroll
+      for (int t = 0; t < TN; ++t) bv[t] = bp[16 * t];
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Af[q], bv[t], acc[t], 0, 0, 0);
+    }
+    const int py4 = prow + (4 * kq) / S, px4 = (4 * kq) % S;
+    const i32x4_t lab4 = *reinterpret_cast<const i32x4_t*>(s_lab + (S * gy + py4) * 16 + S * gx + px4);
+    int dl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dl[r] = lab4[r] >= 0 ? lab4[r] - m : -1;
+    float mx[4] = {NEG, NEG, NEG, NEG}, sum[4] = {0.f, 0.f, 0.f, 0.f}, zy[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C (a counted label is below C: never selected there)
+        if (16 * t + m >= p.C) acc[t] = f32x4_t{NEG, NEG, NEG, NEG};
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        mx[r] = fmaxf(mx[r], acc[t][r]);
+        zy[r] += dl[r] == 16 * t ? acc[t][r] : 0.f;
+      }
+    }
+    float mxl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); mxl[r] = -mx[r] * LOG2E; }
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sum[r] += __builtin_amdgcn_exp2f(__builtin_fmaf(acc[t][r], LOG2E, mxl[r]));
+    f32x4_u_t out;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float l = (mx[r] + __logf(row16_sum(sum[r]))) - row16_sum(zy[r]);
+      out[r] = lab4[r] >= 0 ? l : 0.f;
+    }
+    if (m == 0) {
+      float* o = loss_px + ((size_t)b * p.H + (Yb + py4)) * p.W + Xb + px4;   // (formed only where a pixel of the quad is inside)
+      if (lab4[0] != -2 && lab4[3] != -2) {
+        *reinterpret_cast<f32x4_u_t*>(o) = out;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (lab4[r] != -2) o[r] = out[r];
+      }
+    }
+  }
+}
+
 // dlo[b, y, x, :] = sum of the footprint cells that map to low-res cell (y, x), over the tiles that cover it, in a fixed order;
 // loss_sum = sum of the blocks' partials in block order.  One wave per low-res cell (lane = channel quad), four cells per block.
 // Tile t along an axis covers the unclamped low-res indices [G t - 1 - OFF, G t - 1 - OFF + F4); indices below 0 / above n - 1 are
@@ -926,6 +1051,41 @@ extern "C" int lc2is_head_upsample_ce_opts(const float* scores_lo, int ld, const
                                            lc2is_stream_t stream) {
   return head_upsample_ce(scores_lo, ld, labels, dscores_lo, scores_hi, loss_sum, B, h, w, C, S, mode, ignore_index,
                           grad_scale, class_weight, label_smoothing, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lc2is_head_upsample_px(const float* scores_lo, int ld, const int64_t* labels, float* loss_px, int B, int h,
+                                      int w, int C, int S, int mode, long ignore_index, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!scores_lo || !labels || !loss_px) return LC2IS_ERR_NULL;
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || ld < C || ld > CMAX || ld % 64) return LC2IS_ERR_SHAPE;
+  if (((size_t)scores_lo | (size_t)loss_px) & 15) return LC2IS_ERR_SHAPE;
+  if (!(S == 4 || S == 8 || S == 16)) return LC2IS_ERR_UNSUPPORTED;
+  if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return LC2IS_ERR_UNSUPPORTED;
+  const int H = h * S, W = w * S;
+  HeadArgs a{scores_lo, ld, labels, nullptr, nullptr, nullptr, B, h, w, H, W, C, S, mode, ignore_index,
+             0.f, nullptr, nullptr, 0, nullptr, 0.f};
+  const int nt = (C + 15) / 16;
+  const int tn = nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12));   // head_upsample_ce's channel-tile counts
+  const HeadGrpPlan gp = head_grp_plan(B, h, w, C, S, mode, false);
+  // the footprint and the tile's labels: at most 7 * 7 * 196 * 4 + 1024 bytes, inside the default dynamic LDS limit
+  const int lds = gp.f4 * gp.f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int);
+#define LC2IS_HEAD_PX(MODE_, TN_, S_) \
+  hipLaunchKernelGGL((head_px_grp_kernel<MODE_, TN_, S_>), dim3(B * gp.t4), dim3(HEAD_THREADS), lds, stream, a, loss_px)
+#define LC2IS_HEAD_PX_TN(MODE_, S_)                                                                 \
+  do {                                                                                              \
+    if (tn == 4) LC2IS_HEAD_PX(MODE_, 4, S_); else if (tn == 8) LC2IS_HEAD_PX(MODE_, 8, S_);        \
+    else if (tn == 10) LC2IS_HEAD_PX(MODE_, 10, S_); else LC2IS_HEAD_PX(MODE_, 12, S_);             \
+  } while (0)
+#define LC2IS_HEAD_PX_S(MODE_)                                                                                            \
+  do {                                                                                                                    \
+    if (S == 4) LC2IS_HEAD_PX_TN(MODE_, 4); else if (S == 8) LC2IS_HEAD_PX_TN(MODE_, 8); else LC2IS_HEAD_PX_TN(MODE_, 16); \
+  } while (0)
+  if (mode == LC2IS_INTERP_BICUBIC) LC2IS_HEAD_PX_S(LC2IS_INTERP_BICUBIC);
+  else LC2IS_HEAD_PX_S(LC2IS_INTERP_BILINEAR);
+#undef LC2IS_HEAD_PX_S
+#undef LC2IS_HEAD_PX_TN
+#undef LC2IS_HEAD_PX
+  return lc2is_check_launch();
 }
 
 extern "C" int lc2is_ce_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, int B,

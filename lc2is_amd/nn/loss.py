@@ -85,6 +85,53 @@ class CrossEntropyLoss(nn.Module):
         return _CEOptsFn.apply(input, target, self.ignore_index, self.weight, self.label_smoothing, self.reduction)
 
 
+def check_ohem(thresh, min_kept) -> tuple[float, int]:
+    """(thresh, min_kept per image) of an OHEM selection, validated: thresh in (0, 1], min_kept an integer >= 0."""
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 < float(thresh) <= 1.0:
+        raise ValueError(f"OHEM thresh must be a number in (0, 1] (thresh=None, pure top-k, is not implemented), got {thresh!r}")
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 0:
+        raise ValueError(f"OHEM min_kept must be an integer >= 0 (pixels per image), got {min_kept!r}")
+    return float(thresh), int(min_kept)
+
+
+class OhemCrossEntropyLoss(CrossEntropyLoss):
+    """Cross-entropy over the hard pixels only (mmseg's OHEMPixelSampler with a threshold, HRNet's OhemCrossEntropy), selected on
+    the device.  With l_i the plain per-pixel CE (weights and smoothing never enter the selection), K = min_kept * batch size,
+    k = min(K, n_valid - 1) and L the valid loss of rank k (descending): a valid pixel is kept iff l_i > min(L, -log(thresh)) —
+    the pixels whose probability of the right class is below ``thresh``, and at least about ``min_kept`` per image when fewer are.
+    The loss is this module's CrossEntropyLoss (weight, label_smoothing, 'mean' over the kept weighted count / 'sum') with every
+    other pixel's label set to ``ignore_index``.  The selection applies while ``self.training``; in ``eval()`` this is the plain
+    criterion.  ``last_info``: the device block (n_valid, k, L, L_eff) of the last selection (``ops.ohem_info_fields`` reads it; nothing
+    here syncs), ``last_labels``: the labels the criterion was then applied to.
+    Under data parallelism each rank selects over its own batch."""
+
+    def __init__(self, thresh: float = 0.7, min_kept: int = 100_000, weight=None, ignore_index: int = -100,
+                 reduction: str = "mean", label_smoothing: float = 0.0) -> None:
+        super().__init__(weight=weight, ignore_index=ignore_index, reduction=reduction, label_smoothing=label_smoothing)
+        if self.reduction == "none":
+            raise ValueError("OhemCrossEntropyLoss: reduction='none' has no meaning for a selection that drops pixels "
+                             "(use 'mean' or 'sum')")
+        self.thresh, self.min_kept = check_ohem(thresh, min_kept)
+        self.last_labels = self.last_info = None
+
+    @property
+    def ohem(self) -> tuple[float, int]:
+        return self.thresh, self.min_kept
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if not self.training:
+            return super().forward(input, target)
+        require_cuda(input, "logits")
+        if input.dim() != 4 or target.dim() != 3:
+            raise ValueError("lc2is_amd OhemCrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        lg = input.detach().float().contiguous()
+        lb = target.contiguous()
+        _, _, lpx = ops.ce_nchw_fwd(lg, lb, self.ignore_index, per_pixel=True)   # plain CE per pixel: no weights, no smoothing
+        self.last_labels, self.last_info = ops.ohem_select(lpx, lb, input.shape[1], self.thresh, self.min_kept * input.shape[0],
+                                                           self.ignore_index)
+        return super().forward(input, self.last_labels)
+
+
 class _AuxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, ignore_index, S, weight, label_smoothing, reduction):

@@ -21,6 +21,7 @@ from .. import ops
 from .base import HipModule, grad_buf, linear_bwd_params, require_cuda, vec_grad
 from .clip import ClipArch, ImageEncoderCLIP, TextEncoderCLIP, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer
+from .loss import check_ohem
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
 KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product)
@@ -100,8 +101,8 @@ class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -109,7 +110,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -166,7 +167,7 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -176,6 +177,10 @@ class BaseModelWithText(HipModule):
             _, _, hi = ops.head_upsample_ce(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_scores=True,
                                             want_loss=False)
             return hi, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None)
+        labels = labels.contiguous()
+        if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
+            labels, info = ops.ohem_labels(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index, ohem)
+            self.last_ohem = (labels, info)
         # the kernel writes the gradient of the SUM of the per-pixel losses and counts the pixels it kept (labels that are
         # negative, == ignore_index or >= K are skipped, head.hip); the 1/count of nn.CrossEntropyLoss's mean is folded
         # into the upstream-gradient multiply of _head_bwd, from the device-side count (no host sync, no label pass)
@@ -267,14 +272,17 @@ class BaseModelWithText(HipModule):
         return dict(outputs=logits)
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", ohem=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
-        nn.CrossEntropyLoss."""
+        nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
+        (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels the head saw, the device info block)."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
+        if ohem is not None:
+            ohem = check_ohem(*ohem)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem)
 
     @torch.no_grad()
     def forward_tuple(self, inputs: dict):

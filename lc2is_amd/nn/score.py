@@ -17,6 +17,7 @@ from torch import nn
 
 from .. import ops
 from .base import require_cuda
+from .loss import check_ohem
 from .model import _reduce, fused_loss_options
 
 KPAD = 192
@@ -59,7 +60,7 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -69,6 +70,9 @@ class _ScoreFn(torch.autograd.Function):
                                             want_loss=False)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
             return hi
+        if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
+            labels, info = ops.ohem_labels(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index, ohem)
+            owner.last_ohem = (labels, info)
         if loss_opts is not None:   # class weights / label smoothing / 'sum' (loss2[1] = sum_i w_{y_i})
             weight, label_smoothing, reduction = loss_opts
             loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
@@ -96,7 +100,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None
+        return dv, dt, None, None, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -113,9 +117,14 @@ class ScoreMapTail(nn.Module):
         return _ScoreFn.apply(visual_embeddings, text_embeddings, None, self.scale_factor, -100, save)
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
-             ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
-        """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss."""
+             ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
+             ohem=None) -> torch.Tensor:
+        """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
+        per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
+        the head saw, the device info block)."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
+        if ohem is not None:
+            ohem = check_ohem(*ohem)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
-        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts)
+        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self)

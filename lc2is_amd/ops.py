@@ -8,6 +8,7 @@ allocator, nothing else).  There is no CPU path: a non-CUDA tensor is an error.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -77,6 +78,9 @@ _ARGTYPES = {
     "lc2is_ce_nchw_fwd_ordered": [_P, _P, _P, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P, _Z, _P],
     "lc2is_ce_nchw_bwd_opts": [_P, _P, _P, _P, _F, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
     "lc2is_upsample_bwd_nchw": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "lc2is_head_upsample_px": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P],
+    "lc2is_ohem_select_workspace_bytes": [_L],
+    "lc2is_ohem_select": [_P, _P, _P, _L, _I, _L, _F, _L, _P, _P, _Z, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -883,6 +887,72 @@ def head_upsample_ce(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, 
                                            w, C, S, mode, ignore_index, grad_scale, _ptr(ws), nbytes, _stream())
     _lib.check(rc, f"head_upsample_ce B={B} h={h} w={w} C={C} S={S}")
     return loss, dlo, hi
+
+
+# ---- online hard example mining: per-pixel loss of the fused head, exact k-th largest on the device, relabelling ----
+def head_upsample_px(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                     ignore_index: int = -100):
+    """scores_lo fp32 [B*h*w, ld], labels int64 [B, h*S, w*S] -> per-pixel plain CE of the upsampled scores, fp32 [B, h*S, w*S]
+    (0 where the pixel is not counted): head_upsample_ce's forward alone (S = 4 / 8 / 16), one launch, no gradient."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    if not scores_lo.is_contiguous():
+        raise RuntimeError("lc2is_amd.head_upsample_px: scores_lo must be contiguous")
+    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.head_upsample_px: labels must be contiguous [{B},{h*S},{w*S}]")
+    lpx = torch.empty((B, h * S, w * S), dtype=torch.float32, device=scores_lo.device)
+    _lib.check(_fn("lc2is_head_upsample_px")(_ptr(scores_lo), scores_lo.shape[1], _ptr(labels), _ptr(lpx), B, h, w, C, S, mode,
+                                             ignore_index, _stream()), f"head_upsample_px B={B} h={h} w={w} C={C} S={S}")
+    return lpx
+
+
+OHEM_INFO_WORDS = 3   # lc2is_ohem_info as int64 [3]: n_valid, k, then (L, L_eff) as the two fp32 halves of the third word
+
+
+def ohem_loss_thresh(thresh: float) -> float:
+    """-log(thresh) formed in fp64 and rounded to fp32 once: the loss a pixel must exceed when the threshold binds."""
+    if not 0.0 < thresh <= 1.0:
+        raise ValueError(f"OHEM thresh must be in (0, 1], got {thresh}")
+    return float(torch.tensor(-math.log(thresh), dtype=torch.float64).to(torch.float32))
+
+
+def ohem_select(loss_px, labels, C: int, thresh: float, min_kept_total: int, ignore_index: int = -100):
+    """Hard-pixel selection over all ``loss_px.numel()`` pixels: returns (labels_out, info).  A pixel is valid iff
+    label != ignore_index and 0 <= label < C; k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (descending);
+    L_eff = min(L, fp32(-log(thresh))); labels_out = label where valid and loss > L_eff, ignore_index elsewhere.  ``info``: the
+    device block lc2is_ohem_info as int64 [3] (``ohem_info_fields`` reads it; nothing here syncs).  Exact, no atomics, the same
+    bytes every run; captures into a graph."""
+    _chk(loss_px, torch.float32, "loss_px", None); _chk(labels, torch.int64, "labels", None)
+    if loss_px is None or labels is None or loss_px.shape != labels.shape or not loss_px.is_contiguous() or not labels.is_contiguous():
+        raise RuntimeError("lc2is_amd.ohem_select: loss_px (fp32) and labels (int64) must be contiguous and of one shape")
+    if int(min_kept_total) < 0:
+        raise ValueError(f"OHEM min_kept must be >= 0, got {min_kept_total}")
+    tau = ohem_loss_thresh(thresh)
+    n = loss_px.numel()
+    need = _fn("lc2is_ohem_select_workspace_bytes")(n)
+    if need == 0:
+        raise RuntimeError(f"lc2is_amd.ohem_select: 1 <= numel < 2^31 required, got {n}")
+    dev = loss_px.device
+    ws = workspace(need, dev, "ohem_select")
+    out = torch.empty_like(labels)
+    info = torch.empty(OHEM_INFO_WORDS, dtype=torch.int64, device=dev)
+    _lib.check(_fn("lc2is_ohem_select")(_ptr(loss_px), _ptr(labels), _ptr(out), n, C, ignore_index, tau, int(min_kept_total),
+                                        _ptr(info), _ptr(ws), ws.numel(), _stream()), f"ohem_select n={n}")
+    return out, info
+
+
+def ohem_info_fields(info) -> dict:
+    """The info block of ``ohem_select`` on the host (this reads the device: a sync): n_valid, k, L, L_eff."""
+    host = info.detach().cpu()
+    L, L_eff = host[2:3].view(torch.float32).tolist()
+    return dict(n_valid=int(host[0]), k=int(host[1]), L=L, L_eff=L_eff)
+
+
+def ohem_labels(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int, ignore_index: int, ohem):
+    """The two launches every fused head shares in front of its CE call: per-pixel loss of the upsampled scores, then the
+    selection.  ``ohem`` = (thresh, min_kept per image).  Returns (labels_out, info)."""
+    thresh, min_kept = ohem
+    lpx = head_upsample_px(scores_lo, labels, B, h, w, C, S, mode, ignore_index=ignore_index)
+    return ohem_select(lpx, labels, C, thresh, int(min_kept) * B, ignore_index)
 
 
 def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, label_smoothing: float = 0.0,

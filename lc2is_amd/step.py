@@ -15,7 +15,10 @@ a single fused HIP launch and the data-parallel reduction is over one contiguous
 the remaining backward (``lc2is_amd.dp.GradReducer``).
 
 ``criterion``: an ``lc2is_amd.nn.CrossEntropyLoss`` (or ``torch.nn.CrossEntropyLoss``) whose ``ignore_index``, ``weight``,
-``label_smoothing`` and ``reduction`` ('mean' / 'sum') configure the fused head; default: ``CrossEntropyLoss()``.
+``label_smoothing`` and ``reduction`` ('mean' / 'sum') configure the fused head; default: ``CrossEntropyLoss()``.  An
+``lc2is_amd.nn.OhemCrossEntropyLoss`` adds its hard-pixel selection in front of the fused head (two launches and the selection's,
+all on the device: eager, captured, under a reducer — each rank selects over its own batch — and with the device-held options);
+``ohem_info`` is the last selection's device info block.
 
 The device-held path (opt-in: any of ``lr_schedule``, ``max_grad_norm``, ``skip_nonfinite``, ``device_state``) adds what the
 reference's loop has around ``optimizer.step()``:
@@ -46,6 +49,12 @@ from .nn.base import HipModule, ParamArena
 
 
 _DEFAULT_LR = 1e-5
+
+
+def _accepts_ohem(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "ohem" in inspect.signature(fl).parameters
 
 
 def lr_table_from_torch(make_scheduler, base_lr: float, steps: int) -> torch.Tensor:
@@ -321,8 +330,9 @@ class TrainStep:
             raise ValueError(f"TrainStep: max_grad_norm must be > 0 (or None / inf for no clipping), got {max_grad_norm}")
         table = _lr_table(lr_schedule, schedule_steps, lr) if (device_path or schedule_steps is not None) else None
         self._loss_opts = False
+        self._ohem = False
         if criterion is not None:
-            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss
+            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, OhemCrossEntropyLoss
             if not isinstance(criterion, (CrossEntropyLoss, nn.CrossEntropyLoss)) or isinstance(criterion, AuxiliaryLoss):
                 raise TypeError("TrainStep: criterion must be a CrossEntropyLoss (lc2is_amd.nn or torch.nn)")
             if ignore_index is not None and ignore_index != -100:
@@ -332,6 +342,10 @@ class TrainStep:
             ignore_index = criterion.ignore_index
             self._loss_opts = (criterion.weight is not None or criterion.label_smoothing != 0.0
                                or criterion.reduction != "mean")
+            self._ohem = isinstance(criterion, OhemCrossEntropyLoss)
+            if self._ohem and not _accepts_ohem(model):
+                raise TypeError("TrainStep: an OhemCrossEntropyLoss needs a model whose forward_loss takes ohem= "
+                                "(BaseModelWithText); the compose models do not select hard pixels")
         self.criterion = criterion
         self.model = model
         self.arena = ParamArena(model)
@@ -402,6 +416,21 @@ class TrainStep:
     @property
     def applied_steps(self) -> torch.Tensor:
         return self._ctrl_view(ops.CTRL_APPLIED, False)
+
+    @property
+    def ohem_info(self):
+        """The device info block (n_valid, k, L, L_eff: ``ops.ohem_info_fields``) of the last step's hard-pixel selection, None
+        before the first step; ``ohem_labels`` are the labels the head saw.  After ``capture`` both are the graph's own buffers:
+        a replay rewrites them in place."""
+        if not self._ohem:
+            raise RuntimeError("TrainStep.ohem_info: the criterion is not an OhemCrossEntropyLoss")
+        return self.criterion.last_info
+
+    @property
+    def ohem_labels(self):
+        if not self._ohem:
+            raise RuntimeError("TrainStep.ohem_labels: the criterion is not an OhemCrossEntropyLoss")
+        return self.criterion.last_labels
 
     @property
     def param_groups(self):
@@ -527,7 +556,14 @@ class TrainStep:
         arena.zero_grad(set_to_none=True)
         if self.reducer is not None:
             self.reducer.begin_step()
-        if self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
+        if self._ohem:   # hard-pixel selection in front of the fused head, while the criterion is in training mode (as its forward)
+            c = self.criterion
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
+                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction,
+                                           ohem=c.ohem if c.training else None)
+            if c.training:
+                c.last_labels, c.last_info = self.model.last_ohem
+        elif self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
             c = self.criterion
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
                                            label_smoothing=float(c.label_smoothing), reduction=c.reduction)
