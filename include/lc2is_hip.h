@@ -191,9 +191,16 @@ int lc2is_ln_partials_reduce(const lc2is_ln_partials* items, int n, lc2is_stream
  * O[b,s,h,:] = softmax_k( scale * Q[b,s,h,:]·K[b,k,h,:] + kbias[b,k] (+ causal) ) · V[b,k,h,:]
  * Q/K/V/O are token-major 2-D views: row (b*S + s), head h in columns [h*D,(h+1)*D), row stride ld*
  * (elements) — Q, K, V may alias one packed projection buffer.  D in {64, 96, 128}.
- * kbias: fp32 [B,Sk] additive key bias (0 = attend, -inf = masked; this is key_padding_mask /
- * attention_mask), NULL = none.  causal != 0 adds the lower-triangular mask (requires Sq == Sk).
- * lse2 (optional, fp32 [B,H,Sq]): log2-domain log-sum-exp of the scaled, masked scores, saved for backward.
+ * kbias: fp32 [B,Sk] additive key bias in natural-log units, NULL = none.  Per key it is any finite value or -inf
+ * (masked); 0 / -inf is key_padding_mask / attention_mask, and the masked keys may be any subset, not only a suffix.
+ * +inf and NaN are not allowed.  causal != 0 adds the lower-triangular mask (requires Sq == Sk).
+ * lse2 (optional, fp32 [B,H,Sq]): log2-domain log-sum-exp of the scaled, biased, masked scores, saved for backward.
+ * Empty rows: a query row with no visible key (every key -inf, the causal mask included) gives O = 0 and lse2 = -inf;
+ * the backward gives that row dQ = 0 and takes nothing from it into dK / dV.  This deliberately differs from torch,
+ * whose softmax over an all -inf row is NaN.
+ * Masked keys: their dK / dV rows are 0, and their K / V rows do not influence any output — provided they are finite
+ * (a masked probability is an exact 0, and 0 * NaN or 0 * Inf is NaN here as in torch).
+ * tests/test_gpu_attention_masks.py holds all of this row by row against fp64.
  * replaces: hf:modeling_clip.py:259-277 eager_attention_forward (+ :298-335), and the attention core of
  *   torch:nn/functional.py multi_head_attention_forward used by model/decoder.py:9-21. */
 int lc2is_attention_fwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, void* O,
@@ -202,6 +209,7 @@ int lc2is_attention_fwd(const void* Q, int ldq, const void* K, int ldk, const vo
 
 /* Backward of lc2is_attention_fwd: dQ, dK, dV (bf16, same 2-D strided views as Q/K/V — they may alias one
  * packed dQKV buffer) from dO, the forward's O and lse2.  `delta` is fp32 [B,H,Sq] scratch (rowsum(dO*O)).
+ * kbias / causal as in the forward (the same values must be passed); empty rows and masked keys as stated there.
  * Two launches (dQ; then dK/dV), no atomics: bitwise reproducible.
  * replaces: autograd of the attention cores above (reference engine.py:100 loss.backward()). */
 int lc2is_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv,

@@ -28,7 +28,7 @@ struct AttnFwdArgs {
   const bf16_t* V; int ldv;
   bf16_t* O; int ldo;
   float* lse2;          // [B,H,Sq], log2-domain logsumexp of the scaled scores (for backward), may be null
-  const float* kbias;   // [B,Sk] additive key bias in natural-log units (0 / -inf), may be null
+  const float* kbias;   // [B,Sk] additive key bias in natural-log units (any finite value, or -inf = masked), may be null
   int B, H, Sq, Sk;
   float scale_log2;     // softmax scale * log2(e)
   int causal;
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256, NQ == 2 ? (D == 64 ? 2 : 1) : ((D == 64) ? 3 :
           const int key = key0 + 8 * c + j;
           float sc = st[4 * c + j];
           if (key >= p.Sk) sc = NEG_INF;                                                       // key tail (the tile's zero rows)
-          else if (p.kbias) sc += p.kbias[(size_t)b * p.Sk + key] * 1.44269504088896341f;      // 0 / -inf key padding
+          else if (p.kbias) sc += p.kbias[(size_t)b * p.Sk + key] * 1.44269504088896341f;      // finite bias, or -inf key padding
           if (diag && key > qr) sc = NEG_INF;
           st[4 * c + j] = sc;
         }
@@ -345,6 +345,8 @@ __global__ __launch_bounds__(256, NQ == 2 ? (D == 64 ? 2 : 1) : ((D == 64) ? 3 :
   for (int g = 0; g < NQ; ++g) {
     const float lsum = lsum2[g][0] + lsum2[g][1];
     const float l_tot = lsum + __shfl_xor(lsum, 32, 64);
+    // a row that met no visible key (never `counted`: every key -inf, causal mask included) has O = 0, l = 0: it leaves as O = 0,
+    // lse2 = -inf, which both backward kernels map to +inf so that its P is 0 everywhere (lc2is_hip.h, "Empty rows")
     const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
     if (p.lse2 && hh == 0 && qrow[g] < p.Sq)
       p.lse2[((size_t)b * p.H + head) * p.Sq + qrow[g]] = l_tot > 0.f ? m_ref[g] + __builtin_amdgcn_logf(l_tot) : NEG_INF;

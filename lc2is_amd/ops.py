@@ -491,7 +491,10 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, H: 
                   scale: float, *, causal: bool = False, kbias: torch.Tensor | None = None,
                   save_lse: bool = True, out: torch.Tensor | None = None, dropout_p: float = 0.0, seed: int = 0):
     """q [B*Sq, H*D], k/v [B*Sk, H*D] bf16 2-D views (any row stride).  Returns (o [B*Sq, H*D] bf16, lse2).
-    dropout_p > 0: dropout on the attention probabilities, decisions = f(seed, (b,h,q), key) (pass the same to attention_bwd)."""
+    dropout_p > 0: dropout on the attention probabilities, decisions = f(seed, (b,h,q), key) (pass the same to attention_bwd).
+    kbias: fp32 contiguous [B,Sk] additive key bias, per key any finite value or -inf (masked); any subset of the keys may be
+    masked.  A query row with no visible key gives O = 0 and lse2 = -inf (torch gives NaN).  The K / V rows of masked keys
+    do not matter as long as they are finite."""
     _chk(q, torch.bfloat16, "q"); _chk(k, torch.bfloat16, "k"); _chk(v, torch.bfloat16, "v")
     _chk(kbias, torch.float32, "kbias")
     if q.shape != (B * Sq, H * D) or k.shape != (B * Sk, H * D) or v.shape != (B * Sk, H * D):
@@ -516,7 +519,9 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, H: 
 def attention_bwd(q, k, v, o, do, lse2, B: int, H: int, Sq: int, Sk: int, D: int, scale: float, *,
                   causal: bool = False, kbias: torch.Tensor | None = None, dq=None, dk=None, dv=None,
                   dropout_p: float = 0.0, seed: int = 0):
-    """Returns (dq, dk, dv) bf16; dq/dk/dv may be preallocated 2-D views (e.g. slices of a packed dQKV)."""
+    """Returns (dq, dk, dv) bf16; dq/dk/dv may be preallocated 2-D views (e.g. slices of a packed dQKV).
+    kbias / causal / dropout_p / seed as passed to attention_fwd.  A row whose lse2 is -inf (no visible key) gets dq = 0 and
+    gives nothing to dk / dv; the dk / dv rows of masked keys are 0."""
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
         _chk(t, torch.bfloat16, n)
     _chk(lse2, torch.float32, "lse2", 3); _chk(kbias, torch.float32, "kbias")
