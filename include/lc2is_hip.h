@@ -675,6 +675,47 @@ int lc2is_ohem_select(const float* loss_px, const int64_t* labels, int64_t* labe
                       float loss_thresh, long min_kept_total, void* info, void* workspace, size_t workspace_bytes,
                       lc2is_stream_t stream);
 
+/* ---- soft Dice + cross-entropy (a region loss beside the per-pixel ones) ----------------------------------------------
+ * p_i = softmax of the class scores at pixel i; V = the counted pixels (label != ignore_index && 0 <= label < C, inside the
+ * image: the rule of the CE head).  Per class over the whole batch of the call:
+ *   I_c = sum_{i in V, y_i = c} p_ic,   P_c = sum_{i in V} p_ic,   T_c = #{i in V : y_i = c},   U_c = P_c + T_c + smooth,
+ *   Dice = (1/C) sum_c m_c (1 - (2 I_c + smooth) / U_c),  m_c = [T_c > 0] if present_only else 1  (a class with U_c = 0 adds 0),
+ *   loss = ce_weight * CE_mean + dice_weight * Dice,       CE_mean = the plain mean CE over V.
+ * present_only != 0 is segmentation_models_pytorch's multiclass DiceLoss, present_only = 0 MONAI's DiceLoss(softmax, batch=True).
+ * Gradient: dDice/dz_ic = p_ic (beta_c - alpha_y [c = y] - q_i), q_i = sum_k p_ik beta_k - alpha_y p_iy, alpha_c = 2 m_c / (C U_c),
+ * beta_c = m_c (2 I_c + smooth) / (C U_c^2): it needs the batch sums, so every call is a statistics pass, a one-block launch
+ * that sums the blocks' rows in a fixed order (fp64; T and the pixel count are integers) and writes a device coefficient block,
+ * and (gradient) a second pass.  Nothing is read on the host; the chain captures into a graph.  NO read-modify-write atomics:
+ * loss, statistics and gradient are the same bytes every run.
+ * loss_out fp32 [4] = {loss, CE_mean, Dice, n_valid}; with no counted pixel all four and the gradient are 0 (nothing is NaN).
+ * ce_weight, dice_weight, smooth: finite and >= 0, the two weights not both 0 (else LC2IS_ERR_SHAPE).
+ * replaces: smp.losses.DiceLoss(mode="multiclass") / monai.losses.DiceLoss(softmax=True, batch=True) + nn.CrossEntropyLoss on
+ *   the upsampled logits (mmseg's [CrossEntropyLoss, DiceLoss] decode-head recipes), plus their autograd.
+ *
+ * lc2is_head_upsample_ce_dice: on the fused head of lc2is_head_upsample_ce (scores_lo fp32 [B,h,w,ld] channels-last, the xS
+ * upsample never materialised), S in {4, 8, 16} (else LC2IS_ERR_UNSUPPORTED), C <= ld <= 192, ld % 64 == 0.  dscores_lo (NULL:
+ * forward only, two launches) receives grad_scale * d loss / d scores_lo — the gradient of the scalar loss, not of a sum; all ld
+ * channels are overwritten.  class_stats: fp32 [3][ld] = I, P, T (zeros past C) or NULL.  workspace: 16-byte aligned,
+ * >= lc2is_head_upsample_ce_dice_workspace_bytes(...) (a pure host function; 0 for a call that would be refused). */
+size_t lc2is_head_upsample_ce_dice_workspace_bytes(int B, int h, int w, int C, int S, int mode, int want_grad);
+int lc2is_head_upsample_ce_dice(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo, float* loss_out,
+                                float* class_stats, int B, int h, int w, int C, int S, int mode, long ignore_index,
+                                float ce_weight, float dice_weight, float smooth, int present_only, float grad_scale,
+                                void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+
+/* The same loss on materialised NCHW fp32 logits [B,C,HW] (the drop-in criterion), C <= 192 (else LC2IS_ERR_UNSUPPORTED).
+ * _fwd: lse fp32 [B,HW] (or NULL), loss_out fp32 [4], class_stats fp32 [3][C] or NULL, and coef — fp32 [2 * cq + 4], cq = C rounded
+ * up to 4: alpha[cq] * dice_weight, beta[cq] * dice_weight, ce_weight / n_valid — which the caller keeps for _bwd.
+ * _bwd: dlogits = grad_scale * (*grad_scale_dev, NULL = 1) * d loss / d logits; every element is written.
+ * replaces: the same criteria applied to model(inputs)["outputs"] (evaluate.py:68, engine.py:94,150), plus their autograd. */
+size_t lc2is_ce_dice_nchw_workspace_bytes(int B, int C, long HW);
+int lc2is_ce_dice_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_out, float* class_stats,
+                           float* coef, int B, int C, long HW, long ignore_index, float ce_weight, float dice_weight,
+                           float smooth, int present_only, void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_ce_dice_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* coef,
+                           const float* grad_scale_dev, float grad_scale, float* dlogits, int B, int C, long HW,
+                           long ignore_index, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -628,6 +628,463 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_px_grp_ke
   }
 }
 
+// ---- soft Dice + cross-entropy on the same head (smp's multiclass DiceLoss / MONAI's batch=True form, combined with mean CE) ----
+// Over the counted pixels V of the whole batch, p = softmax of the upsampled scores:
+//   I_c = sum_{i in V, y_i = c} p_ic,  P_c = sum_{i in V} p_ic,  T_c = #{i in V: y_i = c},  U_c = P_c + T_c + s,
+//   Dice = (1/C) sum_c m_c (1 - (2 I_c + s) / U_c),  m_c = [T_c > 0] (present_only) or 1;  a class with U_c = 0 adds 0.
+// The gradient at one pixel needs the batch sums, so the loss takes two head passes with a small launch between them:
+//   head_dice_stats_grp_kernel  forward only: per-block [I | P | T] rows and (CE sum, counted pixels) partials;
+//   dice_coef_kernel            sums the blocks' rows in a fixed order (fp64; counts are integers) and writes the loss block and
+//                               alpha_c = 2 m_c / (C U_c), beta_c = m_c (2 I_c + s) / (C U_c^2), both times dice_weight * grad_scale,
+//                               and ce_scale = ce_weight * grad_scale / n_valid;
+//   head_ce_dice_grp_kernel     head_ce_grp_kernel's forward + backward products with the per-pixel gradient
+//                               dz_c = p_c (ce_scale + beta_c - q) - [c = y] (ce_scale + alpha_y p_y),  q = sum_k p_k beta_k - alpha_y p_y,
+//                               0 where the pixel is not counted; then head_finish_kernel's fixed-order gather of the slabs.
+// Kernels of their own, so that the instantiations of head_ce_grp_kernel / head_px_grp_kernel compile to what they were.  No
+// read-modify-write atomics: lane exchange, then LDS rows summed in wave order, then slabs summed in block order.
+struct DiceArgs {
+  float* ws_stat;      // [blocks][3][cq]: I, P (fp32) and T (int32 bits) of the block's counted pixels
+  float* ws_part;      // [blocks][2]: sum of the per-pixel CE (fp32), counted pixels (int32 bits)
+};
+
+template <int MODE, int TN, int S>
+__global__ __launch_bounds__(HEAD_THREADS, (S == 4 && TN <= 10 ? 2 : 1)) void head_dice_stats_grp_kernel(HeadArgs p, DiceArgs d) {
+  constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;
+  constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;
+  constexpr int G = HT / S;
+  constexpr int F4 = G + NT - 1;
+  constexpr int NQ = NT * NT / 4;
+  constexpr int UPG = S * S / 16;
+  constexpr int NCH = 16 * TN;                   // channels the tiles cover (>= cq)
+  constexpr int NW = HEAD_THREADS / 64;
+  static_assert(S == 4 || S == 8 || S == 16, "group kernel: S x S pixel groups inside a 16 x 16 tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles_x = (p.W + S / 2 + HT - 1) / HT, tiles_y = (p.H + S / 2 + HT - 1) / HT;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int tyi = (blockIdx.x / tiles_x) % tiles_y, txi = blockIdx.x % tiles_x;
+  const int a0 = G * tyi - 1, b0 = G * txi - 1;
+  const int Y0 = S * a0 + S / 2, X0 = S * b0 + S / 2;
+  const int Cp = p.ld;
+  const int CS = Cp + HEAD_PAD;
+  float* s_lo = (float*)smem;
+  int* s_lab = (int*)(s_lo + F4 * F4 * CS);      // [16][16] pixels of the tile: -2 outside the image, -1 not counted, else label
+  float* s_st = (float*)(s_lab + HT * HT);       // [waves][I | P][NCH]
+  __shared__ float s_ls[NW];
+  const int fsize = F4 * F4 * Cp;
+  for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
+    const int cell = i / Cp, c = i % Cp;
+    int ry = a0 - OFF + cell / F4, rx = b0 - OFF + cell % F4;
+    ry = ry < 0 ? 0 : (ry > p.h - 1 ? p.h - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > p.w - 1 ? p.w - 1 : rx);
+    *reinterpret_cast<float4*>(s_lo + cell * CS + c) =
+        *reinterpret_cast<const float4*>(p.lo + (((size_t)b * p.h + ry) * p.w + rx) * p.ld + c);
+  }
+  if (tid < HT * HT) {
+    const int Y = Y0 + (tid >> 4), X = X0 + (tid & 15);
+    int code = -2;
+    if (Y >= 0 && X >= 0 && Y < p.H && X < p.W) {
+      code = -1;
+      const int64_t lab64 = p.labels[((size_t)b * p.H + Y) * p.W + X];
+      if (lab64 != (int64_t)p.ignore_index && lab64 >= 0 && lab64 < p.C) code = (int)lab64;
+    }
+    s_lab[tid] = code;
+  }
+  __syncthreads();
+
+  const int m = lane & 15, kq = lane >> 4;
+  const float NEG = -__builtin_inff();
+  constexpr float LOG2E = 1.4426950408889634f;
+  int cell_off[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
+  float accI[TN], accP[TN];   // channel 16 t + m over this lane's pixels
+#pragma unroll
+  for (int t = 0; t < TN; ++t) accI[t] = accP[t] = 0.f;
+  float loss_acc = 0.f;
+
+#pragma unroll 1
+  for (int g2 = 0; g2 < 2; ++g2) {
+    const int u = 2 * wid + g2, gi = u / UPG, rt = u % UPG, gy = gi / G, gx = gi % G;
+    const int Yb = Y0 + S * gy, Xb = X0 + S * gx;
+    const int prow = rt * (16 / S);
+    const bool active = !(Yb + prow >= p.H || Xb >= p.W || Yb + prow + 16 / S - 1 < 0 || Xb + S - 1 < 0);  // wave-uniform
+    if (!active) continue;
+    const int gbase = (gy * F4 + gx) * CS;
+    const int py_m = prow + m / S, px_m = m % S;
+    float Af[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + kq) / NT) * tap_w<MODE, S>(px_m, (4 * q + kq) % NT);
+    f32x4_t acc[TN];   // logits, then exp
+#pragma unroll
+    for (int t = 0; t < TN; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const float* bp = s_lo + gbase + cell_off[q] + m;
+      float bv[TN];
+#pragma unroll
+      for (int t = 0; t < TN; ++t) bv[t] = bp[16 * t];
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Af[q], bv[t], acc[t], 0, 0, 0);
+    }
+    const int py4 = prow + (4 * kq) / S, px4 = (4 * kq) % S;
+    const i32x4_t lab4 = *reinterpret_cast<const i32x4_t*>(s_lab + (S * gy + py4) * 16 + S * gx + px4);
+    int dl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dl[r] = lab4[r] >= 0 ? lab4[r] - m : -1;
+    float mx[4] = {NEG, NEG, NEG, NEG}, sum[4] = {0.f, 0.f, 0.f, 0.f}, zy[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C (a counted label is below C: never selected there)
+        if (16 * t + m >= p.C) acc[t] = f32x4_t{NEG, NEG, NEG, NEG};
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        mx[r] = fmaxf(mx[r], acc[t][r]);
+        zy[r] += dl[r] == 16 * t ? acc[t][r] : 0.f;
+      }
+    }
+    float mxl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); mxl[r] = -mx[r] * LOG2E; }
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[t][r], LOG2E, mxl[r]));   // 0 past C
+        acc[t][r] = e;
+        sum[r] += e;
+      }
+    float inv[4];   // 1 / sum of the counted pixels, 0 elsewhere: p = e * inv adds nothing where the pixel is not counted
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float s = row16_sum(sum[r]);
+      const float l = (mx[r] + __logf(s)) - row16_sum(zy[r]);
+      const bool counted = lab4[r] >= 0;
+      inv[r] = counted ? 1.f / s : 0.f;
+      if (counted && m == 0) loss_acc += l;
+    }
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pr = acc[t][r] * inv[r];
+        accP[t] += pr;
+        accI[t] += dl[r] == 16 * t ? pr : 0.f;
+      }
+  }
+
+  // the four kq lane groups of a channel by lane exchange, the waves through LDS in wave order, the block's row as its own slab
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    accI[t] += __shfl_xor(accI[t], 16); accI[t] += __shfl_xor(accI[t], 32);
+    accP[t] += __shfl_xor(accP[t], 16); accP[t] += __shfl_xor(accP[t], 32);
+  }
+  if (kq == 0) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+      s_st[(wid * 2 + 0) * NCH + 16 * t + m] = accI[t];
+      s_st[(wid * 2 + 1) * NCH + 16 * t + m] = accP[t];
+    }
+  }
+  loss_acc = wave_sum(loss_acc);
+  if (lane == 0) s_ls[wid] = loss_acc;
+  __syncthreads();
+  if (tid < p.cq) {   // cq <= NCH
+    float I = 0.f, P = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { I += s_st[(w * 2 + 0) * NCH + tid]; P += s_st[(w * 2 + 1) * NCH + tid]; }
+    int T = 0;   // the tile's counted pixels of class tid (pixels outside the image and not-counted ones carry negative codes)
+    for (int i = 0; i < HT * HT; i += 4) {
+      const i32x4_t v = *reinterpret_cast<const i32x4_t*>(s_lab + i);
+      T += (v[0] == tid) + (v[1] == tid) + (v[2] == tid) + (v[3] == tid);
+    }
+    float* row = d.ws_stat + (size_t)blockIdx.x * 3 * p.cq;
+    row[tid] = I;
+    row[p.cq + tid] = P;
+    reinterpret_cast<int*>(row)[2 * p.cq + tid] = T;
+  }
+  if (wid == NW - 1) {   // (cq <= 192: the last wave holds no channel)
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < HT * HT / 64; ++j) n += __popcll(__ballot(s_lab[64 * j + lane] >= 0));
+    if (lane == 0) {
+      float l = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) l += s_ls[w];
+      d.ws_part[2 * (size_t)blockIdx.x] = l;
+      reinterpret_cast<int*>(d.ws_part)[2 * (size_t)blockIdx.x + 1] = n;
+    }
+  }
+}
+
+// One block.  Thread (slice, c) sums a quarter of the blocks' rows for class c in block order, the four slices are added in slice
+// order: a fixed order, in fp64 (as optim_ctrl_update_kernel sums its partials); T and the pixel count are integers.  Thread
+// (slice, 255) does the same for the (CE sum, counted pixels) partials.  coef = alpha[cq] | beta[cq] | ce_scale, 0, 0, 0.
+struct DiceCoefArgs {
+  const float* ws_stat; const float* ws_part;
+  int nblk, C, cq;
+  float ce_weight, dice_weight, smooth, grad_scale;
+  int present_only;
+  float* coef;          // [2 cq + 4]
+  float* loss_out;      // [4]: total, CE mean, Dice, n_valid
+  float* class_stats;   // [3][ld_stats]: I, P, T (zeros past C) or null
+  int ld_stats;
+};
+
+__global__ __launch_bounds__(1024) void dice_coef_kernel(DiceCoefArgs a) {
+  __shared__ double s_i[4][256], s_p[4][256];
+  __shared__ long long s_t[4][256];
+  __shared__ double s_dice[256];
+  const int c = threadIdx.x & 255, sl = threadIdx.x >> 8;
+  const int per = (a.nblk + 3) / 4;
+  const int k0 = sl * per, k1 = min(a.nblk, k0 + per);
+  double I = 0.0, P = 0.0;
+  long long T = 0;
+  if (c < a.cq) {
+    for (int k = k0; k < k1; ++k) {
+      const float* row = a.ws_stat + (size_t)k * 3 * a.cq;
+      I += (double)row[c];
+      P += (double)row[a.cq + c];
+      T += reinterpret_cast<const int*>(row)[2 * a.cq + c];
+    }
+  } else if (c == 255) {
+    for (int k = k0; k < k1; ++k) {
+      I += (double)a.ws_part[2 * (size_t)k];
+      T += reinterpret_cast<const int*>(a.ws_part)[2 * (size_t)k + 1];
+    }
+  }
+  s_i[sl][c] = I; s_p[sl][c] = P; s_t[sl][c] = T;
+  __syncthreads();
+  const bool first = sl == 0;   // the first 256 threads finish: one per class, thread 255 for the loss
+  long long n_valid = 0;
+  if (first) {
+    I = ((s_i[0][c] + s_i[1][c]) + s_i[2][c]) + s_i[3][c];
+    P = ((s_p[0][c] + s_p[1][c]) + s_p[2][c]) + s_p[3][c];
+    T = ((s_t[0][c] + s_t[1][c]) + s_t[2][c]) + s_t[3][c];
+    n_valid = ((s_t[0][255] + s_t[1][255]) + s_t[2][255]) + s_t[3][255];
+    const double s = (double)a.smooth, gw = (double)a.dice_weight * (double)a.grad_scale;
+    double dice_c = 0.0, al = 0.0, be = 0.0;
+    if (c < a.C && n_valid > 0) {
+      const double U = P + (double)T + s;
+      if ((!a.present_only || T > 0) && U > 0.0) {
+        const double num = 2.0 * I + s;
+        dice_c = 1.0 - num / U;
+        al = 2.0 / ((double)a.C * U);
+        be = num / ((double)a.C * U * U);
+      }
+    }
+    s_dice[c] = dice_c;
+    if (c < a.cq) {
+      a.coef[c] = (float)(al * gw);
+      a.coef[a.cq + c] = (float)(be * gw);
+    }
+    if (a.class_stats && c < a.ld_stats) {
+      const bool in = c < a.C;
+      a.class_stats[c] = in ? (float)I : 0.f;
+      a.class_stats[a.ld_stats + c] = in ? (float)P : 0.f;
+      a.class_stats[2 * a.ld_stats + c] = in ? (float)T : 0.f;
+    }
+  }
+  __syncthreads();
+  if (first && c == 255) {
+    double D = 0.0;
+    for (int k = 0; k < a.C; ++k) D += s_dice[k];   // class order
+    D /= (double)a.C;
+    const double ce = n_valid > 0 ? I / (double)n_valid : 0.0;   // (thread 255 summed the CE partials)
+    a.loss_out[0] = (float)((double)a.ce_weight * ce + (double)a.dice_weight * D);
+    a.loss_out[1] = (float)ce;
+    a.loss_out[2] = (float)D;
+    a.loss_out[3] = (float)n_valid;
+    a.coef[2 * a.cq] = n_valid > 0 ? (float)((double)a.ce_weight * (double)a.grad_scale / (double)n_valid) : 0.f;
+    a.coef[2 * a.cq + 1] = a.coef[2 * a.cq + 2] = a.coef[2 * a.cq + 3] = 0.f;
+  }
+}
+
+template <int MODE, int TN, int S>
+__global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_ce_dice_grp_kernel(HeadArgs p, const float* __restrict__ coef) {
+  constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;
+  constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;
+  constexpr int G = HT / S;
+  constexpr int F4 = G + NT - 1;
+  constexpr int NQ = NT * NT / 4;
+  constexpr int UPG = S * S / 16;
+  constexpr bool SUMD = UPG > 1;
+  static_assert(S == 4 || S == 8 || S == 16, "group kernel: S x S pixel groups inside a 16 x 16 tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles_x = (p.W + S / 2 + HT - 1) / HT, tiles_y = (p.H + S / 2 + HT - 1) / HT;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int tyi = (blockIdx.x / tiles_x) % tiles_y, txi = blockIdx.x % tiles_x;
+  const int a0 = G * tyi - 1, b0 = G * txi - 1;
+  const int Y0 = S * a0 + S / 2, X0 = S * b0 + S / 2;
+  const int Cp = p.ld;
+  const int CS = Cp + HEAD_PAD;
+  float* s_lo = (float*)smem;
+  float* s_dlo = s_lo + F4 * F4 * CS;
+  int* s_lab = (int*)(s_dlo + F4 * F4 * CS);
+  float* s_ab = (float*)(s_lab + HT * HT);       // [alpha | beta][CMAX], zero past C: staged once per block
+  const int fsize = F4 * F4 * Cp;
+  for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
+    const int cell = i / Cp, c = i % Cp;
+    int ry = a0 - OFF + cell / F4, rx = b0 - OFF + cell % F4;
+    ry = ry < 0 ? 0 : (ry > p.h - 1 ? p.h - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > p.w - 1 ? p.w - 1 : rx);
+    *reinterpret_cast<float4*>(s_lo + cell * CS + c) =
+        *reinterpret_cast<const float4*>(p.lo + (((size_t)b * p.h + ry) * p.w + rx) * p.ld + c);
+    *reinterpret_cast<float4*>(s_dlo + cell * CS + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (tid < HT * HT) {
+    const int Y = Y0 + (tid >> 4), X = X0 + (tid & 15);
+    int code = -2;
+    if (Y >= 0 && X >= 0 && Y < p.H && X < p.W) {
+      code = -1;
+      const int64_t lab64 = p.labels[((size_t)b * p.H + Y) * p.W + X];
+      if (lab64 != (int64_t)p.ignore_index && lab64 >= 0 && lab64 < p.C) code = (int)lab64;
+    }
+    s_lab[tid] = code;
+  }
+  if (tid < 2 * CMAX) {
+    const int which = tid >= CMAX, c = tid - which * CMAX;
+    s_ab[tid] = c < p.C ? coef[which * p.cq + c] : 0.f;
+  }
+  const float ces = coef[2 * p.cq];   // ce_weight * grad_scale / n_valid
+  __syncthreads();
+
+  const int m = lane & 15, kq = lane >> 4;
+  const float NEG = -__builtin_inff();
+  constexpr float LOG2E = 1.4426950408889634f;
+  const int cellm_off = ((m / NT) * F4 + m % NT) * CS + 4 * kq;
+  int cell_off[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
+  float Af[NQ], Bb[4];
+  auto make_operands = [&](int prow) {
+    const int py_m = prow + m / S, px_m = m % S;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + kq) / NT) * tap_w<MODE, S>(px_m, (4 * q + kq) % NT);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int n = 4 * kq + jj;
+      Bb[jj] = (m < NT * NT) ? tap_w<MODE, S>(prow + n / S, m / NT) * tap_w<MODE, S>(n % S, m % NT) : 0.f;
+    }
+  };
+  if constexpr (!SUMD) make_operands(0);
+  f32x4_t dsum[SUMD ? TN : 1];
+  if constexpr (SUMD) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) dsum[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  bool have_d = false;
+  int gbase = 0;
+
+#pragma unroll 1
+  for (int g2 = 0; g2 < 2; ++g2) {
+    const int u = 2 * wid + g2, gi = u / UPG, rt = u % UPG, gy = gi / G, gx = gi % G;
+    const int Yb = Y0 + S * gy, Xb = X0 + S * gx;
+    const int prow = rt * (16 / S);
+    const bool active = !(Yb + prow >= p.H || Xb >= p.W || Yb + prow + 16 / S - 1 < 0 || Xb + S - 1 < 0);  // wave-uniform
+    gbase = (gy * F4 + gx) * CS;
+    f32x4_t acc[TN];   // logits, then exp, then (S = 4: in place) the transposed gradient tiles
+    if constexpr (!SUMD) have_d = false;
+    if (active) {
+      if constexpr (SUMD) make_operands(prow);
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float* bp = s_lo + gbase + cell_off[q] + m;
+        float bv[TN];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) bv[t] = bp[16 * t];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Af[q], bv[t], acc[t], 0, 0, 0);
+      }
+      const int py4 = prow + (4 * kq) / S, px4 = (4 * kq) % S;
+      const i32x4_t lab4 = *reinterpret_cast<const i32x4_t*>(s_lab + (S * gy + py4) * 16 + S * gx + px4);
+      int dl[4];   // label - lane's channel offset: the one-hot sits in tile t where dl == 16 t
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dl[r] = lab4[r] >= 0 ? lab4[r] - m : -1;
+      float mx[4] = {NEG, NEG, NEG, NEG};
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C
+          if (16 * t + m >= p.C) acc[t] = f32x4_t{NEG, NEG, NEG, NEG};
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], acc[t][r]);
+      }
+      float mxl[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); mxl[r] = -mx[r] * LOG2E; }
+      float sum[4] = {0.f, 0.f, 0.f, 0.f};
+      float sb[4] = {0.f, 0.f, 0.f, 0.f};   // sum_k e_k beta_k
+      float ey[4] = {0.f, 0.f, 0.f, 0.f};   // e_y, picked by the one-hot select
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        const float bt = s_ab[CMAX + 16 * t + m];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[t][r], LOG2E, mxl[r]));
+          acc[t][r] = e;
+          sum[r] += e;
+          sb[r] += e * bt;
+          ey[r] += dl[r] == 16 * t ? e : 0.f;
+        }
+      }
+      float inv[4], k1[4], oh[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool counted = lab4[r] >= 0;
+        inv[r] = counted ? 1.f / row16_sum(sum[r]) : 0.f;
+        const float ay = s_ab[counted ? lab4[r] : 0];
+        const float apy = ay * (row16_sum(ey[r]) * inv[r]);   // alpha_y p_y
+        k1[r] = ces - (row16_sum(sb[r]) * inv[r] - apy);      // ce_scale - q
+        oh[r] = ces + apy;
+      }
+      have_d = true;
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        const float bt = s_ab[CMAX + 16 * t + m];
+        f32x4_t gv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gv[r] = (acc[t][r] * inv[r]) * (k1[r] + bt) - (dl[r] == 16 * t ? oh[r] : 0.f);
+        f32x4_t dd = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (SUMD) dd = dsum[t];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) dd = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[jj], Bb[jj], dd, 0, 0, 0);
+        if constexpr (SUMD) dsum[t] = dd; else acc[t] = dd;   // dd[r] = channel 16 t + 4 kq + r of cell m
+      }
+    }
+    // the waves take turns to add their transposed gradient tiles to the LDS mirror (head_ce_grp_kernel's scheme, no LDS atomics)
+    if (!SUMD || g2 == 1) {
+      constexpr int NTURN = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? 2 : HEAD_THREADS / 64;
+      const int my_turn = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? ((wid >> 1) & 1) : wid;
+      for (int turn = 0; turn < NTURN; ++turn) {
+        __syncthreads();
+        if (turn == my_turn && have_d && m < NT * NT) {
+          float* dp = s_dlo + gbase + cellm_off;
+#pragma unroll
+          for (int t = 0; t < TN; ++t) {
+            f32x4_t v = *reinterpret_cast<f32x4_t*>(dp + 16 * t);
+            if constexpr (SUMD) v += dsum[t]; else v += acc[t];
+            *reinterpret_cast<f32x4_t*>(dp + 16 * t) = v;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  {   // the mirror leaves as this block's slab: cells in footprint order, cq channels each, 16 bytes per lane
+    const int q4 = p.cq >> 2;
+    float* slab = p.ws_dlo + (size_t)blockIdx.x * (F4 * F4) * p.cq;
+    for (int i = tid; i < F4 * F4 * q4; i += HEAD_THREADS) {
+      const int cell = i / q4, c = (i % q4) * 4;
+      *reinterpret_cast<float4*>(slab + (size_t)cell * p.cq + c) = *reinterpret_cast<const float4*>(s_dlo + cell * CS + c);
+    }
+  }
+}
+
 // dlo[b, y, x, :] = sum of the footprint cells that map to low-res cell (y, x), over the tiles that cover it, in a fixed order;
 // loss_sum = sum of the blocks' partials in block order.  One wave per low-res cell (lane = channel quad), four cells per block.
 // Tile t along an axis covers the unclamped low-res indices [G t - 1 - OFF, G t - 1 - OFF + F4); indices below 0 / above n - 1 are
@@ -809,6 +1266,103 @@ __global__ __launch_bounds__(256) void ce_nchw_bwd_kernel(const float* __restric
         dbase[(size_t)c * HW] = g;
       }
     }
+  }
+}
+
+// Dice + CE on materialised NCHW logits (the drop-in module): the two passes of the fused head, HBM-bound and plain, C <= CMAX.
+// Pass 1: a lane owns a pixel (lse, CE); the class sums of a wave's 64 pixels are wave reductions (T: ballot popcounts) that lane 0
+// adds to the wave's own LDS row; the block's rows are summed in wave order and leave as the block's slab, in the layout of
+// head_dice_stats_grp_kernel: dice_coef_kernel serves both.
+__global__ __launch_bounds__(256) void dice_nchw_stats_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                               float* lse, DiceArgs d, int B, int C, int cq, size_t HW,
+                                                               long ignore_index) {
+  __shared__ float s_row[4][2][CMAX];
+  __shared__ int s_cnt[4][CMAX];
+  __shared__ float s_l[4];
+  __shared__ int s_n[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  for (int c = lane; c < CMAX; c += 64) { s_row[wid][0][c] = 0.f; s_row[wid][1][c] = 0.f; s_cnt[wid][c] = 0; }
+  __syncthreads();
+  const size_t total = (size_t)B * HW;
+  float lacc = 0.f;
+  int nacc = 0;   // wave-uniform
+  for (size_t base = (size_t)blockIdx.x * 256; base < total; base += (size_t)gridDim.x * 256) {   // block-uniform trip count
+    const size_t i = base + tid;
+    const float* bp = logits;
+    float l = 0.f;
+    long lab = -1;
+    bool counted = false;
+    if (i < total) {
+      const size_t b = i / HW, px = i % HW;
+      bp = logits + b * C * HW + px;
+      float m = -__builtin_inff();
+      for (int c = 0; c < C; ++c) m = fmaxf(m, bp[(size_t)c * HW]);
+      float s = 0.f;
+      for (int c = 0; c < C; ++c) s += __expf(bp[(size_t)c * HW] - m);
+      l = m + __logf(s);
+      if (lse) lse[i] = l;
+      lab = (long)labels[i];
+      counted = lab != ignore_index && lab >= 0 && lab < C;
+      if (counted) lacc += l - bp[(size_t)lab * HW];
+    }
+    const unsigned long long cm = __ballot(counted);
+    if (cm == 0ull) continue;   // wave-uniform
+    nacc += __popcll(cm);
+    for (int c = 0; c < C; ++c) {
+      const float pr = counted ? __expf(bp[(size_t)c * HW] - l) : 0.f;
+      const float ps = wave_sum(pr);
+      const unsigned long long ym = __ballot(counted && lab == c);
+      float is = 0.f;
+      if (ym != 0ull) is = wave_sum(counted && lab == c ? pr : 0.f);   // wave-uniform branch
+      if (lane == 0) {
+        s_row[wid][1][c] += ps;
+        if (ym != 0ull) { s_row[wid][0][c] += is; s_cnt[wid][c] += __popcll(ym); }
+      }
+    }
+  }
+  lacc = wave_sum(lacc);
+  if (lane == 0) { s_l[wid] = lacc; s_n[wid] = nacc; }
+  __syncthreads();
+  if (tid < cq) {
+    float* row = d.ws_stat + (size_t)blockIdx.x * 3 * cq;
+    row[tid] = ((s_row[0][0][tid] + s_row[1][0][tid]) + s_row[2][0][tid]) + s_row[3][0][tid];
+    row[cq + tid] = ((s_row[0][1][tid] + s_row[1][1][tid]) + s_row[2][1][tid]) + s_row[3][1][tid];
+    reinterpret_cast<int*>(row)[2 * cq + tid] = ((s_cnt[0][tid] + s_cnt[1][tid]) + s_cnt[2][tid]) + s_cnt[3][tid];
+  }
+  if (tid == 255) {
+    d.ws_part[2 * (size_t)blockIdx.x] = ((s_l[0] + s_l[1]) + s_l[2]) + s_l[3];
+    reinterpret_cast<int*>(d.ws_part)[2 * (size_t)blockIdx.x + 1] = ((s_n[0] + s_n[1]) + s_n[2]) + s_n[3];
+  }
+}
+
+// Pass 2: dlogits = gs * (p_c (ce_scale + beta_c - q) - [c = y] (ce_scale + alpha_y p_y)), 0 where the pixel is not counted; the
+// coefficients (already times the weights and the host grad_scale) come from dice_coef_kernel's block.
+__global__ __launch_bounds__(256) void dice_nchw_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                             const float* __restrict__ lse, const float* __restrict__ coef,
+                                                             const float* __restrict__ gscale_dev, float gscale, float* dlogits,
+                                                             int B, int C, int cq, size_t HW, long ignore_index) {
+  const size_t total = (size_t)B * HW;
+  const float gs = gscale * (gscale_dev ? *gscale_dev : 1.f);
+  const float ces = coef[2 * cq];
+  const float* alpha = coef;
+  const float* beta = coef + cq;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / HW, px = i % HW;
+    const float* base = logits + b * C * HW + px;
+    float* dbase = dlogits + b * C * HW + px;
+    const long lab = (long)labels[i];
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    if (!counted) {
+      for (int c = 0; c < C; ++c) dbase[(size_t)c * HW] = 0.f;
+      continue;
+    }
+    const float l = lse[i];
+    float sb = 0.f;
+    for (int c = 0; c < C; ++c) sb += __expf(base[(size_t)c * HW] - l) * beta[c];
+    const float apy = alpha[lab] * __expf(base[(size_t)lab * HW] - l);
+    const float k1 = ces - (sb - apy), oh = ces + apy;
+    for (int c = 0; c < C; ++c)
+      dbase[(size_t)c * HW] = gs * (__expf(base[(size_t)c * HW] - l) * (k1 + beta[c]) - (c == lab ? oh : 0.f));
   }
 }
 
@@ -1085,6 +1639,162 @@ extern "C" int lc2is_head_upsample_px(const float* scores_lo, int ld, const int6
 #undef LC2IS_HEAD_PX_S
 #undef LC2IS_HEAD_PX_TN
 #undef LC2IS_HEAD_PX
+  return lc2is_check_launch();
+}
+
+// ---- Dice + cross-entropy: host side ----
+namespace {
+struct DicePlan { HeadGrpPlan g; int nblk; size_t stat_bytes, part_bytes, coef_bytes; };
+size_t dice_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// workspace: [I | P | T] rows, (CE sum, count) partials, the coefficient block, then (gradient) head_ce_grp_kernel's slabs
+DicePlan dice_head_plan(int B, int h, int w, int C, int S, int mode, bool want_grad) {
+  DicePlan d;
+  d.g = head_grp_plan(B, h, w, C, S, mode, want_grad);
+  d.nblk = B * d.g.t4;
+  d.stat_bytes = dice_align((size_t)d.nblk * 3 * d.g.cq * sizeof(float));
+  d.part_bytes = dice_align((size_t)d.nblk * 2 * sizeof(float));
+  d.coef_bytes = dice_align((size_t)(2 * d.g.cq + 4) * sizeof(float));
+  return d;
+}
+bool dice_weights_ok(float ce_weight, float dice_weight, float smooth, float grad_scale) {
+  auto ok = [](float v) { return v >= 0.f && v <= 3.0e38f; };   // finite and not negative (a NaN fails both comparisons)
+  return ok(ce_weight) && ok(dice_weight) && ok(smooth) && (ce_weight > 0.f || dice_weight > 0.f) && grad_scale == grad_scale;
+}
+int dice_nchw_grid(int B, long HW) {
+  const size_t g = ((size_t)B * HW + 255) / 256;
+  return (int)(g > 2048 ? 2048 : g);
+}
+}  // namespace
+
+extern "C" size_t lc2is_head_upsample_ce_dice_workspace_bytes(int B, int h, int w, int C, int S, int mode, int want_grad) {
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || !(S == 4 || S == 8 || S == 16)) return 0;
+  if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return 0;
+  const DicePlan d = dice_head_plan(B, h, w, C, S, mode, want_grad != 0);
+  return d.stat_bytes + d.part_bytes + d.coef_bytes + d.g.dlo_bytes;
+}
+
+extern "C" int lc2is_head_upsample_ce_dice(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                           float* loss_out, float* class_stats, int B, int h, int w, int C, int S, int mode,
+                                           long ignore_index, float ce_weight, float dice_weight, float smooth,
+                                           int present_only, float grad_scale, void* workspace, size_t workspace_bytes,
+                                           lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!scores_lo || !labels || !loss_out) return LC2IS_ERR_NULL;
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || ld < C || ld > CMAX || ld % 64) return LC2IS_ERR_SHAPE;
+  if (((size_t)scores_lo | (size_t)dscores_lo) & 15) return LC2IS_ERR_SHAPE;
+  if (!dice_weights_ok(ce_weight, dice_weight, smooth, grad_scale)) return LC2IS_ERR_SHAPE;
+  if (!(S == 4 || S == 8 || S == 16)) return LC2IS_ERR_UNSUPPORTED;
+  if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return LC2IS_ERR_UNSUPPORTED;
+  const DicePlan dp = dice_head_plan(B, h, w, C, S, mode, dscores_lo != nullptr);
+  if (!workspace || ((size_t)workspace & 15) ||
+      workspace_bytes < dp.stat_bytes + dp.part_bytes + dp.coef_bytes + dp.g.dlo_bytes)
+    return LC2IS_ERR_WORKSPACE;
+  char* wsp = (char*)workspace;
+  DiceArgs da{(float*)wsp, (float*)(wsp + dp.stat_bytes)};
+  float* coef = (float*)(wsp + dp.stat_bytes + dp.part_bytes);
+  const int H = h * S, W = w * S;
+  HeadArgs a{scores_lo, ld, labels, dscores_lo, nullptr, nullptr, B, h, w, H, W, C, S, mode, ignore_index,
+             1.f, nullptr, dscores_lo ? (float*)(wsp + dp.stat_bytes + dp.part_bytes + dp.coef_bytes) : nullptr, dp.g.cq,
+             nullptr, 0.f};
+  const int nt = (C + 15) / 16;
+  const int tn = nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12));   // head_upsample_ce's channel-tile counts
+  const int f4 = dp.g.f4;
+  // pass 1: the footprint, the tile's labels and the waves' [I | P] rows: at most 38 416 + 1 024 + 12 288 bytes of dynamic LDS
+  const int lds1 = f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +
+                   (HEAD_THREADS / 64) * 2 * 16 * tn * (int)sizeof(float);
+  const int lds2 = 2 * f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) + 2 * CMAX * (int)sizeof(float);
+#define LC2IS_DICE_ST(MODE_, TN_, S_) \
+  hipLaunchKernelGGL((head_dice_stats_grp_kernel<MODE_, TN_, S_>), dim3(dp.nblk), dim3(HEAD_THREADS), lds1, stream, a, da)
+#define LC2IS_DICE_BW(MODE_, TN_, S_)                                                                                        \
+  do {                                                                                                                      \
+    static DevOnce attr;                                                                                                    \
+    if (attr.need()) {                                                                                                      \
+      if (hipFuncSetAttribute((const void*)head_ce_dice_grp_kernel<MODE_, TN_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              2 * 7 * 7 * (CMAX + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +             \
+                                  2 * CMAX * (int)sizeof(float)) != hipSuccess)                                             \
+        return LC2IS_ERR_LAUNCH;                                                                                            \
+      attr.done();                                                                                                          \
+    }                                                                                                                       \
+    hipLaunchKernelGGL((head_ce_dice_grp_kernel<MODE_, TN_, S_>), dim3(dp.nblk), dim3(HEAD_THREADS), lds2, stream, a, coef); \
+  } while (0)
+#define LC2IS_DICE_TN(K_, MODE_, S_)                                                      \
+  do {                                                                                    \
+    if (tn == 4) K_(MODE_, 4, S_); else if (tn == 8) K_(MODE_, 8, S_);                     \
+    else if (tn == 10) K_(MODE_, 10, S_); else K_(MODE_, 12, S_);                          \
+  } while (0)
+#define LC2IS_DICE_S(K_, MODE_)                                                                                           \
+  do {                                                                                                                    \
+    if (S == 4) LC2IS_DICE_TN(K_, MODE_, 4); else if (S == 8) LC2IS_DICE_TN(K_, MODE_, 8); else LC2IS_DICE_TN(K_, MODE_, 16); \
+  } while (0)
+  if (mode == LC2IS_INTERP_BICUBIC) LC2IS_DICE_S(LC2IS_DICE_ST, LC2IS_INTERP_BICUBIC);
+  else LC2IS_DICE_S(LC2IS_DICE_ST, LC2IS_INTERP_BILINEAR);
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  const DiceCoefArgs ca{da.ws_stat, da.ws_part, dp.nblk, C, dp.g.cq, ce_weight, dice_weight, smooth, grad_scale,
+                        present_only != 0, coef, loss_out, class_stats, ld};
+  hipLaunchKernelGGL(dice_coef_kernel, dim3(1), dim3(1024), 0, stream, ca);
+  rc = lc2is_check_launch();
+  if (rc || !dscores_lo) return rc;
+  if (mode == LC2IS_INTERP_BICUBIC) LC2IS_DICE_S(LC2IS_DICE_BW, LC2IS_INTERP_BICUBIC);
+  else LC2IS_DICE_S(LC2IS_DICE_BW, LC2IS_INTERP_BILINEAR);
+#undef LC2IS_DICE_S
+#undef LC2IS_DICE_TN
+#undef LC2IS_DICE_BW
+#undef LC2IS_DICE_ST
+  rc = lc2is_check_launch();
+  if (rc) return rc;
+  // head_finish_kernel's fixed-order gather of the slabs (no loss partials: loss_sum is null)
+  const int fgrid = (int)(((long)B * h * w + 3) / 4);
+#define LC2IS_HEAD_FIN(MODE_, S_) hipLaunchKernelGGL((head_finish_kernel<MODE_, S_>), dim3(fgrid), dim3(256), 0, stream, a, dp.nblk)
+  if (mode == LC2IS_INTERP_BICUBIC) { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 16); }
+  else { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 16); }
+#undef LC2IS_HEAD_FIN
+  return lc2is_check_launch();
+}
+
+extern "C" size_t lc2is_ce_dice_nchw_workspace_bytes(int B, int C, long HW) {
+  if (B <= 0 || C <= 0 || C > CMAX || HW <= 0) return 0;
+  const int cq = (C + 3) & ~3;
+  const size_t g = (size_t)dice_nchw_grid(B, HW);
+  return dice_align(g * 3 * cq * sizeof(float)) + dice_align(g * 2 * sizeof(float));
+}
+
+extern "C" int lc2is_ce_dice_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_out,
+                                      float* class_stats, float* coef, int B, int C, long HW, long ignore_index,
+                                      float ce_weight, float dice_weight, float smooth, int present_only, void* workspace,
+                                      size_t workspace_bytes, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !loss_out || !coef) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
+  if (!dice_weights_ok(ce_weight, dice_weight, smooth, 1.f)) return LC2IS_ERR_SHAPE;
+  if (C > CMAX) return LC2IS_ERR_UNSUPPORTED;
+  const int cq = (C + 3) & ~3;
+  const int g = dice_nchw_grid(B, HW);
+  const size_t stat_bytes = dice_align((size_t)g * 3 * cq * sizeof(float));
+  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < stat_bytes + dice_align((size_t)g * 2 * sizeof(float)))
+    return LC2IS_ERR_WORKSPACE;
+  DiceArgs da{(float*)workspace, (float*)((char*)workspace + stat_bytes)};
+  hipLaunchKernelGGL(dice_nchw_stats_kernel, dim3(g), dim3(256), 0, stream, logits, labels, lse, da, B, C, cq, (size_t)HW,
+                     ignore_index);
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  const DiceCoefArgs ca{da.ws_stat, da.ws_part, g, C, cq, ce_weight, dice_weight, smooth, 1.f, present_only != 0,
+                        coef, loss_out, class_stats, C};
+  hipLaunchKernelGGL(dice_coef_kernel, dim3(1), dim3(1024), 0, stream, ca);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_ce_dice_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* coef,
+                                      const float* grad_scale_dev, float grad_scale, float* dlogits, int B, int C, long HW,
+                                      long ignore_index, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !lse || !coef || !dlogits) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0) return LC2IS_ERR_SHAPE;
+  if (C > CMAX) return LC2IS_ERR_UNSUPPORTED;
+  size_t g = ((size_t)B * HW + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(dice_nchw_bwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, coef, grad_scale_dev,
+                     grad_scale, dlogits, B, C, (C + 3) & ~3, (size_t)HW, ignore_index);
   return lc2is_check_launch();
 }
 

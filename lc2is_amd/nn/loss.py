@@ -132,6 +132,62 @@ class OhemCrossEntropyLoss(CrossEntropyLoss):
         return super().forward(input, self.last_labels)
 
 
+def check_dice(ce_weight, dice_weight, smooth, present_only) -> tuple[float, float, float, bool]:
+    """(ce_weight, dice_weight, smooth, present_only) of a Dice + CE loss, validated: finite numbers >= 0, the weights not both 0,
+    present_only a bool."""
+    return ops.dice_options(ce_weight, dice_weight, smooth, present_only)
+
+
+class _DiceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, dice, owner):
+        lg = logits.float().contiguous()
+        lb = labels.contiguous()
+        ce_weight, dice_weight, smooth, present_only = dice
+        loss4, stats, lse, coef = ops.ce_dice_nchw_fwd(lg, lb, ignore_index, ce_weight=ce_weight, dice_weight=dice_weight,
+                                                       smooth=smooth, present_only=present_only)
+        owner.last_stats = (stats[0], stats[1], stats[2], loss4)
+        ctx.saved = (lg, lb, lse, coef, ignore_index)
+        return loss4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lb, lse, coef, ignore_index = ctx.saved
+        scale = g.reshape(1).float().contiguous()   # device scalar: the upstream gradient of the scalar loss
+        return ops.ce_dice_nchw_bwd(lg, lb, lse, coef, scale, 1.0, ignore_index), None, None, None, None
+
+
+class DiceCrossEntropyLoss(CrossEntropyLoss):
+    """``ce_weight`` * mean cross-entropy + ``dice_weight`` * soft Dice, the region loss beside the per-pixel ones.  With p the
+    softmax, V the counted pixels (label != ignore_index, 0 <= label < C) of the whole batch, I_c = sum_{i in V, y_i = c} p_ic,
+    P_c = sum_{i in V} p_ic, T_c = #{i in V: y_i = c}:  Dice = (1/C) sum_c m_c (1 - (2 I_c + smooth) / (P_c + T_c + smooth)) with
+    m_c = [T_c > 0] for ``present_only=True`` (segmentation_models_pytorch's multiclass DiceLoss) and 1 otherwise (MONAI's
+    DiceLoss(softmax=True, batch=True)); the divisor is always C.  The statistics are summed on the device in a fixed order: the
+    loss and its gradient are the same bytes every run, and nothing syncs.  The loss is deterministic: ``eval()`` changes nothing.
+    ``last_stats``: the device tensors (I, P, T, loss block = [loss, CE mean, Dice, n_valid]) of the last call.
+    Class weights, label smoothing and reductions other than 'mean' are not part of this criterion (ValueError).
+    Under data parallelism each rank takes the statistics of its own batch."""
+
+    def __init__(self, ce_weight: float = 1.0, dice_weight: float = 1.0, smooth: float = 1.0, present_only: bool = True,
+                 ignore_index: int = -100, *, weight=None, reduction: str = "mean", label_smoothing: float = 0.0) -> None:
+        if weight is not None or label_smoothing != 0.0 or reduction != "mean":
+            raise ValueError("DiceCrossEntropyLoss: class weights, label smoothing and reductions other than 'mean' are not "
+                             "supported together with the Dice term")
+        super().__init__(ignore_index=ignore_index)
+        self.ce_weight, self.dice_weight, self.smooth, self.present_only = check_dice(ce_weight, dice_weight, smooth, present_only)
+        self.last_stats = None
+
+    @property
+    def dice(self) -> tuple[float, float, float, bool]:
+        return self.ce_weight, self.dice_weight, self.smooth, self.present_only
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        require_cuda(input, "logits")
+        if input.dim() != 4 or target.dim() != 3:
+            raise ValueError("lc2is_amd DiceCrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        return _DiceFn.apply(input, target, self.ignore_index, check_dice(*self.dice), self)
+
+
 class _AuxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, ignore_index, S, weight, label_smoothing, reduction):

@@ -21,7 +21,7 @@ from .. import ops
 from .base import HipModule, grad_buf, linear_bwd_params, require_cuda, vec_grad
 from .clip import ClipArch, ImageEncoderCLIP, TextEncoderCLIP, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer
-from .loss import check_ohem
+from .loss import check_dice, check_ohem
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
 KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product)
@@ -88,6 +88,17 @@ def fused_loss_options(weight, label_smoothing: float, reduction: str):
     return weight, float(label_smoothing), reduction
 
 
+def fused_dice_options(dice, opts, ohem):
+    """``dice`` = (ce_weight, dice_weight, smooth, present_only) validated, or None; the Dice term does not combine with class
+    weights, label smoothing, a non-mean reduction (``opts`` of fused_loss_options) or a hard-pixel selection."""
+    if dice is None:
+        return None
+    if opts is not None or ohem is not None:
+        raise ValueError("lc2is_amd: dice= cannot be combined with weight=, label_smoothing, a reduction other than 'mean' "
+                         "or ohem=")
+    return check_dice(*dice)
+
+
 def _reduce(loss2, reduction: str, save: bool):
     """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
     gives torch's NaN mean and a zero gradient, with no host sync."""
@@ -101,8 +112,8 @@ class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -110,7 +121,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -167,7 +178,7 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -178,6 +189,14 @@ class BaseModelWithText(HipModule):
                                             want_loss=False)
             return hi, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None)
         labels = labels.contiguous()
+        if dice is not None:   # CE + soft Dice: statistics pass, coefficients, gradient pass — dlo is the gradient of the scalar loss
+            ce_weight, dice_weight, smooth, present_only = dice
+            loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
+                                                          ignore_index=ignore_index, ce_weight=ce_weight, dice_weight=dice_weight,
+                                                          smooth=smooth, present_only=present_only)
+            self.last_dice = (stats[0], stats[1], stats[2], loss4)
+            return loss4[0], (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=None)
+                              if save else None)
         if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
             labels, info = ops.ohem_labels(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index, ohem)
             self.last_ohem = (labels, info)
@@ -272,17 +291,21 @@ class BaseModelWithText(HipModule):
         return dict(outputs=logits)
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean", ohem=None) -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
-        (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels the head saw, the device info block)."""
+        (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels the head saw, the device info block).
+        ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE + dice_weight * soft Dice over the batch
+        (DiceCrossEntropyLoss's definition), not combinable with the other options; ``self.last_dice`` then holds the device
+        tensors (I, P, T, loss block = [loss, CE mean, Dice, n_valid])."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
+        dice = fused_dice_options(dice, opts, ohem)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice)
 
     @torch.no_grad()
     def forward_tuple(self, inputs: dict):

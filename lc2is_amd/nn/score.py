@@ -18,7 +18,7 @@ from torch import nn
 from .. import ops
 from .base import require_cuda
 from .loss import check_ohem
-from .model import _reduce, fused_loss_options
+from .model import _reduce, fused_dice_options, fused_loss_options
 
 KPAD = 192
 
@@ -60,7 +60,7 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -70,6 +70,14 @@ class _ScoreFn(torch.autograd.Function):
                                             want_loss=False)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
             return hi
+        if dice is not None:   # CE + soft Dice: dlo is the gradient of the scalar loss
+            ce_weight, dice_weight, smooth, present_only = dice
+            loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
+                                                          want_grad=save, ignore_index=ignore_index, ce_weight=ce_weight,
+                                                          dice_weight=dice_weight, smooth=smooth, present_only=present_only)
+            owner.last_dice = (stats[0], stats[1], stats[2], loss4)
+            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
+            return loss4[0]
         if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
             labels, info = ops.ohem_labels(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index, ohem)
             owner.last_ohem = (labels, info)
@@ -100,7 +108,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None, None, None
+        return dv, dt, None, None, None, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -118,13 +126,16 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None) -> torch.Tensor:
+             ohem=None, dice=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
-        the head saw, the device info block)."""
+        the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
+        dice_weight * soft Dice over the batch (DiceCrossEntropyLoss's definition), not combinable with the other options;
+        ``self.last_dice`` then holds the device tensors (I, P, T, loss block)."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
+        dice = fused_dice_options(dice, opts, ohem)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
-        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self)
+        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self, dice)

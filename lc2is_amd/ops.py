@@ -81,6 +81,11 @@ _ARGTYPES = {
     "lc2is_head_upsample_px": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P],
     "lc2is_ohem_select_workspace_bytes": [_L],
     "lc2is_ohem_select": [_P, _P, _P, _L, _I, _L, _F, _L, _P, _P, _Z, _P],
+    "lc2is_head_upsample_ce_dice_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
+    "lc2is_head_upsample_ce_dice": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _F, _F, _I, _F, _P, _Z, _P],
+    "lc2is_ce_dice_nchw_workspace_bytes": [_I, _I, _L],
+    "lc2is_ce_dice_nchw_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _F, _F, _F, _I, _P, _Z, _P],
+    "lc2is_ce_dice_nchw_bwd": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _L, _L, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -958,6 +963,101 @@ def ohem_labels(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode:
     thresh, min_kept = ohem
     lpx = head_upsample_px(scores_lo, labels, B, h, w, C, S, mode, ignore_index=ignore_index)
     return ohem_select(lpx, labels, C, thresh, int(min_kept) * B, ignore_index)
+
+
+# ---- soft Dice + cross-entropy: batch statistics on the device, then the gradient pass ----
+DICE_CMAX = 192   # classes the Dice kernels take (the fused head's limit)
+
+
+def dice_options(ce_weight, dice_weight, smooth, present_only) -> tuple[float, float, float, bool]:
+    """(ce_weight, dice_weight, smooth, present_only) of a Dice + CE loss, validated: finite numbers >= 0, the two weights not
+    both 0, present_only a bool."""
+    for name, v in (("ce_weight", ce_weight), ("dice_weight", dice_weight), ("smooth", smooth)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"Dice + CE: {name} must be a finite number >= 0, got {v!r}")
+    if float(ce_weight) == 0.0 and float(dice_weight) == 0.0:
+        raise ValueError("Dice + CE: ce_weight and dice_weight must not both be 0")
+    if not isinstance(present_only, bool):
+        raise ValueError(f"Dice + CE: present_only must be a bool, got {present_only!r}")
+    return float(ce_weight), float(dice_weight), float(smooth), present_only
+
+
+def head_upsample_ce_dice(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                          want_grad: bool = False, ignore_index: int = -100, ce_weight: float = 1.0, dice_weight: float = 1.0,
+                          smooth: float = 1.0, present_only: bool = True, grad_scale: float = 1.0):
+    """ce_weight * mean CE + dice_weight * soft Dice of the upsampled scores (S = 4 / 8 / 16): scores_lo fp32 [B*h*w, ld], labels
+    int64 [B, h*S, w*S].  Returns (loss_out fp32 [4] = loss, CE mean, Dice, n_valid; class_stats fp32 [3, ld] = I, P, T;
+    dscores_lo or None = grad_scale * d loss / d scores_lo, the gradient of the scalar loss).  The per-class sums run over the
+    whole batch of the call; nothing syncs, the same bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    ce_weight, dice_weight, smooth, present_only = dice_options(ce_weight, dice_weight, smooth, present_only)
+    if not math.isfinite(grad_scale):
+        raise ValueError(f"lc2is_amd.head_upsample_ce_dice: grad_scale must be finite, got {grad_scale}")
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError("lc2is_amd.head_upsample_ce_dice: scores_lo must be contiguous")
+    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: labels must be contiguous [{B},{h*S},{w*S}]")
+    if S not in (4, 8, 16):
+        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: S must be 4, 8 or 16, got {S}")
+    ld = scores_lo.shape[1]
+    if scores_lo.shape[0] != B * h * w or not C <= ld <= DICE_CMAX or ld % 64:
+        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: scores_lo must be [{B * h * w}, ld] with C <= ld <= {DICE_CMAX}, "
+                           f"ld % 64 == 0, got {tuple(scores_lo.shape)}")
+    dev = scores_lo.device
+    nbytes = _fn("lc2is_head_upsample_ce_dice_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
+    if nbytes == 0:
+        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    loss = torch.empty(4, dtype=torch.float32, device=dev)
+    stats = torch.empty((3, ld), dtype=torch.float32, device=dev)
+    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: rows, coefficients and slabs live until the last launch)
+    _lib.check(_fn("lc2is_head_upsample_ce_dice")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), _ptr(stats), B, h, w,
+                                                  C, S, mode, ignore_index, ce_weight, dice_weight, smooth, int(present_only),
+                                                  grad_scale, _ptr(ws), nbytes, _stream()),
+               f"head_upsample_ce_dice B={B} h={h} w={w} C={C} S={S}")
+    return loss, stats, dlo
+
+
+def ce_dice_nchw_fwd(logits, labels, ignore_index: int = -100, *, ce_weight: float = 1.0, dice_weight: float = 1.0,
+                     smooth: float = 1.0, present_only: bool = True):
+    """The same loss on NCHW fp32 logits (C <= 192).  Returns (loss_out [4], class_stats [3, C], lse [B,H,W], coef): ``coef`` is
+    the device coefficient block ``ce_dice_nchw_bwd`` takes."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    ce_weight, dice_weight, smooth, present_only = dice_options(ce_weight, dice_weight, smooth, present_only)
+    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
+        raise RuntimeError("lc2is_amd.ce_dice_nchw_fwd: logits/labels must be contiguous")
+    B, Cc, H, W = logits.shape
+    if tuple(labels.shape) != (B, H, W):
+        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_fwd: labels must be [{B},{H},{W}]")
+    if not 1 <= Cc <= DICE_CMAX:
+        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_fwd: 1 <= C <= {DICE_CMAX} required, got {Cc}")
+    dev = logits.device
+    nbytes = _fn("lc2is_ce_dice_nchw_workspace_bytes")(B, Cc, H * W)
+    loss = torch.empty(4, dtype=torch.float32, device=dev)
+    stats = torch.empty((3, Cc), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    coef = torch.empty(2 * ((Cc + 3) // 4 * 4) + 4, dtype=torch.float32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(_fn("lc2is_ce_dice_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(stats), _ptr(coef), B, Cc,
+                                             H * W, ignore_index, ce_weight, dice_weight, smooth, int(present_only), _ptr(ws),
+                                             nbytes, _stream()), "ce_dice_nchw_fwd")
+    return loss, stats, lse, coef
+
+
+def ce_dice_nchw_bwd(logits, labels, lse, coef, grad_scale_dev, grad_scale: float = 1.0, ignore_index: int = -100):
+    """dlogits = grad_scale * grad_scale_dev (device scalar or None) * d loss / d logits, from ``ce_dice_nchw_fwd``'s lse and coef."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    _chk(lse, torch.float32, "lse", 3); _chk(coef, torch.float32, "coef", 1); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    B, Cc, H, W = logits.shape
+    if (not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W)
+            or tuple(lse.shape) != (B, H, W) or not lse.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_bwd: contiguous logits [B,C,H,W] with labels / lse [{B},{H},{W}] required")
+    if not 1 <= Cc <= DICE_CMAX or coef.numel() != 2 * ((Cc + 3) // 4 * 4) + 4:
+        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_bwd: coef must be ce_dice_nchw_fwd's block for C={Cc} (C <= {DICE_CMAX})")
+    d = torch.empty_like(logits)
+    _lib.check(_fn("lc2is_ce_dice_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(coef), _ptr(grad_scale_dev), grad_scale,
+                                             _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_dice_nchw_bwd")
+    return d
 
 
 def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, label_smoothing: float = 0.0,

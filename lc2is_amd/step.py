@@ -18,7 +18,10 @@ the remaining backward (``lc2is_amd.dp.GradReducer``).
 ``label_smoothing`` and ``reduction`` ('mean' / 'sum') configure the fused head; default: ``CrossEntropyLoss()``.  An
 ``lc2is_amd.nn.OhemCrossEntropyLoss`` adds its hard-pixel selection in front of the fused head (two launches and the selection's,
 all on the device: eager, captured, under a reducer — each rank selects over its own batch — and with the device-held options);
-``ohem_info`` is the last selection's device info block.
+``ohem_info`` is the last selection's device info block.  An ``lc2is_amd.nn.DiceCrossEntropyLoss`` trains on ce_weight * mean CE
++ dice_weight * soft Dice through the fused head (a statistics pass, a one-block launch and the gradient pass, all on the device:
+eager, captured, under a reducer — each rank takes the statistics of its own batch); ``dice_stats`` are the last step's device
+tensors (I, P, T, loss block).  The loss is deterministic, so the criterion's ``eval()`` mode changes nothing.
 
 The device-held path (opt-in: any of ``lr_schedule``, ``max_grad_norm``, ``skip_nonfinite``, ``device_state``) adds what the
 reference's loop has around ``optimizer.step()``:
@@ -55,6 +58,12 @@ def _accepts_ohem(model) -> bool:
     import inspect
     fl = getattr(model, "forward_loss", None)
     return fl is not None and "ohem" in inspect.signature(fl).parameters
+
+
+def _accepts_dice(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "dice" in inspect.signature(fl).parameters
 
 
 def lr_table_from_torch(make_scheduler, base_lr: float, steps: int) -> torch.Tensor:
@@ -331,8 +340,9 @@ class TrainStep:
         table = _lr_table(lr_schedule, schedule_steps, lr) if (device_path or schedule_steps is not None) else None
         self._loss_opts = False
         self._ohem = False
+        self._dice = False
         if criterion is not None:
-            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, OhemCrossEntropyLoss
+            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, DiceCrossEntropyLoss, OhemCrossEntropyLoss
             if not isinstance(criterion, (CrossEntropyLoss, nn.CrossEntropyLoss)) or isinstance(criterion, AuxiliaryLoss):
                 raise TypeError("TrainStep: criterion must be a CrossEntropyLoss (lc2is_amd.nn or torch.nn)")
             if ignore_index is not None and ignore_index != -100:
@@ -346,6 +356,10 @@ class TrainStep:
             if self._ohem and not _accepts_ohem(model):
                 raise TypeError("TrainStep: an OhemCrossEntropyLoss needs a model whose forward_loss takes ohem= "
                                 "(BaseModelWithText); the compose models do not select hard pixels")
+            self._dice = isinstance(criterion, DiceCrossEntropyLoss)
+            if self._dice and not _accepts_dice(model):
+                raise TypeError("TrainStep: a DiceCrossEntropyLoss needs a model whose forward_loss takes dice= "
+                                "(BaseModelWithText); the compose models have no Dice head")
         self.criterion = criterion
         self.model = model
         self.arena = ParamArena(model)
@@ -431,6 +445,14 @@ class TrainStep:
         if not self._ohem:
             raise RuntimeError("TrainStep.ohem_labels: the criterion is not an OhemCrossEntropyLoss")
         return self.criterion.last_labels
+
+    @property
+    def dice_stats(self):
+        """The device tensors (I, P, T, loss block = [loss, CE mean, Dice, n_valid]) of the last step's Dice + CE loss, None before
+        the first step.  After ``capture`` they are the graph's own buffers: a replay rewrites them in place."""
+        if not self._dice:
+            raise RuntimeError("TrainStep.dice_stats: the criterion is not a DiceCrossEntropyLoss")
+        return self.criterion.last_stats
 
     @property
     def param_groups(self):
@@ -563,6 +585,10 @@ class TrainStep:
                                            ohem=c.ohem if c.training else None)
             if c.training:
                 c.last_labels, c.last_info = self.model.last_ohem
+        elif self._dice:   # CE + soft Dice on the fused head (deterministic: the criterion's training flag does not matter)
+            c = self.criterion
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index, dice=c.dice)
+            c.last_stats = self.model.last_dice
         elif self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
             c = self.criterion
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
