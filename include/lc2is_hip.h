@@ -469,6 +469,35 @@ int lc2is_resize_argmax(const float* scores, int ld, int N, int h, int w, int K,
                         long total_px, const void* gt, int gt_bytes, uint8_t* pred, int* counts, void* workspace,
                         size_t workspace_bytes, lc2is_stream_t stream);
 
+/* ---- sliding-window evaluation: window-mean resize + argmax -----------------------------------------------------------
+ * lc2is_resize_argmax with another source.  Image b is resized from a canvas of Hc_b x Wc_b score cells that is never formed:
+ * a canvas cell is the mean of the window views that cover it (mmseg's slide_inference on the score-cell grid, logits averaged).
+ *   views: channels-last fp32 [V,h,w,ld], K valid channels, ld % 4 == 0, ld >= K, 16-byte aligned: one score grid per window
+ *     forward.
+ *   desc: DEVICE int64 [N][8] = {H_b, W_b, first pixel, first tile (all four as in lc2is_resize_argmax), Hc_b, Wc_b, first
+ *     window of image b in win, its number of windows}.
+ *   win: DEVICE int32 [n_win][4] = {view index, oy, ox, flags}, 16-byte aligned; the origin is in canvas cells; flags bit 0: the
+ *     view is mirrored along x (view column j is canvas column ox + w - 1 - j).
+ *   Canvas cell (cy, cx), channel c: the fp32 sum over the image's windows, in list order and starting from the first one that
+ *     covers the cell, divided (IEEE fp32 division) by their number; a cell that no window covers reads 0.  The output pixel is
+ *     torch's bicubic resize of that canvas (align_corners=False, explicit size, scale Hc / H, Wc / W), then the argmax, the
+ *     per-wave histograms and per-tile slabs of lc2is_resize_argmax (same workspace: lc2is_resize_argmax_workspace_bytes).
+ *   Every descriptor value is range-checked on the device: a window whose view is outside [0, V) or whose origin is outside
+ *     [0, Hc - h] x [0, Wc - w] is skipped; an image with more than LC2IS_SLIDE_MAX_WIN windows, a window range outside
+ *     [0, n_win], Hc < h or Wc < w is not followed: its pred pixels are left as they were and its counts are UNDEFINED (its
+ *     slabs are not written; lc2is_resize_argmax treats a descriptor it does not follow the same way).  Nothing outside the
+ *     buffers is read or written.
+ *   ignore_index: -1 = lc2is_resize_argmax's counting rule (every pixel counts in "predicted"); >= 0 = mmseg's rule: a pixel
+ *     whose gt equals ignore_index or lies outside [0, K) counts in none of the three rows.
+ * Error codes as lc2is_resize_argmax (ignore_index < -1: LC2IS_ERR_SHAPE).  No atomics: bitwise reproducible, batch independent.
+ * replaces: nothing in the reference, which scores the centre crop only (metrics.py:137-143 original_size_interpolate of one
+ *   forward); this is the slide mode of the published ADE20K protocol on top of the same resize + argmax. */
+#define LC2IS_SLIDE_MAX_WIN 64
+int lc2is_resize_argmax_windows(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt, int gt_bytes,
+                                int ignore_index, uint8_t* pred, int* counts, void* workspace, size_t workspace_bytes,
+                                lc2is_stream_t stream);
+
 /* ---- the device-held optimizer path (optim.hip) -----------------------------------------------------------------------
  * The scalars of an optimizer step that change from call to call live in this block in DEVICE memory (48 bytes, 4-byte
  * aligned, all zero before the first step), so a step needs no host value that differs between calls and can be replayed

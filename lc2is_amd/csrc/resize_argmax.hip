@@ -13,6 +13,12 @@
 // Counts: every wave histograms its own 64 pixels in LDS (one writer per histogram: ballot + popcount per distinct class), the
 // block sums its waves in a fixed order into a per-tile slab of the workspace, and ra_finish_kernel sums each image's slabs in a
 // fixed order.  No read-modify-write atomics: pred and counts are bitwise reproducible and independent of the batch.
+//
+// ra_win_kernel (lc2is_resize_argmax_windows) is the same kernel for sliding-window evaluation: the source of an image is a canvas
+// of Hc x Wc score cells that is never formed, each cell the mean of the window views that cover it (mmseg's slide_inference, with
+// an optional mirrored copy of every window).  Only the footprint staging differs: a cell is summed over the image's window list
+// (staged once per block in LDS) in list order and divided by the cover count.
+// replaces: nothing in the reference, which scores the centre crop only (metrics.py:137-143 on one forward).
 #include "common.h"
 #include "interp.h"
 #include "lc2is_hip.h"
@@ -203,12 +209,14 @@ __global__ __launch_bounds__(RA_THREADS) void ra_kernel(RaArgs p) {
 }
 
 // counts[b][e] = sum over the image's tiles of slab[tile][e], tiles in increasing order within each of 4 strided parts, the parts
-// added in order: grid (ceil(3K / 64), N), 256 threads
+// added in order: grid (ceil(3K / 64), N), 256 threads.  DS: int64 words per descriptor (4: lc2is_resize_argmax, 8: the windowed call,
+// whose first four words mean the same)
+template <int DS>
 __global__ __launch_bounds__(256) void ra_finish_kernel(const int64_t* desc, const int* slab, int* counts, int K, int n_tiles) {
   __shared__ int part[4][64];
   const int b = blockIdx.y, tid = threadIdx.x, q = tid >> 6;
   const int e = blockIdx.x * 64 + (tid & 63);
-  const long H = desc[4 * b], W = desc[4 * b + 1], tile0 = desc[4 * b + 3];
+  const long H = desc[DS * b], W = desc[DS * b + 1], tile0 = desc[DS * b + 3];
   long nt = ((H + RA_T - 1) / RA_T) * ((W + RA_T - 1) / RA_T);
   if (H < 1 || W < 1 || tile0 < 0 || tile0 >= n_tiles) nt = 0;
   else if (tile0 + nt > n_tiles) nt = n_tiles - tile0;
@@ -222,6 +230,192 @@ __global__ __launch_bounds__(256) void ra_finish_kernel(const int64_t* desc, con
 
 constexpr size_t RA_LDS = (size_t)(RA_FMAX * RA_FMAX + RA_FMAX * RA_T) * RA_CP * sizeof(float) + RA_T * (sizeof(int4) + sizeof(float4));
 static_assert((size_t)RA_FMAX * RA_FMAX * RA_CP * sizeof(float) >= 4 * 3 * RA_KMAX * sizeof(int), "histograms fit the footprint");
+
+// ---- sliding-window source: the canvas mean of the covering views ----------------------------------------------------------
+constexpr int RA_WMAX = LC2IS_SLIDE_MAX_WIN;
+
+struct RaWinArgs {
+  const float* views;       // [V, h, w, ld] channels-last fp32, K valid channels: one score grid per window forward
+  const int64_t* desc;      // [N][8]: H, W, first pixel, first tile (as RaArgs), Hc, Wc (canvas cells), first window, n_windows
+  const int32_t* win;       // [n_win][4]: view, oy, ox (origin in canvas cells), flags (bit 0: the view is mirrored along x)
+  const void* gt;
+  uint8_t* pred;
+  int* slab;
+  long total_px, n_win;
+  int N, V, h, w, ld, K, n_tiles, gt_bytes, ignore_index;
+};
+
+// A restatement of ra_kernel, not a shared body: ra_kernel has to keep the instructions it had, and a body shared through a source
+// functor changes its register allocation.  Apart from the descriptor, the window list, the staging loop and the counting rule the two
+// are line for line the same: a change to bands, taps or histograms goes into both (tests/test_gpu_slide.py holds the one-view case
+// to ra_kernel's bits).
+__global__ __launch_bounds__(RA_THREADS) void ra_win_kernel(RaWinArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_foot = (float*)smem;                         // as ra_kernel
+  float* s_hb = s_foot + RA_FMAX * RA_FMAX * RA_CP;
+  int4* s_xi = (int4*)(s_hb + RA_FMAX * RA_T * RA_CP);
+  float4* s_xw = (float4*)(s_xi + RA_T);
+  int4* s_win = (int4*)(s_xw + RA_T);                   // [RA_WMAX] the image's usable windows, in list order
+  int* s_nw = (int*)(s_win + RA_WMAX);                  // their number
+  int* s_hist = (int*)smem;
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int K = p.K;
+
+  const int t = blockIdx.x;
+  int lo = 0, hi = p.N - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p.desc[8 * mid + 3] <= t) lo = mid; else hi = mid - 1;
+  }
+  const int b = lo;
+  const int64_t* d = p.desc + 8 * b;
+  const long H = d[0], W = d[1], pix0 = d[2], tile0 = d[3], Hc_ = d[4], Wc_ = d[5], win0 = d[6], nwin = d[7];
+  const long tiles_x = (W + RA_T - 1) / RA_T;
+  // a descriptor that does not fit the buffers, the window limit or the views is not followed
+  if (H < 1 || W < 1 || t < tile0 || pix0 < 0 || pix0 + H * W > p.total_px) return;
+  if (Hc_ < p.h || Wc_ < p.w || Hc_ > (1L << 24) || Wc_ > (1L << 24)) return;
+  if (nwin < 0 || nwin > RA_WMAX || win0 < 0 || win0 + nwin > p.n_win) return;
+  const int Hc = (int)Hc_, Wc = (int)Wc_;
+  const long tl = t - tile0;
+  const int Y0 = (int)(tl / tiles_x) * RA_T, X0 = (int)(tl % tiles_x) * RA_T;
+  if (Y0 >= H) return;
+  const int TH = (int)min((long)RA_T, H - Y0), TW = (int)min((long)RA_T, W - X0);
+  const float sy = (float)Hc / (float)H, sx = (float)Wc / (float)W;
+
+  // the window list, once per block: wave 0 keeps the windows whose view and origin are in range, order preserved
+  if (wid == 0) {
+    int4 wv = make_int4(0, 0, 0, 0);
+    bool ok = false;
+    if (lane < nwin) {
+      wv = *reinterpret_cast<const int4*>(p.win + 4 * (win0 + lane));
+      ok = wv.x >= 0 && wv.x < p.V && wv.y >= 0 && wv.y <= Hc - p.h && wv.z >= 0 && wv.z <= Wc - p.w;
+    }
+    const unsigned long long m = __ballot(ok);
+    if (ok) s_win[__popcll(m & ((1ull << lane) - 1ull))] = wv;
+    if (lane == 0) *s_nw = __popcll(m);
+  }
+  __syncthreads();
+  const int nw = *s_nw;
+
+  const int py = tid / RA_T, px = tid % RA_T;
+  const bool valid = py < TH && px < TW;
+  float best = -INFINITY;
+  int arg = 0;
+  const size_t view_stride = (size_t)p.h * p.w * p.ld;
+
+  for (int rb0 = 0; rb0 < TH;) {
+    const int R = ra_band(Y0 + rb0, TH - rb0, sy, Hc);
+    const int2 ys = ra_span(Y0 + rb0, Y0 + rb0 + R - 1, sy, Hc);
+    const int fy0 = ys.x, FH = ys.y - ys.x + 1;
+    const bool row_in = valid && py >= rb0 && py < rb0 + R;
+    int yi[4] = {0, 0, 0, 0};
+    float yw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (row_in) {
+      const Taps ty = make_taps(Y0 + py, sy, Hc, LC2IS_INTERP_BICUBIC);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { yi[k] = ty.idx[k] - fy0; yw[k] = ty.w[k]; }
+    }
+    for (int cb0 = 0; cb0 < TW;) {
+      const int CW = ra_band(X0 + cb0, TW - cb0, sx, Wc);
+      const int2 xs = ra_span(X0 + cb0, X0 + cb0 + CW - 1, sx, Wc);
+      const int fx0 = xs.x, FW = xs.y - xs.x + 1;
+      const bool in = row_in && px >= cb0 && px < cb0 + CW;
+      __syncthreads();
+      if (tid < CW) {
+        const Taps tx = make_taps(X0 + cb0 + tid, sx, Wc, LC2IS_INTERP_BICUBIC);
+        s_xi[tid] = make_int4(tx.idx[0] - fx0, tx.idx[1] - fx0, tx.idx[2] - fx0, tx.idx[3] - fx0);
+        s_xw[tid] = make_float4(tx.w[0], tx.w[1], tx.w[2], tx.w[3]);
+      }
+      for (int c0 = 0; c0 < K; c0 += RA_CC) {
+        // stage the footprint's channels [c0, c0 + 32): each canvas cell is the sum of the views that cover it, in list order from
+        // the first one, divided by their number (a cell that nothing covers reads 0)
+        for (int i = tid; i < FH * FW * (RA_CC / 4); i += RA_THREADS) {
+          const int c4 = i % (RA_CC / 4), cell = i / (RA_CC / 4);
+          const int cy = fy0 + cell / FW, cx = fx0 + cell % FW;
+          const int c = c0 + 4 * c4;
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (c < p.ld) {
+            int n = 0;
+            for (int j = 0; j < nw; ++j) {
+              const int4 wv = s_win[j];
+              const int ry = cy - wv.y, rx = cx - wv.z;
+              if (ry < 0 || ry >= p.h || rx < 0 || rx >= p.w) continue;
+              const int col = (wv.w & 1) ? p.w - 1 - rx : rx;
+              const float4 x = *reinterpret_cast<const float4*>(p.views + (size_t)wv.x * view_stride + ((size_t)ry * p.w + col) * p.ld + c);
+              v = n ? make_float4(v.x + x.x, v.y + x.y, v.z + x.z, v.w + x.w) : x;
+              ++n;
+            }
+            if (n > 1) {
+              const float fn = (float)n;
+              v = make_float4(v.x / fn, v.y / fn, v.z / fn, v.w / fn);
+            }
+          }
+          *reinterpret_cast<float4*>(s_foot + cell * RA_CP + 4 * c4) = v;
+        }
+        __syncthreads();
+        for (int i = tid; i < FH * CW * (RA_CC / 4); i += RA_THREADS) {
+          const int c4 = i % (RA_CC / 4), x = (i / (RA_CC / 4)) % CW, r = i / (RA_CC / 4 * CW);
+          const int4 xi = s_xi[x];
+          const float4 xw = s_xw[x];
+          const float* row = s_foot + r * FW * RA_CP + 4 * c4;
+          float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+          a = fma4(xw.x, *reinterpret_cast<const float4*>(row + xi.x * RA_CP), a);
+          a = fma4(xw.y, *reinterpret_cast<const float4*>(row + xi.y * RA_CP), a);
+          a = fma4(xw.z, *reinterpret_cast<const float4*>(row + xi.z * RA_CP), a);
+          a = fma4(xw.w, *reinterpret_cast<const float4*>(row + xi.w * RA_CP), a);
+          *reinterpret_cast<float4*>(s_hb + (r * RA_T + cb0 + x) * RA_CP + 4 * c4) = a;
+        }
+        __syncthreads();
+        if (in) {
+          const int nc = min(RA_CC, K - c0);
+          for (int c4 = 0; c4 < RA_CC / 4; ++c4) {
+            if (4 * c4 >= nc) break;
+            const float* col = s_hb + px * RA_CP + 4 * c4;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a = fma4(yw[k], *reinterpret_cast<const float4*>(col + yi[k] * RA_T * RA_CP), a);
+            const int c = c0 + 4 * c4;
+            if (a.x > best) { best = a.x; arg = c; }
+            if (4 * c4 + 1 < nc && a.y > best) { best = a.y; arg = c + 1; }
+            if (4 * c4 + 2 < nc && a.z > best) { best = a.z; arg = c + 2; }
+            if (4 * c4 + 3 < nc && a.w > best) { best = a.w; arg = c + 3; }
+          }
+        }
+        __syncthreads();
+      }
+      cb0 += CW;
+    }
+    rb0 += R;
+  }
+
+  const size_t o = (size_t)pix0 + (size_t)(Y0 + py) * W + X0 + px;
+  if (valid && p.pred) p.pred[o] = (uint8_t)arg;
+  if (!p.slab) return;
+
+  // ignore_index < 0: every pixel counts in "predicted" (ra_kernel's rule); >= 0: a pixel whose gt is ignore_index or outside
+  // [0, K) counts in none of the three rows (mmseg's intersect_and_union)
+  int g = -1;
+  if (valid && p.gt) {
+    long v;
+    if (p.gt_bytes == 1) v = ((const uint8_t*)p.gt)[o];
+    else if (p.gt_bytes == 4) v = ((const int32_t*)p.gt)[o];
+    else v = ((const int64_t*)p.gt)[o];
+    g = (v >= 0 && v < K && !(p.ignore_index >= 0 && v == p.ignore_index)) ? (int)v : -1;
+  }
+  int* hw = s_hist + wid * 3 * K;
+  for (int i = lane; i < 3 * K; i += 64) hw[i] = 0;
+  __syncthreads();
+  wave_hist(hw + K, p.ignore_index >= 0 ? g >= 0 : valid, arg, lane);
+  wave_hist(hw, valid && g == arg, arg, lane);
+  wave_hist(hw + 2 * K, g >= 0, g, lane);
+  __syncthreads();
+  int* out = p.slab + (size_t)t * 3 * K;
+  for (int i = tid; i < 3 * K; i += RA_THREADS)
+    out[i] = ((s_hist[i] + s_hist[3 * K + i]) + s_hist[6 * K + i]) + s_hist[9 * K + i];
+}
+
+constexpr size_t RA_WIN_LDS = RA_LDS + RA_WMAX * sizeof(int4) + 16;
 
 }  // namespace
 
@@ -248,7 +442,33 @@ extern "C" int lc2is_resize_argmax(const float* scores, int ld, int N, int h, in
   hipLaunchKernelGGL(ra_kernel, dim3((unsigned)n_tiles), dim3(RA_THREADS), RA_LDS, stream, a);
   int rc = lc2is_check_launch();
   if (rc || !counts) return rc;
-  hipLaunchKernelGGL(ra_finish_kernel, dim3((3 * K + 63) / 64, N), dim3(256), 0, stream, desc, (const int*)workspace, counts, K,
+  hipLaunchKernelGGL(ra_finish_kernel<4>, dim3((3 * K + 63) / 64, N), dim3(256), 0, stream, desc, (const int*)workspace, counts, K,
+                     (int)n_tiles);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_resize_argmax_windows(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                           const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt,
+                                           int gt_bytes, int ignore_index, uint8_t* pred, int* counts, void* workspace,
+                                           size_t workspace_bytes, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!views || !desc || !win || (!pred && !counts)) return LC2IS_ERR_NULL;
+  if (counts && (!gt || !workspace)) return LC2IS_ERR_NULL;
+  if (N <= 0 || V <= 0 || h <= 0 || w <= 0 || K <= 0 || ld < K || ld % 4 || ((uintptr_t)views & 15) || ((uintptr_t)win & 15) ||
+      n_win <= 0 || n_tiles <= 0 || n_tiles > 0x7fffffffL || total_px <= 0 || ignore_index < -1)
+    return LC2IS_ERR_SHAPE;
+  if (K > RA_KMAX) return LC2IS_ERR_UNSUPPORTED;
+  if (counts && gt_bytes != 1 && gt_bytes != 4 && gt_bytes != 8) return LC2IS_ERR_UNSUPPORTED;
+  if (counts && workspace_bytes < lc2is_resize_argmax_workspace_bytes(n_tiles, K)) return LC2IS_ERR_WORKSPACE;
+  RaWinArgs a;
+  a.views = views; a.desc = desc; a.win = win; a.gt = counts ? gt : nullptr; a.pred = pred;
+  a.slab = counts ? (int*)workspace : nullptr;
+  a.total_px = total_px; a.n_win = n_win; a.N = N; a.V = V; a.h = h; a.w = w; a.ld = ld; a.K = K; a.n_tiles = (int)n_tiles;
+  a.gt_bytes = gt_bytes; a.ignore_index = ignore_index;
+  hipLaunchKernelGGL(ra_win_kernel, dim3((unsigned)n_tiles), dim3(RA_THREADS), RA_WIN_LDS, stream, a);
+  int rc = lc2is_check_launch();
+  if (rc || !counts) return rc;
+  hipLaunchKernelGGL(ra_finish_kernel<8>, dim3((3 * K + 63) / 64, N), dim3(256), 0, stream, desc, (const int*)workspace, counts, K,
                      (int)n_tiles);
   return lc2is_check_launch();
 }

@@ -118,18 +118,23 @@ class ClipImagePreprocessor(_Base):
         m, s = np.array(image_mean, dtype=np.float32), np.array(image_std, dtype=np.float32)
         self.lut = torch.from_numpy(((v[None, :] - m[:, None]) / s[:, None]).astype(np.float32)).to(self.device).contiguous()
 
+    def resized(self, im, nh: int, nw: int) -> torch.Tensor:
+        """One uint8 HWC image on the device, resized to nh x nw as Pillow's BICUBIC does (horizontal pass, then vertical)."""
+        x = self._upload(im)
+        if x.dim() != 3 or x.shape[2] != 3:
+            raise ValueError("lc2is_amd.data: images must be HWC with 3 channels")
+        h, w = x.shape[0], x.shape[1]
+        if nw != w:
+            x = ops.resample_u8(x, nw, 1, *self._dev(("cubic", w, nw), lambda: _bicubic_tables(w, nw)))
+        if nh != h:
+            x = ops.resample_u8(x, nh, 0, *self._dev(("cubic", h, nh), lambda: _bicubic_tables(h, nh)))
+        return x
+
     def __call__(self, images) -> torch.Tensor:
         out = torch.empty(len(images), 3, self.crop, self.crop, dtype=torch.float32, device=self.device)
         for i, im in enumerate(images):
-            x = self._upload(im)
-            if x.dim() != 3 or x.shape[2] != 3:
-                raise ValueError("lc2is_amd.data: images must be HWC with 3 channels")
-            h, w = x.shape[0], x.shape[1]
-            nh, nw = _target_size(h, w, self.size)
-            if nw != w:
-                x = ops.resample_u8(x, nw, 1, *self._dev(("cubic", w, nw), lambda: _bicubic_tables(w, nw)))
-            if nh != h:
-                x = ops.resample_u8(x, nh, 0, *self._dev(("cubic", h, nh), lambda: _bicubic_tables(h, nh)))
+            nh, nw = _target_size(im.shape[0], im.shape[1], self.size)
+            x = self.resized(im, nh, nw)
             top, left = self._crop_origin(nh, nw)
             ops.crop_lut(x, top, left, self.crop, lut_f32=self.lut, out_f32=out[i])
         return out

@@ -6,6 +6,8 @@ metrics.py:45-58,82-102).
     metrics = ev.evaluate()        # {"eval_loss": ..., ["eval_aux_loss": ...], "eval_mIOU_label": ...}
     ev = Evaluator(..., gt_from_metas=lambda metas: [m["gt"] for m in metas])
     metrics = ev.evaluate()        # ... and "eval_mIOU_gt": the mIoU at each image's original size (compute_gt_mIOU)
+    ev = SlideEvaluator(slide.SlidingWindowInference(model, text_inputs, flip=True), loader)   # loader: (images, gt_list)
+    metrics = ev.evaluate()        # {"eval_mIoU", "eval_mAcc", "eval_aAcc"} over the dataset (sliding windows), "eval_mIOU_gt"
 
 Semantics kept from the reference:
   * ``model.eval()``; per batch ``inputs, metas = data``; ``labels = inputs.pop("label")``; ``torch.no_grad()`` forward;
@@ -112,3 +114,31 @@ class Evaluator:
             if self.gt_from_metas is not None:
                 eval_outputs["per_image_mIOU_gt"] = torch.cat(gt_outs)
         return eval_metrics, eval_outputs
+
+
+class SlideEvaluator:
+    """Whole-image evaluation by sliding windows (``slide.SlidingWindowInference``): the dataset-level mIoU / mAcc / aAcc of the
+    published ADE20K protocol (``metrics.dataset_iou`` of the counts summed over all images, mmseg's counting rule: an ignored
+    or out-of-range pixel counts nowhere) and the reference's per-image mean over the same predictions (``eval_mIOU_gt``,
+    metrics.py:61-79, counted as ``Evaluator``'s: every pixel counts in "predicted", ``ignore_index`` only leaves the mean — a
+    second fused launch over the same window forwards).  ``loader`` yields ``(images, gt_list)``: decoded uint8 HWC
+    images and their label maps at the same sizes.  The counts stay on the device; the four scores are read once at the end."""
+
+    def __init__(self, inference, loader: Iterable, ignore_index: int | None = 0) -> None:
+        self.inference, self.loader, self.ignore_index = inference, loader, ignore_index
+
+    def evaluate(self) -> dict:
+        total, per_image = None, []
+        for images, gt_list in self.loader:
+            if self.ignore_index is None:
+                c = c_ref = self.inference.counts(images, gt_list, ignore_index=None)
+            else:
+                c, c_ref = self.inference.counts_both(images, gt_list, self.ignore_index)
+            s = c.sum(0, dtype=torch.int64)
+            total = s if total is None else total + s
+            per_image.append(_metrics._per_image_iou(c_ref, self.ignore_index))
+        if total is None:
+            raise ValueError("lc2is_amd.evalloop.SlideEvaluator: the loader yielded nothing")
+        d = _metrics.dataset_iou(total, self.ignore_index)
+        vals = torch.stack([d["mIoU"], d["mAcc"], d["aAcc"], torch.cat(per_image).mean()]).tolist()   # the one host read
+        return dict(zip(("eval_mIoU", "eval_mAcc", "eval_aAcc", "eval_mIOU_gt"), vals))

@@ -9,7 +9,10 @@ Returns ``dict(mIOU_label=float)`` like the reference.  (torchmetrics is not nee
 logits to ``sizes[i]`` (any size), argmax and counts against the original-resolution annotation ``gt_list[i]`` in one fused HIP
 kernel (``ops.resize_argmax``) that never forms the [K, H, W] score map.  Returns ``dict(mIOU_gt=float)``.
 ``original_size_predictions(outputs, sizes)`` is the reference's ``original_size_interpolate`` (metrics.py:137-143) followed by
-the argmax: a uint8 class map per image at its own size."""
+the argmax: a uint8 class map per image at its own size.
+
+``dataset_iou(counts_sum)``: the dataset-level scores of the published protocol (mmseg's IoUMetric: mIoU, mAcc, aAcc) from
+{intersection, predicted, labelled} counts summed over all images, as ``slide.SlidingWindowInference.counts`` produces them."""
 from __future__ import annotations
 
 import torch
@@ -66,3 +69,28 @@ def original_size_predictions(outputs: torch.Tensor, sizes) -> list[torch.Tensor
     outputs[i] to sizes[i], exact ties to the lowest class)."""
     preds, _ = ops.resize_argmax(outputs, sizes, want_pred=True)
     return preds
+
+
+def dataset_iou(counts_sum: torch.Tensor, ignore_index: int | None = 0) -> dict:
+    """Dataset-level scores from [3, K] {intersection, predicted, labelled} counts SUMMED over the images (int64; counted with
+    ``ignore_index`` excluded, ``ops.resize_argmax_windows(ignore_index=)``).  float64 tensors on the counts' device, nothing is
+    read to the host: ``IoU`` [K] (NaN for a class with an empty union), ``mIoU`` = its mean over the classes with a non-empty
+    union, ``mAcc`` = the mean of intersection / labelled over the labelled classes, ``aAcc`` = all intersections / all labelled;
+    ``ignore_index`` takes part in none of them."""
+    if counts_sum.dim() != 2 or counts_sum.shape[0] != 3:
+        raise ValueError(f"lc2is_amd.metrics.dataset_iou: counts must be [3, K] summed over images, got {tuple(counts_sum.shape)}")
+    c = counts_sum.to(torch.float64)
+    inter, pred, lab = c[0], c[1], c[2]
+    keep = torch.ones_like(inter, dtype=torch.bool)
+    if ignore_index is not None and 0 <= ignore_index < keep.numel():
+        keep[ignore_index] = False
+    union = pred + lab - inter
+    nan = torch.full_like(inter, float("nan"))
+    iou = torch.where(union > 0, inter / union.clamp_min(1), nan)
+    acc = torch.where(lab > 0, inter / lab.clamp_min(1), nan)
+    seen, labelled = keep & (union > 0), keep & (lab > 0)
+    zero = torch.zeros_like(inter)
+    return dict(mIoU=torch.where(seen, iou, zero).sum() / seen.sum(),
+                mAcc=torch.where(labelled, acc, zero).sum() / labelled.sum(),
+                aAcc=torch.where(keep, inter, zero).sum() / torch.where(keep, lab, zero).sum(),
+                IoU=torch.where(keep, iou, nan))

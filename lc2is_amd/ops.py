@@ -99,6 +99,7 @@ _ARGTYPES = {
     "lc2is_miou_counts": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_resize_argmax_workspace_bytes": [_L, _I],
     "lc2is_resize_argmax": [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _I, _P, _P, _P, _Z, _P],
+    "lc2is_resize_argmax_windows": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _Z, _P],
     "lc2is_npair_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_gemm_tn_grouped_workspace_bytes": [_P, _I],
     "lc2is_gemm_tn_grouped": [_P, _I, _P, _Z, _P],
@@ -1283,6 +1284,30 @@ def resize_sizes(N: int, sizes, gt=None) -> list[tuple[int, int]]:
     return hw
 
 
+def _resize_layout(hw):
+    """Per image the pixel count, first pixel and first tile of the packed pred / gt buffers, and the totals."""
+    T = RESIZE_TILE
+    tiles = [-(-H // T) * -(-W // T) for H, W in hw]
+    px = [H * W for H, W in hw]
+    first_px = [sum(px[:i]) for i in range(len(hw))]
+    first_tile = [sum(tiles[:i]) for i in range(len(hw))]
+    return px, first_px, first_tile, sum(tiles), sum(px)
+
+
+def _resize_gt(gt, dts, N, K, n_tiles, dev):
+    """(packed gt, counts, workspace, its bytes) of a call with gt maps."""
+    dt = dts.pop() if len(dts) == 1 else torch.int64
+    flat = [x.reshape(-1) for x in gt]
+    if all(not x.is_cuda for x in flat):
+        g = torch.cat([x.to(dt) for x in flat]).to(dev)          # one host -> device copy
+    else:
+        g = torch.cat([x.to(dev, dt) for x in flat])
+    counts = torch.empty((N, 3, K), dtype=torch.int32, device=dev)
+    nbytes = _fn("lc2is_resize_argmax_workspace_bytes")(n_tiles, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)     # per-tile counts (per call: live until the second launch)
+    return g, counts, ws, nbytes
+
+
 def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     """Per image, F.interpolate(scores[i:i+1], size=sizes[i], mode="bicubic", align_corners=False) and the argmax over the classes
     (exact ties: the lowest index), fused: the [K, H, W] score map is never formed (lc2is_resize_argmax).
@@ -1311,30 +1336,93 @@ def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     lo[..., :K] = scores.permute(0, 2, 3, 1)
     if ld > K:
         lo[..., K:] = 0
-    T = RESIZE_TILE
-    tiles = [-(-H // T) * -(-W // T) for H, W in hw]
-    px = [H * W for H, W in hw]
-    first_px = [sum(px[:i]) for i in range(N)]
-    first_tile = [sum(tiles[:i]) for i in range(N)]
-    n_tiles, total_px = sum(tiles), sum(px)
+    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
     desc = torch.tensor([[H, W, p0, t0] for (H, W), p0, t0 in zip(hw, first_px, first_tile)], dtype=torch.int64).to(dev)
     pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
     counts = g = ws = None
     nbytes = 0
     if gt is not None:
-        dt = dts.pop() if len(dts) == 1 else torch.int64
-        flat = [x.reshape(-1) for x in gt]
-        if all(not x.is_cuda for x in flat):
-            g = torch.cat([x.to(dt) for x in flat]).to(dev)          # one host -> device copy
-        else:
-            g = torch.cat([x.to(dev, dt) for x in flat])
-        counts = torch.empty((N, 3, K), dtype=torch.int32, device=dev)
-        nbytes = _fn("lc2is_resize_argmax_workspace_bytes")(n_tiles, K)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)     # per-tile counts (per call: live until the second launch)
+        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
     rc = _fn("lc2is_resize_argmax")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g),
                                     _GT_BYTES[g.dtype] if g is not None else 0, _ptr(pred), _ptr(counts), _ptr(ws), nbytes,
                                     _stream())
     _lib.check(rc, f"resize_argmax N={N} K={K} h={h} w={w}")
+    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
+    return preds, counts
+
+
+SLIDE_MAX_WIN = 64                      # LC2IS_SLIDE_MAX_WIN: windows per image of lc2is_resize_argmax_windows
+
+
+def resize_argmax_windows(views, windows, canvases, sizes, gt=None, want_pred: bool = True, ignore_index: int | None = None):
+    """``resize_argmax`` for sliding-window evaluation (lc2is_resize_argmax_windows): image i is resized from a canvas of
+    canvases[i] = (Hc, Wc) score cells that is never formed, each cell the mean of the window views covering it.
+    views: the model's NCHW [V, K, h, w] logits on the GPU, one score grid per window forward (the channels-last fp32 copy is made
+    here).  windows: per image a list of (view, oy, ox, mirrored): the view's index, its origin on the canvas in cells, and whether
+    it is stored mirrored along x (a forward of the flipped window).  At most 64 windows per image, every canvas cell covered.
+    sizes, gt, want_pred and the returned (pred, counts): as ``resize_argmax``.  ignore_index: None = its counting rule; an int
+    >= 0 = mmseg's: a pixel whose gt is ignore_index or outside [0, K) counts in none of the three rows.
+    Everything is validated on the host before anything is allocated."""
+    if views.dim() != 4:
+        raise RuntimeError(f"lc2is_amd.resize_argmax_windows: views must be NCHW [V, K, h, w], got shape {tuple(views.shape)}")
+    V, K, h, w = views.shape
+    if not 1 <= K <= RESIZE_KMAX:
+        raise RuntimeError(f"lc2is_amd.resize_argmax_windows: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    N = len(windows)
+    if N < 1 or len(canvases) != N:
+        raise ValueError(f"lc2is_amd.resize_argmax_windows: {N} window lists for {len(canvases)} canvases")
+    hw = resize_sizes(N, sizes, gt)
+    if ignore_index is not None and (int(ignore_index) != ignore_index or ignore_index < 0):
+        raise ValueError(f"lc2is_amd.resize_argmax_windows: ignore_index must be None or an int >= 0, got {ignore_index!r}")
+    canv, rows, first_win = [], [], []
+    for i, (wl, cv) in enumerate(zip(windows, canvases)):
+        Hc, Wc = (int(v) for v in cv)
+        if Hc < h or Wc < w:
+            raise ValueError(f"lc2is_amd.resize_argmax_windows: canvas {i} ({Hc} x {Wc}) is smaller than a view ({h} x {w})")
+        if not 1 <= len(wl) <= SLIDE_MAX_WIN:
+            raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i} has {len(wl)} windows (1 to {SLIDE_MAX_WIN})")
+        cover = torch.zeros(Hc, Wc, dtype=torch.bool)
+        first_win.append(len(rows))
+        for view, oy, ox, mirrored in wl:
+            view, oy, ox = int(view), int(oy), int(ox)
+            if not 0 <= view < V:
+                raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: view index {view} is not in [0, {V})")
+            if not (0 <= oy <= Hc - h and 0 <= ox <= Wc - w):
+                raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: window origin ({oy}, {ox}) is outside "
+                                 f"[0, {Hc - h}] x [0, {Wc - w}]")
+            cover[oy:oy + h, ox:ox + w] = True
+            rows.append((view, oy, ox, 1 if mirrored else 0))
+        if not bool(cover.all()):
+            raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: {int((~cover).sum())} canvas cells are covered by no window")
+        canv.append((Hc, Wc))
+    if gt is not None:
+        dts = {g.dtype for g in gt}
+        if not dts <= set(_GT_BYTES):
+            raise RuntimeError(f"lc2is_amd.resize_argmax_windows: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
+    if not want_pred and gt is None:
+        raise ValueError("lc2is_amd.resize_argmax_windows: nothing to compute (want_pred=False and no gt)")
+    if not views.is_cuda:
+        raise RuntimeError("lc2is_amd.resize_argmax_windows: views must be a CUDA(HIP) tensor; there is no CPU path")
+    dev = views.device
+    ld = (K + 3) // 4 * 4
+    lo = torch.empty((V, h, w, ld), dtype=torch.float32, device=dev)
+    lo[..., :K] = views.permute(0, 2, 3, 1)
+    if ld > K:
+        lo[..., K:] = 0
+    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
+    desc = torch.tensor([[H, W, p0, t0, Hc, Wc, w0, len(wl)] for (H, W), p0, t0, (Hc, Wc), w0, wl in
+                         zip(hw, first_px, first_tile, canv, first_win, windows)], dtype=torch.int64).to(dev)
+    win = torch.tensor(rows, dtype=torch.int32).to(dev)
+    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
+    counts = g = ws = None
+    nbytes = 0
+    if gt is not None:
+        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
+    rc = _fn("lc2is_resize_argmax_windows")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(win), len(rows), n_tiles, total_px,
+                                            _ptr(g), _GT_BYTES[g.dtype] if g is not None else 0,
+                                            -1 if ignore_index is None else int(ignore_index), _ptr(pred), _ptr(counts), _ptr(ws),
+                                            nbytes, _stream())
+    _lib.check(rc, f"resize_argmax_windows N={N} V={V} K={K} h={h} w={w}")
     preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
     return preds, counts
 

@@ -1,0 +1,133 @@
+"""Sliding-window (and horizontal-flip) inference at each image's original size: the protocol the published ADE20K numbers of ViT
+segmentors use (mmseg's ``slide_inference`` after ``Resize`` to the short edge + ``ResizeToMultiple``), on this repo's kernels.
+
+    inf = SlidingWindowInference(model, text_inputs, size=512, crop=512, stride=340, flip=True)
+    preds = inf.predict(images)                 # list of uint8 [H_i, W_i] class maps, on the device
+    counts = inf.counts(images, gt_list)        # int32 [N, 3, K] {intersection, predicted, labelled}, mmseg's counting rule
+
+Per image (decoded uint8 HWC): Pillow-exact bicubic resize (``ops.resample_u8``) to ``eval_size`` — the short edge at ``size``,
+both edges rounded to the model's score cell (``cell = crop // grid`` input pixels per score-grid cell); overlapping ``crop`` x
+``crop`` windows cut and normalised by ``ops.crop_lut``; the model run on batches of exactly ``window_batch`` windows; and ONE
+``ops.resize_argmax_windows`` call for all images of the call, which averages the overlapping windows' logits on the score-cell
+grid, resizes to the original size and takes the argmax without forming the canvas or the [K, H, W] score map.
+Windows lie on the score-cell grid (stride and size must be multiples of ``cell``: the default stride is 340, not mmseg's 341).
+Out of scope: multi-scale (one position table per input size), softmax-probability averaging (this averages logits, as mmseg's
+slide mode does), windows off the cell grid.  Nothing here reads device memory back to the host."""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .data.preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, ClipImagePreprocessor, _target_size
+
+
+def plan_windows(n: int, win: int, stride: int) -> list[int]:
+    """Window origins along one axis of length n (mmseg's slide_inference grid, any unit): g = max(n - win + stride - 1, 0) //
+    stride + 1 windows, the i-th at max(min(i * stride + win, n) - win, 0): the last one is pulled back inside."""
+    if n < 1 or win < 1 or stride < 1:
+        raise ValueError(f"lc2is_amd.slide: plan_windows needs positive n, win and stride, got {(n, win, stride)}")
+    g = max(n - win + stride - 1, 0) // stride + 1
+    return [max(min(i * stride + win, n) - win, 0) for i in range(g)]
+
+
+def eval_size(H: int, W: int, size: int, cell: int, crop: int | None = None) -> tuple[int, int]:
+    """The size an H x W image is evaluated at: the short edge at ``size`` keeping the aspect ratio (the preprocessor's
+    ``_target_size``), each edge rounded to the nearest multiple of ``cell`` ((n + cell // 2) // cell * cell, mmseg's
+    ResizeToMultiple) and not below ``crop`` (default: ``size``)."""
+    crop = size if crop is None else crop
+    if cell < 1 or size % cell or crop % cell:
+        raise ValueError(f"lc2is_amd.slide: size {size} and crop {crop} must be multiples of the score cell ({cell} pixels)")
+    nh, nw = _target_size(H, W, size)
+    return tuple(max((n + cell // 2) // cell * cell, crop) for n in (nh, nw))
+
+
+class SlidingWindowInference:
+    """See the module docstring.  ``text_inputs``: the model's text tensors for ONE batch of ``window_batch`` windows (every
+    forward runs at exactly that shape).  ``grid``: the edge of the model's score grid for a ``crop`` x ``crop`` input (default:
+    ``model.out_size``); ``crop % grid == 0``."""
+
+    def __init__(self, model, text_inputs: dict, *, size: int = 512, crop: int = 512, stride: int = 340, flip: bool = False,
+                 window_batch: int = 8, image_mean=OPENAI_CLIP_MEAN, image_std=OPENAI_CLIP_STD, device="cuda",
+                 grid: int | None = None) -> None:
+        self.grid = int(grid if grid is not None else model.out_size)
+        self.size, self.crop, self.stride = int(size), int(crop), int(stride)
+        if self.grid < 1 or self.crop % self.grid:
+            raise ValueError(f"lc2is_amd.slide: crop {self.crop} is not a multiple of the score grid ({self.grid})")
+        self.cell = self.crop // self.grid
+        if self.size % self.cell or self.stride < 1 or self.stride % self.cell:
+            raise ValueError(f"lc2is_amd.slide: size {self.size} and stride {self.stride} must be positive multiples of the score "
+                             f"cell ({self.cell} pixels): windows live on the model's score grid")
+        if window_batch < 1:
+            raise ValueError("lc2is_amd.slide: window_batch must be >= 1")
+        self.flip, self.window_batch = bool(flip), int(window_batch)
+        self.pre = ClipImagePreprocessor(size=self.size, crop_size=self.crop, image_mean=image_mean, image_std=image_std,
+                                         device=device)           # its resize and normalisation lut
+        self.device = self.pre.device
+        self.model = model.to(self.device)
+        bad = {k: tuple(v.shape) for k, v in text_inputs.items() if v.dim() < 1 or v.shape[0] != self.window_batch}
+        if bad:
+            raise ValueError(f"lc2is_amd.slide: text_inputs must hold one row per window of a batch ({self.window_batch}), got {bad}")
+        self.text_inputs = {k: v.to(self.device) for k, v in text_inputs.items()}
+
+    def plan(self, H: int, W: int):
+        """((Hc, Wc) canvas in cells, [(oy, ox)] window origins in cells, rows first) of an H x W image."""
+        nh, nw = eval_size(H, W, self.size, self.cell, self.crop)
+        Hc, Wc = nh // self.cell, nw // self.cell
+        ys = plan_windows(Hc, self.grid, self.stride // self.cell)
+        xs = plan_windows(Wc, self.grid, self.stride // self.cell)
+        return (Hc, Wc), [(oy, ox) for oy in ys for ox in xs]
+
+    def views(self, images):
+        """(views [V, K, grid, grid], windows, canvases, sizes) of the call's images: what ``ops.resize_argmax_windows`` takes.
+        Per image the plain windows come first, then (``flip``) their mirrored copies in the same order."""
+        plans = [self.plan(int(im.shape[0]), int(im.shape[1])) for im in images]
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        per = 2 if self.flip else 1
+        V = sum(len(o) for _, o in plans) * per
+        B = self.window_batch
+        Vp = -(-V // B) * B
+        px = torch.empty(Vp, 3, self.crop, self.crop, dtype=torch.float32, device=self.device)
+        windows, v = [], 0
+        for im, (_, origins) in zip(images, plans):
+            x = self.pre.resized(im, *eval_size(int(im.shape[0]), int(im.shape[1]), self.size, self.cell, self.crop))
+            n = len(origins)
+            for j, (oy, ox) in enumerate(origins):
+                ops.crop_lut(x, oy * self.cell, ox * self.cell, self.crop, lut_f32=self.pre.lut, out_f32=px[v + j])
+            wl = [(v + j, oy, ox, False) for j, (oy, ox) in enumerate(origins)]
+            if self.flip:
+                px[v + n:v + 2 * n] = torch.flip(px[v:v + n], dims=[-1])
+                wl += [(v + n + j, oy, ox, True) for j, (oy, ox) in enumerate(origins)]
+            windows.append(wl)
+            v += n * per
+        if Vp > V:
+            px[V:] = px[V - 1]                                      # the last batch is padded with its last window
+        self.model.eval()
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, Vp, B):
+                outs.append(self.model({"pixel_values": px[b0:b0 + B], **self.text_inputs})["outputs"])
+        out = torch.cat(outs)[:V]
+        if out.dim() != 4 or out.shape[2] != self.grid or out.shape[3] != self.grid:
+            raise RuntimeError(f"lc2is_amd.slide: the model returned scores of shape {tuple(out.shape)}, expected a "
+                               f"{self.grid} x {self.grid} grid")
+        return out, windows, [c for c, _ in plans], sizes
+
+    def predict(self, images) -> list[torch.Tensor]:
+        views, windows, canvases, sizes = self.views(images)
+        preds, _ = ops.resize_argmax_windows(views, windows, canvases, sizes)
+        return preds
+
+    def counts(self, images, gt_list, ignore_index: int | None = 0) -> torch.Tensor:
+        views, windows, canvases, sizes = self.views(images)
+        _, c = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=list(gt_list), want_pred=False,
+                                         ignore_index=ignore_index)
+        return c
+
+    def counts_both(self, images, gt_list, ignore_index: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        """(counts under mmseg's rule, counts under ``ops.resize_argmax``'s rule: every pixel counts in "predicted") from ONE set
+        of forwards and two fused launches: the dataset-level scores take the first, the reference's per-image mIoU the second."""
+        views, windows, canvases, sizes = self.views(images)
+        gt = list(gt_list)
+        _, c = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index)
+        _, c_ref = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=None)
+        return c, c_ref
