@@ -498,6 +498,39 @@ int lc2is_resize_argmax_windows(const float* views, int ld, int V, int h, int w,
                                 int ignore_index, uint8_t* pred, int* counts, void* workspace, size_t workspace_bytes,
                                 lc2is_stream_t stream);
 
+/* ---- multi-scale + flip evaluation: several canvases per image, summed before the argmax --------------------------------
+ * lc2is_resize_argmax_windows with a list of canvases per image (one per scale, or per scale and flip): every canvas is the
+ * window mean of lc2is_resize_argmax_windows, resized to the image's size H_b x W_b with the same arithmetic; the resized
+ * canvases y_0, y_1, ... are combined per class and the argmax (first maximum), counts and workspace are those of
+ * lc2is_resize_argmax_windows.  Neither a canvas nor a [K,H,W] map is formed.
+ *   views, win: as lc2is_resize_argmax_windows; all canvases of all images index the one views tensor.
+ *   desc: DEVICE int64 [N][6] = {H_b, W_b, first pixel, first tile (all four as in lc2is_resize_argmax), first canvas of image b
+ *     in canv, its number of canvases (1 to LC2IS_MS_MAX_CANVAS)}.
+ *   canv: DEVICE int64 [n_canv][4] = {Hc, Wc (canvas cells, each 1 to 2^24), first window of the canvas in win, its number of
+ *     windows (1 to LC2IS_SLIDE_MAX_WIN)}.
+ *   A canvas may be smaller than a view: a window is usable when 0 <= oy < Hc and 0 <= ox < Wc, and only its on-canvas part,
+ *     vh = min(h, Hc - oy) rows by vw = min(w, Wc - ox) columns from the view's top-left, is read.  A mirrored view (flags bit 0)
+ *     is mirrored over that part: view column j < vw is canvas column ox + vw - 1 - j.
+ *   mode: LC2IS_MS_LOGIT: s[c] = y_0[c] + y_1[c] + ..., in canvas order from y_0 (one canvas: lc2is_resize_argmax_windows'
+ *     bits).  LC2IS_MS_PROB: s[c] = sum_a exp(y_a[c] - m_a) / l_a with m_a = max_c y_a[c], l_a = sum_c exp(y_a[c] - m_a) over the
+ *     K valid channels, in canvas order: the softmax of every canvas summed (mmseg's aug_test).  exp is the hardware exp2 path
+ *     (relative error of the order of 1e-6).
+ *   Every descriptor value is range-checked on the device: an unusable window (view outside [0, V), origin off the canvas) is
+ *     skipped; an image whose canvas range lies outside [0, n_canv], with no or more than LC2IS_MS_MAX_CANVAS canvases, or with a
+ *     canvas whose size or window range does not fit or that has no usable window, is not followed: its pred pixels are left
+ *     as they were and its counts are UNDEFINED.  Nothing outside the buffers is read or written.
+ * Error codes as lc2is_resize_argmax_windows; another mode: LC2IS_ERR_SHAPE.  No atomics: bitwise reproducible, batch
+ * independent.
+ * replaces: nothing in the reference (centre crop only, metrics.py:137-143); this is the "ms+flip" row of the published ADE20K
+ *   protocol on top of the same resize + argmax. */
+#define LC2IS_MS_MAX_CANVAS 16
+#define LC2IS_MS_LOGIT 0
+#define LC2IS_MS_PROB 1
+int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                   const int64_t* canv, long n_canv, const int32_t* win, long n_win, long n_tiles,
+                                   long total_px, const void* gt, int gt_bytes, int ignore_index, int mode, uint8_t* pred,
+                                   int* counts, void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+
 /* ---- the device-held optimizer path (optim.hip) -----------------------------------------------------------------------
  * The scalars of an optimizer step that change from call to call live in this block in DEVICE memory (48 bytes, 4-byte
  * aligned, all zero before the first step), so a step needs no host value that differs between calls and can be replayed

@@ -417,6 +417,289 @@ __global__ __launch_bounds__(RA_THREADS) void ra_win_kernel(RaWinArgs p) {
 
 constexpr size_t RA_WIN_LDS = RA_LDS + RA_WMAX * sizeof(int4) + 16;
 
+// ---- multi-scale source: several canvases per image, summed as logits or as softmax probabilities --------------------------
+// ra_ms_kernel<MODE> (lc2is_resize_argmax_multiscale): an image is an ordered list of canvases, each with its own size and window
+// list; every canvas is resized to the image's size with ra_win_kernel's arithmetic and the results are combined per class before
+// the argmax.  The per-class sums of a pixel cannot be kept for all K classes, so the canvases are walked once per channel chunk
+// (32 accumulators per pixel in registers); the softmax statistics (max, 1 / sum) of every canvas at every pixel come from a
+// first walk over all chunks and wait in LDS (16 canvases x 256 pixels x 8 B = 32 KB).  A window may overhang its canvas at the
+// bottom / right (a scale below the crop): only its on-canvas part is read, and a mirrored view is mirrored over that part.
+constexpr int RA_AMAX = LC2IS_MS_MAX_CANVAS;
+
+struct RaMsArgs {
+  const float* views;       // [V, h, w, ld] as RaWinArgs
+  const int64_t* desc;      // [N][6]: H, W, first pixel, first tile (as RaArgs), first canvas, n_canvases
+  const int64_t* canv;      // [n_canv][4]: Hc, Wc (canvas cells), first window, n_windows
+  const int32_t* win;       // [n_win][4] as RaWinArgs
+  const void* gt;
+  uint8_t* pred;
+  int* slab;
+  long total_px, n_canv, n_win;
+  int N, V, h, w, ld, K, n_tiles, gt_bytes, ignore_index;
+};
+
+// a canvas row that fits the window table and the limits
+__device__ __forceinline__ bool ms_canvas_ok(const RaMsArgs& p, const int64_t* c) {
+  return c[0] >= 1 && c[0] <= (1L << 24) && c[1] >= 1 && c[1] <= (1L << 24) && c[2] >= 0 && c[3] >= 1 && c[3] <= RA_WMAX &&
+         c[2] + c[3] <= p.n_win;
+}
+
+// this lane's window of a checked canvas row: true when it is usable (view in range, origin on the canvas)
+__device__ __forceinline__ bool ms_window(const RaMsArgs& p, const int64_t* c, int lane, int4& wv) {
+  wv = make_int4(0, 0, 0, 0);
+  if (lane >= c[3]) return false;
+  wv = *reinterpret_cast<const int4*>(p.win + 4 * (c[2] + lane));
+  return wv.x >= 0 && wv.x < p.V && wv.y >= 0 && wv.y < c[0] && wv.z >= 0 && wv.z < c[1];
+}
+
+// One channel chunk [c0, c0 + 32) of one canvas over the block's tile: ra_win_kernel's bands, staging, horizontal and vertical
+// passes, statement for statement (tests/test_gpu_multiscale.py holds the one-canvas logit case to ra_win_kernel's bits), with the
+// on-canvas part of an overhanging window in the staging loop.  f(c4, y) receives channels c0 + 4 * c4 .. + 3 of the thread's pixel,
+// c4 a constant after unrolling; channels at or past K hold values that must not be used.  Ends on a barrier: the caller may
+// restage s_win or reuse s_foot at once.
+template <class F>
+__device__ __forceinline__ void ms_walk(const RaMsArgs& p, float* s_foot, float* s_hb, int4* s_xi, float4* s_xw, const int4* s_win,
+                                        int nw, int Hc, int Wc, long H, long W, int Y0, int X0, int TH, int TW, int c0, F&& f) {
+  const int tid = threadIdx.x;
+  const int py = tid / RA_T, px = tid % RA_T;
+  const bool valid = py < TH && px < TW;
+  const float sy = (float)Hc / (float)H, sx = (float)Wc / (float)W;
+  const size_t view_stride = (size_t)p.h * p.w * p.ld;
+  const int nc = min(RA_CC, p.K - c0);
+
+  for (int rb0 = 0; rb0 < TH;) {
+    const int R = ra_band(Y0 + rb0, TH - rb0, sy, Hc);
+    const int2 ys = ra_span(Y0 + rb0, Y0 + rb0 + R - 1, sy, Hc);
+    const int fy0 = ys.x, FH = ys.y - ys.x + 1;
+    const bool row_in = valid && py >= rb0 && py < rb0 + R;
+    int yi[4] = {0, 0, 0, 0};
+    float yw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (row_in) {
+      const Taps ty = make_taps(Y0 + py, sy, Hc, LC2IS_INTERP_BICUBIC);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { yi[k] = ty.idx[k] - fy0; yw[k] = ty.w[k]; }
+    }
+    for (int cb0 = 0; cb0 < TW;) {
+      const int CW = ra_band(X0 + cb0, TW - cb0, sx, Wc);
+      const int2 xs = ra_span(X0 + cb0, X0 + cb0 + CW - 1, sx, Wc);
+      const int fx0 = xs.x, FW = xs.y - xs.x + 1;
+      const bool in = row_in && px >= cb0 && px < cb0 + CW;
+      __syncthreads();
+      if (tid < CW) {
+        const Taps tx = make_taps(X0 + cb0 + tid, sx, Wc, LC2IS_INTERP_BICUBIC);
+        s_xi[tid] = make_int4(tx.idx[0] - fx0, tx.idx[1] - fx0, tx.idx[2] - fx0, tx.idx[3] - fx0);
+        s_xw[tid] = make_float4(tx.w[0], tx.w[1], tx.w[2], tx.w[3]);
+      }
+      // stage the footprint: a cell is the sum of the on-canvas parts that cover it, in list order from the first one, divided
+      // by their number.  The footprint lies on the canvas (taps are clamped), so ry < h is ry < min(h, Hc - oy), and so along x.
+      for (int i = tid; i < FH * FW * (RA_CC / 4); i += RA_THREADS) {
+        const int c4 = i % (RA_CC / 4), cell = i / (RA_CC / 4);
+        const int cy = fy0 + cell / FW, cx = fx0 + cell % FW;
+        const int c = c0 + 4 * c4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < p.ld) {
+          int n = 0;
+          for (int j = 0; j < nw; ++j) {
+            const int4 wv = s_win[j];
+            const int ry = cy - wv.y, rx = cx - wv.z;
+            if (ry < 0 || ry >= p.h || rx < 0 || rx >= p.w) continue;
+            const int col = (wv.w & 1) ? min(p.w, Wc - wv.z) - 1 - rx : rx;
+            const float4 x = *reinterpret_cast<const float4*>(p.views + (size_t)wv.x * view_stride + ((size_t)ry * p.w + col) * p.ld + c);
+            v = n ? make_float4(v.x + x.x, v.y + x.y, v.z + x.z, v.w + x.w) : x;
+            ++n;
+          }
+          if (n > 1) {
+            const float fn = (float)n;
+            v = make_float4(v.x / fn, v.y / fn, v.z / fn, v.w / fn);
+          }
+        }
+        *reinterpret_cast<float4*>(s_foot + cell * RA_CP + 4 * c4) = v;
+      }
+      __syncthreads();
+      for (int i = tid; i < FH * CW * (RA_CC / 4); i += RA_THREADS) {
+        const int c4 = i % (RA_CC / 4), x = (i / (RA_CC / 4)) % CW, r = i / (RA_CC / 4 * CW);
+        const int4 xi = s_xi[x];
+        const float4 xw = s_xw[x];
+        const float* row = s_foot + r * FW * RA_CP + 4 * c4;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        a = fma4(xw.x, *reinterpret_cast<const float4*>(row + xi.x * RA_CP), a);
+        a = fma4(xw.y, *reinterpret_cast<const float4*>(row + xi.y * RA_CP), a);
+        a = fma4(xw.z, *reinterpret_cast<const float4*>(row + xi.z * RA_CP), a);
+        a = fma4(xw.w, *reinterpret_cast<const float4*>(row + xi.w * RA_CP), a);
+        *reinterpret_cast<float4*>(s_hb + (r * RA_T + cb0 + x) * RA_CP + 4 * c4) = a;
+      }
+      __syncthreads();
+      if (in) {
+#pragma unroll
+        for (int c4 = 0; c4 < RA_CC / 4; ++c4) {
+          if (4 * c4 < nc) {
+            const float* col = s_hb + px * RA_CP + 4 * c4;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a = fma4(yw[k], *reinterpret_cast<const float4*>(col + yi[k] * RA_T * RA_CP), a);
+            f(c4, a);
+          }
+        }
+      }
+      __syncthreads();
+      cb0 += CW;
+    }
+    rb0 += R;
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(RA_THREADS) void ra_ms_kernel(RaMsArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_foot = (float*)smem;                         // as ra_win_kernel
+  float* s_hb = s_foot + RA_FMAX * RA_FMAX * RA_CP;
+  int4* s_xi = (int4*)(s_hb + RA_FMAX * RA_T * RA_CP);
+  float4* s_xw = (float4*)(s_xi + RA_T);
+  int4* s_win = (int4*)(s_xw + RA_T);                   // [RA_WMAX] the usable windows of the canvas being walked, in list order
+  int* s_nw = (int*)(s_win + RA_WMAX);                  // their number
+  float* s_m = (float*)(s_nw + 4);                      // PROB only: [RA_AMAX][RA_THREADS] max over the classes, per canvas and pixel
+  float* s_rl = s_m + RA_AMAX * RA_THREADS;             //            [RA_AMAX][RA_THREADS] 1 / sum of exp(y - max)
+  int* s_hist = (int*)smem;
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int K = p.K;
+
+  const int t = blockIdx.x;
+  int lo = 0, hi = p.N - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p.desc[6 * mid + 3] <= t) lo = mid; else hi = mid - 1;
+  }
+  const int b = lo;
+  const int64_t* d = p.desc + 6 * b;
+  const long H = d[0], W = d[1], pix0 = d[2], tile0 = d[3], cv0 = d[4], ncv = d[5];
+  const long tiles_x = (W + RA_T - 1) / RA_T;
+  // a descriptor that does not fit the buffers, the tables or the limits is not followed: nothing is written for the image
+  if (H < 1 || W < 1 || t < tile0 || pix0 < 0 || pix0 + H * W > p.total_px) return;
+  if (ncv < 1 || ncv > RA_AMAX || cv0 < 0 || cv0 + ncv > p.n_canv) return;
+  const int A = (int)ncv;
+  const int64_t* cv = p.canv + 4 * cv0;
+  // every canvas needs a row that fits and one usable window.  Each wave looks for itself (the same loads, the same answer), so
+  // the decision is the block's without a barrier.
+  for (int a = 0; a < A; ++a) {
+    if (!ms_canvas_ok(p, cv + 4 * a)) return;
+    int4 wv;
+    if (__ballot(ms_window(p, cv + 4 * a, lane, wv)) == 0ull) return;
+  }
+  const long tl = t - tile0;
+  const int Y0 = (int)(tl / tiles_x) * RA_T, X0 = (int)(tl % tiles_x) * RA_T;
+  if (Y0 >= H) return;
+  const int TH = (int)min((long)RA_T, H - Y0), TW = (int)min((long)RA_T, W - X0);
+
+  const int py = tid / RA_T, px = tid % RA_T;
+  const bool valid = py < TH && px < TW;
+
+  // the window list of canvas a, restaged when the canvas changes: wave 0 keeps the usable windows, order preserved.  The walk
+  // before it ended on a barrier, so nobody still reads the old list.
+  int staged = -1;
+  auto stage = [&](int a) {
+    if (a == staged) return;
+    staged = a;
+    if (wid == 0) {
+      int4 wv;
+      const bool ok = ms_window(p, cv + 4 * a, lane, wv);
+      const unsigned long long m = __ballot(ok);
+      if (ok) s_win[__popcll(m & ((1ull << lane) - 1ull))] = wv;
+      if (lane == 0) *s_nw = __popcll(m);
+    }
+    __syncthreads();
+  };
+
+  if (MODE == LC2IS_MS_PROB) {
+    // pass A: the softmax statistics of every canvas at this thread's pixel, online over the chunks (valid channels only)
+    for (int a = 0; a < A; ++a) {
+      stage(a);
+      float m = -INFINITY, l = 0.f;
+      for (int c0 = 0; c0 < K; c0 += RA_CC) {
+        const int nc = min(RA_CC, K - c0);
+        ms_walk(p, s_foot, s_hb, s_xi, s_xw, s_win, *s_nw, (int)cv[4 * a], (int)cv[4 * a + 1], H, W, Y0, X0, TH, TW, c0,
+                [&](int c4, float4 y) {
+                  const bool v1 = 4 * c4 + 1 < nc, v2 = 4 * c4 + 2 < nc, v3 = 4 * c4 + 3 < nc;
+                  float mn = fmaxf(m, y.x);
+                  if (v1) mn = fmaxf(mn, y.y);
+                  if (v2) mn = fmaxf(mn, y.z);
+                  if (v3) mn = fmaxf(mn, y.w);
+                  l = l * __expf(m - mn) + __expf(y.x - mn);
+                  if (v1) l += __expf(y.y - mn);
+                  if (v2) l += __expf(y.z - mn);
+                  if (v3) l += __expf(y.w - mn);
+                  m = mn;
+                });
+      }
+      s_m[a * RA_THREADS + tid] = m;
+      s_rl[a * RA_THREADS + tid] = 1.f / l;
+    }
+  }
+
+  // pass B: per chunk the sum over the canvases, in canvas order from the first one, then the running argmax as ra_win_kernel's
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c0 = 0; c0 < K; c0 += RA_CC) {
+    const int nc = min(RA_CC, K - c0);
+    float4 acc[RA_CC / 4];
+#pragma unroll
+    for (int c4 = 0; c4 < RA_CC / 4; ++c4) acc[c4] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int a = 0; a < A; ++a) {
+      stage(a);
+      float m = 0.f, rl = 1.f;
+      if (MODE == LC2IS_MS_PROB) { m = s_m[a * RA_THREADS + tid]; rl = s_rl[a * RA_THREADS + tid]; }
+      ms_walk(p, s_foot, s_hb, s_xi, s_xw, s_win, *s_nw, (int)cv[4 * a], (int)cv[4 * a + 1], H, W, Y0, X0, TH, TW, c0,
+              [&](int c4, float4 y) {
+                if (MODE == LC2IS_MS_PROB)
+                  y = make_float4(__expf(y.x - m) * rl, __expf(y.y - m) * rl, __expf(y.z - m) * rl, __expf(y.w - m) * rl);
+                const float4 s = acc[c4];
+                acc[c4] = a ? make_float4(s.x + y.x, s.y + y.y, s.z + y.z, s.w + y.w) : y;
+              });
+    }
+    if (valid) {
+#pragma unroll
+      for (int c4 = 0; c4 < RA_CC / 4; ++c4) {
+        if (4 * c4 < nc) {
+          const float4 s = acc[c4];
+          const int c = c0 + 4 * c4;
+          if (s.x > best) { best = s.x; arg = c; }
+          if (4 * c4 + 1 < nc && s.y > best) { best = s.y; arg = c + 1; }
+          if (4 * c4 + 2 < nc && s.z > best) { best = s.z; arg = c + 2; }
+          if (4 * c4 + 3 < nc && s.w > best) { best = s.w; arg = c + 3; }
+        }
+      }
+    }
+  }
+
+  const size_t o = (size_t)pix0 + (size_t)(Y0 + py) * W + X0 + px;
+  if (valid && p.pred) p.pred[o] = (uint8_t)arg;
+  if (!p.slab) return;
+
+  // counts: ra_win_kernel's rules and histograms (the last walk ended on a barrier: s_foot is free)
+  int g = -1;
+  if (valid && p.gt) {
+    long v;
+    if (p.gt_bytes == 1) v = ((const uint8_t*)p.gt)[o];
+    else if (p.gt_bytes == 4) v = ((const int32_t*)p.gt)[o];
+    else v = ((const int64_t*)p.gt)[o];
+    g = (v >= 0 && v < K && !(p.ignore_index >= 0 && v == p.ignore_index)) ? (int)v : -1;
+  }
+  int* hw = s_hist + wid * 3 * K;
+  for (int i = lane; i < 3 * K; i += 64) hw[i] = 0;
+  __syncthreads();
+  wave_hist(hw + K, p.ignore_index >= 0 ? g >= 0 : valid, arg, lane);
+  wave_hist(hw, valid && g == arg, arg, lane);
+  wave_hist(hw + 2 * K, g >= 0, g, lane);
+  __syncthreads();
+  int* out = p.slab + (size_t)t * 3 * K;
+  for (int i = tid; i < 3 * K; i += RA_THREADS)
+    out[i] = ((s_hist[i] + s_hist[3 * K + i]) + s_hist[6 * K + i]) + s_hist[9 * K + i];
+}
+
+constexpr size_t RA_MS_LDS_LOGIT = RA_WIN_LDS;
+constexpr size_t RA_MS_LDS_PROB = RA_WIN_LDS + 2 * (size_t)RA_AMAX * RA_THREADS * sizeof(float);
+static_assert(RA_MS_LDS_PROB <= 80 * 1024, "two blocks per CU");
+
 }  // namespace
 
 extern "C" size_t lc2is_resize_argmax_workspace_bytes(long n_tiles, int K) {
@@ -469,6 +752,45 @@ extern "C" int lc2is_resize_argmax_windows(const float* views, int ld, int V, in
   int rc = lc2is_check_launch();
   if (rc || !counts) return rc;
   hipLaunchKernelGGL(ra_finish_kernel<8>, dim3((3 * K + 63) / 64, N), dim3(256), 0, stream, desc, (const int*)workspace, counts, K,
+                     (int)n_tiles);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                              const int64_t* canv, long n_canv, const int32_t* win, long n_win, long n_tiles,
+                                              long total_px, const void* gt, int gt_bytes, int ignore_index, int mode,
+                                              uint8_t* pred, int* counts, void* workspace, size_t workspace_bytes,
+                                              lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!views || !desc || !canv || !win || (!pred && !counts)) return LC2IS_ERR_NULL;
+  if (counts && (!gt || !workspace)) return LC2IS_ERR_NULL;
+  if (N <= 0 || V <= 0 || h <= 0 || w <= 0 || K <= 0 || ld < K || ld % 4 || ((uintptr_t)views & 15) || ((uintptr_t)win & 15) ||
+      n_canv <= 0 || n_win <= 0 || n_tiles <= 0 || n_tiles > 0x7fffffffL || total_px <= 0 || ignore_index < -1 ||
+      (mode != LC2IS_MS_LOGIT && mode != LC2IS_MS_PROB))
+    return LC2IS_ERR_SHAPE;
+  if (K > RA_KMAX) return LC2IS_ERR_UNSUPPORTED;
+  if (counts && gt_bytes != 1 && gt_bytes != 4 && gt_bytes != 8) return LC2IS_ERR_UNSUPPORTED;
+  if (counts && workspace_bytes < lc2is_resize_argmax_workspace_bytes(n_tiles, K)) return LC2IS_ERR_WORKSPACE;
+  RaMsArgs a;
+  a.views = views; a.desc = desc; a.canv = canv; a.win = win; a.gt = counts ? gt : nullptr; a.pred = pred;
+  a.slab = counts ? (int*)workspace : nullptr;
+  a.total_px = total_px; a.n_canv = n_canv; a.n_win = n_win; a.N = N; a.V = V; a.h = h; a.w = w; a.ld = ld; a.K = K;
+  a.n_tiles = (int)n_tiles; a.gt_bytes = gt_bytes; a.ignore_index = ignore_index;
+  if (mode == LC2IS_MS_PROB) {
+    static DevOnce attr_set;   // 70 KB of dynamic LDS: above the default limit
+    if (attr_set.need()) {
+      if (hipFuncSetAttribute((const void*)ra_ms_kernel<LC2IS_MS_PROB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)RA_MS_LDS_PROB) != hipSuccess)
+        return LC2IS_ERR_LAUNCH;
+      attr_set.done();
+    }
+    hipLaunchKernelGGL(ra_ms_kernel<LC2IS_MS_PROB>, dim3((unsigned)n_tiles), dim3(RA_THREADS), RA_MS_LDS_PROB, stream, a);
+  } else {
+    hipLaunchKernelGGL(ra_ms_kernel<LC2IS_MS_LOGIT>, dim3((unsigned)n_tiles), dim3(RA_THREADS), RA_MS_LDS_LOGIT, stream, a);
+  }
+  int rc = lc2is_check_launch();
+  if (rc || !counts) return rc;
+  hipLaunchKernelGGL(ra_finish_kernel<6>, dim3((3 * K + 63) / 64, N), dim3(256), 0, stream, desc, (const int*)workspace, counts, K,
                      (int)n_tiles);
   return lc2is_check_launch();
 }

@@ -100,6 +100,7 @@ _ARGTYPES = {
     "lc2is_resize_argmax_workspace_bytes": [_L, _I],
     "lc2is_resize_argmax": [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _I, _P, _P, _P, _Z, _P],
     "lc2is_resize_argmax_windows": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _Z, _P],
+    "lc2is_resize_argmax_multiscale": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _Z, _P],
     "lc2is_npair_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_gemm_tn_grouped_workspace_bytes": [_P, _I],
     "lc2is_gemm_tn_grouped": [_P, _I, _P, _Z, _P],
@@ -1423,6 +1424,92 @@ def resize_argmax_windows(views, windows, canvases, sizes, gt=None, want_pred: b
                                             -1 if ignore_index is None else int(ignore_index), _ptr(pred), _ptr(counts), _ptr(ws),
                                             nbytes, _stream())
     _lib.check(rc, f"resize_argmax_windows N={N} V={V} K={K} h={h} w={w}")
+    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
+    return preds, counts
+
+
+MS_MAX_CANVAS = 16                      # LC2IS_MS_MAX_CANVAS: canvases per image of lc2is_resize_argmax_multiscale
+_MS_MODES = {"logit": 0, "prob": 1}     # LC2IS_MS_LOGIT, LC2IS_MS_PROB
+
+
+def resize_argmax_multiscale(views, canvases, sizes, gt=None, want_pred: bool = True, ignore_index: int | None = None,
+                             mode: str = "prob"):
+    """``resize_argmax_windows`` over several canvases per image (lc2is_resize_argmax_multiscale): multi-scale / flip evaluation.
+    canvases[i]: the ordered list of ((Hc, Wc), windows) of image i, 1 to 16 of them, ``windows`` as in ``resize_argmax_windows``
+    (1 to 64 per canvas, every canvas cell covered).  Every canvas is the window mean, resized to sizes[i]; the resized canvases
+    are summed per class in list order, as logits (mode="logit") or after a softmax over the classes of each (mode="prob", mmseg's
+    aug_test), and the argmax of the sum is taken.  No canvas and no [K, H, W] map is formed.
+    A canvas may be smaller than a view (a scale below the crop): a window's origin must lie on the canvas, and only the part of
+    the view that lies on the canvas is read (its top-left min(h, Hc - oy) x min(w, Wc - ox) cells; a mirrored view is mirrored
+    over that part).
+    views, sizes, gt, want_pred, ignore_index and the returned (pred, counts): as ``resize_argmax_windows``.
+    Everything is validated on the host before anything is allocated."""
+    who = "lc2is_amd.resize_argmax_multiscale"
+    if views.dim() != 4:
+        raise RuntimeError(f"{who}: views must be NCHW [V, K, h, w], got shape {tuple(views.shape)}")
+    V, K, h, w = views.shape
+    if not 1 <= K <= RESIZE_KMAX:
+        raise RuntimeError(f"{who}: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    if mode not in _MS_MODES:
+        raise ValueError(f"{who}: mode must be 'prob' or 'logit', got {mode!r}")
+    N = len(canvases)
+    if N < 1:
+        raise ValueError(f"{who}: no images")
+    hw = resize_sizes(N, sizes, gt)
+    if ignore_index is not None and (int(ignore_index) != ignore_index or ignore_index < 0):
+        raise ValueError(f"{who}: ignore_index must be None or an int >= 0, got {ignore_index!r}")
+    crows, rows, first_canvas = [], [], []
+    for i, cl in enumerate(canvases):
+        if not 1 <= len(cl) <= MS_MAX_CANVAS:
+            raise ValueError(f"{who}: image {i} has {len(cl)} canvases (1 to {MS_MAX_CANVAS})")
+        first_canvas.append(len(crows))
+        for a, (cv, wl) in enumerate(cl):
+            Hc, Wc = (int(v) for v in cv)
+            if Hc < 1 or Wc < 1:
+                raise ValueError(f"{who}: image {i} canvas {a}: size ({Hc}, {Wc}) is not positive")
+            if not 1 <= len(wl) <= SLIDE_MAX_WIN:
+                raise ValueError(f"{who}: image {i} canvas {a} has {len(wl)} windows (1 to {SLIDE_MAX_WIN})")
+            cover = torch.zeros(Hc, Wc, dtype=torch.bool)
+            crows.append((Hc, Wc, len(rows), len(wl)))
+            for view, oy, ox, mirrored in wl:
+                view, oy, ox = int(view), int(oy), int(ox)
+                if not 0 <= view < V:
+                    raise ValueError(f"{who}: image {i} canvas {a}: view index {view} is not in [0, {V})")
+                if not (0 <= oy < Hc and 0 <= ox < Wc):
+                    raise ValueError(f"{who}: image {i} canvas {a}: window origin ({oy}, {ox}) is outside the {Hc} x {Wc} canvas")
+                cover[oy:oy + h, ox:ox + w] = True
+                rows.append((view, oy, ox, 1 if mirrored else 0))
+            if not bool(cover.all()):
+                raise ValueError(f"{who}: image {i} canvas {a}: {int((~cover).sum())} canvas cells are covered by no window")
+    if gt is not None:
+        dts = {g.dtype for g in gt}
+        if not dts <= set(_GT_BYTES):
+            raise RuntimeError(f"{who}: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
+    if not want_pred and gt is None:
+        raise ValueError(f"{who}: nothing to compute (want_pred=False and no gt)")
+    if not views.is_cuda:
+        raise RuntimeError(f"{who}: views must be a CUDA(HIP) tensor; there is no CPU path")
+    dev = views.device
+    ld = (K + 3) // 4 * 4
+    lo = torch.empty((V, h, w, ld), dtype=torch.float32, device=dev)
+    lo[..., :K] = views.permute(0, 2, 3, 1)
+    if ld > K:
+        lo[..., K:] = 0
+    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
+    desc = torch.tensor([[H, W, p0, t0, c0, len(cl)] for (H, W), p0, t0, c0, cl in
+                         zip(hw, first_px, first_tile, first_canvas, canvases)], dtype=torch.int64).to(dev)
+    canv = torch.tensor(crows, dtype=torch.int64).to(dev)
+    win = torch.tensor(rows, dtype=torch.int32).to(dev)
+    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
+    counts = g = ws = None
+    nbytes = 0
+    if gt is not None:
+        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
+    rc = _fn("lc2is_resize_argmax_multiscale")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(canv), len(crows), _ptr(win), len(rows),
+                                               n_tiles, total_px, _ptr(g), _GT_BYTES[g.dtype] if g is not None else 0,
+                                               -1 if ignore_index is None else int(ignore_index), _MS_MODES[mode], _ptr(pred),
+                                               _ptr(counts), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, f"resize_argmax_multiscale N={N} V={V} K={K} h={h} w={w} canvases={len(crows)} mode={mode}")
     preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
     return preds, counts
 

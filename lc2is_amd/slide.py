@@ -11,8 +11,19 @@ both edges rounded to the model's score cell (``cell = crop // grid`` input pixe
 ``ops.resize_argmax_windows`` call for all images of the call, which averages the overlapping windows' logits on the score-cell
 grid, resizes to the original size and takes the argmax without forming the canvas or the [K, H, W] score map.
 Windows lie on the score-cell grid (stride and size must be multiples of ``cell``: the default stride is 340, not mmseg's 341).
-Out of scope: multi-scale (one position table per input size), softmax-probability averaging (this averages logits, as mmseg's
-slide mode does), windows off the cell grid.  Nothing here reads device memory back to the host."""
+Nothing here reads device memory back to the host.
+
+Multi-scale + flip (the "ms+flip" rows of segmentation tables, mmseg's ``aug_test``):
+
+    inf = MultiScaleInference(model, text_inputs, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True, average="prob")
+
+Per scale s the short edge goes to ``scale_size(size, s, cell)`` and the image is windowed as above; every scale (``average="prob"``:
+every scale and flip) is one canvas of ONE ``ops.resize_argmax_multiscale`` call, which resizes each canvas to the original size,
+takes the softmax over the classes of each, sums them and takes the argmax ("logit": sums the resized logits).  A scale whose short
+edge is below ``crop`` gives an image smaller than a window: the window is padded at the bottom / right with 0.0 after normalisation
+(the mean colour, as the training crops are) and only its unpadded cells enter the canvas.
+Out of scope: per-scale weights, windows off the cell grid, models that take variable input sizes (every forward is a ``crop`` x
+``crop`` window)."""
 from __future__ import annotations
 
 import torch
@@ -130,4 +141,136 @@ class SlidingWindowInference:
         gt = list(gt_list)
         _, c = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index)
         _, c_ref = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=None)
+        return c, c_ref
+
+
+def scale_size(size: int, scale: float, cell: int) -> int:
+    """The short-edge target of one scale: size * scale rounded to the nearest multiple of ``cell``, at least one cell."""
+    return max(cell, int(size * scale / cell + 0.5) * cell)
+
+
+def plan_multiscale(H: int, W: int, scales, size: int, crop: int, stride: int, cell: int):
+    """Per scale ((nh, nw) pixels the H x W image is resized to, (Hc, Wc) canvas in cells, [(oy, ox)] window origins in cells, rows
+    first).  A short edge at or above ``crop``: ``eval_size`` and the windows of ``SlidingWindowInference``.  Below it: the
+    preprocessor's ``_target_size`` with each edge rounded to the cell grid as ``eval_size`` does (at least one cell, no floor at
+    ``crop``); an axis shorter than the window has its one window at 0, which overhangs the canvas."""
+    out = []
+    for s in scales:
+        ss = scale_size(size, s, cell)
+        if ss >= crop:
+            nh, nw = eval_size(H, W, ss, cell, crop)
+        else:
+            nh, nw = (max((n + cell // 2) // cell * cell, cell) for n in _target_size(H, W, ss))
+        Hc, Wc = nh // cell, nw // cell
+        ys = plan_windows(Hc, crop // cell, stride // cell)
+        xs = plan_windows(Wc, crop // cell, stride // cell)
+        out.append(((nh, nw), (Hc, Wc), [(oy, ox) for oy in ys for ox in xs]))
+    return out
+
+
+def multiscale_canvases(plan, first_view: int, flip: bool, average: str):
+    """(canvases of one image as ``ops.resize_argmax_multiscale`` takes them, number of views) from its ``plan_multiscale``.  Views are
+    numbered from ``first_view``, scale-major, per scale the plain windows and then (``flip``) their mirrored copies.  "prob": the
+    plain and the mirrored windows of a scale are two canvases, plain first; "logit": one canvas holds both."""
+    canvases, v = [], first_view
+    for _, canvas, origins in plan:
+        n = len(origins)
+        plain = [(v + j, oy, ox, False) for j, (oy, ox) in enumerate(origins)]
+        mirrored = [(v + n + j, oy, ox, True) for j, (oy, ox) in enumerate(origins)] if flip else []
+        if flip and average == "prob":
+            canvases += [(canvas, plain), (canvas, mirrored)]
+        else:
+            canvases.append((canvas, plain + mirrored))
+        v += n * (2 if flip else 1)
+    return canvases, v - first_view
+
+
+class MultiScaleInference(SlidingWindowInference):
+    """See the module docstring.  ``predict``, ``counts`` and ``counts_both`` match ``SlidingWindowInference``'s, so
+    ``evalloop.SlideEvaluator`` takes either.  ``average``: "prob" (softmax of every (scale, flip) view summed: mmseg's aug_test) or
+    "logit" (one canvas per scale holding plain and mirrored windows, the canvases summed as logits).  At most 16 canvases per image:
+    ``len(scales)``, doubled by ``flip`` under "prob"."""
+
+    def __init__(self, model, text_inputs: dict, *, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), size: int = 512, crop: int = 512,
+                 stride: int = 340, flip: bool = True, average: str = "prob", window_batch: int = 8, image_mean=OPENAI_CLIP_MEAN,
+                 image_std=OPENAI_CLIP_STD, device="cuda", grid: int | None = None) -> None:
+        self.scales = tuple(float(s) for s in scales)
+        if not self.scales or any(not s > 0 for s in self.scales):
+            raise ValueError(f"lc2is_amd.slide: scales must be a non-empty sequence of positive numbers, got {scales!r}")
+        if average not in ("prob", "logit"):
+            raise ValueError(f"lc2is_amd.slide: average must be 'prob' or 'logit', got {average!r}")
+        self.average = average
+        self.n_canvases = len(self.scales) * (2 if flip and average == "prob" else 1)
+        if self.n_canvases > ops.MS_MAX_CANVAS:
+            raise ValueError(f"lc2is_amd.slide: {len(self.scales)} scales with flip={bool(flip)} and average={average!r} are "
+                             f"{self.n_canvases} canvases per image (at most {ops.MS_MAX_CANVAS})")
+        super().__init__(model, text_inputs, size=size, crop=crop, stride=stride, flip=flip, window_batch=window_batch,
+                         image_mean=image_mean, image_std=image_std, device=device, grid=grid)
+
+    def plan(self, H: int, W: int):
+        """``plan_multiscale`` of an H x W image: one ((nh, nw), (Hc, Wc), origins) per scale."""
+        return plan_multiscale(H, W, self.scales, self.size, self.crop, self.stride, self.cell)
+
+    def views(self, images):
+        """(views [V, K, grid, grid], canvases, sizes) of the call's images: what ``ops.resize_argmax_multiscale`` takes.  The
+        windows of all scales of all images go through the model in batches of exactly ``window_batch``."""
+        plans = [self.plan(int(im.shape[0]), int(im.shape[1])) for im in images]
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        canvases, V = [], 0
+        for pl in plans:
+            cl, n = multiscale_canvases(pl, V, self.flip, self.average)
+            canvases.append(cl)
+            V += n
+        B, S = self.window_batch, self.crop
+        Vp = -(-V // B) * B
+        px = torch.empty(Vp, 3, S, S, dtype=torch.float32, device=self.device)
+        v = 0
+        for im, pl in zip(images, plans):
+            for (nh, nw), _, origins in pl:
+                x = self.pre.resized(im, nh, nw)
+                if nh < S or nw < S:                                # the window cut needs S x S source pixels: pad, then blank
+                    xp = x.new_zeros(max(nh, S), max(nw, S), 3)
+                    xp[:nh, :nw] = x
+                    x = xp
+                n = len(origins)
+                for j, (oy, ox) in enumerate(origins):
+                    top, left = oy * self.cell, ox * self.cell
+                    ops.crop_lut(x, top, left, S, lut_f32=self.pre.lut, out_f32=px[v + j])
+                    ih, iw = min(S, nh - top), min(S, nw - left)    # the window's image part; the rest is 0.0 after normalisation
+                    px[v + j, :, ih:, :] = 0
+                    px[v + j, :, :, iw:] = 0
+                    if self.flip:                                   # the image part mirrored, then padded
+                        px[v + n + j, :, :, :iw] = torch.flip(px[v + j, :, :, :iw], dims=[-1])
+                        px[v + n + j, :, :, iw:] = 0
+                v += n * (2 if self.flip else 1)
+        if Vp > V:
+            px[V:] = px[V - 1]                                      # the last batch is padded with its last window
+        self.model.eval()
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, Vp, B):
+                outs.append(self.model({"pixel_values": px[b0:b0 + B], **self.text_inputs})["outputs"])
+        out = torch.cat(outs)[:V]
+        if out.dim() != 4 or out.shape[2] != self.grid or out.shape[3] != self.grid:
+            raise RuntimeError(f"lc2is_amd.slide: the model returned scores of shape {tuple(out.shape)}, expected a "
+                               f"{self.grid} x {self.grid} grid")
+        return out, canvases, sizes
+
+    def predict(self, images) -> list[torch.Tensor]:
+        views, canvases, sizes = self.views(images)
+        preds, _ = ops.resize_argmax_multiscale(views, canvases, sizes, mode=self.average)
+        return preds
+
+    def counts(self, images, gt_list, ignore_index: int | None = 0) -> torch.Tensor:
+        views, canvases, sizes = self.views(images)
+        _, c = ops.resize_argmax_multiscale(views, canvases, sizes, gt=list(gt_list), want_pred=False, ignore_index=ignore_index,
+                                            mode=self.average)
+        return c
+
+    def counts_both(self, images, gt_list, ignore_index: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+        views, canvases, sizes = self.views(images)
+        gt = list(gt_list)
+        _, c = ops.resize_argmax_multiscale(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index,
+                                            mode=self.average)
+        _, c_ref = ops.resize_argmax_multiscale(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=None, mode=self.average)
         return c, c_ref
