@@ -698,6 +698,44 @@ int lc2is_aug_apply(const uint8_t* img, size_t img_bytes, const uint8_t* lab, si
                     const lc2is_aug_norm* norm /* HOST */, long pad_label, float* out_img, int64_t* out_lab,
                     lc2is_stream_t stream);
 
+/* aug_crop_select_kernel, an OPTIONAL launch between lc2is_aug_params and lc2is_aug_apply: the class-ratio re-draw of the crop
+ * origin.  One block per sample b < B reads row b of params and the pool's label map and overwrites the row's LC2IS_AUG_TOP /
+ * LC2IS_AUG_LEFT words with the selected candidate; every other word of the row stays.  S = cfg->crop_size, S % L == 0, q = S / L.
+ * Integers only: the result is exact.
+ *   Candidates: candidate 0 is the (top, left) already in the row (draws k = 1, 2); for t = 1 .. tries (1 <= tries <=
+ *     LC2IS_AUG_MAX_TRIES)   top_t = (u24(10 + 2t) * (max(nh - S, 0) + 1)) >> 24,  left_t = (u24(11 + 2t) * (max(nw - S, 0) + 1)) >> 24
+ *     with the sample hash of lc2is_aug_params (cfg's seed, *epoch, key = keys ? keys[b] : slots[b]): draws 12 .. 31.
+ *   Counted for candidate t: exactly the L x L label cells lc2is_aug_apply would write for (nh, nw, top_t, left_t, flip of the
+ *     row) - cell (i, j) looks at output pixel (i*q + q/2, j*q + q/2), the same yr, xr (flip included) and nearest-exact ys, xs.  A
+ *     cell outside [0, nh) x [0, nw) is padding and is not counted, whatever pad_label will be; a cell whose label equals
+ *     ignore_label (0 .. 255, or -1 for none) is not counted.  n_c per class c, n = sum n_c, m = max n_c, d = #{c : n_c > 0}.
+ *   Verdict: candidate t is accepted iff d > 1 && m * 1024 < ratio1024 * n (64-bit), ratio1024 = round(cat_max_ratio * 1024) in
+ *     1 .. 1023: mmseg's `len(cnt) > 1 and max(cnt) / sum(cnt) < cat_max_ratio`, on the labels the loss will see (mmseg counts the
+ *     full-resolution crop; the cells are q * q times fewer reads).
+ *   Selection: candidates 0 .. tries-1 are checked in order and the first accepted one is taken; if none is, candidate `tries` is
+ *     taken unchecked (mmseg draws once more after its last failed check in the same way).
+ *   info (may be NULL): int32 [B][4] = {t*, n, m, d} of the chosen candidate, {tries, 0, 0, 0} when none was accepted.
+ * A slot outside [0, n_images), a descriptor whose sides or lab_off do not fit lab_bytes, or nh / nw outside
+ * 1 .. LC2IS_AUG_MAX_RESIZED (the all-zero row lc2is_aug_params writes for a bad slot included): the row is left untouched, info =
+ * {-1, 0, 0, 0}, and nothing outside the buffers is read.  The class counts are a wave-merged LDS histogram (csrc/label_hist.h):
+ * NO read-modify-write atomics, LDS included; bitwise reproducible; device values only, so a captured launch selects afresh on replay.
+ * Errors: LC2IS_ERR_NULL (lab, desc, slots, epoch, cfg, params); LC2IS_ERR_SHAPE (B, n_images < 1, S % L, ratio1024, ignore_label or
+ * tries out of range, params / info not 4-byte or desc not 8-byte aligned).
+ * replaces: mmseg's RandomCrop(cat_max_ratio=0.75) - np.unique over every candidate crop of the label map, on the host. */
+#define LC2IS_AUG_MAX_TRIES 10
+int lc2is_aug_crop_select(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc, long n_images, const int64_t* slots,
+                          const int64_t* keys, int B, const int32_t* epoch, const lc2is_aug_config* cfg /* HOST */, int32_t* params,
+                          int L, int ratio1024, int ignore_label, int tries, int32_t* info, lc2is_stream_t stream);
+
+/* label_hist_kernel, one block per row b < B with a block-stride loop: counts[b][v] (int32 [B][256], OVERWRITTEN) = the number of
+ * pixels of image slots[b] whose label is v.  Sides are at most LC2IS_AUG_MAX_SIDE, so a count stays below 2^24 + 1.  The same range
+ * checks as above (slot, sides, lab_off against lab_bytes): a bad row gives all zeros and reads nothing.  The same wave-merged LDS
+ * histogram: no atomics, exact.  Errors: LC2IS_ERR_NULL; LC2IS_ERR_SHAPE (B, n_images < 1, counts not 4-byte or desc not 8-byte aligned).
+ * replaces: np.bincount / torch.bincount over every label map of the training split, the input of median-frequency (Eigen &
+ *   Fergus) or ENet class weights for nn.CrossEntropyLoss(weight=). */
+int lc2is_label_histogram(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc, long n_images, const int64_t* slots,
+                          int B, int32_t* counts, lc2is_stream_t stream);
+
 /* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
  * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
  * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with

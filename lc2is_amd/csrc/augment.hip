@@ -7,8 +7,13 @@
 //     HBM-bound by its 3 * 16-byte stores per lane; the source taps are unaligned 8-byte reads (two neighbouring HWC pixels) that
 //     neighbouring lanes take from neighbouring bytes.  Source coordinates are exact integers: the quotient of at most 4096 comes
 //     from one fp32 multiply by a reciprocal and an integer correction instead of hipcc's ~35-instruction udiv.
-// The exact definition is in include/lc2is_hip.h; tests/augment_ref.py restates it in numpy (integers bit for bit).
+//   * aug_crop_select_kernel (optional, between the two): the class-ratio re-draw of mmseg's RandomCrop(cat_max_ratio).  One block
+//     per sample counts the label cells aug_apply would write for each candidate origin and replaces the row's (top, left).
+//   * label_hist_kernel: per-image class counts of the pool's label maps, for class weights.  Both count with label_hist.h.
+// The exact definition is in include/lc2is_hip.h; tests/augment_ref.py and tests/catcrop_ref.py restate it in numpy (integers bit
+// for bit).
 #include "common.h"
+#include "label_hist.h"
 #include "lc2is_hip.h"
 
 namespace {
@@ -252,6 +257,159 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const unsigned char* __r
   for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane) = out[c];   // plain (write-back) stores: patchify reads them next
 }
 
+// ---- class-ratio crop re-draw (mmseg RandomCrop(cat_max_ratio)) and the per-image label histogram ----
+// Both count uint8 labels with the wave histogram of label_hist.h: no read-modify-write atomic, the same bytes every run.
+constexpr int LH_THREADS = 1024;
+constexpr int LH_WAVES = LH_THREADS / 64;
+constexpr int LH_UNROLL = 4;   // independent one-byte loads in flight per lane
+
+struct LabSample {   // block-uniform
+  bool valid;
+  int H, W;
+  long long lab_off;
+};
+__device__ __forceinline__ LabSample lab_sample(const lc2is_aug_image* __restrict__ desc, long n_images, long long slot,
+                                                size_t lab_bytes) {
+  LabSample s;
+  s.valid = slot >= 0 && slot < n_images;
+  const lc2is_aug_image d = s.valid ? desc[slot] : lc2is_aug_image{0, 0, 0, 0};
+  s.H = d.H; s.W = d.W; s.lab_off = d.lab_off;
+  s.valid = s.valid && s.H >= 1 && s.W >= 1 && s.H <= LC2IS_AUG_MAX_SIDE && s.W <= LC2IS_AUG_MAX_SIDE && s.lab_off >= 0 &&
+            (unsigned long long)s.lab_off + (unsigned long long)s.H * s.W <= lab_bytes;
+  return s;
+}
+
+// One block per sample walks the candidates in order and leaves at the first accepted one.  Per candidate: every lane gathers
+// LH_UNROLL label cells per round (the coordinates of aug_apply_kernel's label branch, flip included), the waves count them in
+// their LDS rows, 256 lanes add the rows in wave order and four waves reduce n = sum, m = max, d = classes present; the verdict
+// d > 1 && m * 1024 < ratio1024 * n is block-uniform.  Lane 0 writes the chosen (top, left) into the row and {t*, n, m, d} to info.
+__global__ __launch_bounds__(LH_THREADS) void aug_crop_select_kernel(const unsigned char* __restrict__ lab, size_t lab_bytes,
+                                                                      const lc2is_aug_image* __restrict__ desc, long n_images,
+                                                                      const int64_t* __restrict__ slots, const int64_t* __restrict__ keys,
+                                                                      const int32_t* __restrict__ epoch, unsigned seed_lo,
+                                                                      unsigned seed_hi, int S, int L, int ratio1024, int ignore_label,
+                                                                      int tries, int32_t* params, int32_t* info) {
+  __shared__ unsigned s_hist[LH_WAVES * LH_BINS];
+  __shared__ unsigned s_red[LH_BINS / 64][3];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int32_t* row = params + (size_t)b * AUG_P;
+  int32_t* irow = info ? info + (size_t)b * 4 : nullptr;
+  const long long slot = slots[b];
+  const LabSample s = lab_sample(desc, n_images, slot, lab_bytes);
+  const int nh = row[LC2IS_AUG_NH], nw = row[LC2IS_AUG_NW], flip = row[LC2IS_AUG_FLIP];
+  int top = row[LC2IS_AUG_TOP], left = row[LC2IS_AUG_LEFT];   // candidate 0: the row's own draw
+  if (!(s.valid && nh >= 1 && nw >= 1 && nh <= LC2IS_AUG_MAX_RESIZED && nw <= LC2IS_AUG_MAX_RESIZED)) {   // block-uniform
+    if (tid == 0 && irow) { irow[0] = -1; irow[1] = 0; irow[2] = 0; irow[3] = 0; }
+    return;
+  }
+  const unsigned h = aug_key(seed_lo, seed_hi, *epoch, keys ? (long long)keys[b] : slot);
+  const unsigned long long fh1 = (unsigned long long)(nh > S ? nh - S : 0) + 1, fw1 = (unsigned long long)(nw > S ? nw - S : 0) + 1;
+  const int q = S / L, LL = L * L, H = s.H, W = s.W;
+  const int dy = 2 * nh, dx = 2 * nw;
+  const float rL = __builtin_amdgcn_rcpf((float)L), rdy = __builtin_amdgcn_rcpf((float)dy), rdx = __builtin_amdgcn_rcpf((float)dx);
+  const unsigned char* src = lab + s.lab_off;
+  unsigned* mine = s_hist + wid * LH_BINS;
+  int pick = tries;
+  unsigned pn = 0u, pm = 0u, pd = 0u;
+  for (int t = 0; t < tries; ++t) {
+    if (t > 0) {
+      top = (int)(((unsigned long long)aug_u24(h, 10u + 2u * t) * fh1) >> 24);
+      left = (int)(((unsigned long long)aug_u24(h, 11u + 2u * t) * fw1) >> 24);
+    }
+    lh_wave_clear(mine);
+    for (int base = 0; base < LL; base += LH_THREADS * LH_UNROLL) {   // block-uniform trip count
+      unsigned v[LH_UNROLL];
+      bool counted[LH_UNROLL];
+#pragma unroll
+      for (int e = 0; e < LH_UNROLL; ++e) {
+        int cell = base + e * LH_THREADS + tid;
+        bool in = cell < LL;
+        cell = in ? cell : 0;
+        int cj;
+        const int ci = aug_div(cell, L, rL, cj);
+        const int i = ci * q + (q >> 1), j = cj * q + (q >> 1);
+        const int yr = (int)((unsigned)top + (unsigned)i), xr = (int)((unsigned)left + (unsigned)(flip ? S - 1 - j : j));
+        in = in && (unsigned)yr < (unsigned)nh && (unsigned)xr < (unsigned)nw;   // outside: padding, not counted
+        v[e] = 0u;
+        if (in) {
+          int rem;
+          const int ys = aug_div((2 * yr + 1) * H, dy, rdy, rem), xs = aug_div((2 * xr + 1) * W, dx, rdx, rem);
+          v[e] = src[(long long)ys * W + xs];
+        }
+        counted[e] = in && (int)v[e] != ignore_label;
+      }
+#pragma unroll
+      for (int e = 0; e < LH_UNROLL; ++e) lh_wave_add(mine, v[e], counted[e]);
+    }
+    __syncthreads();
+    if (wid < LH_BINS / 64) {   // whole waves: lane tid holds class tid
+      const unsigned nc = lh_block_sum(s_hist, LH_WAVES, tid);
+      unsigned sum = nc, mx = nc;
+#pragma unroll
+      for (int off = 32; off; off >>= 1) {
+        sum += (unsigned)__shfl_xor((int)sum, off);
+        const unsigned o = (unsigned)__shfl_xor((int)mx, off);
+        mx = o > mx ? o : mx;
+      }
+      const unsigned present = (unsigned)__popcll(__ballot(nc > 0u));
+      if (lane == 0) { s_red[wid][0] = sum; s_red[wid][1] = mx; s_red[wid][2] = present; }
+    }
+    __syncthreads();   // the rows are read: the next candidate may clear them; s_red is written again only after its first barrier
+    unsigned n = 0u, m = 0u, d = 0u;
+#pragma unroll
+    for (int w = 0; w < LH_BINS / 64; ++w) {
+      n += s_red[w][0];
+      m = s_red[w][1] > m ? s_red[w][1] : m;
+      d += s_red[w][2];
+    }
+    if (d > 1u && (long long)m * 1024 < (long long)ratio1024 * (long long)n) {   // block-uniform
+      pick = t; pn = n; pm = m; pd = d;
+      break;
+    }
+  }
+  if (pick == tries) {   // none accepted: one more draw, taken unchecked
+    top = (int)(((unsigned long long)aug_u24(h, 10u + 2u * tries) * fh1) >> 24);
+    left = (int)(((unsigned long long)aug_u24(h, 11u + 2u * tries) * fw1) >> 24);
+  }
+  if (tid == 0) {
+    row[LC2IS_AUG_TOP] = top;
+    row[LC2IS_AUG_LEFT] = left;
+    if (irow) { irow[0] = pick; irow[1] = (int)pn; irow[2] = (int)pm; irow[3] = (int)pd; }
+  }
+}
+
+// One block per image, block-stride over its H * W labels: a wave reads 64 neighbouring bytes per load, LH_UNROLL loads in flight.
+__global__ __launch_bounds__(LH_THREADS) void label_hist_kernel(const unsigned char* __restrict__ lab, size_t lab_bytes,
+                                                                 const lc2is_aug_image* __restrict__ desc, long n_images,
+                                                                 const int64_t* __restrict__ slots, int32_t* __restrict__ counts) {
+  __shared__ unsigned s_hist[LH_WAVES * LH_BINS];
+  const int b = blockIdx.x, tid = threadIdx.x, wid = tid >> 6;
+  int32_t* out = counts + (size_t)b * LH_BINS;
+  const LabSample s = lab_sample(desc, n_images, slots[b], lab_bytes);
+  if (!s.valid) {   // block-uniform
+    if (tid < LH_BINS) out[tid] = 0;
+    return;
+  }
+  const int n = s.H * s.W;   // <= 2^24
+  const unsigned char* src = lab + s.lab_off;
+  unsigned* mine = s_hist + wid * LH_BINS;
+  lh_wave_clear(mine);
+  for (int base = 0; base < n; base += LH_THREADS * LH_UNROLL) {   // block-uniform trip count
+    unsigned v[LH_UNROLL];
+    bool in[LH_UNROLL];
+#pragma unroll
+    for (int e = 0; e < LH_UNROLL; ++e) {
+      const int p = base + e * LH_THREADS + tid;
+      in[e] = p < n;
+      v[e] = in[e] ? (unsigned)src[p] : 0u;
+    }
+#pragma unroll
+    for (int e = 0; e < LH_UNROLL; ++e) lh_wave_add(mine, v[e], in[e]);
+  }
+  __syncthreads();
+  if (tid < LH_BINS) out[tid] = (int)lh_block_sum(s_hist, LH_WAVES, tid);
+}
+
 }  // namespace
 
 extern "C" int lc2is_aug_params(const int64_t* slots, const int64_t* keys, int B, const int32_t* epoch, const lc2is_aug_image* desc,
@@ -280,5 +438,30 @@ extern "C" int lc2is_aug_apply(const uint8_t* img, size_t img_bytes, const uint8
   const int img_blocks = (S * (S >> 2) + 255) / 256, lab_blocks = (L * L + 255) / 256;
   hipLaunchKernelGGL(aug_apply_kernel, dim3(img_blocks + lab_blocks, B), dim3(256), 0, stream, img, img_bytes, lab, lab_bytes, desc,
                      n_images, slots, params, S, L, img_blocks, *norm, pad_label, out_img, out_lab);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_aug_crop_select(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc, long n_images,
+                                     const int64_t* slots, const int64_t* keys, int B, const int32_t* epoch, const lc2is_aug_config* cfg,
+                                     int32_t* params, int L, int ratio1024, int ignore_label, int tries, int32_t* info,
+                                     lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!lab || !desc || !slots || !epoch || !cfg || !params) return LC2IS_ERR_NULL;
+  const int S = cfg->crop_size;
+  if (B <= 0 || n_images <= 0 || S <= 0 || S > LC2IS_AUG_MAX_SIDE || L <= 0 || S % L || ratio1024 < 1 || ratio1024 > 1023 ||
+      ignore_label < -1 || ignore_label > 255 || tries < 1 || tries > LC2IS_AUG_MAX_TRIES || ((uintptr_t)params & 3) ||
+      ((uintptr_t)info & 3) || ((uintptr_t)desc & 7))
+    return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(aug_crop_select_kernel, dim3(B), dim3(LH_THREADS), 0, stream, lab, lab_bytes, desc, n_images, slots, keys, epoch,
+                     cfg->seed_lo, cfg->seed_hi, S, L, ratio1024, ignore_label, tries, params, info);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_label_histogram(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc, long n_images,
+                                     const int64_t* slots, int B, int32_t* counts, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!lab || !desc || !slots || !counts) return LC2IS_ERR_NULL;
+  if (B <= 0 || n_images <= 0 || ((uintptr_t)counts & 3) || ((uintptr_t)desc & 7)) return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(label_hist_kernel, dim3(B), dim3(LH_THREADS), 0, stream, lab, lab_bytes, desc, n_images, slots, counts);
   return lc2is_check_launch();
 }

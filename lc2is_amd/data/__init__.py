@@ -1,8 +1,8 @@
 """Device-side data path in front of the hot path: the reference's CLIPFeatureExtractor image / label
 transforms (evaluate.py:58-61, data/collator.py:82-91), the ADE20K collate (data/collator.py:168-180) and the train-time
 augmentation the reference reserves a hook for (data/dataset.py:144-149)."""
-from .augment import AugmentedBatches, DeviceImagePool, TrainAugment
+from .augment import AugmentedBatches, DeviceImagePool, TrainAugment, class_weights
 from .preprocess import ADE20KCollator, ClipImagePreprocessor, ClipLabelPreprocessor
 
 __all__ = ["ADE20KCollator", "ClipImagePreprocessor", "ClipLabelPreprocessor", "DeviceImagePool", "TrainAugment",
-           "AugmentedBatches"]
+           "AugmentedBatches", "class_weights"]

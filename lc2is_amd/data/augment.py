@@ -20,12 +20,18 @@ training split (about 27 GB of uint8) fits the device many times, so here
 
 Every random number is a pure function of (seed, epoch, dataset index, draw number): an image gets the same augmentation in an
 epoch whatever its batch, its position in the batch, the rank or the batch size, and no host value changes between steps, so the
-two launches can be captured in a graph whose replays draw fresh parameters from the static index / epoch tensors.
+launches can be captured in a graph whose replays draw fresh parameters from the static index / epoch tensors.
 
 Geometry: the short edge is resized to ``base_size * ratio`` (ratio uniform in ``ratio_range``, bilinear without antialiasing,
 ``F.interpolate(..., align_corners=False)``), an S x S window is cut at a uniform position; where the resized image is smaller than
 the window it sits at the top left and the rest is padding (0.0 = the mean colour after normalisation; ``pad_label`` for labels).
 Labels take the same geometry with nearest-exact sampling at the centres of the (S / L)^2 cells.
+
+Class-ratio re-draw (``cat_max_ratio``, mmseg's ``RandomCrop(cat_max_ratio=0.75)``): a crop in which one class covers that share
+or more of the labelled cells, or which holds one class only, is rejected and its origin drawn again, up to ``cat_tries`` times; a
+third launch (``ops.aug_crop_select``) between the two does it on the device.  It counts the L x L label cells the crop will
+produce - the labels the loss sees - and not the full-resolution crop as mmseg does ((S / L)^2 times fewer reads); cells that are
+padding or hold ``cat_ignore_label`` do not count.  ``None`` (the default) adds no launch and changes no bit.
 
 Colour: brightness (add b), contrast (multiply by c), saturation (blend with the 0.299 / 0.587 / 0.114 grey by s) and hue
 (rotation about the grey axis by h), each applied with its probability, in this order, folded into ONE 3 x 3 matrix plus offset per
@@ -189,6 +195,22 @@ class DeviceImagePool:
     def labels(self) -> torch.Tensor:
         return self._lab
 
+    def class_counts(self, indices=None, chunk: int = 4096) -> torch.Tensor:
+        """Pixels per label value of the images `indices` (None: every image of the pool): int64 [n, 256] on the device
+        (ops.label_histogram, `chunk` images per launch).  The input of ``class_weights``."""
+        dev = _need_cuda(self.device)
+        if indices is None:
+            idx = torch.arange(len(self), dtype=torch.int64, device=dev)
+        else:
+            idx = TrainAugment._indices(indices, dev)
+        out = torch.empty((idx.numel(), ops.LABEL_BINS), dtype=torch.int64, device=dev)
+        if idx.numel():
+            desc = self.desc
+            for lo in range(0, idx.numel(), max(int(chunk), 1)):
+                part = idx[lo:lo + max(int(chunk), 1)]
+                out[lo:lo + part.numel()] = ops.label_histogram(self._lab, desc, part)
+        return out
+
     @property
     def desc(self) -> torch.Tensor:
         """The descriptor table on the device: int64 [n, 3] = img_off, lab_off, H | W << 32 (lc2is_aug_image)."""
@@ -205,8 +227,46 @@ def _threshold(p: float, what: str) -> int:
     return int(round(p * (1 << 24)))
 
 
+def class_weights(counts: torch.Tensor, n_classes: int = 151, ignore_index: int | None = 0, mode: str = "median_freq",
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Class weights fp32 [n_classes] for ``CrossEntropyLoss(weight=)`` / ``TrainStep(criterion=)`` from per-image class counts
+    [n, >= n_classes] (``DeviceImagePool.class_counts``), computed in fp64 with torch ops on the counts' device, no host read.
+    Only the pixels of classes 0 .. n_classes - 1 other than ``ignore_index`` count.
+    "median_freq" (Eigen & Fergus): f_c = pixels of c / counted pixels of the images in which c occurs; w_c = median of f over the
+    classes that occur (the mean of the two middle values for an even number) / f_c.
+    "enet" (Paszke et al.): w_c = 1 / ln(1.02 + p_c), p_c = the share of c in all counted pixels.
+    A class that never occurs and ``ignore_index`` get weight 0.  ``dtype=torch.float64`` returns the values before the one rounding."""
+    if mode not in ("median_freq", "enet"):
+        raise ValueError(f"lc2is_amd.data: class_weights mode must be 'median_freq' or 'enet', got {mode!r}")
+    if not torch.is_tensor(counts) or counts.dim() != 2 or counts.is_floating_point() or not 1 <= int(n_classes) <= counts.shape[1]:
+        raise ValueError("lc2is_amd.data: class_weights takes integer counts [n, >= n_classes]")
+    c = counts[:, :int(n_classes)].to(torch.int64).clone()
+    if ignore_index is not None and 0 <= int(ignore_index) < int(n_classes):
+        c[:, int(ignore_index)] = 0
+    pix = c.sum(dim=0)
+    occurs = pix > 0
+    if mode == "median_freq":
+        total = ((c > 0) * c.sum(dim=1, keepdim=True)).sum(dim=0)
+        f = pix.double() / total.clamp(min=1).double()
+        s = torch.sort(torch.where(occurs, f, torch.full_like(f, float("inf")))).values      # the occurring classes come first
+        k = occurs.sum()
+        mid = torch.stack([(k - 1).clamp(min=0) // 2, k // 2]).clamp(max=int(n_classes) - 1)
+        w = 0.5 * s[mid].sum() / f
+    else:
+        w = 1.0 / torch.log(1.02 + pix.double() / pix.sum().clamp(min=1).double())
+    return torch.where(occurs, w, torch.zeros_like(w)).to(dtype)
+
+
+_PAD_LABEL = "pad_label"          # cat_ignore_label's default: whatever pad_label is
+
+
 class TrainAugment:
     """Random rescale + crop + flip + photometric jitter of a batch on the device; see the module docstring for the definition.
+
+    ``cat_max_ratio``: None, or the share in (0, 1) (mmseg: 0.75) a single class must stay below among the counted label cells of
+    a crop; ``cat_ignore_label``: the label that is not counted (0..255; default: pad_label; None: every label counts);
+    ``cat_tries``: the number of candidates that are checked (1..10) before one more is taken unchecked.  ``last_crop_info``: the
+    device tensor int32 [B, 4] = (candidate taken, counted cells, largest class, classes) of the last call, never read back here.
 
     ``photometric``: True (PHOTOMETRIC_DEFAULTS), False (identity colour) or a dict overriding some of brightness_delta (0..255
     scale), contrast_range, saturation_range, hue_delta (degrees), prob (one probability, or four: brightness, contrast,
@@ -214,7 +274,8 @@ class TrainAugment:
 
     def __init__(self, crop_size: int = 512, label_size: int = 128, base_size: int = 512, ratio_range=(0.5, 2.0),
                  flip_prob: float = 0.5, photometric=True, image_mean=OPENAI_CLIP_MEAN, image_std=OPENAI_CLIP_STD,
-                 pad_label: int = 0, seed: int = 0):
+                 pad_label: int = 0, seed: int = 0, cat_max_ratio: float | None = None, cat_ignore_label=_PAD_LABEL,
+                 cat_tries: int = 10):
         S, L = int(crop_size), int(label_size)
         if S < 4 or S > MAX_SIDE or S % 4:
             raise ValueError(f"lc2is_amd.data: crop_size must be a multiple of 4 in 4..{MAX_SIDE}, got {S}")
@@ -226,6 +287,19 @@ class TrainAugment:
         if len(image_mean) != 3 or len(image_std) != 3 or min(image_std) <= 0:
             raise ValueError("lc2is_amd.data: image_mean / image_std must hold three values, std positive")
         self.crop_size, self.label_size, self.pad_label, self.seed = S, L, int(pad_label), int(seed) & (2 ** 64 - 1)
+        ignore = cat_ignore_label
+        if isinstance(ignore, str) and ignore == _PAD_LABEL:      # defaulted: only a crop rule that is on needs it in range
+            ignore = int(pad_label) if cat_max_ratio is not None or 0 <= int(pad_label) <= 255 else None
+        if ignore is not None and not 0 <= int(ignore) <= 255:
+            raise ValueError(f"lc2is_amd.data: cat_ignore_label must be a label 0..255 or None, got {ignore}")
+        if not 1 <= int(cat_tries) <= ops.AUG_MAX_TRIES:
+            raise ValueError(f"lc2is_amd.data: cat_tries must be 1..{ops.AUG_MAX_TRIES}, got {cat_tries}")
+        if cat_max_ratio is not None and not (0.0 < float(cat_max_ratio) < 1.0 and 1 <= int(round(float(cat_max_ratio) * 1024)) <= 1023):
+            raise ValueError(f"lc2is_amd.data: cat_max_ratio must lie in (0, 1) (in 1/1024 units: 1..1023), got {cat_max_ratio}")
+        self.cat_max_ratio = None if cat_max_ratio is None else float(cat_max_ratio)
+        self.cat_ratio1024 = None if cat_max_ratio is None else int(round(float(cat_max_ratio) * 1024))
+        self.cat_ignore_label, self.cat_tries = -1 if ignore is None else int(ignore), int(cat_tries)
+        self.last_crop_info = None
         ph = dict(PHOTOMETRIC_DEFAULTS)
         if isinstance(photometric, dict):
             unknown = set(photometric) - set(ph)
@@ -253,7 +327,7 @@ class TrainAugment:
             n.inv_std[i] = 1.0 / float(image_std[i])
         self._stage = self._stage_free = None
 
-    # ---- the two halves ----
+    # ---- the launches ----
     @staticmethod
     def _indices(indices, device) -> torch.Tensor:
         if torch.is_tensor(indices) and indices.is_cuda:
@@ -278,6 +352,18 @@ class TrainAugment:
         return ops.aug_params(idx, self._epoch(epoch, dev), pool.desc, self.config,
                               keys=None if keys is None else self._indices(keys, dev), out=out)
 
+    def select(self, pool: DeviceImagePool, indices, epoch, params: torch.Tensor, *, keys=None) -> torch.Tensor:
+        """The class-ratio re-draw (ops.aug_crop_select): replaces top / left of `params` IN PLACE and returns it; the info
+        tensor is kept in ``last_crop_info``.  With cat_max_ratio=None: nothing is launched."""
+        if self.cat_ratio1024 is None:
+            return params
+        dev = _need_cuda(pool.device)
+        self.last_crop_info = ops.aug_crop_select(pool.labels, pool.desc, self._indices(indices, dev), self._epoch(epoch, dev),
+                                                  self.config, params, self.label_size, ratio1024=self.cat_ratio1024,
+                                                  ignore_label=self.cat_ignore_label, tries=self.cat_tries,
+                                                  keys=None if keys is None else self._indices(keys, dev))
+        return params
+
     def apply(self, pool: DeviceImagePool, indices, params: torch.Tensor, out: dict | None = None) -> dict:
         """Cut the batch: {"pixel_values": fp32 [B,3,S,S], "label": int64 [B,L,L]} (ops.aug_apply), into `out`'s tensors if given."""
         dev = _need_cuda(pool.device)
@@ -298,7 +384,8 @@ class TrainAugment:
             if images is not None or labels is not None:
                 raise ValueError("lc2is_amd.data: give a pool or images / labels, not both")
             idx = self._indices(indices, _need_cuda(pool.device))
-            return self.apply(pool, idx, self.params(pool, idx, epoch), out)
+            epoch = self._epoch(epoch, idx.device)
+            return self.apply(pool, idx, self.select(pool, idx, epoch, self.params(pool, idx, epoch)), out)
         if images is None or labels is None or len(images) != len(labels) or not len(images):
             raise ValueError("lc2is_amd.data: the streaming form takes as many images as labels, at least one")
         dev = indices.device if torch.is_tensor(indices) and indices.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -307,7 +394,8 @@ class TrainAugment:
             raise ValueError(f"lc2is_amd.data: {keys.numel()} indices for {len(images)} images")
         transient = self._stream_pool(images, labels, dev)
         slots = torch.arange(len(images), dtype=torch.int64, device=dev)
-        return self.apply(transient, slots, self.params(transient, slots, epoch, keys=keys), out)
+        epoch = self._epoch(epoch, dev)
+        return self.apply(transient, slots, self.select(transient, slots, epoch, self.params(transient, slots, epoch, keys=keys), keys=keys), out)
 
     def _stream_pool(self, images, labels, dev) -> DeviceImagePool:
         shapes = [DeviceImagePool.check(im, lb) for im, lb in zip(images, labels)]

@@ -113,6 +113,8 @@ _ARGTYPES = {
     "lc2is_crop_lut": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "lc2is_aug_params": [_P, _P, _I, _P, _P, _L, _P, _P, _P],
     "lc2is_aug_apply": [_P, _Z, _P, _Z, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P],
+    "lc2is_aug_crop_select": [_P, _Z, _P, _L, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "lc2is_label_histogram": [_P, _Z, _P, _L, _P, _I, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -1650,6 +1652,7 @@ def crop_lut(src: torch.Tensor, top: int, left: int, S: int, *, lut_f32: torch.T
 # ---- train-time augmentation (device image pool) -------------------------------------------------------------------
 AUG_PARAM_WORDS, AUG_MAX_SIDE = 20, 4096      # LC2IS_AUG_PARAM_WORDS, LC2IS_AUG_MAX_SIDE
 AUG_NH, AUG_NW, AUG_TOP, AUG_LEFT, AUG_FLIP, AUG_M, AUG_O = 0, 1, 2, 3, 4, 5, 14
+AUG_MAX_TRIES, LABEL_BINS = 10, 256                # LC2IS_AUG_MAX_TRIES; one histogram bin per uint8 label value
 
 
 class AugConfig(C.Structure):
@@ -1717,6 +1720,57 @@ def aug_apply(img: torch.Tensor, lab: torch.Tensor, desc: torch.Tensor, slots: t
                                 B, S, L, C.addressof(norm), int(pad_label), _ptr(out_img), _ptr(out_lab), _stream())
     _lib.check(rc, f"aug_apply B={B} S={S} L={L}")
     return out_img, out_lab
+
+
+def aug_crop_select(lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, epoch: torch.Tensor, cfg: AugConfig,
+                    params: torch.Tensor, L: int, *, ratio1024: int, ignore_label: int = -1, tries: int = AUG_MAX_TRIES,
+                    keys: torch.Tensor | None = None, info: torch.Tensor | None = None) -> torch.Tensor:
+    """The class-ratio re-draw of the crop origin (lc2is_aug_crop_select), between aug_params and aug_apply: for every sample the
+    candidates 0 (the row's own top / left) .. tries - 1 are checked in order on the L x L label cells aug_apply would write, the
+    first one with more than one class and max count * 1024 < ratio1024 * counted cells is taken, else candidate `tries`
+    unchecked.  `params` int32 [B, AUG_PARAM_WORDS] is changed IN PLACE (words AUG_TOP, AUG_LEFT).  Cells that are padding or
+    hold ignore_label (0..255; -1: none) are not counted.  Returns info int32 [B, 4] = t*, n, m, d on the device ({tries, 0, 0, 0}:
+    none accepted; {-1, 0, 0, 0}: a row out of range, left untouched).  lab: the pool's packed label buffer; desc / slots / keys /
+    epoch / cfg as in aug_params.  Nothing but device memory decides the result."""
+    _aug_tables(desc, slots, "aug_crop_select")
+    _chk(lab, torch.uint8, "lab", 1); _chk(params, torch.int32, "params")
+    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
+    B, S, L = slots.numel(), int(cfg.crop_size), int(L)
+    if epoch.numel() != 1 or (keys is not None and keys.numel() != B):
+        raise RuntimeError("lc2is_amd.aug_crop_select: epoch must hold one int32 and keys one int64 per sample")
+    if tuple(params.shape) != (B, AUG_PARAM_WORDS) or not params.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.aug_crop_select: params must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    if S < 1 or S > AUG_MAX_SIDE or L < 1 or S % L:
+        raise ValueError(f"lc2is_amd.aug_crop_select: crop size {S} must be a multiple of the label size {L}, at most {AUG_MAX_SIDE}")
+    if not 1 <= int(ratio1024) <= 1023 or not -1 <= int(ignore_label) <= 255 or not 1 <= int(tries) <= AUG_MAX_TRIES:
+        raise ValueError(f"lc2is_amd.aug_crop_select: ratio1024 {ratio1024} must be 1..1023, ignore_label {ignore_label} -1..255 and "
+                         f"tries {tries} 1..{AUG_MAX_TRIES}")
+    if info is None:
+        info = torch.empty((B, 4), dtype=torch.int32, device=slots.device)
+    _chk(info, torch.int32, "info")
+    if tuple(info.shape) != (B, 4) or not info.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.aug_crop_select: info must be contiguous int32 [{B}, 4]")
+    rc = _fn("lc2is_aug_crop_select")(_ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), _ptr(keys), B, _ptr(epoch),
+                                      C.addressof(cfg), _ptr(params), L, int(ratio1024), int(ignore_label), int(tries), _ptr(info),
+                                      _stream())
+    _lib.check(rc, f"aug_crop_select B={B} S={S} L={L}")
+    return info
+
+
+def label_histogram(lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-image class counts (lc2is_label_histogram): int32 [B, 256], out[b, v] = pixels of image slots[b] whose label is v.  lab:
+    the pool's packed label buffer; desc / slots as in aug_params.  A slot outside the table gives a row of zeros.  Exact, no atomics."""
+    _aug_tables(desc, slots, "label_histogram")
+    _chk(lab, torch.uint8, "lab", 1)
+    B = slots.numel()
+    if out is None:
+        out = torch.empty((B, LABEL_BINS), dtype=torch.int32, device=slots.device)
+    _chk(out, torch.int32, "out")
+    if tuple(out.shape) != (B, LABEL_BINS) or not out.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.label_histogram: out must be contiguous int32 [{B}, {LABEL_BINS}]")
+    rc = _fn("lc2is_label_histogram")(_ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), B, _ptr(out), _stream())
+    _lib.check(rc, f"label_histogram B={B}")
+    return out
 
 
 def set_cu_budget(ncu: int) -> None:
