@@ -816,6 +816,27 @@ int lc2is_ce_dice_nchw_bwd(const float* logits, const int64_t* labels, const flo
                            const float* grad_scale_dev, float grad_scale, float* dlogits, int B, int C, long HW,
                            long ignore_index, lc2is_stream_t stream);
 
+/* ---- class map and accuracy / IoU counts of the fused head at its own output size ------------------------------------------
+ * lc2is_head_upsample_argmax: the forward product of lc2is_head_upsample_ce alone (scores_lo fp32 [B,h,w,ld] channels-last, 16-byte
+ * aligned, C <= ld <= 192, ld % 64 == 0, S in {4, 8, 16}, else LC2IS_ERR_UNSUPPORTED), then the argmax over the C classes of every
+ * output pixel in the accumulators: exact ties go to the lowest class (torch.argmax), a pixel whose scores are all -inf gets class
+ * 0, and the class is clamped into [0, C) (a NaN score may pick any class).  The xS map is never materialised.
+ *   pred   uint8 [B,H,W] or NULL: the class map, every pixel written.
+ *   counts int32 [B][3][C] or NULL: per image {intersection, predicted, labelled}.  A pixel counts iff label != ignore_index &&
+ *          0 <= label < C (the rule of the CE head, and mmseg's); a counted pixel adds to predicted[pred] and labelled[label], and
+ *          to intersection[pred] when pred == label; any other pixel adds to none of the three.  Needs labels (int64 [B,H,W]) and
+ *          a 16-byte aligned workspace >= lc2is_head_upsample_argmax_workspace_bytes(...) (a pure host function; 0 for a call that
+ *          would be refused): B * tiles * 3 * cq int32 slabs, cq = C rounded up to 4, summed per image in a fixed order by a second
+ *          launch.  Every element of counts is overwritten.
+ * pred and counts both NULL, or counts without labels: LC2IS_ERR_NULL.  A pred-only call takes no workspace (and labels may be NULL).
+ * NO read-modify-write atomics, LDS included; the same bytes every run; captures into a graph.
+ * replaces: model(inputs)["outputs"].argmax(1) on the materialised [B,K,H,W] logits of a second forward, and mmseg's accuracy() /
+ *   intersect_and_union() on it (decode.acc_seg, the running train mIoU). */
+size_t lc2is_head_upsample_argmax_workspace_bytes(int B, int h, int w, int C, int S, int mode);
+int lc2is_head_upsample_argmax(const float* scores_lo, int ld, const int64_t* labels, uint8_t* pred, int32_t* counts, int B, int h,
+                               int w, int C, int S, int mode, long ignore_index, void* workspace, size_t workspace_bytes,
+                               lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from .. import ops
 from .base import assign_rng_names, require_cuda
 from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
@@ -68,13 +69,22 @@ class PromptFTN(nn.Module):
         return None, self.tail(visual_embeddings, text_embeddings)                                # model.py:204-214
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
-        materialising the [B,K,512,512] map ('mean' or 'sum')."""
+        materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
+        {intersection, predicted, labelled} counts (``ScoreMapTail.loss``)."""
         fused_loss_options(weight, label_smoothing, reduction)   # (refused before the towers run)
+        if seg_counts is not None:
+            ops.check_seg_counts(seg_counts)
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
-                              label_smoothing=label_smoothing, reduction=reduction)
+                              label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts)
+
+    @torch.no_grad()
+    def predict(self, inputs: dict) -> torch.Tensor:
+        """The class map of the score map, uint8 [B,512,512]: ``forward(inputs)[1].argmax(1)`` without writing the map."""
+        visual_embeddings, text_embeddings = self._embeddings(inputs)
+        return self.tail.predict(visual_embeddings, text_embeddings)
 
 
 class _ScoreGridFn(torch.autograd.Function):

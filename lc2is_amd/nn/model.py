@@ -112,8 +112,8 @@ class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -121,7 +121,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -178,7 +178,7 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -189,6 +189,8 @@ class BaseModelWithText(HipModule):
                                             want_loss=False)
             return hi, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None)
         labels = labels.contiguous()
+        if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
+            ops.seg_counts_add(seg_counts, scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index)
         if dice is not None:   # CE + soft Dice: statistics pass, coefficients, gradient pass — dlo is the gradient of the scalar loss
             ce_weight, dice_weight, smooth, present_only = dice
             loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
@@ -291,21 +293,41 @@ class BaseModelWithText(HipModule):
         return dict(outputs=logits)
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None) -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
+                     seg_counts=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
         (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels the head saw, the device info block).
         ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE + dice_weight * soft Dice over the batch
         (DiceCrossEntropyLoss's definition), not combinable with the other options; ``self.last_dice`` then holds the device
-        tensors (I, P, T, loss block = [loss, CE mean, Dice, n_valid])."""
+        tensors (I, P, T, loss block = [loss, CE mean, Dice, n_valid]).
+        ``seg_counts``: an int64 [3, K] device tensor that takes ``+= counts.sum(0)`` of this batch — {intersection, predicted,
+        labelled} of the argmax of the same upsampled scores against ``labels`` as given (under ``ohem=``: before relabelling), over
+        the pixels the loss counts (``ops.head_upsample_argmax``; ``metrics.dataset_iou`` turns them into aAcc / mAcc / mIoU).  One
+        more forward pass of the head and a small device add, no host read; loss and gradients are unchanged.  None: no launch."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
         dice = fused_dice_options(dice, opts, ohem)
+        if seg_counts is not None:
+            ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts)
+
+    @torch.no_grad()
+    def predict(self, inputs: dict) -> torch.Tensor:
+        """The class map of the model output, uint8 [B, out, out]: ``forward(inputs)["outputs"].argmax(1)`` (exact ties to the lowest
+        class) without forming the logits — the argmax is taken in the fused head (``ops.head_upsample_argmax``)."""
+        dec_v = self._decode(inputs)
+        B, P, C = dec_v.shape
+        g = self.in_size // self.patch_size
+        K = self.class_prototypes.shape[0]
+        dec16 = ops.cast_bf16(dec_v.reshape(B * P, C).float().contiguous())
+        _, _, scores = self._head_scores(dec16)
+        pred, _ = ops.head_upsample_argmax(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_counts=False)
+        return pred
 
     @torch.no_grad()
     def forward_tuple(self, inputs: dict):

@@ -60,7 +60,7 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None, seg_counts=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -70,6 +70,8 @@ class _ScoreFn(torch.autograd.Function):
                                             want_loss=False)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
             return hi
+        if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
+            ops.seg_counts_add(seg_counts, scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index)
         if dice is not None:   # CE + soft Dice: dlo is the gradient of the scalar loss
             ce_weight, dice_weight, smooth, present_only = dice
             loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
@@ -108,7 +110,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None, None, None, None
+        return dv, dt, None, None, None, None, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -126,16 +128,33 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None, dice=None) -> torch.Tensor:
+             ohem=None, dice=None, seg_counts=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
         the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
         dice_weight * soft Dice over the batch (DiceCrossEntropyLoss's definition), not combinable with the other options;
-        ``self.last_dice`` then holds the device tensors (I, P, T, loss block)."""
+        ``self.last_dice`` then holds the device tensors (I, P, T, loss block).  ``seg_counts``: an int64 [3, K] device tensor that
+        takes ``+= counts.sum(0)`` of this batch ({intersection, predicted, labelled} of the argmax of the same upsampled scores
+        against ``labels`` as given, over the pixels the loss counts; ``BaseModelWithText.forward_loss`` has the details)."""
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
         dice = fused_dice_options(dice, opts, ohem)
+        if seg_counts is not None:
+            ops.check_seg_counts(seg_counts, text_embeddings.shape[1])
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
-        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self, dice)
+        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self, dice,
+                              seg_counts)
+
+    @torch.no_grad()
+    def predict(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor) -> torch.Tensor:
+        """The class map of the score map, uint8 [B, S*h, S*w]: ``forward(visual, text).argmax(1)`` (exact ties to the lowest class)
+        without writing the map — the argmax is taken in the fused head (``ops.head_upsample_argmax``)."""
+        require_cuda(visual_embeddings, "visual_embeddings")
+        B, P, _ = visual_embeddings.shape
+        K = text_embeddings.shape[1]
+        h = int(round(P ** 0.5))
+        scores, _ = _scores_lo(visual_embeddings, text_embeddings)
+        pred, _ = ops.head_upsample_argmax(scores, None, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, want_counts=False)
+        return pred

@@ -79,6 +79,8 @@ _ARGTYPES = {
     "lc2is_ce_nchw_bwd_opts": [_P, _P, _P, _P, _F, _P, _P, _I, _I, C.c_long, C.c_long, _P, _F, _P],
     "lc2is_upsample_bwd_nchw": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_head_upsample_px": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P],
+    "lc2is_head_upsample_argmax_workspace_bytes": [_I, _I, _I, _I, _I, _I],
+    "lc2is_head_upsample_argmax": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P, _Z, _P],
     "lc2is_ohem_select_workspace_bytes": [_L],
     "lc2is_ohem_select": [_P, _P, _P, _L, _I, _L, _F, _L, _P, _P, _Z, _P],
     "lc2is_head_upsample_ce_dice_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I],
@@ -917,6 +919,62 @@ def head_upsample_px(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, 
     _lib.check(_fn("lc2is_head_upsample_px")(_ptr(scores_lo), scores_lo.shape[1], _ptr(labels), _ptr(lpx), B, h, w, C, S, mode,
                                              ignore_index, _stream()), f"head_upsample_px B={B} h={h} w={w} C={C} S={S}")
     return lpx
+
+
+# ---- class map and accuracy / IoU counts of the fused head: the argmax sibling of head_upsample_px ----
+def head_upsample_argmax(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                         ignore_index: int = -100, want_pred: bool = True, want_counts: bool = True):
+    """scores_lo fp32 [B*h*w, ld], labels int64 [B, h*S, w*S] or None -> (pred uint8 [B, h*S, w*S] or None, counts int32 [B, 3, C]
+    or None): the argmax over the C classes of the upsampled scores (S = 4 / 8 / 16; exact ties to the lowest class) and, per image,
+    the {intersection, predicted, labelled} counts over the pixels the loss counts (label != ignore_index and 0 <= label < C).  The
+    [B, C, H, W] map is never formed; nothing syncs, no atomics, the same bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    if not want_pred and not want_counts:
+        raise ValueError("lc2is_amd.head_upsample_argmax: want_pred and want_counts are both False")
+    if want_counts and labels is None:
+        raise ValueError("lc2is_amd.head_upsample_argmax: want_counts needs labels")
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError("lc2is_amd.head_upsample_argmax: scores_lo must be contiguous")
+    if labels is not None and (tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: labels must be contiguous [{B},{h*S},{w*S}]")
+    if S not in (4, 8, 16):
+        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: S must be 4, 8 or 16, got {S}")
+    ld = scores_lo.shape[1]
+    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
+        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
+                           f"got {tuple(scores_lo.shape)}")
+    dev = scores_lo.device
+    nbytes = 0
+    if want_counts:
+        nbytes = _fn("lc2is_head_upsample_argmax_workspace_bytes")(B, h, w, C, S, mode)
+        if nbytes == 0:
+            raise RuntimeError(f"lc2is_amd.head_upsample_argmax: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    pred = torch.empty((B, h * S, w * S), dtype=torch.uint8, device=dev) if want_pred else None
+    counts = torch.empty((B, 3, C), dtype=torch.int32, device=dev) if want_counts else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None   # (per call: the slabs live until the second launch)
+    _lib.check(_fn("lc2is_head_upsample_argmax")(_ptr(scores_lo), ld, _ptr(labels), _ptr(pred), _ptr(counts), B, h, w, C, S, mode,
+                                                 ignore_index, _ptr(ws), nbytes, _stream()),
+               f"head_upsample_argmax B={B} h={h} w={w} C={C} S={S}")
+    return pred, counts
+
+
+def seg_counts_add(seg_counts, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int, ignore_index: int):
+    """``seg_counts += counts.sum(0)`` for the batch behind ``scores_lo``: what every fused head does for ``seg_counts=``.  int64
+    [3, C] on the device, added in place by one small device op (no host read)."""
+    check_seg_counts(seg_counts, C)
+    _, counts = head_upsample_argmax(scores_lo, labels, B, h, w, C, S, mode, ignore_index=ignore_index, want_pred=False)
+    seg_counts.add_(counts.sum(0))
+
+
+def check_seg_counts(seg_counts, C: int | None = None) -> None:
+    """``seg_counts`` of the fused heads: an int64 [3, C] tensor on a HIP device (TypeError / ValueError / RuntimeError otherwise)."""
+    if not isinstance(seg_counts, torch.Tensor) or seg_counts.dtype != torch.int64:
+        raise TypeError("lc2is_amd: seg_counts must be an int64 [3, K] tensor on the device")
+    if seg_counts.dim() != 2 or seg_counts.shape[0] != 3 or (C is not None and seg_counts.shape[1] != C) or not seg_counts.is_contiguous():
+        raise ValueError(f"lc2is_amd: seg_counts must be a contiguous int64 [3, {'K' if C is None else C}] tensor, "
+                         f"got {tuple(seg_counts.shape)}")
+    if not seg_counts.is_cuda:
+        raise RuntimeError("lc2is_amd: seg_counts must be a CUDA(HIP) tensor; there is no CPU path")
 
 
 OHEM_INFO_WORDS = 3   # lc2is_ohem_info as int64 [3]: n_valid, k, then (L, L_eff) as the two fp32 halves of the third word

@@ -66,6 +66,18 @@ def _accepts_dice(model) -> bool:
     return fl is not None and "dice" in inspect.signature(fl).parameters
 
 
+def _accepts_seg_counts(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "seg_counts" in inspect.signature(fl).parameters
+
+
+def _n_classes(model) -> int | None:
+    """Class count of a model's fused head: the prototypes' rows, or the prompts' (known only from a batch: None)."""
+    protos = getattr(model, "class_prototypes", None)
+    return None if protos is None else int(protos.shape[0])
+
+
 def lr_table_from_torch(make_scheduler, base_lr: float, steps: int) -> torch.Tensor:
     """Tabulate a real ``torch.optim.lr_scheduler`` for ``TrainStep(lr_schedule=...)``: ``make_scheduler(optimizer)`` is run on a
     dummy CPU optimizer whose lr is ``base_lr``, and entry i is the rate in force at iteration i in ``Engine``'s order —
@@ -320,16 +332,39 @@ class TrainStep:
     initialised from it, takes ``ema += (1 - ema_decay) * (p - ema)`` after every APPLIED optimizer update (every ``ema_every``-th
     one; with ``ema_warmup`` the j-th EMA update uses the decay ``min(ema_decay, (1 + j) / (10 + j))``).  One launch over the arena,
     captured with the step.  ``ema_state_dict()`` is the averaged model, ``with ts.ema_weights():`` evaluates with it in place,
-    ``reset_ema()`` restarts it from the current parameters (after loading weights into the model)."""
+    ``reset_ema()`` restarts it from the current parameters (after loading weights into the model).
+
+    ``seg_metrics=True`` (keyword-only): every step also counts, on the device, how the argmax of the head's own upsampled scores
+    meets the batch's labels (``forward_loss(seg_counts=)``: one more forward pass of the fused head, the logits are never formed;
+    loss, gradients and parameters keep their bits).  ``ts.seg_counts`` is the running int64 [3, K] {intersection, predicted,
+    labelled} buffer, ``ts.seg_metrics(reset=False)`` its ``metrics.dataset_iou``: ``aAcc`` (mmseg's ``acc_seg`` / 100), ``mAcc``,
+    ``mIoU``, ``IoU`` [K] as device float64 tensors.  Under OHEM the counts are those of the labels before relabelling.  K is the
+    model's ``class_prototypes`` row count, or ``seg_classes=`` for a model that takes its classes from the batch (PromptFTN).  The
+    buffer exists before ``capture``; the captured launches keep adding into it across replays, and reading or resetting happens
+    outside the graph (the warm-up steps of ``capture`` are real steps and count).  The counts are this rank's own (no collective)
+    and are not part of ``state_dict`` / ``save_train_state``: a resumed run starts its counters at zero."""
 
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
                  ignore_index: int | None = None, criterion: nn.Module | None = None, lr_schedule=None,
                  schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
                  device_state: bool = False, param_groups=None, ema_decay: float | None = None, ema_warmup: bool = False,
-                 ema_every: int = 1) -> None:
+                 ema_every: int = 1, seg_metrics: bool = False, seg_classes: int | None = None) -> None:
         # (argument checks first: nothing is built or allocated for a step that cannot run)
         _check_ema_args(ema_decay, ema_warmup, ema_every)
+        if not isinstance(seg_metrics, bool):
+            raise TypeError(f"TrainStep: seg_metrics must be a bool, got {seg_metrics!r}")
+        n_seg = None
+        if seg_metrics:
+            if not _accepts_seg_counts(model):
+                raise TypeError("TrainStep: seg_metrics=True needs a model whose forward_loss takes seg_counts= "
+                                "(BaseModelWithText, PromptFTN)")
+            n_seg = _n_classes(model) if seg_classes is None else seg_classes
+            if isinstance(n_seg, bool) or not isinstance(n_seg, int) or not 1 <= n_seg <= 192:
+                raise ValueError("TrainStep: seg_metrics=True needs the class count of the fused head, 1..192: the model's "
+                                 f"class_prototypes rows, or seg_classes= for a model without them (got {seg_classes!r})")
+        elif seg_classes is not None:
+            raise ValueError("TrainStep: seg_classes is only meaningful with seg_metrics=True")
         device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None
                            or param_groups is not None or ema_decay is not None)
         groups = None
@@ -402,6 +437,8 @@ class TrainStep:
             # still cache-warm; 401 against 415 us per launch, faster in both repetitions of profiles/ema_cost.txt
             self.ema_reverse_walk = True
             self.ema = self.arena.flat.clone()
+        # accuracy / IoU counts of the training batches: None = forward_loss is called as before, no launch is added
+        self._seg_counts = torch.zeros((3, n_seg), dtype=torch.int64, device=dev) if seg_metrics else None
 
     # -- views of the control block: device tensors, no sync unless the caller asks (.item()) --------------------------------
     def _ctrl_view(self, word: int, as_float: bool) -> torch.Tensor:
@@ -453,6 +490,27 @@ class TrainStep:
         if not self._dice:
             raise RuntimeError("TrainStep.dice_stats: the criterion is not a DiceCrossEntropyLoss")
         return self.criterion.last_stats
+
+    @property
+    def seg_counts(self) -> torch.Tensor:
+        """The running int64 [3, K] {intersection, predicted, labelled} counts of the steps so far (the buffer itself: the steps,
+        captured ones included, add into it in place)."""
+        if self._seg_counts is None:
+            raise RuntimeError("TrainStep.seg_counts: this TrainStep counts nothing (seg_metrics=False)")
+        return self._seg_counts
+
+    def seg_metrics(self, reset: bool = False) -> dict:
+        """``metrics.dataset_iou`` of ``seg_counts``: ``aAcc``, ``mAcc``, ``mIoU`` and ``IoU`` [K] as float64 tensors on the device
+        (nothing is read to the host).  The ignored class takes part in none of them when ``0 <= ignore_index < K`` (pixels
+        predicted as it would drag the means).  ``reset=True`` zeroes the buffer in place after reading.  Call it outside a graph
+        capture."""
+        from .metrics import dataset_iou
+        counts = self.seg_counts
+        K = counts.shape[1]
+        out = dataset_iou(counts, self.ignore_index if 0 <= self.ignore_index < K else None)
+        if reset:
+            counts.zero_()
+        return out
 
     @property
     def param_groups(self):
@@ -578,23 +636,24 @@ class TrainStep:
         arena.zero_grad(set_to_none=True)
         if self.reducer is not None:
             self.reducer.begin_step()
+        seg = {} if self._seg_counts is None else {"seg_counts": self._seg_counts}   # (no keyword at all without seg_metrics)
         if self._ohem:   # hard-pixel selection in front of the fused head, while the criterion is in training mode (as its forward)
             c = self.criterion
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
                                            label_smoothing=float(c.label_smoothing), reduction=c.reduction,
-                                           ohem=c.ohem if c.training else None)
+                                           ohem=c.ohem if c.training else None, **seg)
             if c.training:
                 c.last_labels, c.last_info = self.model.last_ohem
         elif self._dice:   # CE + soft Dice on the fused head (deterministic: the criterion's training flag does not matter)
             c = self.criterion
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index, dice=c.dice)
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index, dice=c.dice, **seg)
             c.last_stats = self.model.last_dice
         elif self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
             c = self.criterion
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
-                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction)
+                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction, **seg)
         else:
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index)
+            loss = self.model.forward_loss(inputs, labels, self.ignore_index, **seg)
         loss.backward()
         live = arena.finalize_grads()
         gscale = 1.0
