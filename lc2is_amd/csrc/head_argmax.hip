@@ -10,8 +10,8 @@
 // lanes — the larger value wins, equal values keep the lower index: torch.argmax's tie rule.  The index is clamped into [0, C): a NaN
 // score may pick any class but never indexes outside a histogram row; a pixel whose scores are all -inf gets class 0.
 // The 16 results of a unit go to a [16][16] tile in LDS beside the labels' tile; after one barrier the first 256 threads own one pixel
-// each (as in ra_kernel, resize_argmax.hip): pred[b, Y, X] leaves as a byte, and waves 0-3 count their 64 pixels into wave-private
-// LDS rows [3][cq] with the ballot + popcount leader scheme of wave_hist (one plain add per distinct class, the wave the only writer).
+// each (as in the kernels of resize_argmax.hip): pred[b, Y, X] leaves as a byte, and waves 0-3 count their 64 pixels into wave-private
+// LDS rows [3][cq] with wave_hist (label_hist.h: ballot + popcount, one plain add per distinct class, the wave the only writer).
 // Counting rule (the loss's own, and mmseg's): a pixel counts iff label != ignore_index && 0 <= label < C; it adds to
 // predicted[pred] and labelled[label], and to intersection[pred] when pred == label; any other pixel adds to none of the three.
 // The block sums its four waves in wave order into its own slab [3][cq] of the workspace and head_argmax_finish_kernel sums each
@@ -19,6 +19,7 @@
 // A file of its own with the few helpers of head.hip restated, so that head.hip compiles to the object it was.
 #include "common.h"
 #include "interp.h"
+#include "label_hist.h"
 #include "lc2is_hip.h"
 
 namespace {
@@ -60,20 +61,6 @@ template <int CTRL> __device__ __forceinline__ void argmax_step(float& v, int& i
 __device__ __forceinline__ int row16_argmax(float v, int i) {   // every lane of the row ends with the row's winner
   argmax_step<0xB1>(v, i); argmax_step<0x4E>(v, i); argmax_step<0x141>(v, i); argmax_step<0x140>(v, i);
   return i;
-}
-
-// one wave: hist[cls] += number of its lanes with `on` and key == cls (wave_hist of resize_argmax.hip)
-__device__ __forceinline__ void wave_hist(int* hist, bool on, int key, int lane) {
-  while (true) {
-    const unsigned long long m = __ballot(on);
-    if (m == 0ull) break;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    const int cls = __shfl(key, leader);
-    const bool mine = on && key == cls;
-    const unsigned long long e = __ballot(mine);
-    if (lane == leader) hist[cls] += __popcll(e);
-    on = on && !mine;
-  }
 }
 
 template <int MODE, int TN, int S>

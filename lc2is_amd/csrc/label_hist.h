@@ -1,4 +1,5 @@
-// Atomics-free histogram of uint8 labels (gfx950, wave64), shared by aug_crop_select_kernel and label_hist_kernel (augment.hip).
+// Atomics-free histogram of uint8 labels (gfx950, wave64), shared by aug_crop_select_kernel and label_hist_kernel (augment.hip);
+// at the end wave_hist, the same scheme on int keys for the class counts of resize_argmax.hip and head_argmax.hip.
 // Every wave owns one row of LH_BINS counts in LDS, which no other wave writes.  The lanes of the wave that hold the same label
 // are merged before the add: the first lane still to be served is the leader, its label is broadcast (v_readlane), one ballot
 // finds the lanes that match, and the leader alone does a plain `row[v] += popcount`; the loop ends when every lane is served.
@@ -36,4 +37,19 @@ __device__ __forceinline__ unsigned lh_block_sum(const unsigned* rows, int waves
   unsigned s = 0u;
   for (int w = 0; w < waves; ++w) s += rows[w * LH_BINS + bin];
   return s;
+}
+
+// The same leader scheme on int keys with the bin count left to the caller (resize_argmax.hip, head_argmax.hip):
+// hist[cls] += number of this wave's lanes with `on` and key == cls.  One iteration per distinct key; the wave is the only writer.
+__device__ __forceinline__ void wave_hist(int* hist, bool on, int key, int lane) {
+  while (true) {
+    const unsigned long long m = __ballot(on);
+    if (m == 0ull) break;
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    const int cls = __shfl(key, leader);
+    const bool mine = on && key == cls;
+    const unsigned long long e = __ballot(mine);
+    if (lane == leader) hist[cls] += __popcll(e);
+    on = on && !mine;
+  }
 }

@@ -1369,6 +1369,84 @@ def _resize_gt(gt, dts, N, K, n_tiles, dev):
     return g, counts, ws, nbytes
 
 
+def _resize_front(who, x, what):
+    """The first checks of the three resize + argmax wrappers: x is NCHW with 1 <= K <= 192.  Returns its shape."""
+    if x.dim() != 4:
+        raise RuntimeError(f"{who}: {what}, got shape {tuple(x.shape)}")
+    K = x.shape[1]
+    if not 1 <= K <= RESIZE_KMAX:
+        raise RuntimeError(f"{who}: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    return tuple(x.shape)
+
+
+def _resize_ignore_index(who, ignore_index):
+    if ignore_index is not None and (int(ignore_index) != ignore_index or ignore_index < 0):
+        raise ValueError(f"{who}: ignore_index must be None or an int >= 0, got {ignore_index!r}")
+
+
+def _resize_windows(who, where, wl, canvas, V, h, w, rows, overhang):
+    """Validates one window list against its (Hc, Wc) canvas and appends its (view, oy, ox, mirrored) rows to ``rows``.
+    overhang=False: every window lies on the canvas; True: its origin does, and only its on-canvas part covers cells."""
+    Hc, Wc = canvas
+    if not 1 <= len(wl) <= SLIDE_MAX_WIN:
+        raise ValueError(f"{who}: {where} has {len(wl)} windows (1 to {SLIDE_MAX_WIN})")
+    cover = torch.zeros(Hc, Wc, dtype=torch.bool)
+    for view, oy, ox, mirrored in wl:
+        view, oy, ox = int(view), int(oy), int(ox)
+        if not 0 <= view < V:
+            raise ValueError(f"{who}: {where}: view index {view} is not in [0, {V})")
+        if overhang and not (0 <= oy < Hc and 0 <= ox < Wc):
+            raise ValueError(f"{who}: {where}: window origin ({oy}, {ox}) is outside the {Hc} x {Wc} canvas")
+        if not overhang and not (0 <= oy <= Hc - h and 0 <= ox <= Wc - w):
+            raise ValueError(f"{who}: {where}: window origin ({oy}, {ox}) is outside [0, {Hc - h}] x [0, {Wc - w}]")
+        cover[oy:oy + h, ox:ox + w] = True
+        rows.append((view, oy, ox, 1 if mirrored else 0))
+    if not bool(cover.all()):
+        raise ValueError(f"{who}: {where}: {int((~cover).sum())} canvas cells are covered by no window")
+
+
+def _resize_back(who, x, what, gt, want_pred):
+    """The last host checks, in their order: gt dtypes, something to compute, and (last of all) x on the GPU.  Returns the gt
+    dtypes (None without gt)."""
+    dts = None
+    if gt is not None:
+        dts = {g.dtype for g in gt}
+        if not dts <= set(_GT_BYTES):
+            raise RuntimeError(f"{who}: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
+    if not want_pred and gt is None:
+        raise ValueError(f"{who}: nothing to compute (want_pred=False and no gt)")
+    if not x.is_cuda:
+        raise RuntimeError(f"{who}: {what} must be a CUDA(HIP) tensor; there is no CPU path")
+    return dts
+
+
+def _resize_channels_last(x):
+    """(fp32 [N, h, w, ld] copy of NCHW x with the channels padded by zeros to ld, a multiple of 4; ld)."""
+    N, K, h, w = x.shape
+    ld = (K + 3) // 4 * 4
+    lo = torch.empty((N, h, w, ld), dtype=torch.float32, device=x.device)
+    lo[..., :K] = x.permute(0, 2, 3, 1)
+    if ld > K:
+        lo[..., K:] = 0
+    return lo, ld
+
+
+def _resize_run(hw, K, gt, dts, want_pred, dev, launch):
+    """The common tail: the packed layout, pred / gt / counts / workspace, the launch and the split of the packed pred.
+    launch(layout, pred, g, gt_bytes, counts, ws, nbytes) makes the descriptors from layout = (first_px, first_tile, n_tiles,
+    total_px), calls the library and checks its return code."""
+    N = len(hw)
+    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
+    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
+    counts = g = ws = None
+    nbytes = 0
+    if gt is not None:
+        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
+    launch((first_px, first_tile, n_tiles, total_px), pred, g, _GT_BYTES[g.dtype] if g is not None else 0, counts, ws, nbytes)
+    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
+    return preds, counts
+
+
 def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     """Per image, F.interpolate(scores[i:i+1], size=sizes[i], mode="bicubic", align_corners=False) and the argmax over the classes
     (exact ties: the lowest index), fused: the [K, H, W] score map is never formed (lc2is_resize_argmax).
@@ -1377,39 +1455,20 @@ def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     (uint8 / int32 / int64, host or device).
     Returns (pred, counts): pred a list of uint8 [H_i, W_i] (views of one packed buffer) or None (want_pred=False);
     counts int32 [N, 3, K] = {intersection, predicted, labelled} (labelled: 0 <= gt < K) when gt is given, else None."""
-    if scores.dim() != 4:
-        raise RuntimeError(f"lc2is_amd.resize_argmax: scores must be NCHW [N, K, h, w], got shape {tuple(scores.shape)}")
-    N, K, h, w = scores.shape
-    if not 1 <= K <= RESIZE_KMAX:
-        raise RuntimeError(f"lc2is_amd.resize_argmax: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    who = "lc2is_amd.resize_argmax"
+    N, K, h, w = _resize_front(who, scores, "scores must be NCHW [N, K, h, w]")
     hw = resize_sizes(N, sizes, gt)
-    if gt is not None:
-        dts = {g.dtype for g in gt}
-        if not dts <= set(_GT_BYTES):
-            raise RuntimeError(f"lc2is_amd.resize_argmax: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
-    if not want_pred and gt is None:
-        raise ValueError("lc2is_amd.resize_argmax: nothing to compute (want_pred=False and no gt)")
-    if not scores.is_cuda:
-        raise RuntimeError("lc2is_amd.resize_argmax: scores must be a CUDA(HIP) tensor; there is no CPU path")
+    dts = _resize_back(who, scores, "scores", gt, want_pred)
     dev = scores.device
-    ld = (K + 3) // 4 * 4
-    lo = torch.empty((N, h, w, ld), dtype=torch.float32, device=dev)
-    lo[..., :K] = scores.permute(0, 2, 3, 1)
-    if ld > K:
-        lo[..., K:] = 0
-    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
-    desc = torch.tensor([[H, W, p0, t0] for (H, W), p0, t0 in zip(hw, first_px, first_tile)], dtype=torch.int64).to(dev)
-    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
-    counts = g = ws = None
-    nbytes = 0
-    if gt is not None:
-        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
-    rc = _fn("lc2is_resize_argmax")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g),
-                                    _GT_BYTES[g.dtype] if g is not None else 0, _ptr(pred), _ptr(counts), _ptr(ws), nbytes,
-                                    _stream())
-    _lib.check(rc, f"resize_argmax N={N} K={K} h={h} w={w}")
-    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
-    return preds, counts
+    lo, ld = _resize_channels_last(scores)
+
+    def launch(layout, pred, g, gt_bytes, counts, ws, nbytes):
+        first_px, first_tile, n_tiles, total_px = layout
+        desc = torch.tensor([[H, W, p0, t0] for (H, W), p0, t0 in zip(hw, first_px, first_tile)], dtype=torch.int64).to(dev)
+        rc = _fn("lc2is_resize_argmax")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g), gt_bytes, _ptr(pred),
+                                        _ptr(counts), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, f"resize_argmax N={N} K={K} h={h} w={w}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
 
 
 SLIDE_MAX_WIN = 64                      # LC2IS_SLIDE_MAX_WIN: windows per image of lc2is_resize_argmax_windows
@@ -1424,68 +1483,35 @@ def resize_argmax_windows(views, windows, canvases, sizes, gt=None, want_pred: b
     sizes, gt, want_pred and the returned (pred, counts): as ``resize_argmax``.  ignore_index: None = its counting rule; an int
     >= 0 = mmseg's: a pixel whose gt is ignore_index or outside [0, K) counts in none of the three rows.
     Everything is validated on the host before anything is allocated."""
-    if views.dim() != 4:
-        raise RuntimeError(f"lc2is_amd.resize_argmax_windows: views must be NCHW [V, K, h, w], got shape {tuple(views.shape)}")
-    V, K, h, w = views.shape
-    if not 1 <= K <= RESIZE_KMAX:
-        raise RuntimeError(f"lc2is_amd.resize_argmax_windows: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    who = "lc2is_amd.resize_argmax_windows"
+    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]")
     N = len(windows)
     if N < 1 or len(canvases) != N:
-        raise ValueError(f"lc2is_amd.resize_argmax_windows: {N} window lists for {len(canvases)} canvases")
+        raise ValueError(f"{who}: {N} window lists for {len(canvases)} canvases")
     hw = resize_sizes(N, sizes, gt)
-    if ignore_index is not None and (int(ignore_index) != ignore_index or ignore_index < 0):
-        raise ValueError(f"lc2is_amd.resize_argmax_windows: ignore_index must be None or an int >= 0, got {ignore_index!r}")
+    _resize_ignore_index(who, ignore_index)
     canv, rows, first_win = [], [], []
     for i, (wl, cv) in enumerate(zip(windows, canvases)):
         Hc, Wc = (int(v) for v in cv)
         if Hc < h or Wc < w:
-            raise ValueError(f"lc2is_amd.resize_argmax_windows: canvas {i} ({Hc} x {Wc}) is smaller than a view ({h} x {w})")
-        if not 1 <= len(wl) <= SLIDE_MAX_WIN:
-            raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i} has {len(wl)} windows (1 to {SLIDE_MAX_WIN})")
-        cover = torch.zeros(Hc, Wc, dtype=torch.bool)
+            raise ValueError(f"{who}: canvas {i} ({Hc} x {Wc}) is smaller than a view ({h} x {w})")
         first_win.append(len(rows))
-        for view, oy, ox, mirrored in wl:
-            view, oy, ox = int(view), int(oy), int(ox)
-            if not 0 <= view < V:
-                raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: view index {view} is not in [0, {V})")
-            if not (0 <= oy <= Hc - h and 0 <= ox <= Wc - w):
-                raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: window origin ({oy}, {ox}) is outside "
-                                 f"[0, {Hc - h}] x [0, {Wc - w}]")
-            cover[oy:oy + h, ox:ox + w] = True
-            rows.append((view, oy, ox, 1 if mirrored else 0))
-        if not bool(cover.all()):
-            raise ValueError(f"lc2is_amd.resize_argmax_windows: image {i}: {int((~cover).sum())} canvas cells are covered by no window")
+        _resize_windows(who, f"image {i}", wl, (Hc, Wc), V, h, w, rows, overhang=False)
         canv.append((Hc, Wc))
-    if gt is not None:
-        dts = {g.dtype for g in gt}
-        if not dts <= set(_GT_BYTES):
-            raise RuntimeError(f"lc2is_amd.resize_argmax_windows: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
-    if not want_pred and gt is None:
-        raise ValueError("lc2is_amd.resize_argmax_windows: nothing to compute (want_pred=False and no gt)")
-    if not views.is_cuda:
-        raise RuntimeError("lc2is_amd.resize_argmax_windows: views must be a CUDA(HIP) tensor; there is no CPU path")
+    dts = _resize_back(who, views, "views", gt, want_pred)
     dev = views.device
-    ld = (K + 3) // 4 * 4
-    lo = torch.empty((V, h, w, ld), dtype=torch.float32, device=dev)
-    lo[..., :K] = views.permute(0, 2, 3, 1)
-    if ld > K:
-        lo[..., K:] = 0
-    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
-    desc = torch.tensor([[H, W, p0, t0, Hc, Wc, w0, len(wl)] for (H, W), p0, t0, (Hc, Wc), w0, wl in
-                         zip(hw, first_px, first_tile, canv, first_win, windows)], dtype=torch.int64).to(dev)
-    win = torch.tensor(rows, dtype=torch.int32).to(dev)
-    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
-    counts = g = ws = None
-    nbytes = 0
-    if gt is not None:
-        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
-    rc = _fn("lc2is_resize_argmax_windows")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(win), len(rows), n_tiles, total_px,
-                                            _ptr(g), _GT_BYTES[g.dtype] if g is not None else 0,
-                                            -1 if ignore_index is None else int(ignore_index), _ptr(pred), _ptr(counts), _ptr(ws),
-                                            nbytes, _stream())
-    _lib.check(rc, f"resize_argmax_windows N={N} V={V} K={K} h={h} w={w}")
-    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
-    return preds, counts
+    lo, ld = _resize_channels_last(views)
+
+    def launch(layout, pred, g, gt_bytes, counts, ws, nbytes):
+        first_px, first_tile, n_tiles, total_px = layout
+        desc = torch.tensor([[H, W, p0, t0, Hc, Wc, w0, len(wl)] for (H, W), p0, t0, (Hc, Wc), w0, wl in
+                             zip(hw, first_px, first_tile, canv, first_win, windows)], dtype=torch.int64).to(dev)
+        win = torch.tensor(rows, dtype=torch.int32).to(dev)
+        rc = _fn("lc2is_resize_argmax_windows")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(win), len(rows), n_tiles, total_px,
+                                                _ptr(g), gt_bytes, -1 if ignore_index is None else int(ignore_index), _ptr(pred),
+                                                _ptr(counts), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, f"resize_argmax_windows N={N} V={V} K={K} h={h} w={w}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
 
 
 MS_MAX_CANVAS = 16                      # LC2IS_MS_MAX_CANVAS: canvases per image of lc2is_resize_argmax_multiscale
@@ -1505,19 +1531,14 @@ def resize_argmax_multiscale(views, canvases, sizes, gt=None, want_pred: bool = 
     views, sizes, gt, want_pred, ignore_index and the returned (pred, counts): as ``resize_argmax_windows``.
     Everything is validated on the host before anything is allocated."""
     who = "lc2is_amd.resize_argmax_multiscale"
-    if views.dim() != 4:
-        raise RuntimeError(f"{who}: views must be NCHW [V, K, h, w], got shape {tuple(views.shape)}")
-    V, K, h, w = views.shape
-    if not 1 <= K <= RESIZE_KMAX:
-        raise RuntimeError(f"{who}: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]")
     if mode not in _MS_MODES:
         raise ValueError(f"{who}: mode must be 'prob' or 'logit', got {mode!r}")
     N = len(canvases)
     if N < 1:
         raise ValueError(f"{who}: no images")
     hw = resize_sizes(N, sizes, gt)
-    if ignore_index is not None and (int(ignore_index) != ignore_index or ignore_index < 0):
-        raise ValueError(f"{who}: ignore_index must be None or an int >= 0, got {ignore_index!r}")
+    _resize_ignore_index(who, ignore_index)
     crows, rows, first_canvas = [], [], []
     for i, cl in enumerate(canvases):
         if not 1 <= len(cl) <= MS_MAX_CANVAS:
@@ -1527,51 +1548,24 @@ def resize_argmax_multiscale(views, canvases, sizes, gt=None, want_pred: bool = 
             Hc, Wc = (int(v) for v in cv)
             if Hc < 1 or Wc < 1:
                 raise ValueError(f"{who}: image {i} canvas {a}: size ({Hc}, {Wc}) is not positive")
-            if not 1 <= len(wl) <= SLIDE_MAX_WIN:
-                raise ValueError(f"{who}: image {i} canvas {a} has {len(wl)} windows (1 to {SLIDE_MAX_WIN})")
-            cover = torch.zeros(Hc, Wc, dtype=torch.bool)
             crows.append((Hc, Wc, len(rows), len(wl)))
-            for view, oy, ox, mirrored in wl:
-                view, oy, ox = int(view), int(oy), int(ox)
-                if not 0 <= view < V:
-                    raise ValueError(f"{who}: image {i} canvas {a}: view index {view} is not in [0, {V})")
-                if not (0 <= oy < Hc and 0 <= ox < Wc):
-                    raise ValueError(f"{who}: image {i} canvas {a}: window origin ({oy}, {ox}) is outside the {Hc} x {Wc} canvas")
-                cover[oy:oy + h, ox:ox + w] = True
-                rows.append((view, oy, ox, 1 if mirrored else 0))
-            if not bool(cover.all()):
-                raise ValueError(f"{who}: image {i} canvas {a}: {int((~cover).sum())} canvas cells are covered by no window")
-    if gt is not None:
-        dts = {g.dtype for g in gt}
-        if not dts <= set(_GT_BYTES):
-            raise RuntimeError(f"{who}: gt maps must be uint8, int32 or int64, got {sorted(map(str, dts))}")
-    if not want_pred and gt is None:
-        raise ValueError(f"{who}: nothing to compute (want_pred=False and no gt)")
-    if not views.is_cuda:
-        raise RuntimeError(f"{who}: views must be a CUDA(HIP) tensor; there is no CPU path")
+            _resize_windows(who, f"image {i} canvas {a}", wl, (Hc, Wc), V, h, w, rows, overhang=True)
+    dts = _resize_back(who, views, "views", gt, want_pred)
     dev = views.device
-    ld = (K + 3) // 4 * 4
-    lo = torch.empty((V, h, w, ld), dtype=torch.float32, device=dev)
-    lo[..., :K] = views.permute(0, 2, 3, 1)
-    if ld > K:
-        lo[..., K:] = 0
-    px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
-    desc = torch.tensor([[H, W, p0, t0, c0, len(cl)] for (H, W), p0, t0, c0, cl in
-                         zip(hw, first_px, first_tile, first_canvas, canvases)], dtype=torch.int64).to(dev)
-    canv = torch.tensor(crows, dtype=torch.int64).to(dev)
-    win = torch.tensor(rows, dtype=torch.int32).to(dev)
-    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
-    counts = g = ws = None
-    nbytes = 0
-    if gt is not None:
-        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
-    rc = _fn("lc2is_resize_argmax_multiscale")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(canv), len(crows), _ptr(win), len(rows),
-                                               n_tiles, total_px, _ptr(g), _GT_BYTES[g.dtype] if g is not None else 0,
-                                               -1 if ignore_index is None else int(ignore_index), _MS_MODES[mode], _ptr(pred),
-                                               _ptr(counts), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, f"resize_argmax_multiscale N={N} V={V} K={K} h={h} w={w} canvases={len(crows)} mode={mode}")
-    preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
-    return preds, counts
+    lo, ld = _resize_channels_last(views)
+
+    def launch(layout, pred, g, gt_bytes, counts, ws, nbytes):
+        first_px, first_tile, n_tiles, total_px = layout
+        desc = torch.tensor([[H, W, p0, t0, c0, len(cl)] for (H, W), p0, t0, c0, cl in
+                             zip(hw, first_px, first_tile, first_canvas, canvases)], dtype=torch.int64).to(dev)
+        canv = torch.tensor(crows, dtype=torch.int64).to(dev)
+        win = torch.tensor(rows, dtype=torch.int32).to(dev)
+        rc = _fn("lc2is_resize_argmax_multiscale")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(canv), len(crows), _ptr(win),
+                                                   len(rows), n_tiles, total_px, _ptr(g), gt_bytes,
+                                                   -1 if ignore_index is None else int(ignore_index), _MS_MODES[mode], _ptr(pred),
+                                                   _ptr(counts), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, f"resize_argmax_multiscale N={N} V={V} K={K} h={h} w={w} canvases={len(crows)} mode={mode}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
 
 
 # ---- Swin backbone ----------------------------------------------------------------------------------------------

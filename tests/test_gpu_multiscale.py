@@ -60,6 +60,24 @@ def test_one_canvas_summed_as_logits_is_resize_argmax_windows_bitwise(dev):
                 assert a.dtype == torch.uint8 and a.shape == s and torch.equal(a, b), (name, ign, s)
 
 
+def test_the_three_kernels_agree_bitwise_where_the_bands_split_on_both_axes(dev):
+    """One 24 x 24 view, K = 37.  At (9, 11) the one partial tile spans all 24 source rows and columns, so the row band halves
+    9 -> 5 -> 3 and the column band 11 -> 6 -> 3 before a footprint fits 10: the band loops of the shared walk run several times
+    on both axes, which no 8 x 8 grid reaches.  (50, 7) is upscaled along y and downscaled along x, (24, 24) is the identity,
+    (40, 70) has more than one tile per axis.  resize_argmax == resize_argmax_windows == resize_argmax_multiscale(logit),
+    predictions and counts."""
+    sizes = [(9, 11), (50, 7), (24, 24), (40, 70)]
+    x = torch.randn(1, K, 24, 24, generator=torch.Generator().manual_seed(11)).to(dev)
+    gt = [t.to(dev) for t in _gt_maps(sizes, 12)]
+    wl = [(0, 0, 0, False)]
+    p0, c0 = ops.resize_argmax(x.expand(4, -1, -1, -1), sizes, gt)
+    p1, c1 = ops.resize_argmax_windows(x, [wl] * 4, [(24, 24)] * 4, sizes, gt)
+    p2, c2 = ops.resize_argmax_multiscale(x, [[((24, 24), wl)]] * 4, sizes, gt, mode="logit")
+    assert c0.dtype == torch.int32 and torch.equal(c0, c1) and torch.equal(c1, c2)
+    for a, b, c, s in zip(p0, p1, p2, sizes):
+        assert a.dtype == torch.uint8 and a.shape == s and torch.equal(a, b) and torch.equal(b, c), s
+
+
 @pytest.mark.parametrize("mode", ["prob", "logit"])
 @pytest.mark.parametrize("name", list(M.CASES))
 def test_matches_fp64_torch_outside_the_near_tie_margin(dev, name, mode):
