@@ -534,7 +534,8 @@ int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int
 /* ---- the device-held optimizer path (optim.hip) -----------------------------------------------------------------------
  * The scalars of an optimizer step that change from call to call live in this block in DEVICE memory (48 bytes, 4-byte
  * aligned, all zero before the first step), so a step needs no host value that differs between calls and can be replayed
- * from a captured graph.  Only lc2is_optim_ctrl_update writes it: plain vector stores from one lane of its one block. */
+ * from a captured graph.  Only lc2is_optim_ctrl_update (and its _accum form) writes it: plain vector stores from one lane of
+ * its one block. */
 typedef struct {
   int32_t calls;    /* iterations seen: indexes the lr table (the reference advances its scheduler every iteration)        */
   int32_t applied;  /* updates actually applied: AdamW's t                                                                 */
@@ -571,6 +572,41 @@ int lc2is_grad_sumsq(const float* grads, size_t n, void* workspace, size_t works
 int lc2is_optim_ctrl_update(lc2is_optim_ctrl* ctrl, const float* partials, const unsigned int* flags, int nparts,
                             const float* lr_table, int table_len, float grad_scale, float max_norm, int skip_nonfinite,
                             float beta1, float beta2, lc2is_stream_t stream);
+
+/* Gradient accumulation: N micro-batches per optimizer update with the EXACT large-batch mean.  The head writes the gradient
+ * of the SUM of the pixel losses and returns [sum of losses, (weighted) count]; the arena accumulates those sums over the
+ * cycle, and this block in DEVICE memory (32 bytes, 8-byte aligned, all zero before the first cycle) holds the cycle's
+ * denominator, so the update divides by the count of ALL pixels of the cycle - not the mean of micro-batch means, which
+ * weights the pixels of sparsely labelled crops more heavily than the large batch would.  fp64 sums: fp32 stops counting
+ * exactly at 2^24, which 32 micro-batches of 524 288 labels reach.  Written by one lane in plain stores, no atomics; read by the
+ * next launch on the same stream. */
+typedef struct {
+  double loss_sum;   /* open cycle: sum over its micro-batches of loss2[0]                                                  */
+  double denom;      /* open cycle: sum over its micro-batches of loss2[1]                                                  */
+  int32_t micro;     /* open cycle: micro-batches added so far                                                              */
+  int32_t reserved;
+  float last_loss;   /* last closed cycle: loss_sum / denom (use_denom; NaN when denom == 0), or loss_sum                   */
+  float last_denom;  /* last closed cycle: its denom                                                                        */
+} lc2is_accum_block;
+
+/* loss_sum += (double)loss2[0], denom += (double)loss2[1], micro += 1.  loss2: DEVICE fp32 [2] as lc2is_head_upsample_ce
+ * returns it.  One lane of one block.  block 8-byte aligned, loss2 4-byte aligned (else LC2IS_ERR_SHAPE).
+ * replaces: nothing in the reference, which calls optimizer.step() after every batch (engine.py:89-101); stands in for the
+ *   `loss = loss / accum_steps` of the usual accumulation loop, which cannot give the large batch's mean over non-ignored pixels. */
+int lc2is_accum_add(lc2is_accum_block* block, const float* loss2, lc2is_stream_t stream);
+
+/* lc2is_optim_ctrl_update for the call that closes an accumulation cycle: the same kernel body with the gradient scale
+ *   scale64 = (double)grad_scale / d,  d = use_denom ? (block->denom > 0 ? block->denom : 1.0) : 1.0
+ * wherever lc2is_optim_ctrl_update uses grad_scale: grad_norm = scale64 * sqrt(sum), grad_mul = (float)scale64 * clip_coef.
+ * Then it writes the block: last_loss = use_denom ? loss_sum / denom : loss_sum, last_denom = denom, and loss_sum, denom and
+ * micro are zeroed for the next cycle.  With use_denom == 0, or denom == 1.0, *ctrl receives the very bits
+ * lc2is_optim_ctrl_update writes.  use_denom in {0, 1}, block 8-byte aligned, everything else as lc2is_optim_ctrl_update.
+ * replaces: nothing in the reference (engine.py:89-101 steps after every batch); the per-update scheduler step, skip decision
+ *   and clip coefficient of lc2is_optim_ctrl_update, taken once per cycle on the accumulated gradient. */
+int lc2is_optim_ctrl_update_accum(lc2is_optim_ctrl* ctrl, lc2is_accum_block* block, int use_denom, const float* partials,
+                                  const unsigned int* flags, int nparts, const float* lr_table, int table_len,
+                                  float grad_scale, float max_norm, int skip_nonfinite, float beta1, float beta2,
+                                  lc2is_stream_t stream);
 
 /* lc2is_sgd_step / lc2is_adamw_step with lr, bc1, bc2 and the gradient multiplier (grad_scale * clip_coef) read from *ctrl;
  * with ctrl->apply == 0 they return before touching params or any state buffer.  The same expressions: with clip_coef == 1 and

@@ -3,6 +3,8 @@
 // replayed from a captured graph - needs no host value that changes from call to call.
 //   - grad_sumsq:        pass 1 over the flat gradient arena: one fp32 sum-of-squares partial and one non-finite flag per block
 //   - optim_ctrl_update: one block: global norm, clip coefficient, verdict, lr table look-up, counters, bias corrections
+//   - accum_add / optim_ctrl_update_accum: gradient accumulation - the cycle's loss sum and denominator in fp64 on the device,
+//                        and the control update that divides the gradient scale by that denominator
 //   - sgd / adamw _ctrl: sgd_kernel / adamw_kernel of misc.hip, expression for expression, scalars read from the block
 //   - ema_ctrl / swap:   the weight EMA that follows the block's verdict and counter, and the in-place exchange that evaluates it
 // Every reduction has a fixed order and there is no read-modify-write atomic: results are bitwise reproducible.
@@ -63,12 +65,17 @@ __device__ __forceinline__ float pow_uint(float beta, unsigned t) {
 }
 
 // One block.  Lane k sums the k-th run of consecutive partials in index order (fp64), lane 0 adds the 256 run sums in index
-// order and writes the whole control block.
-__global__ __launch_bounds__(256) void optim_ctrl_update_kernel(lc2is_optim_ctrl* ctrl, const float* __restrict__ partials,
-                                                                 const unsigned* __restrict__ flags, int nparts,
-                                                                 const float* __restrict__ lr_table, int table_len,
-                                                                 float grad_scale, float max_norm, int skip_nonfinite,
-                                                                 float beta1, float beta2) {
+// order and writes the whole control block.  Shared by the two control kernels below: ACCUM = false is the per-batch update
+// (the gradient scale is grad_scale, widened exactly), ACCUM = true the update that closes a gradient-accumulation cycle (the
+// scale is grad_scale over the cycle's denominator, formed in fp64; lane 0 alone reads the accumulation block, after the
+// barrier, and rewrites it after the control block).  A divisor of exactly 1.0 leaves (double)grad_scale as it is, so both
+// instantiations then write the same bits.
+template <bool ACCUM>
+__device__ __forceinline__ void optim_ctrl_update_body(lc2is_optim_ctrl* ctrl, lc2is_accum_block* block, int use_denom,
+                                                       const float* __restrict__ partials,
+                                                       const unsigned* __restrict__ flags, int nparts,
+                                                       const float* __restrict__ lr_table, int table_len, float grad_scale,
+                                                       float max_norm, int skip_nonfinite, float beta1, float beta2) {
   __shared__ double run_sum[256];
   __shared__ unsigned run_bad[256];
   const int per = (nparts + 255) / 256;
@@ -89,7 +96,16 @@ __global__ __launch_bounds__(256) void optim_ctrl_update_kernel(lc2is_optim_ctrl
     tot += run_sum[k];
     any_bad |= run_bad[k];
   }
-  const double norm64 = (double)grad_scale * sqrt(tot);
+  double scale64 = (double)grad_scale;
+  double loss_sum = 0.0, denom = 0.0;
+  if (ACCUM) {
+    loss_sum = block->loss_sum;
+    denom = block->denom;
+    // every pixel of the cycle ignored: the gradient is all zeros and the scale is taken as 1 (nothing turns into a NaN)
+    const double d = use_denom ? (denom > 0.0 ? denom : 1.0) : 1.0;
+    scale64 = (double)grad_scale / d;
+  }
+  const double norm64 = scale64 * sqrt(tot);
   const float norm = (float)norm64;
   // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)), from the fp64 norm and rounded once; max_norm = +inf is "no clipping",
   // exactly 1 whatever the norm holds
@@ -104,7 +120,7 @@ __global__ __launch_bounds__(256) void optim_ctrl_update_kernel(lc2is_optim_ctrl
   ctrl->apply = apply;
   ctrl->grad_norm = norm;
   ctrl->clip_coef = coef;
-  ctrl->grad_mul = grad_scale * coef;
+  ctrl->grad_mul = (float)scale64 * coef;
   if (apply) {
     const int t = ctrl->applied + 1;
     ctrl->applied = t;
@@ -113,6 +129,42 @@ __global__ __launch_bounds__(256) void optim_ctrl_update_kernel(lc2is_optim_ctrl
   } else {
     ctrl->skipped = ctrl->skipped + 1;
   }
+  if (ACCUM) {   // the cycle is closed: its mean (0 / 0 = NaN where nothing counted, torch's mean) and count stay readable
+    block->last_loss = (float)(use_denom ? loss_sum / denom : loss_sum);
+    block->last_denom = (float)denom;
+    block->loss_sum = 0.0;
+    block->denom = 0.0;
+    block->micro = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void optim_ctrl_update_kernel(lc2is_optim_ctrl* ctrl, const float* __restrict__ partials,
+                                                                 const unsigned* __restrict__ flags, int nparts,
+                                                                 const float* __restrict__ lr_table, int table_len,
+                                                                 float grad_scale, float max_norm, int skip_nonfinite,
+                                                                 float beta1, float beta2) {
+  optim_ctrl_update_body<false>(ctrl, nullptr, 0, partials, flags, nparts, lr_table, table_len, grad_scale, max_norm,
+                                skip_nonfinite, beta1, beta2);
+}
+
+__global__ __launch_bounds__(256) void optim_ctrl_update_accum_kernel(lc2is_optim_ctrl* ctrl, lc2is_accum_block* block,
+                                                                       int use_denom, const float* __restrict__ partials,
+                                                                       const unsigned* __restrict__ flags, int nparts,
+                                                                       const float* __restrict__ lr_table, int table_len,
+                                                                       float grad_scale, float max_norm, int skip_nonfinite,
+                                                                       float beta1, float beta2) {
+  optim_ctrl_update_body<true>(ctrl, block, use_denom, partials, flags, nparts, lr_table, table_len, grad_scale, max_norm,
+                               skip_nonfinite, beta1, beta2);
+}
+
+// One micro-batch of a gradient-accumulation cycle: the head's [sum of losses, (weighted) count] joins the cycle's fp64 sums
+// (fp32 stops counting exactly at 2^24 labels).  One lane, plain loads and stores, no atomics: the block is written by this
+// launch and read by the next one on the same stream.
+__global__ __launch_bounds__(64) void accum_add_kernel(lc2is_accum_block* block, const float* __restrict__ loss2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  block->loss_sum = block->loss_sum + (double)loss2[0];
+  block->denom = block->denom + (double)loss2[1];
+  block->micro = block->micro + 1;
 }
 
 // sgd_kernel of misc.hip with lr and the gradient multiplier read from the control block; `reverse` walks the arena from its
@@ -324,6 +376,29 @@ extern "C" int lc2is_optim_ctrl_update(lc2is_optim_ctrl* ctrl, const float* part
     return LC2IS_ERR_SHAPE;
   hipLaunchKernelGGL(optim_ctrl_update_kernel, dim3(1), dim3(256), 0, stream, ctrl, partials, flags, nparts, lr_table,
                      table_len, grad_scale, max_norm, skip_nonfinite, beta1, beta2);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_accum_add(lc2is_accum_block* block, const float* loss2, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!block || !loss2) return LC2IS_ERR_NULL;
+  if (((uintptr_t)block & 7u) || ((uintptr_t)loss2 & 3u)) return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(accum_add_kernel, dim3(1), dim3(64), 0, stream, block, loss2);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_optim_ctrl_update_accum(lc2is_optim_ctrl* ctrl, lc2is_accum_block* block, int use_denom,
+                                             const float* partials, const unsigned int* flags, int nparts,
+                                             const float* lr_table, int table_len, float grad_scale, float max_norm,
+                                             int skip_nonfinite, float beta1, float beta2, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctrl || !block || !partials || !flags || !lr_table) return LC2IS_ERR_NULL;
+  if (nparts < 1 || nparts > SUMSQ_MAX_GRID || table_len < 1 || !(max_norm > 0.f) || !(grad_scale > 0.f) ||
+      !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || ((uintptr_t)ctrl & 3u) ||
+      ((uintptr_t)block & 7u) || (use_denom != 0 && use_denom != 1))
+    return LC2IS_ERR_SHAPE;
+  hipLaunchKernelGGL(optim_ctrl_update_accum_kernel, dim3(1), dim3(256), 0, stream, ctrl, block, use_denom, partials, flags,
+                     nparts, lr_table, table_len, grad_scale, max_norm, skip_nonfinite, beta1, beta2);
   return lc2is_check_launch();
 }
 

@@ -43,6 +43,7 @@ class GradReducer:
         self.cu_reserve = max(0, min(128, int(os.environ.get("LC2IS_DP_CU_RESERVE", "0"))))
         self._budget_on = False
         self.collectives_last_step = 0       # all_reduce calls issued by the most recent finished step
+        self._sync = True                    # False inside a gradient-accumulation cycle: the ready callbacks issue nothing
 
     # -- wiring ------------------------------------------------------------------------------------------------
     def attach(self, model, arena) -> None:
@@ -74,7 +75,13 @@ class GradReducer:
         return [(a, b) for a, b in out]
 
     # -- per step ------------------------------------------------------------------------------------------------
-    def begin_step(self) -> None:
+    def begin_step(self, sync: bool = True) -> None:
+        """``sync=False``: a micro-batch of a gradient-accumulation cycle that does not close it (``TrainStep(accumulate=N)``).  The
+        gradients stay local sums, the modules' ready callbacks are no-ops and the call issues no collective; the call that
+        closes the cycle (``sync=True``) reduces the accumulated arena as a plain step does, under its own backward."""
+        self._sync = bool(sync)
+        if not self._sync:
+            self.collectives_last_step = 0
         self._pending.clear()
         self._done.clear()
         self._bucket.clear()
@@ -90,7 +97,7 @@ class GradReducer:
         """A layer of `module` finished its backward while the rest of the module is still running: its slice of the
         arena joins the module's bucket, and a full bucket is all-reduced now, under the remaining backward."""
         key = id(module)
-        if key not in self._module_ranges or key in self._done:
+        if not self._sync or key not in self._module_ranges or key in self._done:
             return
         ps = [p for p in part.parameters() if id(p) in self._arena.ranges]
         self._zero_missing(ps)
@@ -124,7 +131,7 @@ class GradReducer:
 
     def _on_module_done(self, module) -> None:
         key = id(module)
-        if key in self._done or key not in self._module_ranges:
+        if not self._sync or key in self._done or key not in self._module_ranges:
             return
         self._flush_bucket(key)
         self._done.add(key)
@@ -145,6 +152,11 @@ class GradReducer:
             for a in range(lo, hi, self.max_chunk):
                 b = min(a + self.max_chunk, hi)
                 self._pending.append(dist.all_reduce(flat[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+
+    def reduce_block(self, t64: torch.Tensor) -> None:
+        """All-reduce (SUM) a small tensor with the step's gradients — the two fp64 sums of an accumulation cycle, so that every
+        rank divides by the GLOBAL count; waited for in ``finish_step`` with the rest."""
+        self._pending.append(dist.all_reduce(t64, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def finish_step(self) -> None:
         """Reduce whatever has not been reduced yet, then make the compute stream wait for every collective."""

@@ -69,16 +69,18 @@ class PromptFTN(nn.Module):
         return None, self.tail(visual_embeddings, text_embeddings)                                # model.py:204-214
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None) -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
         materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
-        {intersection, predicted, labelled} counts (``ScoreMapTail.loss``)."""
+        {intersection, predicted, labelled} counts (``ScoreMapTail.loss``).  ``accum``: the device block of a gradient-accumulation
+        cycle (``ScoreMapTail.loss``; ``TrainStep(accumulate=N)``)."""
         fused_loss_options(weight, label_smoothing, reduction)   # (refused before the towers run)
         if seg_counts is not None:
             ops.check_seg_counts(seg_counts)
         visual_embeddings, text_embeddings = self._embeddings(inputs)
+        extra = {} if accum is None else {"accum": accum}
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
-                              label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts)
+                              label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, **extra)
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:

@@ -112,8 +112,9 @@ class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None,
+                accum=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -121,7 +122,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -178,7 +179,7 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None, accum=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -216,6 +217,9 @@ class BaseModelWithText(HipModule):
                                                  want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
                                                  class_weight=weight, label_smoothing=label_smoothing)
             loss, inv_count = _reduce(loss2, reduction, save)
+        if accum is not None:   # a micro-batch of an accumulation cycle: its sums join the cycle's on the device, and the backward
+            ops.accum_add(accum, loss2)   # leaves the gradient of the SUM (the 'sum' branch of _head_bwd); the update divides
+            inv_count = None
         return loss, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=inv_count)
                       if save else None)
 
@@ -294,7 +298,7 @@ class BaseModelWithText(HipModule):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                     seg_counts=None) -> torch.Tensor:
+                     seg_counts=None, accum=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
@@ -305,7 +309,13 @@ class BaseModelWithText(HipModule):
         ``seg_counts``: an int64 [3, K] device tensor that takes ``+= counts.sum(0)`` of this batch — {intersection, predicted,
         labelled} of the argmax of the same upsampled scores against ``labels`` as given (under ``ohem=``: before relabelling), over
         the pixels the loss counts (``ops.head_upsample_argmax``; ``metrics.dataset_iou`` turns them into aAcc / mAcc / mIoU).  One
-        more forward pass of the head and a small device add, no host read; loss and gradients are unchanged.  None: no launch."""
+        more forward pass of the head and a small device add, no host read; loss and gradients are unchanged.  None: no launch.
+        ``accum``: the fp64 [4] device block of a gradient-accumulation cycle (``ops.accum_add``; ``TrainStep(accumulate=N)``).  The
+        head's [sum of losses, count] — after ``ohem=``, that of the relabelled call — is added to the block, the returned value is
+        this batch's usual loss, and the backward writes the gradient of the SUM of the pixel losses whatever ``reduction`` says:
+        the update that closes the cycle divides by the block's count.  Not combinable with ``dice=``.  None: no launch."""
+        if accum is not None and dice is not None:
+            raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
@@ -314,7 +324,9 @@ class BaseModelWithText(HipModule):
             ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts)
+        if accum is None:   # (the call as it was: no new argument reaches the head)
+            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum)
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:

@@ -60,7 +60,8 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None, seg_counts=None):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None, seg_counts=None,
+                accum=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -89,14 +90,20 @@ class _ScoreFn(torch.autograd.Function):
                                                  want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
                                                  class_weight=weight, label_smoothing=label_smoothing)
             loss, inv = _reduce(loss2, reduction, save)
-            if inv is not None:
+            if accum is not None:   # accumulation cycle: dlo stays the gradient of the SUM, the cycle's update divides
+                ops.accum_add(accum, loss2)
+            elif inv is not None:
                 dlo.mul_(inv)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
             return loss
         n = float(B * h * scale * h * scale)
         loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
                                              want_grad=save, ignore_index=ignore_index, grad_scale=1.0 / n)
-        if save:   # mean over the pixels the kernel counted (negative / ignore_index / out-of-range labels are skipped)
+        if accum is not None:   # accumulation cycle: undo the kernel's 1/n, dlo is the gradient of the SUM; the update divides
+            ops.accum_add(accum, loss2)
+            if save:
+                dlo.mul_(n)
+        elif save:   # mean over the pixels the kernel counted (negative / ignore_index / out-of-range labels are skipped)
             dlo.mul_(n / loss2[1].clamp_min(1.0))
         ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
         return loss2[0] / loss2[1]
@@ -110,7 +117,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None, None, None, None, None
+        return dv, dt, None, None, None, None, None, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -128,14 +135,18 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None, dice=None, seg_counts=None) -> torch.Tensor:
+             ohem=None, dice=None, seg_counts=None, accum=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
         the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
         dice_weight * soft Dice over the batch (DiceCrossEntropyLoss's definition), not combinable with the other options;
         ``self.last_dice`` then holds the device tensors (I, P, T, loss block).  ``seg_counts``: an int64 [3, K] device tensor that
         takes ``+= counts.sum(0)`` of this batch ({intersection, predicted, labelled} of the argmax of the same upsampled scores
-        against ``labels`` as given, over the pixels the loss counts; ``BaseModelWithText.forward_loss`` has the details)."""
+        against ``labels`` as given, over the pixels the loss counts; ``BaseModelWithText.forward_loss`` has the details).
+        ``accum``: the device block of a gradient-accumulation cycle (``ops.accum_add``): the head's [sum of losses, count] joins it,
+        the backward leaves the gradient of the SUM of the pixel losses; not combinable with ``dice=``."""
+        if accum is not None and dice is not None:
+            raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
@@ -144,8 +155,11 @@ class ScoreMapTail(nn.Module):
             ops.check_seg_counts(seg_counts, text_embeddings.shape[1])
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
+        if accum is None:
+            return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
+                                  dice, seg_counts)
         return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self, dice,
-                              seg_counts)
+                              seg_counts, accum)
 
     @torch.no_grad()
     def predict(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor) -> torch.Tensor:

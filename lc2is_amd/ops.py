@@ -62,6 +62,8 @@ _ARGTYPES = {
     "lc2is_grad_sumsq_workspace_bytes": [_Z],
     "lc2is_grad_sumsq": [_P, _Z, _P, _Z, _P],
     "lc2is_optim_ctrl_update": [_P, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P],
+    "lc2is_accum_add": [_P, _P, _P],
+    "lc2is_optim_ctrl_update_accum": [_P, _P, _I, _P, _P, _I, _P, _I, _F, _F, _I, _F, _F, _P],
     "lc2is_sgd_step_ctrl": [_P, _P, _P, _Z, _P, _F, _F, _I, _P],
     "lc2is_adamw_step_ctrl": [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _I, _P],
     "lc2is_sgd_step_groups": [_P, _P, _P, _Z, _P, _P, _P, _I, _F, _I, _P],
@@ -783,6 +785,50 @@ def optim_ctrl_update(ctrl, partials, flags, lr_table, *, grad_scale=1.0, max_no
     _lib.check(_fn("lc2is_optim_ctrl_update")(_ptr(ctrl), _ptr(partials), _ptr(flags), partials.numel(), _ptr(lr_table),
                                               lr_table.numel(), grad_scale, max_norm, int(bool(skip_nonfinite)), beta1, beta2,
                                               _stream()), "optim_ctrl_update")
+
+
+# ---- gradient accumulation: the lc2is_accum_block as an fp64 [4] tensor (32 bytes; ints and floats through .view) ----
+ACCUM_BLOCK_BYTES = 32
+ACCUM_LOSS_SUM, ACCUM_DENOM = 0, 1          # fp64 words
+ACCUM_MICRO = 4                             # int32 word
+ACCUM_LAST_LOSS, ACCUM_LAST_DENOM = 6, 7    # fp32 words
+
+
+def _chk_accum(block):
+    _chk(block, torch.float64, "accum block", 1)
+    if block.numel() * 8 != ACCUM_BLOCK_BYTES or block.data_ptr() % 8:
+        raise RuntimeError(f"lc2is_amd: the accumulation block must be an 8-byte aligned fp64 [{ACCUM_BLOCK_BYTES // 8}] tensor "
+                           "(lc2is_accum_block)")
+
+
+def accum_add(block, loss2):
+    """One micro-batch joins an accumulation cycle: ``block`` (fp64 [4], lc2is_accum_block) takes ``loss_sum += loss2[0]``,
+    ``denom += loss2[1]``, ``micro += 1`` in fp64 on the device.  ``loss2``: the fp32 [2] the fused head returns."""
+    if block is None or loss2 is None:
+        raise RuntimeError("lc2is_amd.accum_add: block and loss2 are required")
+    _chk_accum(block); _chk(loss2, torch.float32, "loss2", 1)
+    if loss2.numel() != 2 or loss2.device != block.device:
+        raise RuntimeError("lc2is_amd.accum_add: loss2 must be the head's fp32 [2] (sum of losses, count) on the block's device")
+    _lib.check(_fn("lc2is_accum_add")(_ptr(block), _ptr(loss2), _stream()), "accum_add")
+
+
+def optim_ctrl_update_accum(ctrl, block, use_denom, partials, flags, lr_table, *, grad_scale=1.0, max_norm=float("inf"),
+                            skip_nonfinite=False, beta1=0.0, beta2=0.0):
+    """optim_ctrl_update for the call that closes an accumulation cycle: the gradient scale is ``grad_scale / block.denom`` (formed
+    in fp64; 1 in place of a zero denominator, ``grad_scale`` alone with ``use_denom=False``), and the block then holds the cycle's
+    mean loss and count in its ``last_*`` words and zeroed sums."""
+    if block is None:
+        raise RuntimeError("lc2is_amd.optim_ctrl_update_accum: block is required")
+    _chk_ctrl(ctrl); _chk_accum(block); _chk(partials, torch.float32, "partials", 1); _chk(flags, torch.int32, "flags", 1)
+    _chk(lr_table, torch.float32, "lr_table", 1)
+    if flags.numel() != partials.numel() or not partials.is_contiguous() or not flags.is_contiguous():
+        raise RuntimeError("lc2is_amd.optim_ctrl_update_accum: partials and flags must be contiguous and of one length")
+    if lr_table.numel() < 1 or not lr_table.is_contiguous():
+        raise RuntimeError("lc2is_amd.optim_ctrl_update_accum: lr_table must be a non-empty contiguous fp32 tensor")
+    _lib.check(_fn("lc2is_optim_ctrl_update_accum")(_ptr(ctrl), _ptr(block), int(bool(use_denom)), _ptr(partials), _ptr(flags),
+                                                    partials.numel(), _ptr(lr_table), lr_table.numel(), grad_scale, max_norm,
+                                                    int(bool(skip_nonfinite)), beta1, beta2, _stream()),
+               "optim_ctrl_update_accum")
 
 
 def sgd_step_ctrl(params, grads, momentum_buf, ctrl, momentum=0.0, weight_decay=0.0, reverse=False):

@@ -36,6 +36,9 @@ schedule — and AdamW's ``t`` — across replays.
 launch after the optimizer's that follows the control block (a skipped step leaves it alone; it is captured with the step);
 ``ema_weights()`` evaluates with it by exchanging the two buffers in place.  ``state_dict()`` / ``load_state_dict()`` hold
 everything a step reads besides the model and the batch, so a stopped run continues bit for bit (``checkpoint.save_train_state``).
+
+``accumulate=N`` (device-held path too) makes N calls one optimizer update with the exact large-batch mean: the reference calls
+``optimizer.step()`` after every batch (engine.py:89-101) and has no counterpart; the cycle's denominator lives on the device.
 """
 from __future__ import annotations
 
@@ -70,6 +73,12 @@ def _accepts_seg_counts(model) -> bool:
     import inspect
     fl = getattr(model, "forward_loss", None)
     return fl is not None and "seg_counts" in inspect.signature(fl).parameters
+
+
+def _accepts_accum(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "accum" in inspect.signature(fl).parameters
 
 
 def _n_classes(model) -> int | None:
@@ -342,16 +351,47 @@ class TrainStep:
     model's ``class_prototypes`` row count, or ``seg_classes=`` for a model that takes its classes from the batch (PromptFTN).  The
     buffer exists before ``capture``; the captured launches keep adding into it across replays, and reading or resetting happens
     outside the graph (the warm-up steps of ``capture`` are real steps and count).  The counts are this rank's own (no collective)
-    and are not part of ``state_dict`` / ``save_train_state``: a resumed run starts its counters at zero."""
+    and are not part of ``state_dict`` / ``save_train_state``: a resumed run starts its counters at zero.
+
+    ``accumulate=N`` (keyword-only; ``None`` or 1 is the plain step, bit for bit; N >= 2 selects the device-held path): N calls of
+    ``step()`` are one CYCLE and one optimizer update with the gradient of the concatenated batch — (sum of the pixel losses of all
+    N micro-batches) / (count of all their non-ignored pixels), not the mean of the micro-batch means, which would weight the pixels
+    of sparsely labelled crops more heavily.  Calls 1..N-1 run forward and backward only (every gradient writer adds into the arena;
+    the head leaves the gradient of the SUM); call N also takes the norm, advances the lr table and AdamW's t, clips, decides the
+    non-finite skip, updates, runs the EMA launch and invalidates the bf16 shadows — all once per update.  The denominator is held
+    on the device in fp64 across the cycle (``ops.accum_add``) and folded into the gradient scale by ``ops.optim_ctrl_update_accum``:
+    no host sync.  It is the weighted count under class weights / label smoothing, the kept count under OHEM (selected per
+    micro-batch), absent with ``reduction='sum'``; a cycle whose every pixel is ignored applies zero gradients at scale 1 and
+    reports a NaN loss.  ``step()`` returns the micro-batch's own loss; ``ts.accum_loss`` / ``ts.accum_count`` are the last
+    completed cycle's mean loss and denominator (device tensors), ``ts.micro`` the calls so far in the open cycle (host int),
+    ``ts.flush()`` applies the update with the micro-batches seen so far.  ``last_grad_norm`` and the clip are those of the
+    mean-scale gradient.  ``state_dict()`` / ``save_train_state`` raise while a cycle is open; the saved state does not depend on N.
+    A ``DiceCrossEntropyLoss`` is refused (its batch statistics do not add).  Under a ``GradReducer`` calls 1..N-1 issue no
+    collective, call N reduces under its backward and also sums the two fp64 sums over the ranks: for 'mean' the scale is
+    1 / (sum over ranks and micro-batches of the count) with no extra 1/world — the GLOBAL-batch mean, which differs from the
+    N = 1 behaviour (the mean of the ranks' means) when the ranks' counts differ; 'sum' keeps the 1/world of N = 1.  ``capture``
+    then takes sequences of N inputs and N labels and records the whole cycle as one graph."""
 
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
                  ignore_index: int | None = None, criterion: nn.Module | None = None, lr_schedule=None,
                  schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
                  device_state: bool = False, param_groups=None, ema_decay: float | None = None, ema_warmup: bool = False,
-                 ema_every: int = 1, seg_metrics: bool = False, seg_classes: int | None = None) -> None:
+                 ema_every: int = 1, seg_metrics: bool = False, seg_classes: int | None = None,
+                 accumulate: int | None = None) -> None:
         # (argument checks first: nothing is built or allocated for a step that cannot run)
         _check_ema_args(ema_decay, ema_warmup, ema_every)
+        if accumulate is not None and (isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1):
+            raise ValueError(f"TrainStep: accumulate must be None or an integer >= 1, got {accumulate!r}")
+        accum_n = None if accumulate in (None, 1) else int(accumulate)   # None: today's step, no new launch, no new keyword
+        if accum_n is not None:
+            from .nn.loss import DiceCrossEntropyLoss as _Dice
+            if isinstance(criterion, _Dice):
+                raise ValueError("TrainStep: a DiceCrossEntropyLoss cannot be trained with accumulate >= 2: its batch statistics "
+                                 "do not add across micro-batches")
+            if not _accepts_accum(model):
+                raise TypeError("TrainStep: accumulate >= 2 needs a model whose forward_loss takes accum= "
+                                "(BaseModelWithText, PromptFTN)")
         if not isinstance(seg_metrics, bool):
             raise TypeError(f"TrainStep: seg_metrics must be a bool, got {seg_metrics!r}")
         n_seg = None
@@ -366,7 +406,7 @@ class TrainStep:
         elif seg_classes is not None:
             raise ValueError("TrainStep: seg_classes is only meaningful with seg_metrics=True")
         device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None
-                           or param_groups is not None or ema_decay is not None)
+                           or param_groups is not None or ema_decay is not None or accum_n is not None)
         groups = None
         if param_groups is not None:
             groups, group_of = _resolve_param_groups(model, param_groups, weight_decay)
@@ -439,6 +479,13 @@ class TrainStep:
             self.ema = self.arena.flat.clone()
         # accuracy / IoU counts of the training batches: None = forward_loss is called as before, no launch is added
         self._seg_counts = torch.zeros((3, n_seg), dtype=torch.int64, device=dev) if seg_metrics else None
+        # gradient accumulation: the cycle's fp64 loss sum and denominator in a device block (lc2is_accum_block); None = no launch
+        self._accum_n, self.micro, self._accum = accum_n, 0, None
+        if accum_n is not None:
+            self._accum = torch.zeros(ops.ACCUM_BLOCK_BYTES // 8, dtype=torch.float64, device=dev)
+            self._accum_f = self._accum.view(torch.float32)
+            reduction = "mean" if criterion is None else criterion.reduction
+            self._accum_use_denom = reduction != "sum"
 
     # -- views of the control block: device tensors, no sync unless the caller asks (.item()) --------------------------------
     def _ctrl_view(self, word: int, as_float: bool) -> torch.Tensor:
@@ -511,6 +558,24 @@ class TrainStep:
         if reset:
             counts.zero_()
         return out
+
+    def _need_accum(self, what: str) -> None:
+        if self._accum is None:
+            raise RuntimeError(f"TrainStep.{what}: this TrainStep does not accumulate (accumulate=None or 1)")
+
+    @property
+    def accum_loss(self) -> torch.Tensor:
+        """The last completed cycle's loss on the device: (sum of the pixel losses of all its micro-batches) / ``accum_count`` —
+        the concatenated batch's mean, NaN when every pixel was ignored; with ``reduction='sum'`` the sum."""
+        self._need_accum("accum_loss")
+        return self._accum_f[ops.ACCUM_LAST_LOSS]
+
+    @property
+    def accum_count(self) -> torch.Tensor:
+        """The last completed cycle's denominator (device fp32): the count of its non-ignored pixels — the weighted count under
+        class weights, the kept count under OHEM, summed over the ranks under a reducer."""
+        self._need_accum("accum_count")
+        return self._accum_f[ops.ACCUM_LAST_DENOM]
 
     @property
     def param_groups(self):
@@ -603,6 +668,9 @@ class TrainStep:
         strings, lists and dicts only: the file loads with ``torch.load(weights_only=True)``."""
         if self._ema_swapped:
             raise RuntimeError("TrainStep.state_dict: not inside ema_weights()")
+        if self.micro != 0:
+            raise RuntimeError(f"TrainStep.state_dict: an accumulation cycle is open ({self.micro} of {self._accum_n} micro-batches); "
+                               "a checkpoint is taken at an update boundary (finish the cycle or flush())")
         sd = {"format": 1, "meta": self._state_meta(), "t": int(self.t)}
         for k, b in self._state_buffers().items():
             sd[k] = b.detach().to("cpu", copy=True)
@@ -617,6 +685,9 @@ class TrainStep:
         copy IN PLACE into the existing device buffers: no pointer changes, a step captured before the load stays valid."""
         if self._ema_swapped:
             raise RuntimeError("TrainStep.load_state_dict: not inside ema_weights()")
+        if self.micro != 0:
+            raise RuntimeError("TrainStep.load_state_dict: an accumulation cycle is open; a state is loaded at an update boundary "
+                               "(finish the cycle or flush())")
         if not isinstance(sd, dict) or "meta" not in sd or "t" not in sd:
             raise ValueError("TrainStep.load_state_dict: not a TrainStep.state_dict()")
         check_train_state(sd["meta"], self._state_meta())
@@ -633,10 +704,19 @@ class TrainStep:
         if self._ema_swapped:
             raise RuntimeError("TrainStep.step: inside ema_weights() the parameters are the EMA; leave the block before training")
         arena = self.arena
-        arena.zero_grad(set_to_none=True)
+        # accumulate=N: N calls are one cycle.  The first overwrites the gradients, the later ones find p.grad set, so every writer
+        # accumulates; only the last finalizes, reduces, updates and invalidates the shadows.
+        last = self._accum_n is None or self.micro + 1 == self._accum_n
+        if self.micro == 0:
+            arena.zero_grad(set_to_none=True)
         if self.reducer is not None:
-            self.reducer.begin_step()
+            if self._accum_n is None:
+                self.reducer.begin_step()
+            else:
+                self.reducer.begin_step(sync=last)
         seg = {} if self._seg_counts is None else {"seg_counts": self._seg_counts}   # (no keyword at all without seg_metrics)
+        if self._accum is not None:
+            seg["accum"] = self._accum
         if self._ohem:   # hard-pixel selection in front of the fused head, while the criterion is in training mode (as its forward)
             c = self.criterion
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
@@ -655,12 +735,36 @@ class TrainStep:
         else:
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, **seg)
         loss.backward()
+        if not last:   # inside a cycle: nothing but the gradient arena, the accumulation block and the metric counts has moved
+            self.micro += 1
+            return loss.detach()
+        self._apply_update()
+        return loss.detach()
+
+    def flush(self) -> None:
+        """Apply the update with the micro-batches seen so far (a ragged end of an epoch): the denominator is that of those
+        micro-batches, so the update is the exact mean over them.  Does nothing when no cycle is open (``micro == 0``).  Under a
+        reducer every rank calls it at the same point: the arena is reduced here, no collective ran under a backward."""
+        if self.micro == 0:
+            return
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.flush: inside ema_weights() the parameters are the EMA; leave the block before training")
+        self._apply_update()
+
+    def _apply_update(self) -> None:
+        """Everything that happens once per optimizer update: finalize, reduce, norm, control block, optimizer, EMA, shadows."""
+        arena = self.arena
         live = arena.finalize_grads()
         gscale = 1.0
         if self.reducer is not None:
+            if self._accum is not None:   # the two fp64 sums travel with the gradients: every rank divides by the global count
+                self.reducer.reduce_block(self._accum[:2])
             self.reducer.finish_step()
-            gscale = 1.0 / self.reducer.world_size
+            # 'mean' under accumulation: 1 / (sum over ranks and micro-batches of the count) is the whole scale, no extra 1/world
+            if self._accum is None or not self._accum_use_denom:
+                gscale = 1.0 / self.reducer.world_size
         self.t += 1
+        self.micro = 0
         # One fused launch over the whole arena; a zero gradient leaves a parameter untouched unless weight decay is on —
         # then, like torch.optim (which skips parameters whose grad is None), only the live segments are updated so that
         # frozen / unreached parameters stay bit-identical.
@@ -673,8 +777,13 @@ class TrainStep:
             ctrl = self._ctrl
             b1, b2 = self.betas if self.kind == "adamw" else (0.0, 0.0)
             partials, flags = ops.grad_sumsq(arena.grad)
-            ops.optim_ctrl_update(ctrl, partials, flags, self.lr_table, grad_scale=gscale, max_norm=self.max_grad_norm,
-                                  skip_nonfinite=self.skip_nonfinite, beta1=b1, beta2=b2)
+            if self._accum is None:
+                ops.optim_ctrl_update(ctrl, partials, flags, self.lr_table, grad_scale=gscale, max_norm=self.max_grad_norm,
+                                      skip_nonfinite=self.skip_nonfinite, beta1=b1, beta2=b2)
+            else:   # the arena holds the cycle's SUM: the scale becomes gscale / (the cycle's denominator), in fp64 on the device
+                ops.optim_ctrl_update_accum(ctrl, self._accum, self._accum_use_denom, partials, flags, self.lr_table,
+                                            grad_scale=gscale, max_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite,
+                                            beta1=b1, beta2=b2)
             if self._groups is not None:
                 # one launch over the whole arena: parameters without a gradient carry the skip id in the map
                 gmap = arena.group_map()
@@ -707,7 +816,6 @@ class TrainStep:
                                 reverse=self.ema_reverse_walk)
         for m in self._hip_modules:
             m.invalidate_shadows()
-        return loss.detach()
 
     # -- HIP graph replay ------------------------------------------------------------------------------------
     def capture(self, inputs: dict, labels: torch.Tensor, warmup: int = 2):
@@ -718,7 +826,19 @@ class TrainStep:
         is only recorded.
         On the device-held path the learning-rate table index, AdamW's t and the skip counters are device state that the
         captured kernels advance: a schedule moves across replays and AdamW can be captured; so is the EMA launch.
-        Single-process only (the RCCL reduction is not captured)."""
+        Single-process only (the RCCL reduction is not captured).
+        With ``accumulate=N`` both arguments are sequences of N batches: the whole cycle (N forward / backward passes and the one
+        update) is recorded as ONE graph over N static copies, a warm-up step is a whole cycle, and ``replay`` takes the same two
+        sequences and returns the tuple of the N micro-batch losses."""
+        n_micro = self._accum_n or 1
+        if self._accum_n is not None:
+            if isinstance(inputs, dict) or isinstance(labels, torch.Tensor) or len(inputs) != n_micro or len(labels) != n_micro:
+                raise ValueError(f"TrainStep.capture: with accumulate={n_micro} give sequences of {n_micro} inputs and {n_micro} labels")
+            if self.micro != 0:
+                raise RuntimeError("TrainStep.capture: an accumulation cycle is open; finish it or flush() first")
+            many_in, many_lb = list(inputs), list(labels)
+        else:
+            many_in, many_lb = [inputs], [labels]
         if self.reducer is not None:
             raise RuntimeError("TrainStep.capture: graph capture is only wired for single-GPU steps")
         if self._ema_swapped:
@@ -729,13 +849,18 @@ class TrainStep:
             self.model.overlap_text = False   # LC2IS_GRAPH_OVERLAP=0: one captured stream (default: the text-tower fork / join is captured too)
         from .nn.base import DropoutRng
         DropoutRng.last.clear()
-        static_in = {k: v.clone() for k, v in inputs.items()}
-        static_lb = labels.clone()
+        static_ins = [{k: v.clone() for k, v in d.items()} for d in many_in]
+        static_lbs = [lb.clone() for lb in many_lb]
+        static_in, static_lb = static_ins[0], static_lbs[0]
+
+        def cycle():
+            return [self.step(d, lb) for d, lb in zip(static_ins, static_lbs)]
+
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):   # warm-up on the capture stream: lazy inits, workspaces, attributes
             for _ in range(warmup):
-                self.step(static_in, static_lb)
+                cycle()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if DropoutRng.last:   # dropout seeds are kernel ARGUMENTS drawn on the host: a replay would repeat one step's masks
@@ -748,19 +873,28 @@ class TrainStep:
         t_before = self.t
         mark0 = ops.captured_tables_mark()
         with torch.cuda.graph(graph, stream=side):
-            static_loss = self.step(static_in, static_lb)
+            static_losses = cycle()
+        static_loss = static_losses[0] if self._accum_n is None else tuple(static_losses)
         mark1 = ops.captured_tables_mark()   # the pinned descriptor-table images registered in between belong to this graph
         self.t = t_before   # capture records the step; nothing ran
 
-        def replay(new_inputs: dict, new_labels: torch.Tensor) -> torch.Tensor:
+        def replay(new_inputs, new_labels):
             if self._ema_swapped:
                 raise RuntimeError("TrainStep replay: inside ema_weights() the parameters are the EMA; leave the block before "
                                    "training")
-            for k, v in new_inputs.items():
-                if v is not static_in[k]:
-                    static_in[k].copy_(v, non_blocking=True)
-            if new_labels is not static_lb:
-                static_lb.copy_(new_labels, non_blocking=True)
+            if self._accum_n is None:
+                new_inputs, new_labels = [new_inputs], [new_labels]
+            elif isinstance(new_inputs, dict) or len(new_inputs) != n_micro or len(new_labels) != n_micro:
+                raise ValueError(f"TrainStep replay: the captured cycle takes sequences of {n_micro} inputs and {n_micro} labels")
+            elif self.micro != 0:
+                raise RuntimeError("TrainStep replay: an eager accumulation cycle is open; finish it or flush() first")
+            for dst, src in zip(static_ins, new_inputs):
+                for k, v in src.items():
+                    if v is not dst[k]:
+                        dst[k].copy_(v, non_blocking=True)
+            for dst, src in zip(static_lbs, new_labels):
+                if src is not dst:
+                    dst.copy_(src, non_blocking=True)
             graph.replay()
             self.t += 1
             return static_loss
@@ -779,6 +913,8 @@ class TrainStep:
             if getattr(self, "_captured", None) is replay:
                 self._captured = None
 
-        replay.static_inputs, replay.static_labels, replay.graph, replay.release = static_in, static_lb, graph, release
+        replay.static_inputs = static_in if self._accum_n is None else static_ins
+        replay.static_labels = static_lb if self._accum_n is None else static_lbs
+        replay.graph, replay.release = graph, release
         self._captured = replay
         return replay
