@@ -873,6 +873,40 @@ int lc2is_head_upsample_argmax(const float* scores_lo, int ld, const int64_t* la
                                int w, int C, int S, int mode, long ignore_index, void* workspace, size_t workspace_bytes,
                                lc2is_stream_t stream);
 
+/* ---- focal and poly-1 cross-entropy (the focusing per-pixel losses) ----------------------------------------------------------
+ * For a counted pixel i (label != ignore_index && 0 <= label < C: the rule of the CE head) with label y, p = softmax of its class
+ * scores, q = 1 - p_y, ce = -ln p_y and class weight w_y (class_weight: device fp32 [C], the per-class alpha, or NULL = ones):
+ *   l_i      = w_y (q^gamma ce + poly_eps q)                                 gamma = 0, poly_eps = 0: the weighted CE
+ *   dl_i/dz_j = w_y c (p_j - [j == y]),   c = q^gamma + gamma p_y q^(gamma-1) ce + poly_eps p_y
+ * gamma in [0, inf), poly_eps in [-1, inf), both finite (else LC2IS_ERR_SHAPE).  q is formed from the other classes' exponentials,
+ * not as 1 - p_y; q == 0 gives q^gamma = [gamma == 0] and a zero q^(gamma-1) ce term, p_y == 0 a finite ce: nothing is Inf or NaN.
+ * loss_sum[0] = sum_i l_i, loss_sum[1] = sum_i w_y (the denominator of this project's mean, as lc2is_head_upsample_ce_opts; kornia
+ * and MONAI divide by the number of pixels instead).
+ * replaces: kornia.losses.FocalLoss / monai.losses.FocalLoss(use_softmax=True) / mmseg's FocalLoss on softmax logits, and PolyLoss's
+ *   Poly1CrossEntropyLoss, composed from torch ops on model(inputs)["outputs"] (engine.py:94), plus their autograd.
+ *
+ * lc2is_head_upsample_focal: on the fused head of lc2is_head_upsample_ce (scores_lo fp32 [B,h,w,ld] channels-last, 16-byte aligned,
+ * C <= ld <= 192, ld % 64 == 0, else LC2IS_ERR_SHAPE; S in {4, 8, 16} and a known mode, else LC2IS_ERR_UNSUPPORTED), one forward +
+ * backward launch and the fixed-order finish launch.  dscores_lo (NULL: loss only) = grad_scale * U^T (sum_i dl_i/dz), all ld
+ * channels overwritten.  workspace: 16-byte aligned, >= lc2is_head_upsample_ce_workspace_bytes(B, h, w, C, S, mode, dscores_lo !=
+ * NULL) (else LC2IS_ERR_WORKSPACE).  Refusals in the order NULL, SHAPE, UNSUPPORTED, WORKSPACE.  NO read-modify-write atomics, LDS
+ * included: the same bytes every run; captures into a graph. */
+int lc2is_head_upsample_focal(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo, float* loss_sum, int B,
+                              int h, int w, int C, int S, int mode, long ignore_index, float grad_scale,
+                              const float* class_weight, float gamma, float poly_eps, void* workspace, size_t workspace_bytes,
+                              lc2is_stream_t stream);
+/* The same loss on materialised NCHW fp32 logits [B,C,HW] (the drop-in criterion).  _fwd: lse fp32 [B,HW] (or NULL), loss_sum[2]
+ * overwritten through ordered block partials (workspace >= lc2is_ce_nchw_fwd_workspace_bytes(B, HW)), loss_px (optional, [B,HW]) =
+ * l_i, 0 where not counted.  _bwd: dlogits = grad_scale * (*grad_scale_dev, NULL = 1) * grad_px[i] (NULL = 1) * dl_i/dlogits from
+ * _fwd's lse; every element is written.
+ * replaces: the same criteria on model(inputs)["outputs"] with reduction 'mean' / 'sum' / 'none', plus their autograd. */
+int lc2is_focal_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px, int B, int C,
+                         long HW, long ignore_index, const float* class_weight, float gamma, float poly_eps, void* workspace,
+                         size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_focal_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_scale_dev,
+                         float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW, long ignore_index,
+                         const float* class_weight, float gamma, float poly_eps, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@
 //    S x S-pixel groups in units of 16 pixels as two small products on the fp32 matrix pipe, softmax in the accumulator layout,
 //    waves taking turns to add their gradient tiles to the LDS mirror (no LDS atomics: they retire about one lane per three
 //    cycles per CU and were 90 % of the first S = 4 kernel).
+//    Its siblings on the same tiles: head_px_grp_kernel (per-pixel loss, forward only), head_focal_grp_kernel (focal / poly-1 CE,
+//    forward + backward), head_dice_stats_grp_kernel / head_ce_dice_grp_kernel (Dice + CE).
 //  * other S (multiples of 16 from 32): head_ce_kernel — each wave walks 64 output pixels with the 64 lanes spread over CHANNELS (3 per lane, C <= 192),
 //    wave reductions for the softmax, ds_add_f32 for the gradient scatter.
 #include "common.h"
@@ -624,6 +626,241 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_px_grp_ke
         for (int r = 0; r < 4; ++r)
           if (lab4[r] != -2) o[r] = out[r];
       }
+    }
+  }
+}
+
+// ---- focal / poly-1 cross-entropy on the same head, forward and backward in one pass ----
+// For a counted pixel with label y, p = softmax, p_y its label probability, q = 1 - p_y, ce = -ln p_y, class weight w_y:
+//   l      = w_y (q^gamma ce + eps1 q)                    gamma >= 0 (focal, Lin et al.), eps1 >= -1 (poly-1, Leng et al.)
+//   dl/dz_j = w_y c (p_j - [j == y]),   c = q^gamma + gamma p_y q^(gamma-1) ce + eps1 p_y
+// Both are functions of p_y alone, so the gradient is the CE gradient times one scalar per pixel: head_ce_grp_kernel's tiles, forward
+// product, softmax in the accumulator layout, transposed gradient tiles, turns on the LDS mirror, slab and partials, and
+// head_finish_kernel behind it; count = w_y as in the OPT kernel.  What differs:
+//  * the loss does not split into -z_y and lse, so the label's logit meets the log-sum-exp in one lane: the accumulator element of
+//    tile t in the lane with dl[r] == 16 t, one 16-lane row sum (head_px_grp_kernel's way);
+//  * q = (sum of the OTHER classes' exponentials) / sum — 1 - e_y / sum and sum - e_y cancel when the label holds the maximum.  The
+//    exp loop adds every class but the label's to `so`; e_y is formed once per pixel from the row-summed logit (the same bits);
+//  * ce = (max - z_y) + ln(sum) is finite at p_y = 0; below q = 1/64 it is the series of -ln(1 - q), whose relative error stays
+//    at fp32 rounding where ln(1 + so) has lost the small term (gamma < 1 divides ce by q);
+//  * q^gamma = exp2(gamma log2 q), [gamma == 0] at q == 0; the q^(gamma-1) ce term is formed as q^gamma (ce / q), ce / q -> 1: no
+//    Inf or NaN for any gamma >= 0.  A few exp2 / log2 per PIXEL; c enters inv[r] and the label's own coefficient;
+//  * the label's gradient element is -c w_y q from `so`, not p_y - 1: the per-class loop is one multiply and one select.
+// gamma = eps1 = 0 is the OPT kernel's weighted CE to rounding.  A kernel of its own, its two scalars in an argument of their own:
+// HeadArgs and the instantiations of head_ce_grp_kernel / head_px_grp_kernel compile to what they were.
+struct FocalArgs { float gamma, poly_eps; };
+
+// one pixel's focal terms from its label probability pl, q = 1 - pl (formed without cancellation) and ce_big = lse - z_y:
+// returns c, *loss = q^gamma ce + eps1 q
+__device__ __forceinline__ float focal_coef(float pl, float q, float ce_big, FocalArgs f, float* loss) {
+  const bool small = q < 0.015625f;
+  const float ser = 1.f + q * (0.5f + q * ((1.f / 3.f) + q * (0.25f + q * 0.2f)));   // -ln(1 - q) / q, q < 1/64: error < q^5 / 6
+  const float cq = small ? ser : ce_big / q;   // ce / q (the division is taken only where q >= 1/64)
+  const float ce = small ? q * ser : ce_big;
+  float qg = 1.f;                                // q^gamma
+  if (f.gamma != 0.f) qg = q > 0.f ? __builtin_amdgcn_exp2f(f.gamma * __builtin_amdgcn_logf(q)) : 0.f;
+  *loss = qg * ce + f.poly_eps * q;
+  return qg + f.gamma * pl * (qg * cq) + f.poly_eps * pl;
+}
+
+template <int MODE, int TN, int S>
+__global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_focal_grp_kernel(HeadArgs p, FocalArgs f) {
+  constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;
+  constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;
+  constexpr int G = HT / S;
+  constexpr int F4 = G + NT - 1;
+  constexpr int NQ = NT * NT / 4;
+  constexpr int UPG = S * S / 16;
+  constexpr bool SUMD = UPG > 1;
+  static_assert(S == 4 || S == 8 || S == 16, "group kernel: S x S pixel groups inside a 16 x 16 tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles_x = (p.W + S / 2 + HT - 1) / HT, tiles_y = (p.H + S / 2 + HT - 1) / HT;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int tyi = (blockIdx.x / tiles_x) % tiles_y, txi = blockIdx.x % tiles_x;
+  const int a0 = G * tyi - 1, b0 = G * txi - 1;
+  const int Y0 = S * a0 + S / 2, X0 = S * b0 + S / 2;
+  const int Cp = p.ld;
+  const int CS = Cp + HEAD_PAD;
+  float* s_lo = (float*)smem;
+  float* s_dlo = s_lo + F4 * F4 * CS;
+  int* s_lab = (int*)(s_dlo + F4 * F4 * CS);     // [16][16] pixels of the tile: -2 outside the image, -1 not counted, else label
+  float* s_w = (float*)(s_lab + HT * HT);        // [CMAX] class weights (ones without), zero past C
+  const int fsize = F4 * F4 * Cp;
+  for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
+    const int cell = i / Cp, c = i % Cp;
+    int ry = a0 - OFF + cell / F4, rx = b0 - OFF + cell % F4;
+    ry = ry < 0 ? 0 : (ry > p.h - 1 ? p.h - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > p.w - 1 ? p.w - 1 : rx);
+    *reinterpret_cast<float4*>(s_lo + cell * CS + c) =
+        *reinterpret_cast<const float4*>(p.lo + (((size_t)b * p.h + ry) * p.w + rx) * p.ld + c);
+    if (p.dlo) *reinterpret_cast<float4*>(s_dlo + cell * CS + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (tid < HT * HT) {
+    const int Y = Y0 + (tid >> 4), X = X0 + (tid & 15);
+    int code = -2;
+    if (Y >= 0 && X >= 0 && Y < p.H && X < p.W) {
+      code = -1;
+      const int64_t lab64 = p.labels[((size_t)b * p.H + Y) * p.W + X];
+      if (lab64 != (int64_t)p.ignore_index && lab64 >= 0 && lab64 < p.C) code = (int)lab64;
+    }
+    s_lab[tid] = code;
+  }
+  if (tid < CMAX) s_w[tid] = tid < p.C ? (p.cw ? p.cw[tid] : 1.f) : 0.f;
+  __syncthreads();
+
+  const int m = lane & 15, kq = lane >> 4;
+  const float NEG = -__builtin_inff();
+  constexpr float LOG2E = 1.4426950408889634f;
+  const int cellm_off = ((m / NT) * F4 + m % NT) * CS + 4 * kq;
+  int cell_off[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
+  float Af[NQ], Bb[4];
+  auto make_operands = [&](int prow) {
+    const int py_m = prow + m / S, px_m = m % S;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + kq) / NT) * tap_w<MODE, S>(px_m, (4 * q + kq) % NT);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int n = 4 * kq + jj;
+      Bb[jj] = (m < NT * NT) ? tap_w<MODE, S>(prow + n / S, m / NT) * tap_w<MODE, S>(n % S, m % NT) : 0.f;
+    }
+  };
+  if constexpr (!SUMD) make_operands(0);
+  float loss_acc = 0.f, cnt_acc = 0.f;
+  f32x4_t dsum[SUMD ? TN : 1];
+  if constexpr (SUMD) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) dsum[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  bool have_d = false;
+  int gbase = 0;
+
+#pragma unroll 1
+  for (int g2 = 0; g2 < 2; ++g2) {
+    const int u = 2 * wid + g2, gi = u / UPG, rt = u % UPG, gy = gi / G, gx = gi % G;
+    const int Yb = Y0 + S * gy, Xb = X0 + S * gx;
+    const int prow = rt * (16 / S);
+    const bool active = !(Yb + prow >= p.H || Xb >= p.W || Yb + prow + 16 / S - 1 < 0 || Xb + S - 1 < 0);  // wave-uniform
+    gbase = (gy * F4 + gx) * CS;
+    f32x4_t acc[TN];   // logits, then exp, then (S = 4: in place) the transposed gradient tiles
+    if constexpr (!SUMD) have_d = false;
+    if (active) {
+      if constexpr (SUMD) make_operands(prow);
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float* bp = s_lo + gbase + cell_off[q] + m;
+        float bv[TN];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) bv[t] = bp[16 * t];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Af[q], bv[t], acc[t], 0, 0, 0);
+      }
+      // this lane's four accumulator pixels 4 kq .. 4 kq + 3 of the unit: one row of the tile, four consecutive columns
+      const int py4 = prow + (4 * kq) / S, px4 = (4 * kq) % S;
+      const i32x4_t lab4 = *reinterpret_cast<const i32x4_t*>(s_lab + (S * gy + py4) * 16 + S * gx + px4);
+      int dl[4];   // label - lane's channel offset: the label's class sits in tile t where dl == 16 t
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dl[r] = lab4[r] >= 0 ? lab4[r] - m : -1;
+      float mx[4] = {NEG, NEG, NEG, NEG}, so[4] = {0.f, 0.f, 0.f, 0.f}, zy[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C (a counted label is below C: never selected there)
+          if (16 * t + m >= p.C) acc[t] = f32x4_t{NEG, NEG, NEG, NEG};
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          mx[r] = fmaxf(mx[r], acc[t][r]);
+          zy[r] += dl[r] == 16 * t ? acc[t][r] : 0.f;
+        }
+      }
+      float mxl[4];   // -max * log2(e): exp(x - max) = exp2(fma(x, log2(e), mxl))
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); mxl[r] = -mx[r] * LOG2E; zy[r] = row16_sum(zy[r]); }
+#pragma unroll
+      for (int t = 0; t < TN; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[t][r], LOG2E, mxl[r]));
+          acc[t][r] = e;
+          so[r] += dl[r] == 16 * t ? 0.f : e;   // every class but the label's
+        }
+      float inv[4];   // gscale w_y c / sum, 0 where the pixel is not counted
+      float gl[4];   // the label's own gradient element: -gscale w_y c q
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        so[r] = row16_sum(so[r]);
+        const bool counted = lab4[r] >= 0;
+        const float ey = counted ? __builtin_amdgcn_exp2f(__builtin_fmaf(zy[r], LOG2E, mxl[r])) : 0.f;
+        const float sum = so[r] + ey;            // >= 1: the maximum's own term
+        const float rs = 1.f / sum;
+        const float q = so[r] * rs;
+        float li;
+        const float c = focal_coef(ey * rs, q, (mx[r] - zy[r]) + __logf(sum), f, &li);
+        const float wy = counted ? s_w[counted ? lab4[r] : 0] : 0.f;
+        inv[r] = counted ? p.gscale * wy * c * rs : 0.f;
+        gl[r] = -so[r] * inv[r];
+        if (counted && m == 0) {
+          loss_acc += wy * li;
+          cnt_acc += wy;
+        }
+      }
+      if (p.dlo) {
+        have_d = true;
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+          f32x4_t gv;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gv[r] = dl[r] == 16 * t ? gl[r] : acc[t][r] * inv[r];
+          f32x4_t d = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (SUMD) d = dsum[t];
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) d = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[jj], Bb[jj], d, 0, 0, 0);
+          if constexpr (SUMD) dsum[t] = d; else acc[t] = d;   // d[r] = channel 16 t + 4 kq + r of cell m
+        }
+      }
+    }
+    // the waves take turns on the LDS mirror, as in head_ce_grp_kernel: plain 16-byte read-add-write, no LDS atomics
+    if (p.dlo && (!SUMD || g2 == 1)) {
+      constexpr int NTURN = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? 2 : HEAD_THREADS / 64;
+      const int my_turn = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? ((wid >> 1) & 1) : wid;
+      for (int turn = 0; turn < NTURN; ++turn) {
+        __syncthreads();
+        if (turn == my_turn && have_d && m < NT * NT) {
+          float* dp = s_dlo + gbase + cellm_off;
+#pragma unroll
+          for (int t = 0; t < TN; ++t) {
+            f32x4_t v = *reinterpret_cast<f32x4_t*>(dp + 16 * t);
+            if constexpr (SUMD) v += dsum[t]; else v += acc[t];
+            *reinterpret_cast<f32x4_t*>(dp + 16 * t) = v;
+          }
+        }
+      }
+    }
+  }
+
+  // the block's [loss, weighted count] partial and its slab: plain stores, summed in a fixed order by head_finish_kernel
+  __shared__ float s_red[HEAD_THREADS / 64][2];
+  loss_acc = wave_sum(loss_acc);
+  cnt_acc = wave_sum(cnt_acc);
+  if (lane == 0) { s_red[wid][0] = loss_acc; s_red[wid][1] = cnt_acc; }
+  __syncthreads();
+  if (tid == 0) {
+    float l = 0.f, c = 0.f;
+#pragma unroll
+    for (int w = 0; w < HEAD_THREADS / 64; ++w) { l += s_red[w][0]; c += s_red[w][1]; }
+    p.ws_loss[2 * (size_t)blockIdx.x] = l;
+    p.ws_loss[2 * (size_t)blockIdx.x + 1] = c;
+  }
+  if (p.dlo) {
+    const int q4 = p.cq >> 2;
+    float* slab = p.ws_dlo + (size_t)blockIdx.x * (F4 * F4) * p.cq;
+    for (int i = tid; i < F4 * F4 * q4; i += HEAD_THREADS) {
+      const int cell = i / q4, c = (i % q4) * 4;
+      *reinterpret_cast<float4*>(slab + (size_t)cell * p.cq + c) = *reinterpret_cast<const float4*>(s_dlo + cell * CS + c);
     }
   }
 }
@@ -1269,6 +1506,81 @@ __global__ __launch_bounds__(256) void ce_nchw_bwd_kernel(const float* __restric
   }
 }
 
+// Focal / poly-1 CE on materialised NCHW logits (the drop-in module): head_focal_grp_kernel's per-pixel terms (focal_coef), a lane
+// per pixel.  Forward: lse, the (sum of l_i, sum of w_y) block partials summed in a fixed order by ce_nchw_finish_kernel, and
+// (optional) the per-pixel losses.  q is the sum of the other classes' exponentials over the full sum in both directions: the
+// backward takes it from one more walk over the classes with the saved lse.  Kernels of their own: ce_nchw_*_kernel are untouched.
+__global__ __launch_bounds__(256) void focal_nchw_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              float* lse, float* part, int B, int C, size_t HW, long ignore_index,
+                                                              const float* __restrict__ cw, float* loss_px, FocalArgs f) {
+  const size_t total = (size_t)B * HW;
+  float lacc = 0.f, cacc = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / HW, px = i % HW;
+    const float* base = logits + b * C * HW + px;
+    const long lab = (long)labels[i];
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    float m = -__builtin_inff();
+    for (int c = 0; c < C; ++c) m = fmaxf(m, base[(size_t)c * HW]);
+    float so = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float e = __expf(base[(size_t)c * HW] - m);
+      so += (counted && c == lab) ? 0.f : e;
+    }
+    const float zy = counted ? base[(size_t)lab * HW] : 0.f;
+    const float ey = counted ? __expf(zy - m) : 0.f;
+    const float sum = so + ey;
+    const float lsum = __logf(sum);
+    if (lse) lse[i] = m + lsum;
+    float li = 0.f;
+    if (counted) {
+      const float wy = cw ? cw[lab] : 1.f;
+      focal_coef(ey / sum, so / sum, (m - zy) + lsum, f, &li);
+      li *= wy;
+      lacc += li;
+      cacc += wy;
+    }
+    if (loss_px) loss_px[i] = li;
+  }
+  lacc = wave_sum(lacc);
+  cacc = wave_sum(cacc);
+  __shared__ float red[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = lacc;
+    red[1][threadIdx.x >> 6] = cacc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    part[2 * blockIdx.x + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ __launch_bounds__(256) void focal_nchw_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              const float* __restrict__ lse, const float* __restrict__ gscale_dev,
+                                                              float gscale, const float* __restrict__ grad_px, float* dlogits, int B,
+                                                              int C, size_t HW, long ignore_index, const float* __restrict__ cw,
+                                                              FocalArgs f) {
+  const size_t total = (size_t)B * HW;
+  const float gs = gscale * (gscale_dev ? *gscale_dev : 1.f);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / HW, px = i % HW;
+    const float* base = logits + b * C * HW + px;
+    float* dbase = dlogits + b * C * HW + px;
+    const long lab = (long)labels[i];
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    if (!counted) {
+      for (int c = 0; c < C; ++c) dbase[(size_t)c * HW] = 0.f;
+      continue;
+    }
+    const float l = lse[i];
+    float q = 0.f;   // sum of the other classes' probabilities
+    for (int c = 0; c < C; ++c) q += c == lab ? 0.f : __expf(base[(size_t)c * HW] - l);
+    const float zy = base[(size_t)lab * HW];
+    float li;
+    const float coef = gs * (grad_px ? grad_px[i] : 1.f) * (cw ? cw[lab] : 1.f) * focal_coef(__expf(zy - l), q, l - zy, f, &li);
+    for (int c = 0; c < C; ++c) dbase[(size_t)c * HW] = c == lab ? -coef * q : coef * __expf(base[(size_t)c * HW] - l);
+  }
+}
+
 // Dice + CE on materialised NCHW logits (the drop-in module): the two passes of the fused head, HBM-bound and plain, C <= CMAX.
 // Pass 1: a lane owns a pixel (lse, CE); the class sums of a wave's 64 pixels are wave reductions (T: ballot popcounts) that lane 0
 // adds to the wave's own LDS row; the block's rows are summed in wave order and leave as the block's slab, in the layout of
@@ -1836,4 +2148,103 @@ extern "C" int lc2is_ce_nchw_bwd_opts(const float* logits, const int64_t* labels
                                       const float* class_weight, float label_smoothing, lc2is_stream_t stream) {
   return ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale, grad_px, dlogits, B, C, HW, ignore_index,
                      class_weight, label_smoothing, stream);
+}
+
+// ---- focal / poly-1 cross-entropy: host side ----
+namespace {
+// gamma in [0, inf), poly_eps >= -1 and finite (a NaN fails every comparison)
+bool focal_args_ok(float gamma, float poly_eps) {
+  return gamma >= 0.f && gamma <= 3.0e38f && poly_eps >= -1.f && poly_eps <= 3.0e38f;
+}
+}  // namespace
+
+extern "C" int lc2is_head_upsample_focal(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                         float* loss_sum, int B, int h, int w, int C, int S, int mode, long ignore_index,
+                                         float grad_scale, const float* class_weight, float gamma, float poly_eps,
+                                         void* workspace, size_t workspace_bytes, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!scores_lo || !labels || !loss_sum) return LC2IS_ERR_NULL;
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || ld < C || ld > CMAX || ld % 64) return LC2IS_ERR_SHAPE;
+  if (((size_t)scores_lo | (size_t)dscores_lo) & 15) return LC2IS_ERR_SHAPE;
+  if (!focal_args_ok(gamma, poly_eps)) return LC2IS_ERR_SHAPE;
+  if (!(S == 4 || S == 8 || S == 16)) return LC2IS_ERR_UNSUPPORTED;
+  if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return LC2IS_ERR_UNSUPPORTED;
+  const HeadGrpPlan gp = head_grp_plan(B, h, w, C, S, mode, dscores_lo != nullptr);
+  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < gp.loss_bytes + gp.dlo_bytes) return LC2IS_ERR_WORKSPACE;
+  const int H = h * S, W = w * S;
+  HeadArgs a{scores_lo, ld, labels, dscores_lo, nullptr, loss_sum, B, h, w, H, W, C, S, mode, ignore_index,
+             grad_scale, (float*)workspace, dscores_lo ? (float*)((char*)workspace + gp.loss_bytes) : nullptr, gp.cq,
+             class_weight, 0.f};
+  const FocalArgs fa{gamma, poly_eps};
+  const int nt = (C + 15) / 16;
+  const int tn = nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12));   // head_upsample_ce's channel-tile counts
+  const int f4 = gp.f4, t4 = gp.t4;
+  // the footprint, its gradient mirror, the tile's labels and the class weights (the OPT variant's layout)
+  const int lds = 2 * f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) + CMAX * (int)sizeof(float);
+#define LC2IS_FOCAL(MODE_, TN_, S_)                                                                                          \
+  do {                                                                                                                      \
+    static DevOnce attr;                                                                                                    \
+    if (attr.need()) {                                                                                                      \
+      if (hipFuncSetAttribute((const void*)head_focal_grp_kernel<MODE_, TN_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              2 * 7 * 7 * (CMAX + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +             \
+                                  CMAX * (int)sizeof(float)) != hipSuccess)                                                 \
+        return LC2IS_ERR_LAUNCH;                                                                                            \
+      attr.done();                                                                                                          \
+    }                                                                                                                       \
+    hipLaunchKernelGGL((head_focal_grp_kernel<MODE_, TN_, S_>), dim3(B * t4), dim3(HEAD_THREADS), lds, stream, a, fa);      \
+  } while (0)
+#define LC2IS_FOCAL_TN(MODE_, S_)                                                                \
+  do {                                                                                          \
+    if (tn == 4) LC2IS_FOCAL(MODE_, 4, S_); else if (tn == 8) LC2IS_FOCAL(MODE_, 8, S_);         \
+    else if (tn == 10) LC2IS_FOCAL(MODE_, 10, S_); else LC2IS_FOCAL(MODE_, 12, S_);              \
+  } while (0)
+#define LC2IS_FOCAL_S(MODE_)                                                                                           \
+  do {                                                                                                                \
+    if (S == 4) LC2IS_FOCAL_TN(MODE_, 4); else if (S == 8) LC2IS_FOCAL_TN(MODE_, 8); else LC2IS_FOCAL_TN(MODE_, 16);   \
+  } while (0)
+  if (mode == LC2IS_INTERP_BICUBIC) LC2IS_FOCAL_S(LC2IS_INTERP_BICUBIC);
+  else LC2IS_FOCAL_S(LC2IS_INTERP_BILINEAR);
+#undef LC2IS_FOCAL_S
+#undef LC2IS_FOCAL_TN
+#undef LC2IS_FOCAL
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  // second launch: head_finish_kernel's fixed-order sums of the slabs (one wave per low-res cell) and of the loss partials
+  const long ncell = dscores_lo ? (long)B * h * w : 1;
+  const int fgrid = (int)((ncell + 3) / 4);
+#define LC2IS_HEAD_FIN(MODE_, S_) hipLaunchKernelGGL((head_finish_kernel<MODE_, S_>), dim3(fgrid), dim3(256), 0, stream, a, B * t4)
+  if (mode == LC2IS_INTERP_BICUBIC) { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 16); }
+  else { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 16); }
+#undef LC2IS_HEAD_FIN
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_focal_nchw_fwd(const float* logits, const int64_t* labels, float* lse, float* loss_sum, float* loss_px,
+                                    int B, int C, long HW, long ignore_index, const float* class_weight, float gamma,
+                                    float poly_eps, void* workspace, size_t workspace_bytes, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !loss_sum || !workspace) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0 || !focal_args_ok(gamma, poly_eps)) return LC2IS_ERR_SHAPE;
+  const size_t g = ce_nchw_fwd_grid(B, HW);
+  if (workspace_bytes < 2 * sizeof(float) * g) return LC2IS_ERR_WORKSPACE;
+  hipLaunchKernelGGL(focal_nchw_fwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, (float*)workspace, B, C,
+                     (size_t)HW, ignore_index, class_weight, loss_px, FocalArgs{gamma, poly_eps});
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(ce_nchw_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)workspace, (int)g, loss_sum);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_focal_nchw_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_scale_dev,
+                                    float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW,
+                                    long ignore_index, const float* class_weight, float gamma, float poly_eps,
+                                    lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !lse || !dlogits) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0 || !focal_args_ok(gamma, poly_eps)) return LC2IS_ERR_SHAPE;
+  size_t g = ((size_t)B * HW + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(focal_nchw_bwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, grad_scale_dev, grad_scale,
+                     grad_px, dlogits, B, C, (size_t)HW, ignore_index, class_weight, FocalArgs{gamma, poly_eps});
+  return lc2is_check_launch();
 }

@@ -25,7 +25,7 @@ from .base import assign_rng_names, require_cuda
 from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import FTNDecoder
-from .model import TextToPatch, fused_loss_options
+from .model import TextToPatch, fused_focal_options, fused_loss_options
 from .score import KPAD, ScoreMapTail, _scores_bwd, _scores_lo
 from .swin import SWIN_B, SwinArch, SwinTransformer
 
@@ -69,16 +69,21 @@ class PromptFTN(nn.Module):
         return None, self.tail(visual_embeddings, text_embeddings)                                # model.py:204-214
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
-                     label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None) -> torch.Tensor:
+                     label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None,
+                     focal=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
         materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
         {intersection, predicted, labelled} counts (``ScoreMapTail.loss``).  ``accum``: the device block of a gradient-accumulation
-        cycle (``ScoreMapTail.loss``; ``TrainStep(accumulate=N)``)."""
-        fused_loss_options(weight, label_smoothing, reduction)   # (refused before the towers run)
+        cycle (``ScoreMapTail.loss``; ``TrainStep(accumulate=N)``).  ``focal=(gamma, poly_eps)``: FocalLoss's per-pixel loss in
+        place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``."""
+        fused_focal_options(focal, label_smoothing, None)        # (refused before the towers run)
+        fused_loss_options(weight, label_smoothing, reduction)
         if seg_counts is not None:
             ops.check_seg_counts(seg_counts)
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         extra = {} if accum is None else {"accum": accum}
+        if focal is not None:
+            extra["focal"] = focal
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
                               label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, **extra)
 

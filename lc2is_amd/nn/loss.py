@@ -188,6 +188,78 @@ class DiceCrossEntropyLoss(CrossEntropyLoss):
         return _DiceFn.apply(input, target, self.ignore_index, check_dice(*self.dice), self)
 
 
+def check_focal(gamma, poly_eps) -> tuple[float, float]:
+    """(gamma, poly_eps) of a focal / poly-1 loss, validated: gamma a finite number >= 0, poly_eps a finite number >= -1."""
+    return ops.focal_options(gamma, poly_eps)
+
+
+class _FocalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, focal, reduction):
+        lg = logits.float().contiguous()
+        lb = labels.contiguous()
+        kw = dict(class_weight=weight, gamma=focal[0], poly_eps=focal[1])
+        loss2, lse, *lpx = ops.focal_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
+        ctx.saved = (lg, lb, lse, loss2, ignore_index, kw, reduction)
+        if reduction == "none":
+            return lpx[0]
+        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lb, lse, loss2, ignore_index, kw, reduction = ctx.saved
+        if reduction == "none":
+            d = ops.focal_nchw_bwd(lg, lb, lse, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
+        else:   # device scalar: upstream gradient (over the weighted count for 'mean')
+            scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
+            d = ops.focal_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index, **kw)
+        return d, None, None, None, None, None
+
+
+class FocalLoss(CrossEntropyLoss):
+    """Focal loss (Lin et al. 2017) with an optional poly-1 term (Leng et al. 2022) on softmax logits.  Per counted pixel (label !=
+    ignore_index, 0 <= label < C) with label y, p the softmax probability of y and q = 1 - p:
+    l = weight[y] * (q^gamma * (-log p) + poly_eps * q).  ``weight`` is the per-class alpha; gamma = 0 and poly_eps = 0 is this
+    module's CrossEntropyLoss.  'mean' divides the sum by the sum of weight[y] over the counted pixels — this project's
+    cross-entropy rule, exact under ``ignore_index``; kornia and MONAI divide by the number of pixels, which is the same value when
+    no pixel is ignored and ``weight`` is None.  q comes from the other classes' exponentials, so a saturated pixel (p = 1 or p = 0 in
+    fp32) gives a finite loss and gradient for every gamma >= 0.  ``label_smoothing`` has no agreed definition here (ValueError).
+    ``TrainStep(criterion=FocalLoss(...))`` trains through the fused head (``forward_loss(focal=...)``)."""
+
+    def __init__(self, gamma: float = 2.0, poly_eps: float = 0.0, weight=None, ignore_index: int = -100, reduction: str = "mean",
+                 label_smoothing: float = 0.0) -> None:
+        if label_smoothing != 0.0:
+            raise ValueError("FocalLoss: label_smoothing has no agreed definition for a focal / poly-1 loss")
+        super().__init__(weight=weight, ignore_index=ignore_index, reduction=reduction)
+        self.gamma, self.poly_eps = check_focal(gamma, poly_eps)
+
+    @property
+    def focal(self) -> tuple[float, float]:
+        return self.gamma, self.poly_eps
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        require_cuda(input, "logits")
+        if input.dim() != 4 or target.dim() != 3:
+            raise ValueError("lc2is_amd FocalLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        if self.label_smoothing != 0.0:
+            raise ValueError("FocalLoss: label_smoothing has no agreed definition for a focal / poly-1 loss")
+        return _FocalFn.apply(input, target, self.ignore_index, self.weight, check_focal(*self.focal), self.reduction)
+
+
+class Poly1CrossEntropyLoss(FocalLoss):
+    """Poly-1 cross-entropy (PolyLoss, Leng et al. 2022): l = weight[y] * (-log p + epsilon * (1 - p)), i.e.
+    ``FocalLoss(gamma=0, poly_eps=epsilon)`` with its reductions and its 'mean' denominator."""
+
+    def __init__(self, epsilon: float = 1.0, weight=None, ignore_index: int = -100, reduction: str = "mean",
+                 label_smoothing: float = 0.0) -> None:
+        super().__init__(gamma=0.0, poly_eps=epsilon, weight=weight, ignore_index=ignore_index, reduction=reduction,
+                         label_smoothing=label_smoothing)
+
+    @property
+    def epsilon(self) -> float:
+        return self.poly_eps
+
+
 class _AuxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, ignore_index, S, weight, label_smoothing, reduction):

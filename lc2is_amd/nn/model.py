@@ -21,7 +21,7 @@ from .. import ops
 from .base import HipModule, grad_buf, linear_bwd_params, require_cuda, vec_grad
 from .clip import ClipArch, ImageEncoderCLIP, TextEncoderCLIP, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer
-from .loss import check_dice, check_ohem
+from .loss import check_dice, check_focal, check_ohem
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
 KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product)
@@ -99,6 +99,16 @@ def fused_dice_options(dice, opts, ohem):
     return check_dice(*dice)
 
 
+def fused_focal_options(focal, label_smoothing: float, dice):
+    """``focal`` = (gamma, poly_eps) validated, or None; the focal / poly-1 loss keeps weight=, reduction=, ohem=, seg_counts= and
+    accum=, and does not combine with a Dice term or label smoothing."""
+    if focal is None:
+        return None
+    if dice is not None or label_smoothing != 0.0:
+        raise ValueError("lc2is_amd: focal= cannot be combined with dice= or label_smoothing")
+    return check_focal(*focal)
+
+
 def _reduce(loss2, reduction: str, save: bool):
     """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
     gives torch's NaN mean and a zero gradient, with no host sync."""
@@ -113,8 +123,8 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None,
-                accum=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum)
+                accum=None, focal=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -122,7 +132,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -179,7 +189,8 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None, accum=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None, accum=None,
+                  focal=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -206,7 +217,13 @@ class BaseModelWithText(HipModule):
         # the kernel writes the gradient of the SUM of the per-pixel losses and counts the pixels it kept (labels that are
         # negative, == ignore_index or >= K are skipped, head.hip); the 1/count of nn.CrossEntropyLoss's mean is folded
         # into the upstream-gradient multiply of _head_bwd, from the device-side count (no host sync, no label pass)
-        if loss_opts is None:
+        if focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
+            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
+            loss2, dlo = ops.head_upsample_focal(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
+                                                 ignore_index=ignore_index, grad_scale=1.0, class_weight=weight, gamma=focal[0],
+                                                 poly_eps=focal[1])
+            loss, inv_count = _reduce(loss2, reduction, save)
+        elif loss_opts is None:
             loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
                                                  want_grad=save, ignore_index=ignore_index, grad_scale=1.0)
             loss = loss2[0] / loss2[1]
@@ -298,7 +315,7 @@ class BaseModelWithText(HipModule):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                     seg_counts=None, accum=None) -> torch.Tensor:
+                     seg_counts=None, accum=None, focal=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
@@ -313,9 +330,15 @@ class BaseModelWithText(HipModule):
         ``accum``: the fp64 [4] device block of a gradient-accumulation cycle (``ops.accum_add``; ``TrainStep(accumulate=N)``).  The
         head's [sum of losses, count] — after ``ohem=``, that of the relabelled call — is added to the block, the returned value is
         this batch's usual loss, and the backward writes the gradient of the SUM of the pixel losses whatever ``reduction`` says:
-        the update that closes the cycle divides by the block's count.  Not combinable with ``dice=``.  None: no launch."""
+        the update that closes the cycle divides by the block's count.  Not combinable with ``dice=``.  None: no launch.
+        ``focal=(gamma, poly_eps)``: the focal / poly-1 loss w_y ((1 - p_y)^gamma (-log p_y) + poly_eps (1 - p_y)) per counted
+        pixel in place of the cross-entropy (FocalLoss's definition: 'mean' divides by the sum of w_y), one forward + backward
+        launch of the head.  Keeps ``weight``, ``reduction``, ``seg_counts``, ``accum`` (a per-pixel loss: the sums add) and ``ohem``
+        (the selection still ranks by the plain CE; the relabelled call is the focal one); not combinable with ``dice=`` or
+        ``label_smoothing``.  None: the call as it was."""
         if accum is not None and dice is not None:
             raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
+        focal = fused_focal_options(focal, label_smoothing, dice)
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
@@ -324,6 +347,9 @@ class BaseModelWithText(HipModule):
             ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
+        if focal is not None:
+            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum,
+                                 focal)
         if accum is None:   # (the call as it was: no new argument reaches the head)
             return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts)
         return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum)

@@ -18,7 +18,7 @@ from torch import nn
 from .. import ops
 from .base import require_cuda
 from .loss import check_ohem
-from .model import _reduce, fused_dice_options, fused_loss_options
+from .model import _reduce, fused_dice_options, fused_focal_options, fused_loss_options
 
 KPAD = 192
 
@@ -61,7 +61,7 @@ def _scores_bwd(ds32, sv):
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None, seg_counts=None,
-                accum=None):
+                accum=None, focal=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
@@ -84,11 +84,16 @@ class _ScoreFn(torch.autograd.Function):
         if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
             labels, info = ops.ohem_labels(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index, ohem)
             owner.last_ohem = (labels, info)
-        if loss_opts is not None:   # class weights / label smoothing / 'sum' (loss2[1] = sum_i w_{y_i})
-            weight, label_smoothing, reduction = loss_opts
-            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
-                                                 class_weight=weight, label_smoothing=label_smoothing)
+        if loss_opts is not None or focal is not None:   # class weights / label smoothing / 'sum' (loss2[1] = sum_i w_{y_i})
+            weight, label_smoothing, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
+            if focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
+                loss2, dlo = ops.head_upsample_focal(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
+                                                     want_grad=save, ignore_index=ignore_index, grad_scale=1.0, class_weight=weight,
+                                                     gamma=focal[0], poly_eps=focal[1])
+            else:
+                loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
+                                                     want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
+                                                     class_weight=weight, label_smoothing=label_smoothing)
             loss, inv = _reduce(loss2, reduction, save)
             if accum is not None:   # accumulation cycle: dlo stays the gradient of the SUM, the cycle's update divides
                 ops.accum_add(accum, loss2)
@@ -117,7 +122,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None, None, None, None, None, None
+        return dv, dt, None, None, None, None, None, None, None, None, None, None, None
 
 
 class ScoreMapTail(nn.Module):
@@ -135,7 +140,7 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None, dice=None, seg_counts=None, accum=None) -> torch.Tensor:
+             ohem=None, dice=None, seg_counts=None, accum=None, focal=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
         the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
@@ -144,9 +149,13 @@ class ScoreMapTail(nn.Module):
         takes ``+= counts.sum(0)`` of this batch ({intersection, predicted, labelled} of the argmax of the same upsampled scores
         against ``labels`` as given, over the pixels the loss counts; ``BaseModelWithText.forward_loss`` has the details).
         ``accum``: the device block of a gradient-accumulation cycle (``ops.accum_add``): the head's [sum of losses, count] joins it,
-        the backward leaves the gradient of the SUM of the pixel losses; not combinable with ``dice=``."""
+        the backward leaves the gradient of the SUM of the pixel losses; not combinable with ``dice=``.
+        ``focal=(gamma, poly_eps)``: the focal / poly-1 loss per counted pixel in place of the cross-entropy (FocalLoss's
+        definition; ``BaseModelWithText.forward_loss`` has the details); keeps ``weight``, ``reduction``, ``ohem``, ``seg_counts`` and
+        ``accum``, not combinable with ``dice=`` or ``label_smoothing``."""
         if accum is not None and dice is not None:
             raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
+        focal = fused_focal_options(focal, label_smoothing, dice)
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
             ohem = check_ohem(*ohem)
@@ -155,6 +164,9 @@ class ScoreMapTail(nn.Module):
             ops.check_seg_counts(seg_counts, text_embeddings.shape[1])
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
+        if focal is not None:
+            return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
+                                  dice, seg_counts, accum, focal)
         if accum is None:
             return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
                                   dice, seg_counts)

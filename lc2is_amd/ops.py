@@ -90,6 +90,9 @@ _ARGTYPES = {
     "lc2is_ce_dice_nchw_workspace_bytes": [_I, _I, _L],
     "lc2is_ce_dice_nchw_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _F, _F, _F, _I, _P, _Z, _P],
     "lc2is_ce_dice_nchw_bwd": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _L, _L, _P],
+    "lc2is_head_upsample_focal": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _F, _P, _Z, _P],
+    "lc2is_focal_nchw_fwd": [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _F, _F, _P, _Z, _P],
+    "lc2is_focal_nchw_bwd": [_P, _P, _P, _P, _F, _P, _P, _I, _I, _L, _L, _P, _F, _F, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -1165,6 +1168,100 @@ def ce_dice_nchw_bwd(logits, labels, lse, coef, grad_scale_dev, grad_scale: floa
     d = torch.empty_like(logits)
     _lib.check(_fn("lc2is_ce_dice_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(coef), _ptr(grad_scale_dev), grad_scale,
                                              _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_dice_nchw_bwd")
+    return d
+
+
+# ---- focal / poly-1 cross-entropy: per-pixel losses of the label's probability alone, one pass ----
+def focal_options(gamma, poly_eps) -> tuple[float, float]:
+    """(gamma, poly_eps) of a focal / poly-1 loss, validated: gamma a finite number >= 0, poly_eps a finite number >= -1."""
+    for name, v, lo in (("gamma", gamma, 0.0), ("poly_eps", poly_eps, -1.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < lo:
+            raise ValueError(f"focal loss: {name} must be a finite number >= {lo:g}, got {v!r}")
+    return float(gamma), float(poly_eps)
+
+
+def _focal_weight(class_weight, C: int, dev):
+    if class_weight is not None:
+        _ce_options(class_weight, 0.0, C, dev)
+
+
+def head_upsample_focal(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                        want_grad: bool = False, ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None,
+                        gamma: float = 2.0, poly_eps: float = 0.0):
+    """Focal / poly-1 cross-entropy of the upsampled scores (S = 4 / 8 / 16): scores_lo fp32 [B*h*w, ld], labels int64
+    [B, h*S, w*S].  Per counted pixel, with p the label's softmax probability and q = 1 - p:
+    l = w_y (q^gamma (-ln p) + poly_eps q).  Returns (loss2 = [sum of l, sum of w_y over the counted pixels], dscores_lo or None =
+    grad_scale * d(sum of l) / d scores_lo).  One forward + backward launch and the finish launch of ``head_upsample_ce``; nothing
+    syncs, no atomics, the same bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    gamma, poly_eps = focal_options(gamma, poly_eps)
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError("lc2is_amd.head_upsample_focal: scores_lo must be contiguous")
+    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.head_upsample_focal: labels must be contiguous [{B},{h*S},{w*S}]")
+    if S not in (4, 8, 16):
+        raise RuntimeError(f"lc2is_amd.head_upsample_focal: S must be 4, 8 or 16, got {S}")
+    ld = scores_lo.shape[1]
+    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
+        raise RuntimeError(f"lc2is_amd.head_upsample_focal: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
+                           f"got {tuple(scores_lo.shape)}")
+    dev = scores_lo.device
+    _focal_weight(class_weight, C, dev)
+    nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
+    if nbytes == 0:
+        raise RuntimeError(f"lc2is_amd.head_upsample_focal: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    _lib.check(_fn("lc2is_head_upsample_focal")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
+                                                ignore_index, grad_scale, _ptr(class_weight), gamma, poly_eps, _ptr(ws), nbytes,
+                                                _stream()), f"head_upsample_focal B={B} h={h} w={w} C={C} S={S}")
+    return loss, dlo
+
+
+def focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, gamma: float = 2.0, poly_eps: float = 0.0,
+                   per_pixel: bool = False):
+    """The same loss on NCHW fp32 logits.  Returns (loss2 = [sum of l, sum of w_y], lse [B,H,W]) and, with per_pixel=True, a third
+    tensor: the per-pixel losses [B,H,W] (0 where not counted)."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    gamma, poly_eps = focal_options(gamma, poly_eps)
+    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
+        raise RuntimeError("lc2is_amd.focal_nchw_fwd: logits/labels must be contiguous")
+    B, Cc, H, W = logits.shape
+    if tuple(labels.shape) != (B, H, W):
+        raise RuntimeError(f"lc2is_amd.focal_nchw_fwd: labels must be [{B},{H},{W}]")
+    dev = logits.device
+    _focal_weight(class_weight, Cc, dev)
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    loss = torch.empty(2, dtype=torch.float32, device=dev)   # overwritten: block partials summed in a fixed order
+    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lpx = torch.empty((B, H, W), dtype=torch.float32, device=dev) if per_pixel else None
+    _lib.check(_fn("lc2is_focal_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W, ignore_index,
+                                           _ptr(class_weight), gamma, poly_eps, _ptr(ws), nbytes, _stream()), "focal_nchw_fwd")
+    return (loss, lse, lpx) if per_pixel else (loss, lse)
+
+
+def focal_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float = 1.0, ignore_index: int = -100, *, class_weight=None,
+                   gamma: float = 2.0, poly_eps: float = 0.0, grad_px=None):
+    """dlogits = grad_scale * grad_scale_dev (device scalar or None) * grad_px (per pixel, [B,H,W] fp32, optional) * dl_i/dlogits,
+    from ``focal_nchw_fwd``'s lse."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    _chk(lse, torch.float32, "lse", 3); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    gamma, poly_eps = focal_options(gamma, poly_eps)
+    B, Cc, H, W = logits.shape
+    if (not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W)
+            or tuple(lse.shape) != (B, H, W) or not lse.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.focal_nchw_bwd: contiguous logits [B,C,H,W] with labels / lse [{B},{H},{W}] required")
+    _focal_weight(class_weight, Cc, logits.device)
+    if grad_px is not None:
+        _chk(grad_px, torch.float32, "grad_px", 3)
+        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
+            raise RuntimeError(f"lc2is_amd.focal_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    d = torch.empty_like(logits)
+    _lib.check(_fn("lc2is_focal_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale, _ptr(grad_px),
+                                           _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight), gamma, poly_eps, _stream()),
+               "focal_nchw_bwd")
     return d
 
 

@@ -21,7 +21,10 @@ all on the device: eager, captured, under a reducer — each rank selects over i
 ``ohem_info`` is the last selection's device info block.  An ``lc2is_amd.nn.DiceCrossEntropyLoss`` trains on ce_weight * mean CE
 + dice_weight * soft Dice through the fused head (a statistics pass, a one-block launch and the gradient pass, all on the device:
 eager, captured, under a reducer — each rank takes the statistics of its own batch); ``dice_stats`` are the last step's device
-tensors (I, P, T, loss block).  The loss is deterministic, so the criterion's ``eval()`` mode changes nothing.
+tensors (I, P, T, loss block).  The loss is deterministic, so the criterion's ``eval()`` mode changes nothing.  An
+``lc2is_amd.nn.FocalLoss`` / ``Poly1CrossEntropyLoss`` trains on its per-pixel loss through the fused head in the launches of the
+plain step (``forward_loss(focal=...)``; its ``weight`` and 'mean' / 'sum' apply): eager, captured, under ``accumulate=N``, with
+``seg_metrics=True`` and under a reducer.
 
 The device-held path (opt-in: any of ``lr_schedule``, ``max_grad_norm``, ``skip_nonfinite``, ``device_state``) adds what the
 reference's loop has around ``optimizer.step()``:
@@ -67,6 +70,12 @@ def _accepts_dice(model) -> bool:
     import inspect
     fl = getattr(model, "forward_loss", None)
     return fl is not None and "dice" in inspect.signature(fl).parameters
+
+
+def _accepts_focal(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "focal" in inspect.signature(fl).parameters
 
 
 def _accepts_seg_counts(model) -> bool:
@@ -417,7 +426,7 @@ class TrainStep:
         self._ohem = False
         self._dice = False
         if criterion is not None:
-            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, DiceCrossEntropyLoss, OhemCrossEntropyLoss
+            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, DiceCrossEntropyLoss, FocalLoss, OhemCrossEntropyLoss
             if not isinstance(criterion, (CrossEntropyLoss, nn.CrossEntropyLoss)) or isinstance(criterion, AuxiliaryLoss):
                 raise TypeError("TrainStep: criterion must be a CrossEntropyLoss (lc2is_amd.nn or torch.nn)")
             if ignore_index is not None and ignore_index != -100:
@@ -435,6 +444,11 @@ class TrainStep:
             if self._dice and not _accepts_dice(model):
                 raise TypeError("TrainStep: a DiceCrossEntropyLoss needs a model whose forward_loss takes dice= "
                                 "(BaseModelWithText); the compose models have no Dice head")
+            if isinstance(criterion, FocalLoss):   # rides the options call: weight=, reduction= and focal=(gamma, poly_eps)
+                if not _accepts_focal(model):
+                    raise TypeError("TrainStep: a FocalLoss / Poly1CrossEntropyLoss needs a model whose forward_loss takes focal= "
+                                    "(BaseModelWithText, PromptFTN)")
+                self._loss_opts = True
         self.criterion = criterion
         self.model = model
         self.arena = ParamArena(model)
@@ -730,6 +744,9 @@ class TrainStep:
             c.last_stats = self.model.last_dice
         elif self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
             c = self.criterion
+            focal = getattr(c, "focal", None)   # a FocalLoss / Poly1CrossEntropyLoss: its (gamma, poly_eps) as they are now
+            if focal is not None:
+                seg["focal"] = focal
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
                                            label_smoothing=float(c.label_smoothing), reduction=c.reduction, **seg)
         else:
