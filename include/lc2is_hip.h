@@ -907,6 +907,49 @@ int lc2is_focal_nchw_bwd(const float* logits, const int64_t* labels, const float
                          float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW, long ignore_index,
                          const float* class_weight, float gamma, float poly_eps, lc2is_stream_t stream);
 
+/* ---- sigmoid cross-entropy and sigmoid focal loss (the per-class binary losses) ----------------------------------------------
+ * For a counted pixel i (label != ignore_index && 0 <= label < C: the rule of the CE head) with label y and a class c < C, z = z_ic
+ * the class score, t = [c == y], p = sigmoid(z), p_t = t ? p : 1 - p, class weight w_c (class_weight: device fp32 [C], the weight of
+ * class c's binary term, or NULL = ones):
+ *   bce       = softplus(z) - t z                                  ( = -ln p_t )
+ *   l_ic      = w_c a_t (1 - p_t)^gamma bce,   a_t = alpha given ? (t ? alpha : 1 - alpha) : 1
+ *   dl_ic/dz  = w_c a_t ( t ? (1-p)^gamma (gamma p ln p - (1-p)) : p^gamma (p - gamma (1-p) ln(1-p)) )
+ *   l_i       = class_scale * sum_{c<C} l_ic
+ * gamma in [0, inf) and finite; alpha <= 1, any negative value = no alpha, not a NaN; class_scale in (0, inf) and finite (else
+ * LC2IS_ERR_SHAPE).  gamma = 0 without alpha is binary cross-entropy with logits on one-hot targets; gamma > 0 is RetinaNet's focal
+ * loss elementwise.  ln p and ln(1 - p) are -softplus(-z) and -softplus(z), never the logarithm of a rounded p: z = +-1e4 gives
+ * finite losses and gradients for every gamma; at gamma = 0 the modulating factor is not formed (no 0^0).  No softmax: the classes
+ * of a pixel do not compete, and the gradient of a class depends on its own score alone.
+ * loss_sum[0] = sum_i l_i, loss_sum[1] = the NUMBER of counted pixels, unweighted and exact: the mean of a binary loss divides by a
+ * count of elements (torch's and mmseg's rule), not by a weight sum as this project's softmax cross-entropy does.  class_scale = 1 / C
+ * makes loss_sum[0] / loss_sum[1] torch's elementwise mean over counted pixels x C; class_scale = 1 the per-pixel mean of the
+ * class sums.
+ * replaces: torch.nn.BCEWithLogitsLoss on one-hot targets / mmseg's CrossEntropyLoss(use_sigmoid=True), and
+ *   torchvision.ops.sigmoid_focal_loss / mmseg's FocalLoss, composed from torch ops on model(inputs)["outputs"] (engine.py:94), plus
+ *   their autograd.
+ *
+ * lc2is_head_upsample_sigmoid: on the fused head of lc2is_head_upsample_ce (scores_lo fp32 [B,h,w,ld] channels-last, 16-byte
+ * aligned, C <= ld <= 192, ld % 64 == 0, else LC2IS_ERR_SHAPE; S in {4, 8, 16} and a known mode, else LC2IS_ERR_UNSUPPORTED), one
+ * forward + backward launch and the fixed-order finish launch.  dscores_lo (NULL: loss only) = grad_scale * U^T (sum_i dl_i/dz), all
+ * ld channels overwritten, exactly 0 at and past C.  workspace: 16-byte aligned, >= lc2is_head_upsample_ce_workspace_bytes(B, h, w,
+ * C, S, mode, dscores_lo != NULL) (else LC2IS_ERR_WORKSPACE).  Refusals in the order NULL, SHAPE, UNSUPPORTED, WORKSPACE.  NO
+ * read-modify-write atomics, LDS included: the same bytes every run; captures into a graph. */
+int lc2is_head_upsample_sigmoid(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo, float* loss_sum, int B,
+                                int h, int w, int C, int S, int mode, long ignore_index, float grad_scale,
+                                const float* class_weight, float gamma, float alpha, float class_scale, void* workspace,
+                                size_t workspace_bytes, lc2is_stream_t stream);
+/* The same loss on materialised NCHW fp32 logits [B,C,HW] (the drop-in criteria).  _fwd: loss_sum[2] overwritten through ordered
+ * block partials (workspace >= lc2is_ce_nchw_fwd_workspace_bytes(B, HW)), loss_px (optional, [B,HW]) = l_i, 0 where not counted.
+ * _bwd: dlogits = grad_scale * (*grad_scale_dev, NULL = 1) * grad_px[i] (NULL = 1) * dl_i/dlogits; nothing saved by _fwd is needed
+ * (no lse); every element is written.
+ * replaces: the same criteria on model(inputs)["outputs"] with reduction 'mean' / 'sum' / 'none', plus their autograd. */
+int lc2is_sigmoid_focal_nchw_fwd(const float* logits, const int64_t* labels, float* loss_sum, float* loss_px, int B, int C, long HW,
+                                 long ignore_index, const float* class_weight, float gamma, float alpha, float class_scale,
+                                 void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_sigmoid_focal_nchw_bwd(const float* logits, const int64_t* labels, const float* grad_scale_dev, float grad_scale,
+                                 const float* grad_px, float* dlogits, int B, int C, long HW, long ignore_index,
+                                 const float* class_weight, float gamma, float alpha, float class_scale, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

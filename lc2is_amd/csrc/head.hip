@@ -865,6 +865,245 @@ __global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? 2 : 1)) void head_focal_grp
   }
 }
 
+// ---- sigmoid cross-entropy / sigmoid focal loss on the same head: per-class binary terms, forward and backward in one pass ----
+// For a counted pixel with label y and a class c < C: z the upsampled score, t = [c == y], p = sigmoid(z), p_t = t ? p : 1 - p:
+//   bce   = softplus(z) - t z = -ln p_t
+//   l_c   = w_c a_t (1 - p_t)^gamma bce,   a_t = alpha given ? (t ? alpha : 1 - alpha) : 1      (RetinaNet's focal loss; gamma = 0
+//   l     = class_scale sum_{c < C} l_c                                                          without alpha: BCE with logits)
+// No row maximum, no log-sum-exp, no coupling between the classes: everything is elementwise in the accumulator layout, and the
+// pixel's loss is the sum over the TN tiles and the 16 lanes of a row.  With s = t ? -z : z (so bce = softplus(s), 1 - p_t =
+// sigmoid(s) = u, p_t = sigmoid(-s) = v) both branches of the definition are one expression:
+//   d l_c / dz = (t ? -1 : 1) w_c a_t u^gamma (gamma v bce + u)
+// One e = exp2(-|z| log2 e) in (0, 1] serves everything:
+//  * L = ln(1 + e): below e = 1/64 the alternating series (relative error < e^5 / 6), where 1 + e has rounded the small term away
+//    — 150 of 151 classes are such negatives, and their sum is the loss; above, log2(1 + e);
+//  * softplus(s) = max(s, 0) + L;  1 / (1 + e) and e / (1 + e) are the larger and the smaller of (p, 1 - p): no 1 - p;
+//  * u^gamma = exp2(-gamma log2(e) softplus(-s)): ln u is never the logarithm of a rounded u, so |z| = 1e4 gives finite values for
+//    every gamma >= 0; at gamma == 0 (a uniform branch) the factor is not formed at all — no 0^0, one transcendental fewer.
+// Three (gamma == 0) or four quarter-rate operations per ELEMENT; the branch on gamma is uniform and taken once per tile.  Channels at or past C enter with z = 0 and w_c = 0: exactly 0 in
+// loss and gradient.  count = the number of counted pixels, unweighted (the element-count rule of binary losses).  The tiles, LDS
+// staging, products, mirror turns, partials and slabs are head_focal_grp_kernel's; head_finish_kernel gathers.  A kernel of its own
+// with an argument struct of its own: HeadArgs and the existing instantiations compile to what they were.
+struct SigmoidArgs { float gamma, ng2, cpos, cneg; };   // ng2 = -gamma log2(e); cpos / cneg = class_scale a_t for t = 1 / 0
+
+// one (pixel, class) element: *l = (1 - p_t)^gamma bce, returns d *l / dz.  FOCUS = false: gamma == 0, no modulating factor
+template <bool FOCUS>
+__device__ __forceinline__ float sigmoid_elem(float z, bool tl, SigmoidArgs f, float* l) {
+  constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+  const float s = tl ? -z : z;
+  const float e = __builtin_amdgcn_exp2f(-fabsf(z) * LOG2E);
+  const float ser = e * (1.f - e * (0.5f - e * ((1.f / 3.f) - e * (0.25f - e * 0.2f))));
+  const float L = e < 0.015625f ? ser : LN2 * __builtin_amdgcn_logf(1.f + e);
+  const float sp = fmaxf(s, 0.f) + L;               // bce
+  const float big = __builtin_amdgcn_rcpf(1.f + e), sm = e * big;
+  const bool pos = s >= 0.f;
+  const float u = pos ? big : sm, v = pos ? sm : big;
+  float lo = sp, g = u;
+  if constexpr (FOCUS) {
+    const float ug = __builtin_amdgcn_exp2f(f.ng2 * (fmaxf(-s, 0.f) + L));
+    lo = ug * sp;
+    g = ug * __builtin_fmaf(f.gamma * v, sp, u);
+  }
+  *l = lo;
+  return tl ? -g : g;
+}
+
+template <int MODE, int TN, int S>
+__global__ __launch_bounds__(HEAD_THREADS, (S == 4 ? (TN <= 10 ? 4 : 2) : 1)) void head_sigmoid_grp_kernel(HeadArgs p, SigmoidArgs f) {
+  constexpr int NT = (MODE == LC2IS_INTERP_BICUBIC) ? 4 : 2;
+  constexpr int OFF = (MODE == LC2IS_INTERP_BICUBIC) ? 1 : 0;
+  constexpr int G = HT / S;
+  constexpr int F4 = G + NT - 1;
+  constexpr int NQ = NT * NT / 4;
+  constexpr int UPG = S * S / 16;
+  constexpr bool SUMD = UPG > 1;
+  static_assert(S == 4 || S == 8 || S == 16, "group kernel: S x S pixel groups inside a 16 x 16 tile");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles_x = (p.W + S / 2 + HT - 1) / HT, tiles_y = (p.H + S / 2 + HT - 1) / HT;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int tyi = (blockIdx.x / tiles_x) % tiles_y, txi = blockIdx.x % tiles_x;
+  const int a0 = G * tyi - 1, b0 = G * txi - 1;
+  const int Y0 = S * a0 + S / 2, X0 = S * b0 + S / 2;
+  const int Cp = p.ld;
+  const int CS = Cp + HEAD_PAD;
+  float* s_lo = (float*)smem;
+  float* s_dlo = s_lo + F4 * F4 * CS;
+  int* s_lab = (int*)(s_dlo + F4 * F4 * CS);     // [16][16] pixels of the tile: -2 outside the image, -1 not counted, else label
+  float* s_w = (float*)(s_lab + HT * HT);        // [CMAX] class weights (ones without), zero past C
+  const int fsize = F4 * F4 * Cp;
+  for (int i = tid * 4; i < fsize; i += HEAD_THREADS * 4) {
+    const int cell = i / Cp, c = i % Cp;
+    int ry = a0 - OFF + cell / F4, rx = b0 - OFF + cell % F4;
+    ry = ry < 0 ? 0 : (ry > p.h - 1 ? p.h - 1 : ry);
+    rx = rx < 0 ? 0 : (rx > p.w - 1 ? p.w - 1 : rx);
+    *reinterpret_cast<float4*>(s_lo + cell * CS + c) =
+        *reinterpret_cast<const float4*>(p.lo + (((size_t)b * p.h + ry) * p.w + rx) * p.ld + c);
+    if (p.dlo) *reinterpret_cast<float4*>(s_dlo + cell * CS + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (tid < HT * HT) {
+    const int Y = Y0 + (tid >> 4), X = X0 + (tid & 15);
+    int code = -2;
+    if (Y >= 0 && X >= 0 && Y < p.H && X < p.W) {
+      code = -1;
+      const int64_t lab64 = p.labels[((size_t)b * p.H + Y) * p.W + X];
+      if (lab64 != (int64_t)p.ignore_index && lab64 >= 0 && lab64 < p.C) code = (int)lab64;
+    }
+    s_lab[tid] = code;
+  }
+  if (tid < CMAX) s_w[tid] = tid < p.C ? (p.cw ? p.cw[tid] : 1.f) : 0.f;
+  __syncthreads();
+
+  const int m = lane & 15, kq = lane >> 4;
+  const int cellm_off = ((m / NT) * F4 + m % NT) * CS + 4 * kq;
+  int cell_off[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
+  // The interpolation operands are formed per unit where they are used, the forward one in front of the forward product and the
+  // backward one behind the element loop, from a lane index the compiler cannot see through.  At S = 4 they do not depend on the
+  // unit and would be hoisted; held across the 4 TN elements, their eight registers cost the second block per CU (S = 4, TN <= 10
+  // is compiled for 4 waves per SIMD = two blocks of 512 threads per CU: 126 VGPRs, no scratch; TN = 12 does not fit and keeps
+  // one block per CU).
+  auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
+  float loss_acc = 0.f, cnt_acc = 0.f;
+  f32x4_t dsum[SUMD ? TN : 1];
+  if constexpr (SUMD) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) dsum[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  bool have_d = false;
+  int gbase = 0;
+
+#pragma unroll 1
+  for (int g2 = 0; g2 < 2; ++g2) {
+    const int u = 2 * wid + g2, gi = u / UPG, rt = u % UPG, gy = gi / G, gx = gi % G;
+    const int Yb = Y0 + S * gy, Xb = X0 + S * gx;
+    const int prow = rt * (16 / S);
+    const bool active = !(Yb + prow >= p.H || Xb >= p.W || Yb + prow + 16 / S - 1 < 0 || Xb + S - 1 < 0);  // wave-uniform
+    gbase = (gy * F4 + gx) * CS;
+    f32x4_t acc[TN];   // scores, then (in place) the gradient elements, then (S = 4) the transposed gradient tiles
+    if constexpr (!SUMD) have_d = false;
+    if (active) {
+      float Af[NQ];
+      {
+        const int mo = opaque(m), ko = opaque(kq);
+        const int py_m = prow + mo / S, px_m = mo % S;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + ko) / NT) * tap_w<MODE, S>(px_m, (4 * q + ko) % NT);
+      }
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const float* bp = s_lo + gbase + cell_off[q] + m;
+        float bv[TN];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) bv[t] = bp[16 * t];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Af[q], bv[t], acc[t], 0, 0, 0);
+      }
+      // this lane's four accumulator pixels 4 kq .. 4 kq + 3 of the unit (one row of the tile, four consecutive columns), channel
+      // 16 t + m of tile t
+      const int py4 = prow + (4 * kq) / S, px4 = (4 * kq) % S;
+      const i32x4_t lab4 = *reinterpret_cast<const i32x4_t*>(s_lab + (S * gy + py4) * 16 + S * gx + px4);
+      int dl[4];      // label - lane's channel offset: the label's class sits in tile t where dl == 16 t; -16 where not counted
+      float lsum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dl[r] = lab4[r] >= 0 ? lab4[r] - m : -16;
+      const bool focus = f.gamma != 0.f;   // uniform: gamma == 0 forms no (1 - p_t)^gamma — no 0^0, one transcendental fewer
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        if (16 * t + 16 > p.C) {   // uniform: a tile with channels past C — z = 0 there, and their weight is 0
+          if (16 * t + m >= p.C) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+        const float wc = s_w[16 * t + m];
+        float li[4], g[4];
+        if (focus) {   // a branch per tile
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { g[r] = sigmoid_elem<true>(acc[t][r], dl[r] == 16 * t, f, &li[r]); }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { g[r] = sigmoid_elem<false>(acc[t][r], dl[r] == 16 * t, f, &li[r]); }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float k = wc * (dl[r] == 16 * t ? f.cpos : f.cneg);
+          lsum[r] = __builtin_fmaf(k, li[r], lsum[r]);
+          acc[t][r] = k * g[r];   // (of a pixel that is not counted too: its column of the back-projection is zero)
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float lp = row16_sum(lsum[r]);   // the pixel's loss: its TN tiles in this lane, the 16 lanes of its row
+        if (dl[r] > -16 && m == 0) {
+          loss_acc += lp;
+          cnt_acc += 1.f;
+        }
+      }
+      if (p.dlo) {
+        have_d = true;
+        // pixel 4 kq + jj of the back-projection's K index is this lane's own pixel jj: gscale and the counted mask ride on Bb
+        float Bz[4];
+        const int mo = opaque(m), ko = opaque(kq);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int n = 4 * ko + jj;
+          const float bb = (mo < NT * NT) ? tap_w<MODE, S>(prow + n / S, mo / NT) * tap_w<MODE, S>(n % S, mo % NT) : 0.f;
+          Bz[jj] = dl[jj] > -16 ? bb * p.gscale : 0.f;
+        }
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+          const f32x4_t gv = acc[t];
+          f32x4_t d = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (SUMD) d = dsum[t];
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) d = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[jj], Bz[jj], d, 0, 0, 0);
+          if constexpr (SUMD) dsum[t] = d; else acc[t] = d;   // d[r] = channel 16 t + 4 kq + r of cell m
+        }
+      }
+    }
+    // the waves take turns on the LDS mirror, as in head_ce_grp_kernel: plain 16-byte read-add-write, no LDS atomics
+    if (p.dlo && (!SUMD || g2 == 1)) {
+      constexpr int NTURN = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? 2 : HEAD_THREADS / 64;
+      const int my_turn = (S == 4 && MODE != LC2IS_INTERP_BICUBIC) ? ((wid >> 1) & 1) : wid;
+      for (int turn = 0; turn < NTURN; ++turn) {
+        __syncthreads();
+        if (turn == my_turn && have_d && m < NT * NT) {
+          float* dp = s_dlo + gbase + cellm_off;
+#pragma unroll
+          for (int t = 0; t < TN; ++t) {
+            f32x4_t v = *reinterpret_cast<f32x4_t*>(dp + 16 * t);
+            if constexpr (SUMD) v += dsum[t]; else v += acc[t];
+            *reinterpret_cast<f32x4_t*>(dp + 16 * t) = v;
+          }
+        }
+      }
+    }
+  }
+
+  // the block's [loss, count] partial and its slab: plain stores, summed in a fixed order by head_finish_kernel
+  __shared__ float s_red[HEAD_THREADS / 64][2];
+  loss_acc = wave_sum(loss_acc);
+  cnt_acc = wave_sum(cnt_acc);
+  if (lane == 0) { s_red[wid][0] = loss_acc; s_red[wid][1] = cnt_acc; }
+  __syncthreads();
+  if (tid == 0) {
+    float l = 0.f, c = 0.f;
+#pragma unroll
+    for (int w = 0; w < HEAD_THREADS / 64; ++w) { l += s_red[w][0]; c += s_red[w][1]; }
+    p.ws_loss[2 * (size_t)blockIdx.x] = l;
+    p.ws_loss[2 * (size_t)blockIdx.x + 1] = c;
+  }
+  if (p.dlo) {
+    const int q4 = p.cq >> 2;
+    float* slab = p.ws_dlo + (size_t)blockIdx.x * (F4 * F4) * p.cq;
+    for (int i = tid; i < F4 * F4 * q4; i += HEAD_THREADS) {
+      const int cell = i / q4, c = (i % q4) * 4;
+      *reinterpret_cast<float4*>(slab + (size_t)cell * p.cq + c) = *reinterpret_cast<const float4*>(s_dlo + cell * CS + c);
+    }
+  }
+}
+
 // ---- soft Dice + cross-entropy on the same head (smp's multiclass DiceLoss / MONAI's batch=True form, combined with mean CE) ----
 // Over the counted pixels V of the whole batch, p = softmax of the upsampled scores:
 //   I_c = sum_{i in V, y_i = c} p_ic,  P_c = sum_{i in V} p_ic,  T_c = #{i in V: y_i = c},  U_c = P_c + T_c + s,
@@ -1581,6 +1820,71 @@ __global__ __launch_bounds__(256) void focal_nchw_bwd_kernel(const float* __rest
   }
 }
 
+// Sigmoid cross-entropy / sigmoid focal loss on materialised NCHW logits (the drop-in modules): head_sigmoid_grp_kernel's element
+// terms (sigmoid_elem), a lane per pixel walking its C classes.  Forward: the (sum of l_i, number of counted pixels) block partials,
+// summed in a fixed order by ce_nchw_finish_kernel, and (optional) the per-pixel losses.  Nothing is saved for the backward: no lse.
+__global__ __launch_bounds__(256) void sigmoid_focal_nchw_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                      float* part, int B, int C, size_t HW, long ignore_index,
+                                                                      const float* __restrict__ cw, float* loss_px, SigmoidArgs f) {
+  const size_t total = (size_t)B * HW;
+  float lacc = 0.f, cacc = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / HW, px = i % HW;
+    const float* base = logits + b * C * HW + px;
+    const long lab = (long)labels[i];
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    float li = 0.f;
+    if (counted) {
+      for (int c = 0; c < C; ++c) {
+        float le;
+        if (f.gamma != 0.f) sigmoid_elem<true>(base[(size_t)c * HW], c == lab, f, &le);
+        else sigmoid_elem<false>(base[(size_t)c * HW], c == lab, f, &le);
+        li = __builtin_fmaf((cw ? cw[c] : 1.f) * (c == lab ? f.cpos : f.cneg), le, li);
+      }
+      lacc += li;
+      cacc += 1.f;
+    }
+    if (loss_px) loss_px[i] = li;
+  }
+  lacc = wave_sum(lacc);
+  cacc = wave_sum(cacc);
+  __shared__ float red[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = lacc;
+    red[1][threadIdx.x >> 6] = cacc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    part[2 * blockIdx.x + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ __launch_bounds__(256) void sigmoid_focal_nchw_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                      const float* __restrict__ gscale_dev, float gscale,
+                                                                      const float* __restrict__ grad_px, float* dlogits, int B, int C,
+                                                                      size_t HW, long ignore_index, const float* __restrict__ cw,
+                                                                      SigmoidArgs f) {
+  const size_t total = (size_t)B * HW;
+  const float gs = gscale * (gscale_dev ? *gscale_dev : 1.f);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / HW, px = i % HW;
+    const float* base = logits + b * C * HW + px;
+    float* dbase = dlogits + b * C * HW + px;
+    const long lab = (long)labels[i];
+    const bool counted = lab != ignore_index && lab >= 0 && lab < C;
+    if (!counted) {
+      for (int c = 0; c < C; ++c) dbase[(size_t)c * HW] = 0.f;
+      continue;
+    }
+    const float coef = gs * (grad_px ? grad_px[i] : 1.f);
+    for (int c = 0; c < C; ++c) {
+      float le;
+      const float g = f.gamma != 0.f ? sigmoid_elem<true>(base[(size_t)c * HW], c == lab, f, &le)
+                                     : sigmoid_elem<false>(base[(size_t)c * HW], c == lab, f, &le);
+      dbase[(size_t)c * HW] = (coef * (cw ? cw[c] : 1.f) * (c == lab ? f.cpos : f.cneg)) * g;
+    }
+  }
+}
+
 // Dice + CE on materialised NCHW logits (the drop-in module): the two passes of the fused head, HBM-bound and plain, C <= CMAX.
 // Pass 1: a lane owns a pixel (lse, CE); the class sums of a wave's 64 pixels are wave reductions (T: ballot popcounts) that lane 0
 // adds to the wave's own LDS row; the block's rows are summed in wave order and leave as the block's slab, in the layout of
@@ -2246,5 +2550,109 @@ extern "C" int lc2is_focal_nchw_bwd(const float* logits, const int64_t* labels, 
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(focal_nchw_bwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, lse, grad_scale_dev, grad_scale,
                      grad_px, dlogits, B, C, (size_t)HW, ignore_index, class_weight, FocalArgs{gamma, poly_eps});
+  return lc2is_check_launch();
+}
+
+// ---- sigmoid cross-entropy / sigmoid focal loss: host side ----
+namespace {
+// gamma in [0, inf); alpha <= 1 and not a NaN (any negative value: no alpha); class_scale in (0, inf) (a NaN fails every comparison)
+bool sigmoid_args_ok(float gamma, float alpha, float class_scale) {
+  return gamma >= 0.f && gamma <= 3.0e38f && alpha <= 1.f && class_scale > 0.f && class_scale <= 3.0e38f;
+}
+SigmoidArgs sigmoid_args(float gamma, float alpha, float class_scale) {
+  const bool has = !(alpha < 0.f);
+  return SigmoidArgs{gamma, -gamma * 1.4426950408889634f, class_scale * (has ? alpha : 1.f), class_scale * (has ? 1.f - alpha : 1.f)};
+}
+}  // namespace
+
+extern "C" int lc2is_head_upsample_sigmoid(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo,
+                                           float* loss_sum, int B, int h, int w, int C, int S, int mode, long ignore_index,
+                                           float grad_scale, const float* class_weight, float gamma, float alpha,
+                                           float class_scale, void* workspace, size_t workspace_bytes, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!scores_lo || !labels || !loss_sum) return LC2IS_ERR_NULL;
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || C > CMAX || ld < C || ld > CMAX || ld % 64) return LC2IS_ERR_SHAPE;
+  if (((size_t)scores_lo | (size_t)dscores_lo) & 15) return LC2IS_ERR_SHAPE;
+  if (!sigmoid_args_ok(gamma, alpha, class_scale)) return LC2IS_ERR_SHAPE;
+  if (!(S == 4 || S == 8 || S == 16)) return LC2IS_ERR_UNSUPPORTED;
+  if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return LC2IS_ERR_UNSUPPORTED;
+  const HeadGrpPlan gp = head_grp_plan(B, h, w, C, S, mode, dscores_lo != nullptr);
+  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < gp.loss_bytes + gp.dlo_bytes) return LC2IS_ERR_WORKSPACE;
+  const int H = h * S, W = w * S;
+  HeadArgs a{scores_lo, ld, labels, dscores_lo, nullptr, loss_sum, B, h, w, H, W, C, S, mode, ignore_index,
+             grad_scale, (float*)workspace, dscores_lo ? (float*)((char*)workspace + gp.loss_bytes) : nullptr, gp.cq,
+             class_weight, 0.f};
+  const SigmoidArgs sa = sigmoid_args(gamma, alpha, class_scale);
+  const int nt = (C + 15) / 16;
+  const int tn = nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 10 ? 10 : 12));   // head_upsample_ce's channel-tile counts
+  const int f4 = gp.f4, t4 = gp.t4;
+  // the footprint, its gradient mirror, the tile's labels and the class weights (the OPT variant's layout)
+  const int lds = 2 * f4 * f4 * (ld + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) + CMAX * (int)sizeof(float);
+#define LC2IS_SIGM(MODE_, TN_, S_)                                                                                             \
+  do {                                                                                                                        \
+    static DevOnce attr;                                                                                                      \
+    if (attr.need()) {                                                                                                        \
+      if (hipFuncSetAttribute((const void*)head_sigmoid_grp_kernel<MODE_, TN_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              2 * 7 * 7 * (CMAX + HEAD_PAD) * (int)sizeof(float) + HT * HT * (int)sizeof(int) +               \
+                                  CMAX * (int)sizeof(float)) != hipSuccess)                                                   \
+        return LC2IS_ERR_LAUNCH;                                                                                              \
+      attr.done();                                                                                                            \
+    }                                                                                                                         \
+    hipLaunchKernelGGL((head_sigmoid_grp_kernel<MODE_, TN_, S_>), dim3(B * t4), dim3(HEAD_THREADS), lds, stream, a, sa);      \
+  } while (0)
+#define LC2IS_SIGM_TN(MODE_, S_)                                                                 \
+  do {                                                                                          \
+    if (tn == 4) LC2IS_SIGM(MODE_, 4, S_); else if (tn == 8) LC2IS_SIGM(MODE_, 8, S_);           \
+    else if (tn == 10) LC2IS_SIGM(MODE_, 10, S_); else LC2IS_SIGM(MODE_, 12, S_);                \
+  } while (0)
+#define LC2IS_SIGM_S(MODE_)                                                                                          \
+  do {                                                                                                              \
+    if (S == 4) LC2IS_SIGM_TN(MODE_, 4); else if (S == 8) LC2IS_SIGM_TN(MODE_, 8); else LC2IS_SIGM_TN(MODE_, 16);   \
+  } while (0)
+  if (mode == LC2IS_INTERP_BICUBIC) LC2IS_SIGM_S(LC2IS_INTERP_BICUBIC);
+  else LC2IS_SIGM_S(LC2IS_INTERP_BILINEAR);
+#undef LC2IS_SIGM_S
+#undef LC2IS_SIGM_TN
+#undef LC2IS_SIGM
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  // second launch: head_finish_kernel's fixed-order sums of the slabs (one wave per low-res cell) and of the loss partials
+  const long ncell = dscores_lo ? (long)B * h * w : 1;
+  const int fgrid = (int)((ncell + 3) / 4);
+#define LC2IS_HEAD_FIN(MODE_, S_) hipLaunchKernelGGL((head_finish_kernel<MODE_, S_>), dim3(fgrid), dim3(256), 0, stream, a, B * t4)
+  if (mode == LC2IS_INTERP_BICUBIC) { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BICUBIC, 16); }
+  else { if (S == 4) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 4); else if (S == 8) LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 8); else LC2IS_HEAD_FIN(LC2IS_INTERP_BILINEAR, 16); }
+#undef LC2IS_HEAD_FIN
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_sigmoid_focal_nchw_fwd(const float* logits, const int64_t* labels, float* loss_sum, float* loss_px, int B,
+                                            int C, long HW, long ignore_index, const float* class_weight, float gamma,
+                                            float alpha, float class_scale, void* workspace, size_t workspace_bytes,
+                                            lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !loss_sum || !workspace) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0 || !sigmoid_args_ok(gamma, alpha, class_scale)) return LC2IS_ERR_SHAPE;
+  const size_t g = ce_nchw_fwd_grid(B, HW);
+  if (workspace_bytes < 2 * sizeof(float) * g) return LC2IS_ERR_WORKSPACE;
+  hipLaunchKernelGGL(sigmoid_focal_nchw_fwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, (float*)workspace, B, C,
+                     (size_t)HW, ignore_index, class_weight, loss_px, sigmoid_args(gamma, alpha, class_scale));
+  int rc = lc2is_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(ce_nchw_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)workspace, (int)g, loss_sum);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_sigmoid_focal_nchw_bwd(const float* logits, const int64_t* labels, const float* grad_scale_dev,
+                                            float grad_scale, const float* grad_px, float* dlogits, int B, int C, long HW,
+                                            long ignore_index, const float* class_weight, float gamma, float alpha,
+                                            float class_scale, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!logits || !labels || !dlogits) return LC2IS_ERR_NULL;
+  if (B <= 0 || C <= 0 || HW <= 0 || !sigmoid_args_ok(gamma, alpha, class_scale)) return LC2IS_ERR_SHAPE;
+  size_t g = ((size_t)B * HW + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(sigmoid_focal_nchw_bwd_kernel, dim3((int)g), dim3(256), 0, stream, logits, labels, grad_scale_dev, grad_scale,
+                     grad_px, dlogits, B, C, (size_t)HW, ignore_index, class_weight, sigmoid_args(gamma, alpha, class_scale));
   return lc2is_check_launch();
 }

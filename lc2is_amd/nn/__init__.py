@@ -6,7 +6,7 @@ from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import (CrossABlock, FTNBlock, FTNDecoder, HierarchicalCrossA, HierarchicalSelfA, SelfABlock,
                    SRTransformerCrossA, SRTransformerDecoder, SRTransformerSelfA)
 from .loss import (AuxiliaryLoss, ContrastiveLoss, CrossEntropyLoss, DiceCrossEntropyLoss, FocalLoss, NPairLoss, OhemCrossEntropyLoss,
-                   Poly1CrossEntropyLoss)
+                   Poly1CrossEntropyLoss, SigmoidCrossEntropyLoss, SigmoidFocalLoss)
 from .model import BaseModelWithText, ContrastiveModel, TextToPatch
 from .compose import DenseClip, PromptFTN
 from .score import ScoreMapTail
@@ -14,7 +14,7 @@ from . import ftn  # model/ftn.py's Decoder / Transformer keep their (generic) n
 from .swin import SWIN_B, SWIN_S, SWIN_T, SwinArch, SwinTransformer
 
 __all__ = ["HipModule", "ParamArena", "ClipArch", "ImageEncoderCLIP", "ImageEncoderCLIPFull", "TextEncoderCLIP",
-           "TextEncoderCLIPPooler", "DecoderBlock", "DecoderLayer", "PromptDecoder", "PromptLayer", "AuxiliaryLoss", "ContrastiveLoss", "CrossEntropyLoss", "NPairLoss", "OhemCrossEntropyLoss", "DiceCrossEntropyLoss", "FocalLoss", "Poly1CrossEntropyLoss",
+           "TextEncoderCLIPPooler", "DecoderBlock", "DecoderLayer", "PromptDecoder", "PromptLayer", "AuxiliaryLoss", "ContrastiveLoss", "CrossEntropyLoss", "NPairLoss", "OhemCrossEntropyLoss", "DiceCrossEntropyLoss", "FocalLoss", "Poly1CrossEntropyLoss", "SigmoidFocalLoss", "SigmoidCrossEntropyLoss",
            "BaseModelWithText", "ContrastiveModel", "TextToPatch", "PromptFTN", "DenseClip", "ScoreMapTail", "CrossABlock", "FTNBlock", "FTNDecoder", "HierarchicalCrossA",
            "HierarchicalSelfA", "SelfABlock", "SRTransformerCrossA", "SRTransformerDecoder", "SRTransformerSelfA", "VIT_B16", "VIT_L14", "TEXT_B", "TEXT_L", "SwinTransformer", "SwinArch",
            "SWIN_T", "SWIN_S", "SWIN_B", "ftn"]

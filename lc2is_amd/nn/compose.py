@@ -25,7 +25,7 @@ from .base import assign_rng_names, require_cuda
 from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import FTNDecoder
-from .model import TextToPatch, fused_focal_options, fused_loss_options
+from .model import TextToPatch, fused_focal_options, fused_loss_options, fused_sigmoid_options
 from .score import KPAD, ScoreMapTail, _scores_bwd, _scores_lo
 from .swin import SWIN_B, SwinArch, SwinTransformer
 
@@ -70,13 +70,16 @@ class PromptFTN(nn.Module):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None,
-                     focal=None) -> torch.Tensor:
+                     focal=None, sigmoid=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
         materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
         {intersection, predicted, labelled} counts (``ScoreMapTail.loss``).  ``accum``: the device block of a gradient-accumulation
         cycle (``ScoreMapTail.loss``; ``TrainStep(accumulate=N)``).  ``focal=(gamma, poly_eps)``: FocalLoss's per-pixel loss in
-        place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``."""
-        fused_focal_options(focal, label_smoothing, None)        # (refused before the towers run)
+        place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``.  ``sigmoid=(gamma, alpha,
+        normalize)``: SigmoidFocalLoss's per-class binary loss instead (``ScoreMapTail.loss``); not combinable with ``focal=`` or
+        ``label_smoothing``."""
+        fused_sigmoid_options(sigmoid, label_smoothing, None, focal)   # (refused before the towers run)
+        fused_focal_options(focal, label_smoothing, None)
         fused_loss_options(weight, label_smoothing, reduction)
         if seg_counts is not None:
             ops.check_seg_counts(seg_counts)
@@ -84,6 +87,8 @@ class PromptFTN(nn.Module):
         extra = {} if accum is None else {"accum": accum}
         if focal is not None:
             extra["focal"] = focal
+        if sigmoid is not None:
+            extra["sigmoid"] = sigmoid
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
                               label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, **extra)
 

@@ -260,6 +260,81 @@ class Poly1CrossEntropyLoss(FocalLoss):
         return self.poly_eps
 
 
+def check_sigmoid(gamma, alpha, normalize="elements"):
+    """(gamma, alpha, normalize) of a sigmoid focal / sigmoid cross-entropy loss, validated: gamma a finite number >= 0, alpha None
+    or a number in [0, 1], normalize 'elements' or 'pixels'."""
+    return ops.sigmoid_options(gamma, alpha, normalize)
+
+
+class _SigmoidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, weight, sigmoid, reduction):
+        lg = logits.float().contiguous()
+        lb = labels.contiguous()
+        kw = dict(class_weight=weight, gamma=sigmoid[0], alpha=sigmoid[1],
+                  class_scale=ops.sigmoid_class_scale(sigmoid[2], reduction, lg.shape[1]))
+        out = ops.sigmoid_focal_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
+        loss2 = out[0] if reduction == "none" else out
+        ctx.saved = (lg, lb, loss2, ignore_index, kw, reduction)
+        if reduction == "none":
+            return out[1]
+        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lb, loss2, ignore_index, kw, reduction = ctx.saved
+        if reduction == "none":
+            d = ops.sigmoid_focal_nchw_bwd(lg, lb, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
+        else:   # device scalar: upstream gradient (over the number of counted pixels for 'mean')
+            scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
+            d = ops.sigmoid_focal_nchw_bwd(lg, lb, scale, 1.0, ignore_index, **kw)
+        return d, None, None, None, None, None
+
+
+class SigmoidFocalLoss(CrossEntropyLoss):
+    """Sigmoid focal loss (Lin et al. 2017, RetinaNet): ``torchvision.ops.sigmoid_focal_loss`` / mmseg's ``FocalLoss`` on one-hot
+    targets.  Per counted pixel (label != ignore_index, 0 <= label < C) and class c, with t = [c == label], p = sigmoid(z_c) and
+    p_t = t ? p : 1 - p:  l_c = weight[c] * a_t * (1 - p_t)^gamma * (-log p_t), a_t = alpha for the label's class and 1 - alpha for
+    the others (1 when ``alpha`` is None).  No softmax: the classes of a pixel do not compete.  ``weight`` scales class c's binary
+    term (mmseg's ``class_weight``).  'none' is the [B,H,W] map of the sums over the classes; 'sum' adds them up; 'mean' divides by
+    a COUNT of elements, torch's and mmseg's rule for binary losses — counted pixels x C with ``normalize='elements'`` (torch's
+    elementwise mean), counted pixels with ``normalize='pixels'`` — never by a weight sum: this deliberately differs from the
+    softmax ``CrossEntropyLoss`` / ``FocalLoss`` of this package, whose 'mean' divides by the summed class weights.  log p and
+    log(1 - p) are formed as -softplus(-z) and -softplus(z), so saturated scores give finite losses and gradients for every
+    gamma >= 0.  ``label_smoothing`` must be 0 (ValueError).  ``TrainStep(criterion=SigmoidFocalLoss(...))`` trains through the fused
+    head (``forward_loss(sigmoid=...)``)."""
+
+    def __init__(self, gamma: float = 2.0, alpha=0.25, weight=None, ignore_index: int = -100, reduction: str = "mean",
+                 normalize: str = "elements", label_smoothing: float = 0.0) -> None:
+        if label_smoothing != 0.0:
+            raise ValueError("SigmoidFocalLoss: label_smoothing is not defined for the sigmoid losses")
+        super().__init__(weight=weight, ignore_index=ignore_index, reduction=reduction)
+        self.gamma, self.alpha, self.normalize = check_sigmoid(gamma, alpha, normalize)
+
+    @property
+    def sigmoid(self):
+        return self.gamma, self.alpha, self.normalize
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        require_cuda(input, "logits")
+        if input.dim() != 4 or target.dim() != 3:
+            raise ValueError("lc2is_amd SigmoidFocalLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        if self.label_smoothing != 0.0:
+            raise ValueError("SigmoidFocalLoss: label_smoothing is not defined for the sigmoid losses")
+        return _SigmoidFn.apply(input, target, self.ignore_index, self.weight, check_sigmoid(*self.sigmoid), self.reduction)
+
+
+class SigmoidCrossEntropyLoss(SigmoidFocalLoss):
+    """Binary cross-entropy with logits on one-hot targets (``torch.nn.BCEWithLogitsLoss``, mmseg's
+    ``CrossEntropyLoss(use_sigmoid=True)``): ``SigmoidFocalLoss(gamma=0, alpha=None)`` with its reductions and its 'mean'
+    denominator (a count of elements, not a weight sum)."""
+
+    def __init__(self, weight=None, ignore_index: int = -100, reduction: str = "mean", normalize: str = "elements",
+                 label_smoothing: float = 0.0) -> None:
+        super().__init__(gamma=0.0, alpha=None, weight=weight, ignore_index=ignore_index, reduction=reduction, normalize=normalize,
+                         label_smoothing=label_smoothing)
+
+
 class _AuxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, ignore_index, S, weight, label_smoothing, reduction):

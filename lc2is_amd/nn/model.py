@@ -21,7 +21,7 @@ from .. import ops
 from .base import HipModule, grad_buf, linear_bwd_params, require_cuda, vec_grad
 from .clip import ClipArch, ImageEncoderCLIP, TextEncoderCLIP, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer
-from .loss import check_dice, check_focal, check_ohem
+from .loss import check_dice, check_focal, check_ohem, check_sigmoid
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
 KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product)
@@ -109,6 +109,16 @@ def fused_focal_options(focal, label_smoothing: float, dice):
     return check_focal(*focal)
 
 
+def fused_sigmoid_options(sigmoid, label_smoothing: float, dice, focal):
+    """``sigmoid`` = (gamma, alpha, normalize) validated, or None; the sigmoid focal / sigmoid cross-entropy loss keeps weight=,
+    reduction=, ohem=, seg_counts= and accum=, and does not combine with a Dice term, the softmax focal loss or label smoothing."""
+    if sigmoid is None:
+        return None
+    if dice is not None or focal is not None or label_smoothing != 0.0:
+        raise ValueError("lc2is_amd: sigmoid= cannot be combined with dice=, focal= or label_smoothing")
+    return check_sigmoid(*sigmoid)
+
+
 def _reduce(loss2, reduction: str, save: bool):
     """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
     gives torch's NaN mean and a zero gradient, with no host sync."""
@@ -123,8 +133,11 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None,
-                accum=None, focal=None):
-        out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal)
+                accum=None, focal=None, sigmoid=None):
+        if sigmoid is None:   # (the call as it was)
+            out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal)
+        else:
+            out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal, sigmoid)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -132,7 +145,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None, None, None, None, None
+        return ddec, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class BaseModelWithText(HipModule):
@@ -190,7 +203,7 @@ class BaseModelWithText(HipModule):
         return ft16, fv16, scores
 
     def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None, accum=None,
-                  focal=None):
+                  focal=None, sigmoid=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
@@ -217,7 +230,13 @@ class BaseModelWithText(HipModule):
         # the kernel writes the gradient of the SUM of the per-pixel losses and counts the pixels it kept (labels that are
         # negative, == ignore_index or >= K are skipped, head.hip); the 1/count of nn.CrossEntropyLoss's mean is folded
         # into the upstream-gradient multiply of _head_bwd, from the device-side count (no host sync, no label pass)
-        if focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
+        if sigmoid is not None:   # sigmoid focal / sigmoid CE: per-class binary terms, [sum, NUMBER of counted pixels]
+            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
+            loss2, dlo = ops.head_upsample_sigmoid(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
+                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight, gamma=sigmoid[0],
+                                                   alpha=sigmoid[1], class_scale=ops.sigmoid_class_scale(sigmoid[2], reduction, K))
+            loss, inv_count = _reduce(loss2, reduction, save)
+        elif focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
             weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
             loss2, dlo = ops.head_upsample_focal(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
                                                  ignore_index=ignore_index, grad_scale=1.0, class_weight=weight, gamma=focal[0],
@@ -315,7 +334,7 @@ class BaseModelWithText(HipModule):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                     seg_counts=None, accum=None, focal=None) -> torch.Tensor:
+                     seg_counts=None, accum=None, focal=None, sigmoid=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
@@ -335,9 +354,18 @@ class BaseModelWithText(HipModule):
         pixel in place of the cross-entropy (FocalLoss's definition: 'mean' divides by the sum of w_y), one forward + backward
         launch of the head.  Keeps ``weight``, ``reduction``, ``seg_counts``, ``accum`` (a per-pixel loss: the sums add) and ``ohem``
         (the selection still ranks by the plain CE; the relabelled call is the focal one); not combinable with ``dice=`` or
-        ``label_smoothing``.  None: the call as it was."""
+        ``label_smoothing``.  None: the call as it was.
+        ``sigmoid=(gamma, alpha, normalize)``: the sigmoid focal loss (gamma = 0, alpha None: binary cross-entropy with logits on
+        one-hot targets) in place of the cross-entropy — per counted pixel the sum over the K classes of w_c a_t (1 - p_t)^gamma
+        (-log p_t) with p = sigmoid(score), no softmax (SigmoidFocalLoss's definition), one forward + backward launch of the head.
+        'mean' divides by a COUNT — counted pixels x K with normalize 'elements', counted pixels with 'pixels' — not by a weight sum:
+        torch's and mmseg's rule for binary losses, deliberately different from the softmax losses above.  Keeps ``weight`` (on
+        class c's binary term), ``reduction``, ``seg_counts``, ``accum`` and ``ohem`` (the selection still ranks by the plain softmax
+        CE; the relabelled call is the sigmoid one); not combinable with ``dice=``, ``focal=`` or ``label_smoothing``
+        (``ValueError`` before the towers run).  None: the call as it was."""
         if accum is not None and dice is not None:
             raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
+        sigmoid = fused_sigmoid_options(sigmoid, label_smoothing, dice, focal)
         focal = fused_focal_options(focal, label_smoothing, dice)
         opts = fused_loss_options(weight, label_smoothing, reduction)
         if ohem is not None:
@@ -347,6 +375,9 @@ class BaseModelWithText(HipModule):
             ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
+        if sigmoid is not None:
+            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum,
+                                 None, sigmoid)
         if focal is not None:
             return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum,
                                  focal)

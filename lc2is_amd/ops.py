@@ -93,6 +93,9 @@ _ARGTYPES = {
     "lc2is_head_upsample_focal": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _F, _P, _Z, _P],
     "lc2is_focal_nchw_fwd": [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _F, _F, _P, _Z, _P],
     "lc2is_focal_nchw_bwd": [_P, _P, _P, _P, _F, _P, _P, _I, _I, _L, _L, _P, _F, _F, _P],
+    "lc2is_head_upsample_sigmoid": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _F, _F, _P, _Z, _P],
+    "lc2is_sigmoid_focal_nchw_fwd": [_P, _P, _P, _P, _I, _I, _L, _L, _P, _F, _F, _F, _P, _Z, _P],
+    "lc2is_sigmoid_focal_nchw_bwd": [_P, _P, _P, _F, _P, _P, _I, _I, _L, _L, _P, _F, _F, _F, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -1262,6 +1265,110 @@ def focal_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float = 1.0,
     _lib.check(_fn("lc2is_focal_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale, _ptr(grad_px),
                                            _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight), gamma, poly_eps, _stream()),
                "focal_nchw_bwd")
+    return d
+
+
+# ---- sigmoid cross-entropy / sigmoid focal loss: per-class binary terms, no softmax, one pass ----
+def sigmoid_options(gamma, alpha, normalize: str = "elements"):
+    """(gamma, alpha, normalize) of a sigmoid focal / sigmoid cross-entropy loss, validated: gamma a finite number >= 0 (returned as
+    a float), alpha None or a number in [0, 1] (returned as None or a float), normalize 'elements' or 'pixels'."""
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma) or gamma < 0:
+        raise ValueError(f"sigmoid focal loss: gamma must be a finite number >= 0, got {gamma!r}")
+    if alpha is not None and (isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha <= 1.0):
+        raise ValueError(f"sigmoid focal loss: alpha must be None or a number in [0, 1], got {alpha!r}")
+    if normalize not in ("elements", "pixels"):
+        raise ValueError(f"sigmoid focal loss: normalize must be 'elements' or 'pixels', got {normalize!r}")
+    return float(gamma), None if alpha is None else float(alpha), normalize
+
+
+def sigmoid_class_scale(normalize: str, reduction: str, C: int) -> float:
+    """The factor on a pixel's sum over its C classes: 1 / C for a 'mean' over elements (torch's mean of a binary loss), else 1."""
+    return 1.0 / C if (normalize == "elements" and reduction == "mean") else 1.0
+
+
+def _sigmoid_args(gamma, alpha, class_scale):
+    gamma, alpha, _ = sigmoid_options(gamma, alpha)
+    if isinstance(class_scale, bool) or not isinstance(class_scale, (int, float)) or not math.isfinite(class_scale) or class_scale <= 0:
+        raise ValueError(f"sigmoid focal loss: class_scale must be a finite number > 0, got {class_scale!r}")
+    return gamma, -1.0 if alpha is None else alpha, float(class_scale)   # (the C entry points read any negative alpha as "none")
+
+
+def head_upsample_sigmoid(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                          want_grad: bool = False, ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None,
+                          gamma: float = 2.0, alpha=0.25, class_scale: float = 1.0):
+    """Sigmoid focal loss / sigmoid cross-entropy of the upsampled scores (S = 4 / 8 / 16): scores_lo fp32 [B*h*w, ld], labels int64
+    [B, h*S, w*S].  Per counted pixel and class c, with t = [c == label], p = sigmoid(z), p_t = t ? p : 1 - p:
+    l_c = w_c a_t (1 - p_t)^gamma (-ln p_t), a_t = alpha / 1 - alpha (1 when alpha is None); the pixel's loss is class_scale * sum_c
+    l_c.  Returns (loss2 = [sum of the pixel losses, NUMBER of counted pixels], dscores_lo or None = grad_scale * d(sum) / d
+    scores_lo).  One forward + backward launch and the finish launch of ``head_upsample_ce``; nothing syncs, no atomics, the same
+    bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError("lc2is_amd.head_upsample_sigmoid: scores_lo must be contiguous")
+    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: labels must be contiguous [{B},{h*S},{w*S}]")
+    if S not in (4, 8, 16):
+        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: S must be 4, 8 or 16, got {S}")
+    ld = scores_lo.shape[1]
+    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
+        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
+                           f"got {tuple(scores_lo.shape)}")
+    dev = scores_lo.device
+    _focal_weight(class_weight, C, dev)
+    nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
+    if nbytes == 0:
+        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    _lib.check(_fn("lc2is_head_upsample_sigmoid")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
+                                                  ignore_index, grad_scale, _ptr(class_weight), gamma, alpha, class_scale, _ptr(ws),
+                                                  nbytes, _stream()), f"head_upsample_sigmoid B={B} h={h} w={w} C={C} S={S}")
+    return loss, dlo
+
+
+def sigmoid_focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, gamma: float = 2.0, alpha=0.25,
+                           class_scale: float = 1.0, per_pixel: bool = False):
+    """The same loss on NCHW fp32 logits.  Returns loss2 = [sum of the pixel losses, number of counted pixels] and, with
+    per_pixel=True, (loss2, the per-pixel losses [B,H,W], 0 where not counted).  Nothing is saved for the backward."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
+    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
+        raise RuntimeError("lc2is_amd.sigmoid_focal_nchw_fwd: logits/labels must be contiguous")
+    B, Cc, H, W = logits.shape
+    if tuple(labels.shape) != (B, H, W):
+        raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_fwd: labels must be [{B},{H},{W}]")
+    dev = logits.device
+    _focal_weight(class_weight, Cc, dev)
+    loss = torch.empty(2, dtype=torch.float32, device=dev)   # overwritten: block partials summed in a fixed order
+    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lpx = torch.empty((B, H, W), dtype=torch.float32, device=dev) if per_pixel else None
+    _lib.check(_fn("lc2is_sigmoid_focal_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(loss), _ptr(lpx), B, Cc, H * W, ignore_index,
+                                                   _ptr(class_weight), gamma, alpha, class_scale, _ptr(ws), nbytes, _stream()),
+               "sigmoid_focal_nchw_fwd")
+    return (loss, lpx) if per_pixel else loss
+
+
+def sigmoid_focal_nchw_bwd(logits, labels, grad_scale_dev, grad_scale: float = 1.0, ignore_index: int = -100, *, class_weight=None,
+                           gamma: float = 2.0, alpha=0.25, class_scale: float = 1.0, grad_px=None):
+    """dlogits = grad_scale * grad_scale_dev (device scalar or None) * grad_px (per pixel, [B,H,W] fp32, optional) * dl_i/dlogits."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
+    B, Cc, H, W = logits.shape
+    if not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W):
+        raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_bwd: contiguous logits [B,C,H,W] with labels [{B},{H},{W}] required")
+    _focal_weight(class_weight, Cc, logits.device)
+    if grad_px is not None:
+        _chk(grad_px, torch.float32, "grad_px", 3)
+        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
+            raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    d = torch.empty_like(logits)
+    _lib.check(_fn("lc2is_sigmoid_focal_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(grad_scale_dev), grad_scale, _ptr(grad_px),
+                                                   _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight), gamma, alpha, class_scale,
+                                                   _stream()), "sigmoid_focal_nchw_bwd")
     return d
 
 

@@ -24,6 +24,9 @@ eager, captured, under a reducer — each rank takes the statistics of its own b
 tensors (I, P, T, loss block).  The loss is deterministic, so the criterion's ``eval()`` mode changes nothing.  An
 ``lc2is_amd.nn.FocalLoss`` / ``Poly1CrossEntropyLoss`` trains on its per-pixel loss through the fused head in the launches of the
 plain step (``forward_loss(focal=...)``; its ``weight`` and 'mean' / 'sum' apply): eager, captured, under ``accumulate=N``, with
+``seg_metrics=True`` and under a reducer.  An ``lc2is_amd.nn.SigmoidFocalLoss`` / ``SigmoidCrossEntropyLoss`` (per-class binary
+terms, no softmax; 'mean' divides by a count of elements or pixels, not a weight sum) trains the same way through
+``forward_loss(sigmoid=...)``: eager, captured, under ``accumulate=N`` (``accum_count`` is then the number of counted pixels), with
 ``seg_metrics=True`` and under a reducer.
 
 The device-held path (opt-in: any of ``lr_schedule``, ``max_grad_norm``, ``skip_nonfinite``, ``device_state``) adds what the
@@ -76,6 +79,12 @@ def _accepts_focal(model) -> bool:
     import inspect
     fl = getattr(model, "forward_loss", None)
     return fl is not None and "focal" in inspect.signature(fl).parameters
+
+
+def _accepts_sigmoid(model) -> bool:
+    import inspect
+    fl = getattr(model, "forward_loss", None)
+    return fl is not None and "sigmoid" in inspect.signature(fl).parameters
 
 
 def _accepts_seg_counts(model) -> bool:
@@ -426,7 +435,8 @@ class TrainStep:
         self._ohem = False
         self._dice = False
         if criterion is not None:
-            from .nn.loss import AuxiliaryLoss, CrossEntropyLoss, DiceCrossEntropyLoss, FocalLoss, OhemCrossEntropyLoss
+            from .nn.loss import (AuxiliaryLoss, CrossEntropyLoss, DiceCrossEntropyLoss, FocalLoss, OhemCrossEntropyLoss,
+                                  SigmoidFocalLoss)
             if not isinstance(criterion, (CrossEntropyLoss, nn.CrossEntropyLoss)) or isinstance(criterion, AuxiliaryLoss):
                 raise TypeError("TrainStep: criterion must be a CrossEntropyLoss (lc2is_amd.nn or torch.nn)")
             if ignore_index is not None and ignore_index != -100:
@@ -448,6 +458,11 @@ class TrainStep:
                 if not _accepts_focal(model):
                     raise TypeError("TrainStep: a FocalLoss / Poly1CrossEntropyLoss needs a model whose forward_loss takes focal= "
                                     "(BaseModelWithText, PromptFTN)")
+                self._loss_opts = True
+            if isinstance(criterion, SigmoidFocalLoss):   # rides the options call too: weight=, reduction= and sigmoid=(gamma, alpha, normalize)
+                if not _accepts_sigmoid(model):
+                    raise TypeError("TrainStep: a SigmoidFocalLoss / SigmoidCrossEntropyLoss needs a model whose forward_loss takes "
+                                    "sigmoid= (BaseModelWithText, PromptFTN)")
                 self._loss_opts = True
         self.criterion = criterion
         self.model = model
@@ -747,6 +762,9 @@ class TrainStep:
             focal = getattr(c, "focal", None)   # a FocalLoss / Poly1CrossEntropyLoss: its (gamma, poly_eps) as they are now
             if focal is not None:
                 seg["focal"] = focal
+            sigmoid = getattr(c, "sigmoid", None)   # a SigmoidFocalLoss / SigmoidCrossEntropyLoss: (gamma, alpha, normalize) as they are now
+            if sigmoid is not None:
+                seg["sigmoid"] = sigmoid
             loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
                                            label_smoothing=float(c.label_smoothing), reduction=c.reduction, **seg)
         else:
