@@ -950,6 +950,40 @@ int lc2is_sigmoid_focal_nchw_bwd(const float* logits, const int64_t* labels, con
                                  const float* grad_px, float* dlogits, int B, int C, long HW, long ignore_index,
                                  const float* class_weight, float gamma, float alpha, float class_scale, lc2is_stream_t stream);
 
+/* ---- the fused head past 192 classes: cross-entropy, class map and counts for C <= 1024 ------------------------------------
+ * The entry points above keep every class of a pixel in registers and the whole footprint in LDS, and stop at 192 classes.  These
+ * two walk the class axis in chunks of 192 channels (the tile plan, products and summation orders are lc2is_head_upsample_ce's):
+ * 1 <= C <= ld <= LC2IS_HEAD_WIDE_CMAX, ld % 64 == 0 (ld need not be the smallest pad), scores_lo fp32 [B,h,w,ld] channels-last,
+ * 16-byte aligned, else LC2IS_ERR_SHAPE; S == 4 and a known mode, else LC2IS_ERR_UNSUPPORTED.  C <= 192 is accepted (the narrow
+ * entry points are the faster ones there).  The [B,C,H,W] map is never materialised.
+ *
+ * lc2is_head_upsample_ce_wide: lc2is_head_upsample_ce_opts with label_smoothing = 0.  Two sweeps over the chunks — an online
+ * softmax (running maximum, rescaled sum, the label's logit), then the gradient with the logits formed again — and the fixed-order
+ * finish launch.  loss_sum[0] = sum_i w_y (lse_i - z_iy), loss_sum[1] = sum_i w_y over the counted pixels (label != ignore_index &&
+ * 0 <= label < C); class_weight: device fp32 [C] or NULL (all ones).  dscores_lo (NULL: loss only, one sweep) = grad_scale * U^T
+ * (w_y (softmax - onehot)), all ld channels overwritten, exactly 0 at and past C.  workspace: 16-byte aligned, >=
+ * lc2is_head_upsample_ce_wide_workspace_bytes(B, h, w, C, ld, S, mode, dscores_lo != NULL) = B * tiles * 2 floats rounded up to 256
+ * bytes + (gradient wanted) B * tiles * f^2 * cq floats, tiles = ceil((4h + 2) / 16) * ceil((4w + 2) / 16), f = 7 bicubic / 5 bilinear,
+ * cq = C rounded up to 4 (else LC2IS_ERR_WORKSPACE).
+ * lc2is_head_upsample_argmax_wide: lc2is_head_upsample_argmax with pred int16 [B,H,W]; the running (value, class) of a pixel is
+ * replaced only by a strictly larger value of a later chunk, so exact ties go to the lowest class.  counts int32 [B][3][C] needs
+ * labels and a workspace >= lc2is_head_upsample_argmax_wide_workspace_bytes(...) = B * tiles * 3 * cq int32; a pred-only call takes
+ * no workspace (and labels may be NULL).
+ * Both: refusals in the order NULL, SHAPE, UNSUPPORTED, WORKSPACE, from the arguments alone, before any launch; the workspace queries
+ * are pure host functions, 0 for a call that would be refused.  NO read-modify-write atomics, LDS included: the same bytes every
+ * run; captures into a graph.
+ * replaces: F.interpolate(scale_factor=4) + nn.CrossEntropyLoss(weight=) and .argmax(1) + intersect_and_union() on the [B,K,H,W]
+ *   logits of an open-vocabulary class set (PC-459, ADE20K-full 847, ImageNet-S-919), plus their autograd. */
+#define LC2IS_HEAD_WIDE_CMAX 1024
+size_t lc2is_head_upsample_ce_wide_workspace_bytes(int B, int h, int w, int C, int ld, int S, int mode, int want_grad);
+int lc2is_head_upsample_ce_wide(const float* scores_lo, int ld, const int64_t* labels, float* dscores_lo, float* loss_sum, int B,
+                                int h, int w, int C, int S, int mode, long ignore_index, float grad_scale,
+                                const float* class_weight, void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+size_t lc2is_head_upsample_argmax_wide_workspace_bytes(int B, int h, int w, int C, int S, int mode);
+int lc2is_head_upsample_argmax_wide(const float* scores_lo, int ld, const int64_t* labels, int16_t* pred, int32_t* counts, int B,
+                                    int h, int w, int C, int S, int mode, long ignore_index, void* workspace,
+                                    size_t workspace_bytes, lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

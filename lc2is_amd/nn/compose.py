@@ -26,7 +26,7 @@ from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import FTNDecoder
 from .model import TextToPatch, fused_focal_options, fused_loss_options, fused_sigmoid_options
-from .score import KPAD, ScoreMapTail, _scores_bwd, _scores_lo
+from .score import ScoreMapTail, _scores_bwd, _scores_lo
 from .swin import SWIN_B, SwinArch, SwinTransformer
 
 
@@ -94,7 +94,8 @@ class PromptFTN(nn.Module):
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:
-        """The class map of the score map, uint8 [B,512,512]: ``forward(inputs)[1].argmax(1)`` without writing the map."""
+        """The class map of the score map, uint8 [B,512,512] (int16 past 192 classes): ``forward(inputs)[1].argmax(1)`` without writing
+        the map."""
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         return self.tail.predict(visual_embeddings, text_embeddings)
 
@@ -107,15 +108,16 @@ class _ScoreGridFn(torch.autograd.Function):
         B, P, _ = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
-        scores, sv = _scores_lo(visual, text)                                                    # [B*P, KPAD] fp32
+        scores, sv = _scores_lo(visual, text)                                                    # [B*P, class_pad(K)] fp32
         ctx.sv, ctx.dims = (sv if save else None), (B, P, K, h)
-        return scores.view(B, P, KPAD)[:, :, :K].transpose(1, 2).reshape(B, K, h, h)
+        return scores.view(B, P, -1)[:, :, :K].transpose(1, 2).reshape(B, K, h, h)
 
     @staticmethod
     def backward(ctx, gout):
         B, P, K, h = ctx.dims
-        ds = torch.zeros(B * P, KPAD, dtype=torch.float32, device=gout.device)
-        ds.view(B, P, KPAD)[:, :, :K] = gout.reshape(B, K, P).transpose(1, 2)
+        kpad = ops.class_pad(K)
+        ds = torch.zeros(B * P, kpad, dtype=torch.float32, device=gout.device)
+        ds.view(B, P, kpad)[:, :, :K] = gout.reshape(B, K, P).transpose(1, 2)
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = None
         return dv, dt, None

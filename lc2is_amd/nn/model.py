@@ -24,7 +24,7 @@ from .decoder import DecoderBlock, DecoderLayer
 from .loss import check_dice, check_focal, check_ohem, check_sigmoid
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
-KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product)
+KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product); past 192 classes: ops.class_pad(K)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -119,6 +119,49 @@ def fused_sigmoid_options(sigmoid, label_smoothing: float, dice, focal):
     return check_sigmoid(*sigmoid)
 
 
+def wide_refuse(who: str, K: int, scale: int, label_smoothing: float, ohem, dice, focal, sigmoid) -> None:
+    """Past 192 classes the fused head is the chunked cross-entropy (``ops.head_upsample_ce_wide``): plain CE with ``weight=``,
+    'mean' / 'sum', ``ignore_index``, ``seg_counts=`` and ``accum=`` at scale 4.  Every other criterion keeps its kernel's 192-class
+    limit and is refused here, before anything is allocated or launched."""
+    if K <= ops.HEAD_CMAX:
+        return
+    if K > ops.HEAD_WIDE_CMAX:
+        raise NotImplementedError(f"lc2is_amd {who}: at most {ops.HEAD_WIDE_CMAX} classes are supported by the fused head, got {K}")
+    for name, on in (("label_smoothing", label_smoothing != 0.0), ("ohem=", ohem is not None), ("dice=", dice is not None),
+                     ("focal=", focal is not None), ("sigmoid=", sigmoid is not None)):
+        if on:
+            raise NotImplementedError(f"lc2is_amd {who}: {name} is limited to {ops.HEAD_CMAX} classes (its fused kernel keeps every "
+                                      f"class of a pixel in registers); {K} classes train with the plain cross-entropy "
+                                      "(weight=, reduction=, ignore_index, seg_counts=, accum=)")
+    if scale != 4:
+        raise NotImplementedError(f"lc2is_amd {who}: past {ops.HEAD_CMAX} classes the fused head upsamples by 4 only, got {scale}")
+
+
+def head_scores_hi(scores, B: int, h: int, w: int, K: int, S: int, mode: int):
+    """The materialised [B, K, S h, S w] map of low-resolution scores [B*h*w, ld].  Past 192 classes: contiguous 192-channel slices
+    through the same kernel, concatenated (the reference composition of the wide head; the loss and prediction paths never form it)."""
+    if K <= ops.HEAD_CMAX:
+        return ops.head_upsample_ce(scores, None, B, h, w, K, S, mode, want_scores=True, want_loss=False)[2]
+    outs = []
+    for c0 in range(0, K, ops.HEAD_CMAX):
+        n = min(ops.HEAD_CMAX, K - c0)
+        part = scores[:, c0:c0 + (n + 63) // 64 * 64].contiguous()
+        outs.append(ops.head_upsample_ce(part, None, B, h, w, n, S, mode, want_scores=True, want_loss=False)[2])
+    return torch.cat(outs, dim=1)
+
+
+def head_scores_hi_bwd(gout, B: int, h: int, w: int, K: int, S: int, mode: int, ld: int):
+    """Gradient of head_scores_hi wrt the low-resolution scores, fp32 [B*h*w, ld] (zero padded columns)."""
+    gout = gout.float()
+    if K <= ops.HEAD_CMAX:
+        return ops.upsample_bwd_nchw(gout.contiguous(), B, h, w, K, S, mode, ld)
+    ds = torch.zeros(B * h * w, ld, dtype=torch.float32, device=gout.device)
+    for c0 in range(0, K, ops.HEAD_CMAX):
+        n = min(ops.HEAD_CMAX, K - c0)
+        ds[:, c0:c0 + n] = ops.upsample_bwd_nchw(gout[:, c0:c0 + n].contiguous(), B, h, w, n, S, mode, (n + 63) // 64 * 64)[:, :n]
+    return ds
+
+
 def _reduce(loss2, reduction: str, save: bool):
     """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
     gives torch's NaN mean and a zero gradient, with no host sync."""
@@ -178,8 +221,9 @@ class BaseModelWithText(HipModule):
                              batch_first=True, norm_first=True)
         self.vision_decoder = DecoderBlock(decoder_layer=layer, num_layers=num_layers)
         self.pixel_patch = TextToPatch(out=out_dim, img_in=cv, text_in=self.class_prototypes.shape[1])
-        if self.class_prototypes.shape[0] > KPAD:
-            raise ValueError(f"BaseModelWithText: at most {KPAD} classes are supported by the fused head")
+        if self.class_prototypes.shape[0] > ops.HEAD_WIDE_CMAX:
+            raise ValueError(f"BaseModelWithText: at most {ops.HEAD_WIDE_CMAX} classes are supported by the fused head "
+                             f"({ops.HEAD_CMAX} by every criterion, more by the plain cross-entropy)")
         self.overlap_text = True     # text tower on a side stream (set False to serialise, e.g. under graph capture)
         self._text_stream = None
 
@@ -189,7 +233,7 @@ class BaseModelWithText(HipModule):
 
     def _build_shadows(self, device):
         K, Ct = self.class_prototypes.shape
-        p16 = torch.zeros(KPAD, Ct, dtype=torch.bfloat16, device=device)
+        p16 = torch.zeros(ops.class_pad(K), Ct, dtype=torch.bfloat16, device=device)
         return dict(p16=p16, K=K), [(self.class_prototypes, p16[:K], None)]
 
     # -- head ------------------------------------------------------------------------------------------------
@@ -210,12 +254,21 @@ class BaseModelWithText(HipModule):
         dec16 = ops.cast_bf16(dec.reshape(B * P, C).float().contiguous())
         ft16, fv16, scores = self._head_scores(dec16)
         if labels is None:
-            _, _, hi = ops.head_upsample_ce(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_scores=True,
-                                            want_loss=False)
+            hi = head_scores_hi(scores, B, g, g, K, 4, ops.INTERP_BICUBIC)
             return hi, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None)
         labels = labels.contiguous()
         if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
             ops.seg_counts_add(seg_counts, scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index)
+        if K > ops.HEAD_CMAX:   # the chunked cross-entropy (forward_loss refused every other criterion before the towers ran)
+            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
+            loss2, dlo = ops.head_upsample_ce_wide(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
+                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight)
+            loss, inv_count = _reduce(loss2, reduction, save)
+            if accum is not None:
+                ops.accum_add(accum, loss2)
+                inv_count = None
+            return loss, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=inv_count)
+                          if save else None)
         if dice is not None:   # CE + soft Dice: statistics pass, coefficients, gradient pass — dlo is the gradient of the scalar loss
             ce_weight, dice_weight, smooth, present_only = dice
             loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
@@ -271,7 +324,7 @@ class BaseModelWithText(HipModule):
             else:
                 ds16 = ops.cast_bf16(ds * (inv if gout is None else gout * inv))
         else:
-            ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, KPAD)
+            ds = head_scores_hi_bwd(gout, B, g, g, K, 4, ops.INTERP_BICUBIC, ops.class_pad(K))
             ds16 = ops.cast_bf16(ds)
         ft16, fv16, dec16 = saved["ft16"], saved["fv16"], saved["dec16"]
         ftT = ops.transpose_bf16(ft16)                                   # [out, KPAD]
@@ -373,6 +426,7 @@ class BaseModelWithText(HipModule):
         dice = fused_dice_options(dice, opts, ohem)
         if seg_counts is not None:
             ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
+        wide_refuse("BaseModelWithText.forward_loss", self.class_prototypes.shape[0], 4, label_smoothing, ohem, dice, focal, sigmoid)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
         if sigmoid is not None:
@@ -387,15 +441,17 @@ class BaseModelWithText(HipModule):
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:
-        """The class map of the model output, uint8 [B, out, out]: ``forward(inputs)["outputs"].argmax(1)`` (exact ties to the lowest
-        class) without forming the logits — the argmax is taken in the fused head (``ops.head_upsample_argmax``)."""
+        """The class map of the model output, uint8 [B, out, out] (int16 past 192 classes): ``forward(inputs)["outputs"].argmax(1)``
+        (exact ties to the lowest class) without forming the logits — the argmax is taken in the fused head
+        (``ops.head_upsample_argmax``, ``ops.head_upsample_argmax_wide``)."""
         dec_v = self._decode(inputs)
         B, P, C = dec_v.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
         dec16 = ops.cast_bf16(dec_v.reshape(B * P, C).float().contiguous())
         _, _, scores = self._head_scores(dec16)
-        pred, _ = ops.head_upsample_argmax(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_counts=False)
+        argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
+        pred, _ = argmax(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_counts=False)
         return pred
 
     @torch.no_grad()
@@ -407,8 +463,7 @@ class BaseModelWithText(HipModule):
         K = self.class_prototypes.shape[0]
         dec16 = ops.cast_bf16(dec_v.reshape(B * P, C).float().contiguous())
         ft16, fv16, scores = self._head_scores(dec16)
-        _, _, logits = ops.head_upsample_ce(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_scores=True,
-                                            want_loss=False)
+        logits = head_scores_hi(scores, B, g, g, K, 4, ops.INTERP_BICUBIC)
         fv = fv16.float()
         outs = []
         for c0 in range(0, fv.shape[1], KPAD):  # upsample the visual features 192 channels at a time

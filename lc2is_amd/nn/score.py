@@ -18,35 +18,39 @@ from torch import nn
 from .. import ops
 from .base import require_cuda
 from .loss import check_ohem
-from .model import _reduce, fused_dice_options, fused_focal_options, fused_loss_options, fused_sigmoid_options
+from .model import (_reduce, fused_dice_options, fused_focal_options, fused_loss_options, fused_sigmoid_options, head_scores_hi,
+                    head_scores_hi_bwd, wide_refuse)
 
-KPAD = 192
+KPAD = 192   # class pitch up to 192 classes; past them ops.class_pad(K)
 
 
 def _scores_lo(visual, text):
     B, P, C = visual.shape
     K = text.shape[1]
-    if K > KPAD or C % 64:
-        raise NotImplementedError("lc2is_amd ScoreMapTail: at most 192 classes, channel count a multiple of 64")
+    if K > ops.HEAD_WIDE_CMAX or C % 64:
+        raise NotImplementedError(f"lc2is_amd ScoreMapTail: at most {ops.HEAD_WIDE_CMAX} classes ({ops.HEAD_CMAX} for every criterion "
+                                  "but the plain cross-entropy), channel count a multiple of 64")
+    kpad = ops.class_pad(K)
     v32 = visual.reshape(B * P, C).float().contiguous()
     t32 = text.reshape(B * K, C).float().contiguous()
     _, vn16, vinv = ops.l2norm_fwd(v32, want_f32=False)
     _, tn16, tinv = ops.l2norm_fwd(t32, want_f32=False)
-    tpad = torch.zeros(B, KPAD, C, dtype=torch.bfloat16, device=visual.device)
+    tpad = torch.zeros(B, kpad, C, dtype=torch.bfloat16, device=visual.device)
     tpad[:, :K] = tn16.view(B, K, C)
     # per-image class embeddings: ONE strided-batched NT launch (blockIdx.y = image)
     _, scores = ops.gemm_nt_batched(vn16.view(B, P, C), tpad)
-    scores = scores.view(B * P, KPAD)
+    scores = scores.view(B * P, kpad)
     return scores, dict(v32=v32, t32=t32, vn16=vn16, tpad=tpad, vinv=vinv, tinv=tinv, dims=(B, P, C, K))
 
 
 def _scores_bwd(ds32, sv):
-    """ds32: gradient wrt the low-resolution scores [B*P, KPAD] (fp32)."""
+    """ds32: gradient wrt the low-resolution scores [B*P, class_pad(K)] (fp32)."""
     B, P, C, K = sv["dims"]
+    kpad = ops.class_pad(K)
     ds16 = ops.cast_bf16(ds32)
-    dtn = torch.empty(B, KPAD, C, dtype=torch.float32, device=ds32.device)
+    dtn = torch.empty(B, kpad, C, dtype=torch.float32, device=ds32.device)
     tT = ops.transpose_bf16_batched(sv["tpad"])                                    # [B, C, KPAD]
-    _, dvn = ops.gemm_nt_batched(ds16.view(B, P, KPAD), tT)                         # d(normalised visual) [B, P, C]
+    _, dvn = ops.gemm_nt_batched(ds16.view(B, P, kpad), tT)                         # d(normalised visual) [B, P, C]
     dvn = dvn.view(B * P, C)
     vn16 = sv["vn16"]
     probs = [(ds16[b * P:(b + 1) * P], vn16[b * P:(b + 1) * P], dtn[b], None, False) for b in range(B)]
@@ -67,12 +71,22 @@ class _ScoreFn(torch.autograd.Function):
         h = int(round(P ** 0.5))
         scores, sv = _scores_lo(visual, text)
         if labels is None:
-            _, _, hi = ops.head_upsample_ce(scores, None, B, h, h, K, scale, ops.INTERP_BILINEAR, want_scores=True,
-                                            want_loss=False)
+            hi = head_scores_hi(scores, B, h, h, K, scale, ops.INTERP_BILINEAR)
             ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
             return hi
         if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
             ops.seg_counts_add(seg_counts, scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index)
+        if K > ops.HEAD_CMAX:   # the chunked cross-entropy (loss() refused every other criterion before anything ran)
+            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
+            loss2, dlo = ops.head_upsample_ce_wide(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, want_grad=save,
+                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight)
+            loss, inv = _reduce(loss2, reduction, save)
+            if accum is not None:
+                ops.accum_add(accum, loss2)
+            elif inv is not None:
+                dlo.mul_(inv)
+            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
+            return loss
         if dice is not None:   # CE + soft Dice: dlo is the gradient of the scalar loss
             ce_weight, dice_weight, smooth, present_only = dice
             loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
@@ -124,7 +138,7 @@ class _ScoreFn(torch.autograd.Function):
         if ctx.fused is not None:
             ds = ctx.fused * gout
         else:
-            ds = ops.upsample_bwd_nchw(gout.float().contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, KPAD)
+            ds = head_scores_hi_bwd(gout, B, h, h, K, scale, ops.INTERP_BILINEAR, ops.class_pad(K))
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
         return dv, dt, None, None, None, None, None, None, None, None, None, None, None, None
@@ -172,6 +186,7 @@ class ScoreMapTail(nn.Module):
         dice = fused_dice_options(dice, opts, ohem)
         if seg_counts is not None:
             ops.check_seg_counts(seg_counts, text_embeddings.shape[1])
+        wide_refuse("ScoreMapTail.loss", text_embeddings.shape[1], self.scale_factor, label_smoothing, ohem, dice, focal, sigmoid)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
         if sigmoid is not None:
@@ -188,12 +203,14 @@ class ScoreMapTail(nn.Module):
 
     @torch.no_grad()
     def predict(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor) -> torch.Tensor:
-        """The class map of the score map, uint8 [B, S*h, S*w]: ``forward(visual, text).argmax(1)`` (exact ties to the lowest class)
-        without writing the map — the argmax is taken in the fused head (``ops.head_upsample_argmax``)."""
+        """The class map of the score map, uint8 [B, S*h, S*w] (int16 past 192 classes): ``forward(visual, text).argmax(1)`` (exact
+        ties to the lowest class) without writing the map — the argmax is taken in the fused head (``ops.head_upsample_argmax``,
+        ``ops.head_upsample_argmax_wide``)."""
         require_cuda(visual_embeddings, "visual_embeddings")
         B, P, _ = visual_embeddings.shape
         K = text_embeddings.shape[1]
         h = int(round(P ** 0.5))
         scores, _ = _scores_lo(visual_embeddings, text_embeddings)
-        pred, _ = ops.head_upsample_argmax(scores, None, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, want_counts=False)
+        argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
+        pred, _ = argmax(scores, None, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, want_counts=False)
         return pred

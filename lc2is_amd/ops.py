@@ -96,6 +96,10 @@ _ARGTYPES = {
     "lc2is_head_upsample_sigmoid": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _F, _F, _P, _Z, _P],
     "lc2is_sigmoid_focal_nchw_fwd": [_P, _P, _P, _P, _I, _I, _L, _L, _P, _F, _F, _F, _P, _Z, _P],
     "lc2is_sigmoid_focal_nchw_bwd": [_P, _P, _P, _F, _P, _P, _I, _I, _L, _L, _P, _F, _F, _F, _P],
+    "lc2is_head_upsample_ce_wide_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I],
+    "lc2is_head_upsample_ce_wide": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _P, _Z, _P],
+    "lc2is_head_upsample_argmax_wide_workspace_bytes": [_I, _I, _I, _I, _I, _I],
+    "lc2is_head_upsample_argmax_wide": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P, _Z, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -1010,11 +1014,86 @@ def head_upsample_argmax(scores_lo, labels, B: int, h: int, w: int, C: int, S: i
     return pred, counts
 
 
+# ---- the fused head past 192 classes: the class axis walked in chunks of 192 channels (head_wide.hip) ----
+HEAD_CMAX = 192            # classes the narrow head kernels take (every criterion, S = 4 / 8 / 16)
+HEAD_WIDE_CMAX = 1024      # LC2IS_HEAD_WIDE_CMAX: classes the wide cross-entropy / argmax kernels take (S = 4)
+
+
+def class_pad(K: int) -> int:
+    """Channel pitch of the low-resolution score map of a K-class head: 192 up to 192 classes (the narrow kernels' one shape),
+    else K rounded up to 64."""
+    return HEAD_CMAX if K <= HEAD_CMAX else (K + 63) // 64 * 64
+
+
+def _wide_front(who: str, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, need_labels: bool):
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be contiguous")
+    if (need_labels or labels is not None) and (labels is None or tuple(labels.shape) != (B, h * S, w * S)
+                                                or not labels.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.{who}: labels must be contiguous [{B},{h*S},{w*S}]")
+    if S != 4:
+        raise RuntimeError(f"lc2is_amd.{who}: S must be 4, got {S}")
+    ld = scores_lo.shape[1]
+    if scores_lo.shape[0] != B * h * w or not 1 <= C <= ld <= HEAD_WIDE_CMAX or ld % 64:
+        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be [{B * h * w}, ld] with C <= ld <= {HEAD_WIDE_CMAX}, ld % 64 == 0, "
+                           f"got {tuple(scores_lo.shape)}")
+    return ld
+
+
+def head_upsample_ce_wide(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                          want_grad: bool = False, ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None):
+    """Cross-entropy of the x4-upsampled scores for up to 1024 classes: scores_lo fp32 [B*h*w, ld], labels int64 [B, 4h, 4w].
+    Returns (loss2 = [sum of w_y (lse - z_y), sum of w_y over the counted pixels], dscores_lo or None = grad_scale * d loss2[0] /
+    d scores_lo, every one of the ld channels written).  ``head_upsample_ce(class_weight=...)`` without label smoothing, the class
+    axis walked in chunks of 192 channels: an online-softmax sweep, a gradient sweep and the finish launch; nothing syncs, no
+    atomics, the same bytes every run, captures into a graph.  C <= 192 is taken too (the narrow call is the faster one there)."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    ld = _wide_front("head_upsample_ce_wide", scores_lo, labels, B, h, w, C, S, True)
+    dev = scores_lo.device
+    _ce_options(class_weight, 0.0, C, dev)
+    nbytes = _fn("lc2is_head_upsample_ce_wide_workspace_bytes")(B, h, w, C, ld, S, mode, int(want_grad))
+    if nbytes == 0:
+        raise RuntimeError(f"lc2is_amd.head_upsample_ce_wide: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    _lib.check(_fn("lc2is_head_upsample_ce_wide")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
+                                                  ignore_index, grad_scale, _ptr(class_weight), _ptr(ws), nbytes, _stream()),
+               f"head_upsample_ce_wide B={B} h={h} w={w} C={C} S={S}")
+    return loss, dlo
+
+
+def head_upsample_argmax_wide(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                              ignore_index: int = -100, want_pred: bool = True, want_counts: bool = True):
+    """``head_upsample_argmax`` for up to 1024 classes (S = 4): (pred int16 [B, 4h, 4w] or None, counts int32 [B, 3, C] or None).
+    The class axis is walked in chunks of 192 channels with a running (value, class) per pixel; exact ties go to the lowest class."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    if not want_pred and not want_counts:
+        raise ValueError("lc2is_amd.head_upsample_argmax_wide: want_pred and want_counts are both False")
+    if want_counts and labels is None:
+        raise ValueError("lc2is_amd.head_upsample_argmax_wide: want_counts needs labels")
+    ld = _wide_front("head_upsample_argmax_wide", scores_lo, labels, B, h, w, C, S, False)
+    dev = scores_lo.device
+    nbytes = 0
+    if want_counts:
+        nbytes = _fn("lc2is_head_upsample_argmax_wide_workspace_bytes")(B, h, w, C, S, mode)
+        if nbytes == 0:
+            raise RuntimeError(f"lc2is_amd.head_upsample_argmax_wide: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    pred = torch.empty((B, h * S, w * S), dtype=torch.int16, device=dev) if want_pred else None
+    counts = torch.empty((B, 3, C), dtype=torch.int32, device=dev) if want_counts else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None   # (per call: the slabs live until the second launch)
+    _lib.check(_fn("lc2is_head_upsample_argmax_wide")(_ptr(scores_lo), ld, _ptr(labels), _ptr(pred), _ptr(counts), B, h, w, C, S,
+                                                      mode, ignore_index, _ptr(ws), nbytes, _stream()),
+               f"head_upsample_argmax_wide B={B} h={h} w={w} C={C} S={S}")
+    return pred, counts
+
+
 def seg_counts_add(seg_counts, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int, ignore_index: int):
     """``seg_counts += counts.sum(0)`` for the batch behind ``scores_lo``: what every fused head does for ``seg_counts=``.  int64
-    [3, C] on the device, added in place by one small device op (no host read)."""
+    [3, C] on the device, added in place by one small device op (no host read).  Past 192 classes the wide kernel counts."""
     check_seg_counts(seg_counts, C)
-    _, counts = head_upsample_argmax(scores_lo, labels, B, h, w, C, S, mode, ignore_index=ignore_index, want_pred=False)
+    argmax = head_upsample_argmax_wide if C > HEAD_CMAX else head_upsample_argmax
+    _, counts = argmax(scores_lo, labels, B, h, w, C, S, mode, ignore_index=ignore_index, want_pred=False)
     seg_counts.add_(counts.sum(0))
 
 

@@ -418,9 +418,12 @@ class TrainStep:
                 raise TypeError("TrainStep: seg_metrics=True needs a model whose forward_loss takes seg_counts= "
                                 "(BaseModelWithText, PromptFTN)")
             n_seg = _n_classes(model) if seg_classes is None else seg_classes
-            if isinstance(n_seg, bool) or not isinstance(n_seg, int) or not 1 <= n_seg <= 192:
-                raise ValueError("TrainStep: seg_metrics=True needs the class count of the fused head, 1..192: the model's "
+            if isinstance(n_seg, bool) or not isinstance(n_seg, int) or not 1 <= n_seg <= 1024:
+                raise ValueError("TrainStep: seg_metrics=True needs the class count of the fused head, 1..1024: the model's "
                                  f"class_prototypes rows, or seg_classes= for a model without them (got {seg_classes!r})")
+            if _n_classes(model) not in (None, n_seg):   # the head counts the model's own classes: a [3, K] buffer of another K is refused
+                raise ValueError(f"TrainStep: seg_classes={seg_classes!r} does not match the model's {_n_classes(model)} "
+                                 "class_prototypes rows")
         elif seg_classes is not None:
             raise ValueError("TrainStep: seg_classes is only meaningful with seg_metrics=True")
         device_path = bool(device_state or skip_nonfinite or lr_schedule is not None or max_grad_norm is not None
