@@ -32,17 +32,15 @@
 // profiles/wide_head_cost.txt): the cross-entropy kernel's LDS is 2 x 49 x 196 floats + four [16][16] tiles = 80 928 bytes (+ 64
 // static) bicubic, 43 296 bilinear; the argmax kernel's is max(footprint, count rows) + three tiles <= 52 224 bytes.  Both compile
 // inside 128 registers without scratch, so two blocks per CU hold for both.
-// A file of its own with the few helpers of head.hip restated, so that head.hip and head_argmax.hip compile to the objects they were.
+// The interpolation weights and the 16-lane row steps are head_grp.h's; the chunked work split is this file's own.
 #include "common.h"
+#include "head_grp.h"   // HT, HEAD_THREADS, HEAD_PAD, tap_w and the 16-lane row steps
 #include "interp.h"
 #include "label_hist.h"
 #include "lc2is_hip.h"
 
 namespace {
 
-constexpr int HT = 16;          // output tile edge
-constexpr int HEAD_THREADS = 512;
-constexpr int HEAD_PAD = 4;     // floats added to a footprint cell's LDS stride (head.hip)
 constexpr int S = 4;            // the only scale of the wide head
 constexpr int G = HT / S;       // groups per tile edge
 constexpr int CHUNK = 192;      // channels of the class axis in LDS at a time
@@ -74,40 +72,6 @@ struct WideArgmaxArgs {
   int B, h, w, H, W, C, cq;
   long ignore_index;
 };
-
-template <int MODE> __device__ __forceinline__ float tap_w(int ph, int k) {
-  const float t = ((float)ph + 0.5f) * (1.f / (float)S);
-  if constexpr (MODE == LC2IS_INTERP_BICUBIC)
-    return k == 0 ? cubic2(t + 1.f) : (k == 1 ? cubic1(t) : (k == 2 ? cubic1(1.f - t) : cubic2(2.f - t)));
-  else
-    return k == 0 ? 1.f - t : t;
-}
-
-template <int CTRL> __device__ __forceinline__ float row_dpp(float v) {   // lane permutation inside each row of 16 lanes
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL> __device__ __forceinline__ int row_dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, row_dpp<0xB1>(v)); v = fmaxf(v, row_dpp<0x4E>(v)); v = fmaxf(v, row_dpp<0x141>(v));
-  return fmaxf(v, row_dpp<0x140>(v));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += row_dpp<0xB1>(v); v += row_dpp<0x4E>(v); v += row_dpp<0x141>(v);
-  return v + row_dpp<0x140>(v);
-}
-// one exchange of (value, index) pairs: the larger value wins, equal values keep the lower index (a NaN never wins)
-template <int CTRL> __device__ __forceinline__ void argmax_step(float& v, int& i) {
-  const float ov = row_dpp<CTRL>(v);
-  const int oi = row_dpp_i<CTRL>(i);
-  const bool take = ov > v || (ov == v && oi < i);
-  v = take ? ov : v;
-  i = take ? oi : i;
-}
-__device__ __forceinline__ void row16_argmax(float& v, int& i) {   // every lane of the row ends with the row's winner
-  argmax_step<0xB1>(v, i); argmax_step<0x4E>(v, i); argmax_step<0x141>(v, i); argmax_step<0x140>(v, i);
-}
 
 // channels [c0, c0 + 64 ng) of the tile's footprint into s_lo (cell stride CS); ZERO: the same columns of the mirror cleared
 template <int MODE, bool ZERO>
@@ -201,11 +165,11 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_ce_wide_grp_kernel(WideA
   {
     const int py_m = m / S, px_m = m % S;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE>(py_m, (4 * q + kq) / NT) * tap_w<MODE>(px_m, (4 * q + kq) % NT);
+    for (int q = 0; q < NQ; ++q) Af[q] = tap_w<MODE, S>(py_m, (4 * q + kq) / NT) * tap_w<MODE, S>(px_m, (4 * q + kq) % NT);
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int n = 4 * kq + jj;
-      Bb[jj] = (m < NT * NT) ? tap_w<MODE>(n / S, m / NT) * tap_w<MODE>(n % S, m % NT) : 0.f;
+      Bb[jj] = (m < NT * NT) ? tap_w<MODE, S>(n / S, m / NT) * tap_w<MODE, S>(n % S, m % NT) : 0.f;
     }
   }
   float loss_acc = 0.f, cnt_acc = 0.f;
@@ -477,7 +441,7 @@ __global__ __launch_bounds__(HEAD_THREADS, 2) void head_argmax_wide_grp_kernel(W
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     cell_off[q] = (((4 * q + kq) / NT) * F4 + (4 * q + kq) % NT) * CS;
-    Af[q] = tap_w<MODE>(m / S, (4 * q + kq) / NT) * tap_w<MODE>(m % S, (4 * q + kq) % NT);
+    Af[q] = tap_w<MODE, S>(m / S, (4 * q + kq) / NT) * tap_w<MODE, S>(m % S, (4 * q + kq) % NT);
   }
   const int nch = (p.C + CHUNK - 1) / CHUNK;
 #pragma unroll 1

@@ -5,36 +5,31 @@ Per counted pixel (label != ignore_index and 0 <= label < C) with label y, p = s
 composed from ``log_softmax`` with gradients by autograd, and the closed form of the gradient
     dl/dz_j = w_y c (p_j - [j == y]),   c = q^gamma + gamma p_y q^(gamma-1) ce + eps1 p_y.
 q is exp(logsumexp of the OTHER classes' log-probabilities): 1 - exp(log p_y) is exactly 0 in fp64 once the label leads by about
-37, and autograd through 0^gamma is NaN for gamma < 1.  The head cases reuse test_gpu_ce_options._head_case's inputs."""
+37, and autograd through 0^gamma is NaN for gamma < 1.  The head cases reuse head_cases.head_case's inputs."""
 from functools import lru_cache
 
 import torch
 import torch.nn.functional as F
 
-IGN = -100
+from head_cases import IGN, head_case  # noqa: F401  (head_case re-exported)
+
 PARAMS = [(2, 0), (0.5, 0), (0, 1), (1.5, 2), (0, 0)]      # (gamma, poly_eps)
 # (mode, S, C, h, w): the four channel-tile counts (TN = 4: C = 10, 37, 64; 8: 100; 10: 150, 151; 12: 192), the three scales,
 # non-square grids, 16 x 16 tiles that straddle the image edge
 CASES = [("bicubic", 4, 151, 5, 5), ("bicubic", 4, 192, 7, 7), ("bilinear", 4, 10, 12, 12), ("bicubic", 8, 37, 7, 5),
          ("bilinear", 8, 100, 5, 7), ("bicubic", 16, 150, 3, 5), ("bilinear", 16, 64, 5, 5)]
+# behind them, the (mode, S, TN) instantiations of head_focal_grp_kernel / head_sigmoid_grp_kernel that the seven do not reach
+CASES += [
+    ("bicubic", 4, 10, 5, 7), ("bicubic", 4, 100, 5, 7), ("bicubic", 8, 100, 5, 4), ("bicubic", 8, 151, 5, 4),
+    ("bicubic", 8, 192, 5, 4), ("bicubic", 16, 10, 3, 4), ("bicubic", 16, 100, 3, 4), ("bicubic", 16, 192, 3, 4),
+    ("bilinear", 4, 100, 5, 7), ("bilinear", 4, 151, 5, 7), ("bilinear", 4, 192, 5, 7), ("bilinear", 8, 10, 5, 4),
+    ("bilinear", 8, 151, 5, 4), ("bilinear", 8, 192, 5, 4), ("bilinear", 16, 100, 3, 4), ("bilinear", 16, 151, 3, 4),
+    ("bilinear", 16, 192, 3, 4)]
 
 
 def weights(C, seed):
     """Class weights in [0.25, 1.75], fp64."""
     return torch.rand(C, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * 1.5 + 0.25
-
-
-def head_case(B, h, w, C, S, seed):
-    """test_gpu_ce_options._head_case: scores [B*h*w, ld] (zeros past C), labels with some >= C and every fifth row ignored, and the
-    labels the reference sees (>= C mapped to IGN)."""
-    g = torch.Generator().manual_seed(seed)
-    ld = 64 if C <= 64 else (128 if C <= 128 else 192)
-    lo = torch.zeros(B * h * w, ld)
-    lo[:, :C] = torch.randn(B * h * w, C, generator=g) * 3
-    labels = torch.randint(0, C + 3, (B, h * S, w * S), generator=g)
-    labels[:, 1::5] = IGN
-    ref_labels = torch.where(labels >= C, torch.full_like(labels, IGN), labels)
-    return lo, labels, ref_labels
 
 
 def _terms(logits, labels, ignore_index):

@@ -13,6 +13,9 @@ MAX_EXCLUDED = 0.01    # at most this share of a case's pixels may be excluded
 SHAPES = [(2, 9, 9, 4, "bicubic"), (1, 5, 9, 4, "bicubic"), (2, 5, 5, 8, "bilinear"), (1, 3, 3, 16, "bilinear")]
 CLASSES = [5, 64, 65, 129, 151, 161, 192]   # TN = 4, 4, 8, 10, 10, 12, 12; partial last tiles; C == ld
 CASES = [(B, h, w, S, mode, C) for (B, h, w, S, mode) in SHAPES for C in CLASSES]
+# behind the product (indices into it are used by name): the (mode, S) it does not reach, at each TN = 4 / 8 / 10 / 12
+CASES += [(2, h, w, S, mode, C) for (h, w, S, mode) in [(5, 7, 4, "bilinear"), (5, 4, 8, "bicubic"), (3, 4, 16, "bicubic")]
+          for C in (10, 100, 151, 192)]
 PAD_SCORE = 50.0       # what the channels past C hold: above every real score, so a kernel that does not mask them picks one
 
 

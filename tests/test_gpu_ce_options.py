@@ -1,9 +1,16 @@
 """Cross-entropy with class weights, label smoothing and the 'sum' / 'none' reductions on the HIP path, against
 torch.nn.functional.cross_entropy in fp64 on the CPU: the fused upsample + CE head (op, module, model, train step, captured
 step) and the unfused NCHW drop-in."""
+import sys
+from pathlib import Path
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import head_cases  # noqa: E402
+from head_cases import head_case as _head_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -19,21 +26,8 @@ def _weights(C, seed):
     return torch.rand(C, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * 1.5 + 0.25
 
 
-def _head_case(B, h, w, C, S, seed):
-    g = torch.Generator().manual_seed(seed)
-    ld = 64 if C <= 64 else (128 if C <= 128 else 192)
-    lo = torch.zeros(B * h * w, ld)
-    lo[:, :C] = torch.randn(B * h * w, C, generator=g) * 3
-    labels = torch.randint(0, C + 3, (B, h * S, w * S), generator=g)   # >= C: skipped by the kernel
-    labels[:, 1::5] = IGN
-    ref_labels = torch.where(labels >= C, torch.full_like(labels, IGN), labels)   # (torch raises on them)
-    return lo, labels, ref_labels
-
-
-# C covers the four channel-tile counts of the group kernel: TN = 4 (10, 37, 64), 8 (100), 10 (150, 151), 12 (192)
-HEAD_CASES = [("bicubic", 4, 151, 5, 5), ("bicubic", 4, 192, 7, 7), ("bilinear", 4, 10, 12, 12), ("bilinear", 4, 151, 12, 7),
-              ("bicubic", 8, 37, 7, 5), ("bilinear", 8, 100, 5, 7), ("bicubic", 16, 150, 3, 5), ("bilinear", 16, 64, 5, 5),
-              ("bicubic", 16, 100, 4, 4), ("bilinear", 8, 192, 4, 6)]
+# head_cases.HEAD_CASES, and behind it every (mode, S, TN) instantiation of head_ce_grp_kernel that the list does not reach
+HEAD_CASES = head_cases.HEAD_CASES_ALL
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.1])

@@ -13,15 +13,15 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import dice_ref as R  # noqa: E402
+import head_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 IGN = -100
 
-# tests/test_gpu_ce_options.py::HEAD_CASES: TN = 4 (10, 37, 64), 8 (100), 10 (150, 151), 12 (192), all three S, both modes, ragged tiles
-HEAD_CASES = [("bicubic", 4, 151, 5, 5), ("bicubic", 4, 192, 7, 7), ("bilinear", 4, 10, 12, 12), ("bilinear", 4, 151, 12, 7),
-              ("bicubic", 8, 37, 7, 5), ("bilinear", 8, 100, 5, 7), ("bicubic", 16, 150, 3, 5), ("bilinear", 16, 64, 5, 5),
-              ("bicubic", 16, 100, 4, 4), ("bilinear", 8, 192, 4, 6)]
+# head_cases.HEAD_CASES (indices 0-9 are used by name below), and behind it every (mode, S, TN) instantiation of
+# head_dice_stats_grp_kernel / head_ce_dice_grp_kernel that the list does not reach
+HEAD_CASES = head_cases.HEAD_CASES_ALL
 WEIGHTS = [(0.0, 1.0), (1.0, 3.0)]
 
 

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import ohem_ref as R  # noqa: E402
+from head_cases import head_case as _head_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -114,19 +115,15 @@ def test_selection_refuses_bad_arguments(dev):
 
 
 # ---- 2 / 3. per-pixel loss of the fused head, and fused OHEM at op level ---------------------------------------------
-def _head_case(B, h, w, C, S, seed):   # (as test_gpu_ce_options.py builds its head inputs)
-    g = torch.Generator().manual_seed(seed)
-    ld = 64 if C <= 64 else (128 if C <= 128 else 192)
-    lo = torch.zeros(B * h * w, ld)
-    lo[:, :C] = torch.randn(B * h * w, C, generator=g) * 3
-    labels = torch.randint(0, C + 3, (B, h * S, w * S), generator=g)   # >= C: skipped by the kernel
-    labels[:, 1::5] = IGN
-    ref_labels = torch.where(labels >= C, torch.full_like(labels, IGN), labels)   # (torch raises on them)
-    return lo, labels, ref_labels
-
-
 HEAD_CASES = [("bicubic", 4, 151, 5, 5), ("bilinear", 4, 150, 12, 7), ("bicubic", 8, 37, 7, 5), ("bilinear", 16, 64, 5, 5),
               ("bicubic", 16, 150, 3, 5), ("bilinear", 8, 192, 4, 6)]
+# behind them, the (mode, S, TN) instantiations of head_px_grp_kernel that the six do not reach
+HEAD_CASES += [
+    ("bicubic", 4, 10, 5, 7), ("bicubic", 4, 100, 5, 7), ("bicubic", 4, 192, 5, 7), ("bicubic", 8, 100, 5, 4),
+    ("bicubic", 8, 151, 5, 4), ("bicubic", 8, 192, 5, 4), ("bicubic", 16, 10, 3, 4), ("bicubic", 16, 100, 3, 4),
+    ("bicubic", 16, 192, 3, 4), ("bilinear", 4, 10, 5, 7), ("bilinear", 4, 100, 5, 7), ("bilinear", 4, 192, 5, 7),
+    ("bilinear", 8, 10, 5, 4), ("bilinear", 8, 100, 5, 4), ("bilinear", 8, 151, 5, 4), ("bilinear", 16, 100, 3, 4),
+    ("bilinear", 16, 151, 3, 4), ("bilinear", 16, 192, 3, 4)]
 HEAD_B = 2
 
 

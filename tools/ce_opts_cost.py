@@ -64,7 +64,7 @@ def main():
                          text=True)
     head = [ln for ln in res.stdout.splitlines() if re.match(r"(void )?(head_ce_grp_kernel|head_finish_kernel|ce_nchw_)", ln)
             or ln.startswith("kernel ")]
-    lines += ["", "tools/check_kernel_resources.py (head.hip rows; exit status %d):" % res.returncode] + head
+    lines += ["", "tools/check_kernel_resources.py (head.hip and loss_nchw.hip rows; exit status %d):" % res.returncode] + head
     lines.append(res.stdout.strip().splitlines()[-1] if res.stdout.strip() else "(no output)")
     print("\n".join(lines[-len(head) - 3:]), flush=True)
     if a.out:
