@@ -531,6 +531,40 @@ int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int
                                    long total_px, const void* gt, int gt_bytes, int ignore_index, int mode, uint8_t* pred,
                                    int* counts, void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
 
+/* ---- the three resize + argmax entries past 192 classes ----------------------------------------------------------------
+ * lc2is_resize_argmax, lc2is_resize_argmax_windows and lc2is_resize_argmax_multiscale for 1 <= K <= LC2IS_RESIZE_WIDE_KMAX
+ * classes (PC-459, ADE20K-full's 847, ImageNet-S-919).  Every argument, descriptor, device-side range check, counting rule
+ * (ignore_index) and mode is that of the narrow entry of the same name, with two differences:
+ *   pred (optional): int16 [total_px], packed as the narrow pred (a class index does not fit uint8 past 255).
+ *   workspace: >= lc2is_resize_argmax_wide_workspace_bytes(n_tiles, K) = n_tiles * 3 * K * 4 bytes for 1 <= K <= 1024 (0
+ *     otherwise): the same dense per-tile slabs {intersection[K], predicted[K], labelled[K]}, summed per image by the same
+ *     second launch in the same order.  A slab is 12 KB per 16 x 16 tile at K = 1024; one 683 x 512 image (1376 tiles) at
+ *     K = 847 needs 14 MB, one 2048 x 1536 image (12288 tiles) 125 MB.  (The [K,H,W] fp32 score map that is never formed
+ *     would be 1.18 GB and 10.6 GB.)
+ * Per class the arithmetic is the narrow kernels' (same taps, fma order, window-mean order and canvas order), the argmax is
+ * the first maximum and the counts are exact integers: with K <= 192 a wide call returns the narrow call's pred values and
+ * count bytes, only slower in its count epilogue (the three rows of a tile's counts take turns in LDS: [4 waves][K] ints, 16 KB
+ * at K = 1024, inside the footprint area; the multiscale PROB kernel keeps its 70 KB and two blocks per CU).
+ * A descriptor that does not fit is not followed, as in the narrow entries: its pred pixels are left as they were, its counts
+ * are UNDEFINED, nothing outside the buffers is read or written.
+ * Error codes and their order as the narrow entries: LC2IS_ERR_NULL, LC2IS_ERR_SHAPE, LC2IS_ERR_UNSUPPORTED (K > 1024 or
+ * another gt_bytes), LC2IS_ERR_WORKSPACE.  No atomics: bitwise reproducible, batch independent.
+ * replaces: as the narrow entries; the reference has no vocabulary past 151 classes. */
+#define LC2IS_RESIZE_WIDE_KMAX 1024
+size_t lc2is_resize_argmax_wide_workspace_bytes(long n_tiles, int K);
+int lc2is_resize_argmax_wide(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc, long n_tiles,
+                             long total_px, const void* gt, int gt_bytes, int16_t* pred, int* counts, void* workspace,
+                             size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_resize_argmax_windows_wide(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                     const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt,
+                                     int gt_bytes, int ignore_index, int16_t* pred, int* counts, void* workspace,
+                                     size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_resize_argmax_multiscale_wide(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                        const int64_t* canv, long n_canv, const int32_t* win, long n_win, long n_tiles,
+                                        long total_px, const void* gt, int gt_bytes, int ignore_index, int mode,
+                                        int16_t* pred, int* counts, void* workspace, size_t workspace_bytes,
+                                        lc2is_stream_t stream);
+
 /* ---- the device-held optimizer path (optim.hip) -----------------------------------------------------------------------
  * The scalars of an optimizer step that change from call to call live in this block in DEVICE memory (48 bytes, 4-byte
  * aligned, all zero before the first step), so a step needs no host value that differs between calls and can be replayed

@@ -10,12 +10,14 @@
 // footprint: the tile is then walked in bands of rows / columns whose footprint fits RA_FMAX, chosen in the kernel from the same
 // taps it uses (correct at every scale, full tiles whenever the image is upscaled by about 3 or more).
 //
-// Three kernels, one of everything they have in common:
+// Three kernels, each in a narrow (K <= 192, uint8 pred) and a wide (K <= 1024, int16 pred) form that differ in the tile's end
+// alone, and one of everything they have in common:
 //   ra_locate       the block's image and tile from the descriptor table (binary search, bounds checks)
 //   RaLds           the carve-up of the dynamic LDS
 //   ra_walk         bands, tap tables, footprint staging, horizontal and vertical pass.  It reads source cells through a SOURCE
 //                   functor and hands every finished group of four channels of the thread's pixel to a SINK functor
-//   ra_tile_counts  pred store, gt read, counting rule, wave histograms, the tile's slab
+//   ra_tile_counts  pred store, gt read, counting rule, wave histograms, the tile's slab (<WIDE>: int16 pred, one row of
+//                   counts at a time)
 // ra_kernel (lc2is_resize_argmax): the source is one score grid per image (RaGridSrc), the sink the running (max, argmax) in
 //   registers: channels in increasing order, strict > (exact ties: the lowest index wins, as torch.argmax).
 // ra_win_kernel (lc2is_resize_argmax_windows), sliding-window evaluation: the source of an image is a canvas of Hc x Wc score
@@ -28,6 +30,8 @@
 // Counts: every wave histograms its own 64 pixels in LDS (one writer per histogram: ballot + popcount per distinct class), the
 // block sums its waves in a fixed order into a per-tile slab of the workspace, and ra_finish_kernel sums each image's slabs in a
 // fixed order.  No read-modify-write atomics: pred and counts are bitwise reproducible and independent of the batch.
+// The wide forms (lc2is_resize_argmax*_wide): the channel walk has no class limit, so they are the same kernels with
+// ra_tile_counts<true>; per class the arithmetic is the narrow kernels', so at K <= 192 pred values and count bytes are equal.
 #include "common.h"
 #include "interp.h"
 #include "label_hist.h"
@@ -41,6 +45,7 @@ constexpr int RA_FMAX = 10;               // footprint edge (source rows / colum
 constexpr int RA_CC = 32;                 // channels per chunk
 constexpr int RA_CP = RA_CC + 4;          // LDS floats per footprint cell: 16 lanes reading 16 B each across x hit distinct banks
 constexpr int RA_KMAX = 192;
+constexpr int RA_KMAX_WIDE = LC2IS_RESIZE_WIDE_KMAX;
 constexpr int RA_WMAX = LC2IS_SLIDE_MAX_WIN;
 constexpr int RA_AMAX = LC2IS_MS_MAX_CANVAS;
 
@@ -53,7 +58,7 @@ struct RaArgs {
   const int64_t* canv;      // multiscale: [n_canv][4]: Hc, Wc, first window, n_windows
   const int32_t* win;       // [n_win][4]: view, oy, ox (origin in canvas cells), flags (bit 0: the view is mirrored along x)
   const void* gt;           // packed like pred: uint8 / int32 / int64 (gt_bytes = 1 / 4 / 8), or null
-  uint8_t* pred;            // [total_px] or null
+  void* pred;               // [total_px] uint8 (narrow kernels) / int16 (wide kernels), or null
   int* slab;                // [n_tiles][3][K] per-tile counts, or null (no counts)
   long total_px, n_canv, n_win;
   int N, V, h, w, ld, K, n_tiles, gt_bytes;
@@ -69,7 +74,7 @@ struct RaLds {
   int4* win;      // [RA_WMAX] windowed kernels: the usable windows of the canvas being walked, in list order
   int* nw;        // their number
   float* stats;   // ra_ms_kernel<PROB>: the softmax statistics
-  int* hist;      // after the channel loops: [4 waves][3][K] (aliases foot)
+  int* hist;      // after the channel loops: [4 waves][3][K] (narrow: aliases foot) or [4 waves][K] (wide: aliases foot + hb)
   __device__ explicit RaLds(char* smem) {
     foot = (float*)smem;
     hb = foot + RA_FMAX * RA_FMAX * RA_CP;
@@ -85,6 +90,8 @@ constexpr size_t RA_LDS = (size_t)(RA_FMAX * RA_FMAX + RA_FMAX * RA_T) * RA_CP *
 constexpr size_t RA_WIN_LDS = RA_LDS + RA_WMAX * sizeof(int4) + 16;
 constexpr size_t RA_MS_LDS_PROB = RA_WIN_LDS + 2 * (size_t)RA_AMAX * RA_THREADS * sizeof(float);
 static_assert((size_t)RA_FMAX * RA_FMAX * RA_CP * sizeof(float) >= 4 * 3 * RA_KMAX * sizeof(int), "histograms fit the footprint");
+static_assert((size_t)(RA_FMAX * RA_FMAX + RA_FMAX * RA_T) * RA_CP * sizeof(float) >= 4 * RA_KMAX_WIDE * sizeof(int),
+              "one row of wide histograms fits foot + hb");
 static_assert(RA_MS_LDS_PROB <= 80 * 1024, "two blocks per CU");
 
 // the block's tile and the thread's pixel in it
@@ -301,12 +308,19 @@ __device__ __forceinline__ void ra_argmax4(float& best, int& arg, int c, float4 
 // is free: every walk ends on one).
 // Counting rule: g is the pixel's class if it is labelled (0 <= gt < K and gt != ignore_index), else -1.  ignore_index < 0: every
 // pixel of the image counts in "predicted"; >= 0: a pixel with g < 0 counts in none of the three rows (mmseg's intersect_and_union).
+// WIDE: pred is int16, and [4 waves][3][K] ints do not fit at K = 1024, so the three rows take turns in one [4 waves][K] area over
+// s.foot and s.hb (16 KB at K = 1024): predicted, intersection, labelled, each cleared, filled by wave_hist and summed over the
+// waves in the narrow order.  The slab's layout and bytes are the narrow epilogue's.
+template <bool WIDE>
 __device__ __forceinline__ void ra_tile_counts(const RaArgs& p, const RaLds& s, const RaTile& t, int arg) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int K = p.K;
   const bool valid = t.valid;
   const size_t o = (size_t)t.pix0 + (size_t)(t.Y0 + t.py) * t.W + t.X0 + t.px;
-  if (valid && p.pred) p.pred[o] = (uint8_t)arg;
+  if (valid && p.pred) {
+    if (WIDE) ((int16_t*)p.pred)[o] = (int16_t)arg;
+    else ((uint8_t*)p.pred)[o] = (uint8_t)arg;
+  }
   if (!p.slab) return;
 
   int g = -1;
@@ -317,6 +331,24 @@ __device__ __forceinline__ void ra_tile_counts(const RaArgs& p, const RaLds& s, 
     else v = ((const int64_t*)p.gt)[o];
     g = (v >= 0 && v < K && !(p.ignore_index >= 0 && v == p.ignore_index)) ? (int)v : -1;
   }
+  int* out = p.slab + (size_t)blockIdx.x * 3 * K;
+  if (WIDE) {
+    int* hw = s.hist + wid * K;   // this wave's row
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const int row = r == 0 ? 1 : r == 1 ? 0 : 2;   // the slab's row of this turn
+      for (int i = lane; i < K; i += 64) hw[i] = 0;
+      __syncthreads();
+      if (r == 0) wave_hist(hw, p.ignore_index >= 0 ? g >= 0 : valid, arg, lane);
+      else if (r == 1) wave_hist(hw, valid && g == arg, arg, lane);
+      else wave_hist(hw, g >= 0, g, lane);
+      __syncthreads();
+      for (int i = tid; i < K; i += RA_THREADS)
+        out[row * K + i] = ((s.hist[i] + s.hist[K + i]) + s.hist[2 * K + i]) + s.hist[3 * K + i];
+      if (r < 2) __syncthreads();   // the rows are cleared again
+    }
+    return;
+  }
   int* hw = s.hist + wid * 3 * K;   // this wave's three rows
   for (int i = lane; i < 3 * K; i += 64) hw[i] = 0;
   __syncthreads();
@@ -324,11 +356,11 @@ __device__ __forceinline__ void ra_tile_counts(const RaArgs& p, const RaLds& s, 
   wave_hist(hw, valid && g == arg, arg, lane);
   wave_hist(hw + 2 * K, g >= 0, g, lane);
   __syncthreads();
-  int* out = p.slab + (size_t)blockIdx.x * 3 * K;
   for (int i = tid; i < 3 * K; i += RA_THREADS)
     out[i] = ((s.hist[i] + s.hist[3 * K + i]) + s.hist[6 * K + i]) + s.hist[9 * K + i];
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(RA_THREADS) void ra_kernel(RaArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const RaLds s(smem);
@@ -338,9 +370,10 @@ __global__ __launch_bounds__(RA_THREADS) void ra_kernel(RaArgs p) {
   int arg = 0;
   ra_walk(s, t, p.h, p.w, p.ld, 0, p.K, RaGridSrc{p.src + (size_t)t.b * p.h * p.w * p.ld, p.w, p.ld},
           [&](int c0, int c4, float4 y) { ra_argmax4(best, arg, c0 + 4 * c4, y, p.K - c0 - 4 * c4); });
-  ra_tile_counts(p, s, t, arg);
+  ra_tile_counts<WIDE>(p, s, t, arg);
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(RA_THREADS) void ra_win_kernel(RaArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const RaLds s(smem);
@@ -359,7 +392,7 @@ __global__ __launch_bounds__(RA_THREADS) void ra_win_kernel(RaArgs p) {
   int arg = 0;
   ra_walk(s, t, Hc, Wc, p.ld, 0, p.K, RaWinSrc(p, s, Wc),
           [&](int c0, int c4, float4 y) { ra_argmax4(best, arg, c0 + 4 * c4, y, p.K - c0 - 4 * c4); });
-  ra_tile_counts(p, s, t, arg);
+  ra_tile_counts<WIDE>(p, s, t, arg);
 }
 
 // counts[b][e] = sum over the image's tiles of slab[tile][e], tiles in increasing order within each of 4 strided parts, the parts
@@ -395,7 +428,7 @@ __device__ __forceinline__ bool ms_canvas_ok(const RaArgs& p, const int64_t* c) 
          c[2] + c[3] <= p.n_win;
 }
 
-template <int MODE>
+template <int MODE, bool WIDE>
 __global__ __launch_bounds__(RA_THREADS) void ra_ms_kernel(RaArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const RaLds s(smem);
@@ -487,7 +520,7 @@ __global__ __launch_bounds__(RA_THREADS) void ra_ms_kernel(RaArgs p) {
         if (4 * c4 < nc) ra_argmax4(best, arg, c0 + 4 * c4, acc[c4], nc - 4 * c4);
     }
   }
-  ra_tile_counts(p, s, t, arg);
+  ra_tile_counts<WIDE>(p, s, t, arg);
 }
 
 // the main kernel over the tiles, then the per-image sum of the slabs if counts are wanted
@@ -501,82 +534,139 @@ int ra_launch(Kern kern, size_t lds, const RaArgs& a, int* counts, hipStream_t s
   return lc2is_check_launch();
 }
 
-}  // namespace
-
-extern "C" size_t lc2is_resize_argmax_workspace_bytes(long n_tiles, int K) {
-  if (n_tiles <= 0 || K <= 0 || K > RA_KMAX) return 0;
+// the workspace of n_tiles slabs at K classes, 0 when K is outside [1, kmax]
+size_t ra_workspace_bytes(long n_tiles, int K, int kmax) {
+  if (n_tiles <= 0 || K <= 0 || K > kmax) return 0;
   return (size_t)n_tiles * 3 * K * sizeof(int);
 }
 
-extern "C" int lc2is_resize_argmax(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc, long n_tiles,
-                                   long total_px, const void* gt, int gt_bytes, uint8_t* pred, int* counts, void* workspace,
-                                   size_t workspace_bytes, lc2is_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// The three entry points behind their narrow and wide forms (WIDE: int16 pred, K up to RA_KMAX_WIDE): the argument checks in
+// their order (NULL, SHAPE, UNSUPPORTED, WORKSPACE), then the launch.
+template <bool WIDE>
+int ra_run(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc, long n_tiles, long total_px,
+           const void* gt, int gt_bytes, void* pred, int* counts, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  constexpr int KMAX = WIDE ? RA_KMAX_WIDE : RA_KMAX;
   if (!scores || !desc || (!pred && !counts)) return LC2IS_ERR_NULL;
   if (counts && (!gt || !workspace)) return LC2IS_ERR_NULL;
   if (N <= 0 || h <= 0 || w <= 0 || K <= 0 || ld < K || ld % 4 || ((uintptr_t)scores & 15) || n_tiles <= 0 ||
       n_tiles > 0x7fffffffL || total_px <= 0)
     return LC2IS_ERR_SHAPE;
-  if (K > RA_KMAX) return LC2IS_ERR_UNSUPPORTED;
+  if (K > KMAX) return LC2IS_ERR_UNSUPPORTED;
   if (counts && gt_bytes != 1 && gt_bytes != 4 && gt_bytes != 8) return LC2IS_ERR_UNSUPPORTED;
-  if (counts && workspace_bytes < lc2is_resize_argmax_workspace_bytes(n_tiles, K)) return LC2IS_ERR_WORKSPACE;
+  if (counts && workspace_bytes < ra_workspace_bytes(n_tiles, K, KMAX)) return LC2IS_ERR_WORKSPACE;
   RaArgs a = {};
   a.src = scores; a.desc = desc; a.gt = counts ? gt : nullptr; a.pred = pred; a.slab = counts ? (int*)workspace : nullptr;
   a.total_px = total_px; a.N = N; a.h = h; a.w = w; a.ld = ld; a.K = K; a.n_tiles = (int)n_tiles; a.gt_bytes = gt_bytes;
   a.ignore_index = -1;
-  return ra_launch<4>(ra_kernel, RA_LDS, a, counts, stream);
+  return ra_launch<4>(ra_kernel<WIDE>, RA_LDS, a, counts, stream);
 }
 
-extern "C" int lc2is_resize_argmax_windows(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
-                                           const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt,
-                                           int gt_bytes, int ignore_index, uint8_t* pred, int* counts, void* workspace,
-                                           size_t workspace_bytes, lc2is_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+template <bool WIDE>
+int ra_run_windows(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N, const int32_t* win,
+                   long n_win, long n_tiles, long total_px, const void* gt, int gt_bytes, int ignore_index, void* pred,
+                   int* counts, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  constexpr int KMAX = WIDE ? RA_KMAX_WIDE : RA_KMAX;
   if (!views || !desc || !win || (!pred && !counts)) return LC2IS_ERR_NULL;
   if (counts && (!gt || !workspace)) return LC2IS_ERR_NULL;
   if (N <= 0 || V <= 0 || h <= 0 || w <= 0 || K <= 0 || ld < K || ld % 4 || ((uintptr_t)views & 15) || ((uintptr_t)win & 15) ||
       n_win <= 0 || n_tiles <= 0 || n_tiles > 0x7fffffffL || total_px <= 0 || ignore_index < -1)
     return LC2IS_ERR_SHAPE;
-  if (K > RA_KMAX) return LC2IS_ERR_UNSUPPORTED;
+  if (K > KMAX) return LC2IS_ERR_UNSUPPORTED;
   if (counts && gt_bytes != 1 && gt_bytes != 4 && gt_bytes != 8) return LC2IS_ERR_UNSUPPORTED;
-  if (counts && workspace_bytes < lc2is_resize_argmax_workspace_bytes(n_tiles, K)) return LC2IS_ERR_WORKSPACE;
+  if (counts && workspace_bytes < ra_workspace_bytes(n_tiles, K, KMAX)) return LC2IS_ERR_WORKSPACE;
   RaArgs a = {};
   a.src = views; a.desc = desc; a.win = win; a.gt = counts ? gt : nullptr; a.pred = pred;
   a.slab = counts ? (int*)workspace : nullptr;
   a.total_px = total_px; a.n_win = n_win; a.N = N; a.V = V; a.h = h; a.w = w; a.ld = ld; a.K = K; a.n_tiles = (int)n_tiles;
   a.gt_bytes = gt_bytes; a.ignore_index = ignore_index;
-  return ra_launch<8>(ra_win_kernel, RA_WIN_LDS, a, counts, stream);
+  return ra_launch<8>(ra_win_kernel<WIDE>, RA_WIN_LDS, a, counts, stream);
 }
 
-extern "C" int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
-                                              const int64_t* canv, long n_canv, const int32_t* win, long n_win, long n_tiles,
-                                              long total_px, const void* gt, int gt_bytes, int ignore_index, int mode,
-                                              uint8_t* pred, int* counts, void* workspace, size_t workspace_bytes,
-                                              lc2is_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+template <bool WIDE>
+int ra_run_multiscale(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N, const int64_t* canv,
+                      long n_canv, const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt, int gt_bytes,
+                      int ignore_index, int mode, void* pred, int* counts, void* workspace, size_t workspace_bytes,
+                      hipStream_t stream) {
+  constexpr int KMAX = WIDE ? RA_KMAX_WIDE : RA_KMAX;
   if (!views || !desc || !canv || !win || (!pred && !counts)) return LC2IS_ERR_NULL;
   if (counts && (!gt || !workspace)) return LC2IS_ERR_NULL;
   if (N <= 0 || V <= 0 || h <= 0 || w <= 0 || K <= 0 || ld < K || ld % 4 || ((uintptr_t)views & 15) || ((uintptr_t)win & 15) ||
       n_canv <= 0 || n_win <= 0 || n_tiles <= 0 || n_tiles > 0x7fffffffL || total_px <= 0 || ignore_index < -1 ||
       (mode != LC2IS_MS_LOGIT && mode != LC2IS_MS_PROB))
     return LC2IS_ERR_SHAPE;
-  if (K > RA_KMAX) return LC2IS_ERR_UNSUPPORTED;
+  if (K > KMAX) return LC2IS_ERR_UNSUPPORTED;
   if (counts && gt_bytes != 1 && gt_bytes != 4 && gt_bytes != 8) return LC2IS_ERR_UNSUPPORTED;
-  if (counts && workspace_bytes < lc2is_resize_argmax_workspace_bytes(n_tiles, K)) return LC2IS_ERR_WORKSPACE;
+  if (counts && workspace_bytes < ra_workspace_bytes(n_tiles, K, KMAX)) return LC2IS_ERR_WORKSPACE;
   RaArgs a = {};
   a.src = views; a.desc = desc; a.canv = canv; a.win = win; a.gt = counts ? gt : nullptr; a.pred = pred;
   a.slab = counts ? (int*)workspace : nullptr;
   a.total_px = total_px; a.n_canv = n_canv; a.n_win = n_win; a.N = N; a.V = V; a.h = h; a.w = w; a.ld = ld; a.K = K;
   a.n_tiles = (int)n_tiles; a.gt_bytes = gt_bytes; a.ignore_index = ignore_index;
   if (mode == LC2IS_MS_PROB) {
-    static DevOnce attr_set;   // 70 KB of dynamic LDS: above the default limit
+    static DevOnce attr_set;   // 70 KB of dynamic LDS: above the default limit (one flag per instantiation)
     if (attr_set.need()) {
-      if (hipFuncSetAttribute((const void*)ra_ms_kernel<LC2IS_MS_PROB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      if (hipFuncSetAttribute((const void*)ra_ms_kernel<LC2IS_MS_PROB, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)RA_MS_LDS_PROB) != hipSuccess)
         return LC2IS_ERR_LAUNCH;
       attr_set.done();
     }
-    return ra_launch<6>(ra_ms_kernel<LC2IS_MS_PROB>, RA_MS_LDS_PROB, a, counts, stream);
+    return ra_launch<6>(ra_ms_kernel<LC2IS_MS_PROB, WIDE>, RA_MS_LDS_PROB, a, counts, stream);
   }
-  return ra_launch<6>(ra_ms_kernel<LC2IS_MS_LOGIT>, RA_WIN_LDS, a, counts, stream);
+  return ra_launch<6>(ra_ms_kernel<LC2IS_MS_LOGIT, WIDE>, RA_WIN_LDS, a, counts, stream);
+}
+
+}  // namespace
+
+extern "C" size_t lc2is_resize_argmax_workspace_bytes(long n_tiles, int K) { return ra_workspace_bytes(n_tiles, K, RA_KMAX); }
+
+extern "C" size_t lc2is_resize_argmax_wide_workspace_bytes(long n_tiles, int K) {
+  return ra_workspace_bytes(n_tiles, K, RA_KMAX_WIDE);
+}
+
+extern "C" int lc2is_resize_argmax(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc, long n_tiles,
+                                   long total_px, const void* gt, int gt_bytes, uint8_t* pred, int* counts, void* workspace,
+                                   size_t workspace_bytes, lc2is_stream_t stream) {
+  return ra_run<false>(scores, ld, N, h, w, K, desc, n_tiles, total_px, gt, gt_bytes, pred, counts, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+
+extern "C" int lc2is_resize_argmax_wide(const float* scores, int ld, int N, int h, int w, int K, const int64_t* desc,
+                                        long n_tiles, long total_px, const void* gt, int gt_bytes, int16_t* pred, int* counts,
+                                        void* workspace, size_t workspace_bytes, lc2is_stream_t stream) {
+  return ra_run<true>(scores, ld, N, h, w, K, desc, n_tiles, total_px, gt, gt_bytes, pred, counts, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
+extern "C" int lc2is_resize_argmax_windows(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                           const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt,
+                                           int gt_bytes, int ignore_index, uint8_t* pred, int* counts, void* workspace,
+                                           size_t workspace_bytes, lc2is_stream_t stream) {
+  return ra_run_windows<false>(views, ld, V, h, w, K, desc, N, win, n_win, n_tiles, total_px, gt, gt_bytes, ignore_index, pred,
+                               counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lc2is_resize_argmax_windows_wide(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                                const int32_t* win, long n_win, long n_tiles, long total_px, const void* gt,
+                                                int gt_bytes, int ignore_index, int16_t* pred, int* counts, void* workspace,
+                                                size_t workspace_bytes, lc2is_stream_t stream) {
+  return ra_run_windows<true>(views, ld, V, h, w, K, desc, N, win, n_win, n_tiles, total_px, gt, gt_bytes, ignore_index, pred,
+                              counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lc2is_resize_argmax_multiscale(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc, int N,
+                                              const int64_t* canv, long n_canv, const int32_t* win, long n_win, long n_tiles,
+                                              long total_px, const void* gt, int gt_bytes, int ignore_index, int mode,
+                                              uint8_t* pred, int* counts, void* workspace, size_t workspace_bytes,
+                                              lc2is_stream_t stream) {
+  return ra_run_multiscale<false>(views, ld, V, h, w, K, desc, N, canv, n_canv, win, n_win, n_tiles, total_px, gt, gt_bytes,
+                                  ignore_index, mode, pred, counts, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int lc2is_resize_argmax_multiscale_wide(const float* views, int ld, int V, int h, int w, int K, const int64_t* desc,
+                                                   int N, const int64_t* canv, long n_canv, const int32_t* win, long n_win,
+                                                   long n_tiles, long total_px, const void* gt, int gt_bytes, int ignore_index,
+                                                   int mode, int16_t* pred, int* counts, void* workspace, size_t workspace_bytes,
+                                                   lc2is_stream_t stream) {
+  return ra_run_multiscale<true>(views, ld, V, h, w, K, desc, N, canv, n_canv, win, n_win, n_tiles, total_px, gt, gt_bytes,
+                                 ignore_index, mode, pred, counts, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -10,6 +10,9 @@ logits to ``sizes[i]`` (any size), argmax and counts against the original-resolu
 kernel (``ops.resize_argmax``) that never forms the [K, H, W] score map.  Returns ``dict(mIOU_gt=float)``.
 ``original_size_predictions(outputs, sizes)`` is the reference's ``original_size_interpolate`` (metrics.py:137-143) followed by
 the argmax: a uint8 class map per image at its own size.
+Past ``ops.RESIZE_KMAX`` = 192 classes (up to 1024) both go through ``ops.resize_argmax_wide``: the same arithmetic per class and
+int16 class maps (``model.predict``'s convention).  ``compute_mIOU`` / ``per_image_mIOU`` stay at 192 classes (the narrow
+``head_upsample_ce`` + ``miou_counts``); past them the model-size mIoU is ``forward_loss(..., seg_counts=)``.
 
 ``dataset_iou(counts_sum)``: the dataset-level scores of the published protocol (mmseg's IoUMetric: mIoU, mAcc, aAcc) from
 {intersection, predicted, labelled} counts summed over all images, as ``slide.SlidingWindowInference.counts`` produces them."""
@@ -35,6 +38,11 @@ def _per_image_iou(counts: torch.Tensor, ignore_index: int | None) -> torch.Tens
     return (iou * present).sum(1) / present.sum(1).to(torch.float64)
 
 
+def _resize_argmax_op(outputs: torch.Tensor):
+    """``ops.resize_argmax``, or its wide form past 192 classes."""
+    return ops.resize_argmax_wide if outputs.dim() == 4 and outputs.shape[1] > ops.RESIZE_KMAX else ops.resize_argmax
+
+
 def per_image_mIOU(outputs: torch.Tensor, labels: torch.Tensor, n_cls: int = 151, ignore_index: int | None = 0) -> torch.Tensor:
     """The per-image values whose mean ``compute_mIOU`` returns (float64 [N] on the device; NaN for an image whose label holds
     nothing but ``ignore_index``).  ``Evaluator`` accumulates these batch by batch instead of keeping every batch's logits."""
@@ -56,7 +64,7 @@ def per_image_gt_mIOU(outputs: torch.Tensor, gt_list, sizes=None, n_cls: int = 1
     """The per-image values whose mean ``compute_gt_mIOU`` returns (float64 [N] on the device; NaN for an image whose gt holds
     nothing but ``ignore_index``).  gt_list: N label maps [H_i, W_i] (uint8 / int32 / int64, host or device); sizes: N (H, W)
     pairs or an [N, 2] tensor, None = the gt maps' shapes (ValueError when they disagree)."""
-    _, counts = ops.resize_argmax(outputs, sizes, gt=list(gt_list), want_pred=False)
+    _, counts = _resize_argmax_op(outputs)(outputs, sizes, gt=list(gt_list), want_pred=False)
     return _per_image_iou(counts, ignore_index)
 
 
@@ -65,9 +73,9 @@ def compute_gt_mIOU(outputs: torch.Tensor, gt_list, sizes, n_cls: int = 151, ign
 
 
 def original_size_predictions(outputs: torch.Tensor, sizes) -> list[torch.Tensor]:
-    """The class map of each image at its original size: uint8 [H_i, W_i] on the device (the argmax of the bicubic resize of
-    outputs[i] to sizes[i], exact ties to the lowest class)."""
-    preds, _ = ops.resize_argmax(outputs, sizes, want_pred=True)
+    """The class map of each image at its original size: uint8 [H_i, W_i] on the device, int16 past 192 classes (the argmax of
+    the bicubic resize of outputs[i] to sizes[i], exact ties to the lowest class)."""
+    preds, _ = _resize_argmax_op(outputs)(outputs, sizes, want_pred=True)
     return preds
 
 

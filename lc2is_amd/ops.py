@@ -115,6 +115,11 @@ _ARGTYPES = {
     "lc2is_resize_argmax": [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _I, _P, _P, _P, _Z, _P],
     "lc2is_resize_argmax_windows": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _Z, _P],
     "lc2is_resize_argmax_multiscale": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _Z, _P],
+    "lc2is_resize_argmax_wide_workspace_bytes": [_L, _I],
+    "lc2is_resize_argmax_wide": [_P, _I, _I, _I, _I, _I, _P, _L, _L, _P, _I, _P, _P, _P, _Z, _P],
+    "lc2is_resize_argmax_windows_wide": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _Z, _P],
+    "lc2is_resize_argmax_multiscale_wide": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _Z,
+                                            _P],
     "lc2is_npair_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_gemm_tn_grouped_workspace_bytes": [_P, _I],
     "lc2is_gemm_tn_grouped": [_P, _I, _P, _Z, _P],
@@ -1651,6 +1656,7 @@ def miou_counts(scores_hi, labels_lo, S: int):
 
 
 RESIZE_TILE, RESIZE_KMAX = 16, 192      # LC2IS_RESIZE_TILE; the largest class count of lc2is_resize_argmax
+RESIZE_WIDE_KMAX = 1024                 # LC2IS_RESIZE_WIDE_KMAX: the largest class count of the lc2is_resize_argmax*_wide entries
 _GT_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
 
 
@@ -1684,8 +1690,8 @@ def _resize_layout(hw):
     return px, first_px, first_tile, sum(tiles), sum(px)
 
 
-def _resize_gt(gt, dts, N, K, n_tiles, dev):
-    """(packed gt, counts, workspace, its bytes) of a call with gt maps."""
+def _resize_gt(gt, dts, N, K, n_tiles, dev, wide=False):
+    """(packed gt, counts, workspace, its bytes) of a call with gt maps (wide: the workspace query of the wide entries)."""
     dt = dts.pop() if len(dts) == 1 else torch.int64
     flat = [x.reshape(-1) for x in gt]
     if all(not x.is_cuda for x in flat):
@@ -1693,18 +1699,19 @@ def _resize_gt(gt, dts, N, K, n_tiles, dev):
     else:
         g = torch.cat([x.to(dev, dt) for x in flat])
     counts = torch.empty((N, 3, K), dtype=torch.int32, device=dev)
-    nbytes = _fn("lc2is_resize_argmax_workspace_bytes")(n_tiles, K)
+    nbytes = _fn("lc2is_resize_argmax_wide_workspace_bytes" if wide else "lc2is_resize_argmax_workspace_bytes")(n_tiles, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)     # per-tile counts (per call: live until the second launch)
     return g, counts, ws, nbytes
 
 
-def _resize_front(who, x, what):
-    """The first checks of the three resize + argmax wrappers: x is NCHW with 1 <= K <= 192.  Returns its shape."""
+def _resize_front(who, x, what, kmax=RESIZE_KMAX):
+    """The first checks of the resize + argmax wrappers: x is NCHW with 1 <= K <= kmax (192; the wide wrappers pass 1024).
+    Returns its shape."""
     if x.dim() != 4:
         raise RuntimeError(f"{who}: {what}, got shape {tuple(x.shape)}")
     K = x.shape[1]
-    if not 1 <= K <= RESIZE_KMAX:
-        raise RuntimeError(f"{who}: K = {K} classes is not supported (1 <= K <= {RESIZE_KMAX})")
+    if not 1 <= K <= kmax:
+        raise RuntimeError(f"{who}: K = {K} classes is not supported (1 <= K <= {kmax})")
     return tuple(x.shape)
 
 
@@ -1760,17 +1767,18 @@ def _resize_channels_last(x):
     return lo, ld
 
 
-def _resize_run(hw, K, gt, dts, want_pred, dev, launch):
-    """The common tail: the packed layout, pred / gt / counts / workspace, the launch and the split of the packed pred.
+def _resize_run(hw, K, gt, dts, want_pred, dev, launch, wide=False):
+    """The common tail: the packed layout, pred (uint8; wide: int16) / gt / counts / workspace, the launch and the split of the
+    packed pred.
     launch(layout, pred, g, gt_bytes, counts, ws, nbytes) makes the descriptors from layout = (first_px, first_tile, n_tiles,
     total_px), calls the library and checks its return code."""
     N = len(hw)
     px, first_px, first_tile, n_tiles, total_px = _resize_layout(hw)
-    pred = torch.empty(total_px, dtype=torch.uint8, device=dev) if want_pred else None
+    pred = torch.empty(total_px, dtype=torch.int16 if wide else torch.uint8, device=dev) if want_pred else None
     counts = g = ws = None
     nbytes = 0
     if gt is not None:
-        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev)
+        g, counts, ws, nbytes = _resize_gt(gt, dts, N, K, n_tiles, dev, wide)
     launch((first_px, first_tile, n_tiles, total_px), pred, g, _GT_BYTES[g.dtype] if g is not None else 0, counts, ws, nbytes)
     preds = None if pred is None else [x.view(H, W) for x, (H, W) in zip(torch.split(pred, px), hw)]
     return preds, counts
@@ -1779,13 +1787,20 @@ def _resize_run(hw, K, gt, dts, want_pred, dev, launch):
 def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     """Per image, F.interpolate(scores[i:i+1], size=sizes[i], mode="bicubic", align_corners=False) and the argmax over the classes
     (exact ties: the lowest index), fused: the [K, H, W] score map is never formed (lc2is_resize_argmax).
-    scores: the model's NCHW [N, K, h, w] logits on the GPU (any float dtype; the channels-last fp32 copy is made here), K <= 192.
+    scores: the model's NCHW [N, K, h, w] logits on the GPU (any float dtype; the channels-last fp32 copy is made here), K <= 192
+    (193 to 1024 classes: ``resize_argmax_wide``).
     sizes: N (H, W) pairs (sequence or [N, 2] tensor) or None (the gt maps' shapes).  gt: None or N label maps [H_i, W_i]
     (uint8 / int32 / int64, host or device).
     Returns (pred, counts): pred a list of uint8 [H_i, W_i] (views of one packed buffer) or None (want_pred=False);
     counts int32 [N, 3, K] = {intersection, predicted, labelled} (labelled: 0 <= gt < K) when gt is given, else None."""
-    who = "lc2is_amd.resize_argmax"
-    N, K, h, w = _resize_front(who, scores, "scores must be NCHW [N, K, h, w]")
+    return _resize_argmax(scores, sizes, gt, want_pred, wide=False)
+
+
+def _resize_argmax(scores, sizes, gt, want_pred, wide):
+    """``resize_argmax`` (wide=False) and ``resize_argmax_wide``: one body, the entry point, class limit and pred dtype differ."""
+    name = "resize_argmax_wide" if wide else "resize_argmax"
+    who = f"lc2is_amd.{name}"
+    N, K, h, w = _resize_front(who, scores, "scores must be NCHW [N, K, h, w]", RESIZE_WIDE_KMAX if wide else RESIZE_KMAX)
     hw = resize_sizes(N, sizes, gt)
     dts = _resize_back(who, scores, "scores", gt, want_pred)
     dev = scores.device
@@ -1794,10 +1809,18 @@ def resize_argmax(scores, sizes, gt=None, want_pred: bool = True):
     def launch(layout, pred, g, gt_bytes, counts, ws, nbytes):
         first_px, first_tile, n_tiles, total_px = layout
         desc = torch.tensor([[H, W, p0, t0] for (H, W), p0, t0 in zip(hw, first_px, first_tile)], dtype=torch.int64).to(dev)
-        rc = _fn("lc2is_resize_argmax")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g), gt_bytes, _ptr(pred),
-                                        _ptr(counts), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, f"resize_argmax N={N} K={K} h={h} w={w}")
-    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
+        rc = _fn(f"lc2is_{name}")(_ptr(lo), ld, N, h, w, K, _ptr(desc), n_tiles, total_px, _ptr(g), gt_bytes, _ptr(pred),
+                                  _ptr(counts), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, f"{name} N={N} K={K} h={h} w={w}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch, wide)
+
+
+def resize_argmax_wide(scores, sizes, gt=None, want_pred: bool = True):
+    """``resize_argmax`` for 1 <= K <= 1024 classes (lc2is_resize_argmax_wide): the same arguments and checks; pred is a list of
+    int16 [H_i, W_i] views, counts int32 [N, 3, K].  With K <= 192 it returns ``resize_argmax``'s class indices and counts, which
+    is then the faster call (its count epilogue holds the three rows of a tile at once).  The per-tile count workspace is
+    n_tiles * 3 * K * 4 bytes: 14 MB for one 683 x 512 image at K = 847."""
+    return _resize_argmax(scores, sizes, gt, want_pred, wide=True)
 
 
 SLIDE_MAX_WIN = 64                      # LC2IS_SLIDE_MAX_WIN: windows per image of lc2is_resize_argmax_windows
@@ -1812,8 +1835,14 @@ def resize_argmax_windows(views, windows, canvases, sizes, gt=None, want_pred: b
     sizes, gt, want_pred and the returned (pred, counts): as ``resize_argmax``.  ignore_index: None = its counting rule; an int
     >= 0 = mmseg's: a pixel whose gt is ignore_index or outside [0, K) counts in none of the three rows.
     Everything is validated on the host before anything is allocated."""
-    who = "lc2is_amd.resize_argmax_windows"
-    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]")
+    return _resize_argmax_windows(views, windows, canvases, sizes, gt, want_pred, ignore_index, wide=False)
+
+
+def _resize_argmax_windows(views, windows, canvases, sizes, gt, want_pred, ignore_index, wide):
+    """``resize_argmax_windows`` (wide=False) and ``resize_argmax_windows_wide``: one body."""
+    name = "resize_argmax_windows_wide" if wide else "resize_argmax_windows"
+    who = f"lc2is_amd.{name}"
+    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]", RESIZE_WIDE_KMAX if wide else RESIZE_KMAX)
     N = len(windows)
     if N < 1 or len(canvases) != N:
         raise ValueError(f"{who}: {N} window lists for {len(canvases)} canvases")
@@ -1836,11 +1865,18 @@ def resize_argmax_windows(views, windows, canvases, sizes, gt=None, want_pred: b
         desc = torch.tensor([[H, W, p0, t0, Hc, Wc, w0, len(wl)] for (H, W), p0, t0, (Hc, Wc), w0, wl in
                              zip(hw, first_px, first_tile, canv, first_win, windows)], dtype=torch.int64).to(dev)
         win = torch.tensor(rows, dtype=torch.int32).to(dev)
-        rc = _fn("lc2is_resize_argmax_windows")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(win), len(rows), n_tiles, total_px,
-                                                _ptr(g), gt_bytes, -1 if ignore_index is None else int(ignore_index), _ptr(pred),
-                                                _ptr(counts), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, f"resize_argmax_windows N={N} V={V} K={K} h={h} w={w}")
-    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
+        rc = _fn(f"lc2is_{name}")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(win), len(rows), n_tiles, total_px, _ptr(g),
+                                  gt_bytes, -1 if ignore_index is None else int(ignore_index), _ptr(pred), _ptr(counts), _ptr(ws),
+                                  nbytes, _stream())
+        _lib.check(rc, f"{name} N={N} V={V} K={K} h={h} w={w}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch, wide)
+
+
+def resize_argmax_windows_wide(views, windows, canvases, sizes, gt=None, want_pred: bool = True,
+                               ignore_index: int | None = None):
+    """``resize_argmax_windows`` for 1 <= K <= 1024 classes (lc2is_resize_argmax_windows_wide): the same arguments and checks;
+    pred is int16, and with K <= 192 the class indices and counts are ``resize_argmax_windows``'s (the faster call there)."""
+    return _resize_argmax_windows(views, windows, canvases, sizes, gt, want_pred, ignore_index, wide=True)
 
 
 MS_MAX_CANVAS = 16                      # LC2IS_MS_MAX_CANVAS: canvases per image of lc2is_resize_argmax_multiscale
@@ -1859,8 +1895,14 @@ def resize_argmax_multiscale(views, canvases, sizes, gt=None, want_pred: bool = 
     over that part).
     views, sizes, gt, want_pred, ignore_index and the returned (pred, counts): as ``resize_argmax_windows``.
     Everything is validated on the host before anything is allocated."""
-    who = "lc2is_amd.resize_argmax_multiscale"
-    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]")
+    return _resize_argmax_multiscale(views, canvases, sizes, gt, want_pred, ignore_index, mode, wide=False)
+
+
+def _resize_argmax_multiscale(views, canvases, sizes, gt, want_pred, ignore_index, mode, wide):
+    """``resize_argmax_multiscale`` (wide=False) and ``resize_argmax_multiscale_wide``: one body."""
+    name = "resize_argmax_multiscale_wide" if wide else "resize_argmax_multiscale"
+    who = f"lc2is_amd.{name}"
+    V, K, h, w = _resize_front(who, views, "views must be NCHW [V, K, h, w]", RESIZE_WIDE_KMAX if wide else RESIZE_KMAX)
     if mode not in _MS_MODES:
         raise ValueError(f"{who}: mode must be 'prob' or 'logit', got {mode!r}")
     N = len(canvases)
@@ -1889,12 +1931,19 @@ def resize_argmax_multiscale(views, canvases, sizes, gt=None, want_pred: bool = 
                              zip(hw, first_px, first_tile, first_canvas, canvases)], dtype=torch.int64).to(dev)
         canv = torch.tensor(crows, dtype=torch.int64).to(dev)
         win = torch.tensor(rows, dtype=torch.int32).to(dev)
-        rc = _fn("lc2is_resize_argmax_multiscale")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(canv), len(crows), _ptr(win),
-                                                   len(rows), n_tiles, total_px, _ptr(g), gt_bytes,
-                                                   -1 if ignore_index is None else int(ignore_index), _MS_MODES[mode], _ptr(pred),
-                                                   _ptr(counts), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, f"resize_argmax_multiscale N={N} V={V} K={K} h={h} w={w} canvases={len(crows)} mode={mode}")
-    return _resize_run(hw, K, gt, dts, want_pred, dev, launch)
+        rc = _fn(f"lc2is_{name}")(_ptr(lo), ld, V, h, w, K, _ptr(desc), N, _ptr(canv), len(crows), _ptr(win), len(rows), n_tiles,
+                                  total_px, _ptr(g), gt_bytes, -1 if ignore_index is None else int(ignore_index), _MS_MODES[mode],
+                                  _ptr(pred), _ptr(counts), _ptr(ws), nbytes, _stream())
+        _lib.check(rc, f"{name} N={N} V={V} K={K} h={h} w={w} canvases={len(crows)} mode={mode}")
+    return _resize_run(hw, K, gt, dts, want_pred, dev, launch, wide)
+
+
+def resize_argmax_multiscale_wide(views, canvases, sizes, gt=None, want_pred: bool = True, ignore_index: int | None = None,
+                                  mode: str = "prob"):
+    """``resize_argmax_multiscale`` for 1 <= K <= 1024 classes (lc2is_resize_argmax_multiscale_wide): the same arguments, checks
+    and modes; pred is int16, and with K <= 192 the class indices and counts are ``resize_argmax_multiscale``'s (the faster call
+    there)."""
+    return _resize_argmax_multiscale(views, canvases, sizes, gt, want_pred, ignore_index, mode, wide=True)
 
 
 # ---- Swin backbone ----------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 segmentors use (mmseg's ``slide_inference`` after ``Resize`` to the short edge + ``ResizeToMultiple``), on this repo's kernels.
 
     inf = SlidingWindowInference(model, text_inputs, size=512, crop=512, stride=340, flip=True)
-    preds = inf.predict(images)                 # list of uint8 [H_i, W_i] class maps, on the device
+    preds = inf.predict(images)                 # list of uint8 [H_i, W_i] class maps (int16 past 192 classes), on the device
     counts = inf.counts(images, gt_list)        # int32 [N, 3, K] {intersection, predicted, labelled}, mmseg's counting rule
 
 Per image (decoded uint8 HWC): Pillow-exact bicubic resize (``ops.resample_u8``) to ``eval_size`` — the short edge at ``size``,
@@ -22,6 +22,8 @@ every scale and flip) is one canvas of ONE ``ops.resize_argmax_multiscale`` call
 takes the softmax over the classes of each, sums them and takes the argmax ("logit": sums the resized logits).  A scale whose short
 edge is below ``crop`` gives an image smaller than a window: the window is padded at the bottom / right with 0.0 after normalisation
 (the mean colour, as the training crops are) and only its unpadded cells enter the canvas.
+Past ``ops.RESIZE_KMAX`` = 192 classes (up to 1024) both classes call the ``_wide`` forms of the two ops: the same arithmetic per
+class, int16 class maps, int32 [N, 3, K] counts (``model.predict``'s convention).  Nothing changes at 192 classes or fewer.
 Out of scope: per-scale weights, windows off the cell grid, models that take variable input sizes (every forward is a ``crop`` x
 ``crop`` window)."""
 from __future__ import annotations
@@ -30,6 +32,19 @@ import torch
 
 from . import ops
 from .data.preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, ClipImagePreprocessor, _target_size
+
+
+def _wide(views: torch.Tensor) -> bool:
+    """More classes than the narrow resize + argmax kernels take: the call goes to their ``_wide`` forms."""
+    return views.dim() == 4 and views.shape[1] > ops.RESIZE_KMAX
+
+
+def _windows_op(views):
+    return ops.resize_argmax_windows_wide if _wide(views) else ops.resize_argmax_windows
+
+
+def _multiscale_op(views):
+    return ops.resize_argmax_multiscale_wide if _wide(views) else ops.resize_argmax_multiscale
 
 
 def plan_windows(n: int, win: int, stride: int) -> list[int]:
@@ -125,13 +140,12 @@ class SlidingWindowInference:
 
     def predict(self, images) -> list[torch.Tensor]:
         views, windows, canvases, sizes = self.views(images)
-        preds, _ = ops.resize_argmax_windows(views, windows, canvases, sizes)
+        preds, _ = _windows_op(views)(views, windows, canvases, sizes)
         return preds
 
     def counts(self, images, gt_list, ignore_index: int | None = 0) -> torch.Tensor:
         views, windows, canvases, sizes = self.views(images)
-        _, c = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=list(gt_list), want_pred=False,
-                                         ignore_index=ignore_index)
+        _, c = _windows_op(views)(views, windows, canvases, sizes, gt=list(gt_list), want_pred=False, ignore_index=ignore_index)
         return c
 
     def counts_both(self, images, gt_list, ignore_index: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
@@ -139,8 +153,8 @@ class SlidingWindowInference:
         of forwards and two fused launches: the dataset-level scores take the first, the reference's per-image mIoU the second."""
         views, windows, canvases, sizes = self.views(images)
         gt = list(gt_list)
-        _, c = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index)
-        _, c_ref = ops.resize_argmax_windows(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=None)
+        _, c = _windows_op(views)(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index)
+        _, c_ref = _windows_op(views)(views, windows, canvases, sizes, gt=gt, want_pred=False, ignore_index=None)
         return c, c_ref
 
 
@@ -258,19 +272,18 @@ class MultiScaleInference(SlidingWindowInference):
 
     def predict(self, images) -> list[torch.Tensor]:
         views, canvases, sizes = self.views(images)
-        preds, _ = ops.resize_argmax_multiscale(views, canvases, sizes, mode=self.average)
+        preds, _ = _multiscale_op(views)(views, canvases, sizes, mode=self.average)
         return preds
 
     def counts(self, images, gt_list, ignore_index: int | None = 0) -> torch.Tensor:
         views, canvases, sizes = self.views(images)
-        _, c = ops.resize_argmax_multiscale(views, canvases, sizes, gt=list(gt_list), want_pred=False, ignore_index=ignore_index,
-                                            mode=self.average)
+        _, c = _multiscale_op(views)(views, canvases, sizes, gt=list(gt_list), want_pred=False, ignore_index=ignore_index,
+                                     mode=self.average)
         return c
 
     def counts_both(self, images, gt_list, ignore_index: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
         views, canvases, sizes = self.views(images)
         gt = list(gt_list)
-        _, c = ops.resize_argmax_multiscale(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index,
-                                            mode=self.average)
-        _, c_ref = ops.resize_argmax_multiscale(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=None, mode=self.average)
+        _, c = _multiscale_op(views)(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=ignore_index, mode=self.average)
+        _, c_ref = _multiscale_op(views)(views, canvases, sizes, gt=gt, want_pred=False, ignore_index=None, mode=self.average)
         return c, c_ref
