@@ -25,7 +25,8 @@ from .base import assign_rng_names, require_cuda
 from .clip import ClipArch, ImageEncoderCLIPFull, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer, PromptDecoder, PromptLayer
 from .hier import FTNDecoder
-from .model import TextToPatch, fused_focal_options, fused_loss_options, fused_sigmoid_options
+from .head_loss import head_criterion
+from .model import TextToPatch
 from .score import ScoreMapTail, _scores_bwd, _scores_lo
 from .swin import SWIN_B, SwinArch, SwinTransformer
 
@@ -78,19 +79,11 @@ class PromptFTN(nn.Module):
         place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``.  ``sigmoid=(gamma, alpha,
         normalize)``: SigmoidFocalLoss's per-class binary loss instead (``ScoreMapTail.loss``); not combinable with ``focal=`` or
         ``label_smoothing``."""
-        fused_sigmoid_options(sigmoid, label_smoothing, None, focal)   # (refused before the towers run)
-        fused_focal_options(focal, label_smoothing, None)
-        fused_loss_options(weight, label_smoothing, reduction)
-        if seg_counts is not None:
-            ops.check_seg_counts(seg_counts)
+        keywords = dict(weight=weight, label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, accum=accum,
+                        focal=focal, sigmoid=sigmoid)
+        head_criterion("PromptFTN.forward_loss", **keywords)   # refused before the towers run; the tail adds what needs the class count
         visual_embeddings, text_embeddings = self._embeddings(inputs)
-        extra = {} if accum is None else {"accum": accum}
-        if focal is not None:
-            extra["focal"] = focal
-        if sigmoid is not None:
-            extra["sigmoid"] = sigmoid
-        return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, weight=weight,
-                              label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, **extra)
+        return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, **keywords)
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:

@@ -32,29 +32,31 @@ class _CEFn(torch.autograd.Function):
         return ops.ce_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index), None, None
 
 
-class _CEOptsFn(torch.autograd.Function):
-    """Class weights / label smoothing / 'sum' / 'none' (the default configuration stays on _CEFn)."""
+class _PixelLossFn(torch.autograd.Function):
+    """A per-pixel criterion on NCHW logits with 'mean' / 'sum' / 'none': ``fwd`` / ``bwd`` are its pair of ops, ``kw`` their
+    keywords.  ``has_lse``: ``fwd`` returns (loss2, lse[, per-pixel]) and ``bwd`` takes the lse after the labels (the softmax
+    losses); otherwise loss2 or (loss2, per-pixel) and no lse (the sigmoid losses).  The default cross-entropy stays on _CEFn."""
 
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index, weight, label_smoothing, reduction):
+    def forward(ctx, logits, labels, ignore_index, reduction, fwd, bwd, has_lse, kw):
         lg = logits.float().contiguous()
         lb = labels.contiguous()
-        kw = dict(class_weight=weight, label_smoothing=label_smoothing)
-        loss2, lse, *lpx = ops.ce_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
-        ctx.saved = (lg, lb, lse, loss2, ignore_index, kw, reduction)
+        out = fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
+        loss2, *rest = out if (has_lse or reduction == "none") else (out,)
+        ctx.saved = (lg, lb, rest[:1] if has_lse else [], loss2, ignore_index, kw, reduction, bwd)
         if reduction == "none":
-            return lpx[0]
+            return rest[-1]
         return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
 
     @staticmethod
     def backward(ctx, g):
-        lg, lb, lse, loss2, ignore_index, kw, reduction = ctx.saved
+        lg, lb, lse, loss2, ignore_index, kw, reduction, bwd = ctx.saved
         if reduction == "none":
-            d = ops.ce_nchw_bwd(lg, lb, lse, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
-        else:   # device scalar: upstream gradient (over the weighted count for 'mean')
+            d = bwd(lg, lb, *lse, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
+        else:   # device scalar: upstream gradient (over the weighted count / the number of counted pixels for 'mean')
             scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
-            d = ops.ce_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index, **kw)
-        return d, None, None, None, None, None
+            d = bwd(lg, lb, *lse, scale, 1.0, ignore_index, **kw)
+        return (d,) + (None,) * 7
 
 
 class CrossEntropyLoss(nn.Module):
@@ -76,18 +78,23 @@ class CrossEntropyLoss(nn.Module):
         self.reduction = reduction
         self.label_smoothing = label_smoothing
 
-    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def _check_nchw(self, input: torch.Tensor, target: torch.Tensor, name: str) -> None:
+        """The guard of every ``forward`` of this family; ``name``: the class whose forward it is."""
         require_cuda(input, "logits")
         if input.dim() != 4 or target.dim() != 3:
-            raise ValueError("lc2is_amd CrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
+            raise ValueError(f"lc2is_amd {name} expects [B,C,H,W] logits and [B,H,W] labels")
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        self._check_nchw(input, target, "CrossEntropyLoss")
         if self.weight is None and self.label_smoothing == 0.0 and self.reduction == "mean":
             return _CEFn.apply(input, target, self.ignore_index)
-        return _CEOptsFn.apply(input, target, self.ignore_index, self.weight, self.label_smoothing, self.reduction)
+        return _PixelLossFn.apply(input, target, self.ignore_index, self.reduction, ops.ce_nchw_fwd, ops.ce_nchw_bwd, True,
+                                  dict(class_weight=self.weight, label_smoothing=self.label_smoothing))
 
 
 def check_ohem(thresh, min_kept) -> tuple[float, int]:
     """(thresh, min_kept per image) of an OHEM selection, validated: thresh in (0, 1], min_kept an integer >= 0."""
-    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 < float(thresh) <= 1.0:
+    if not ops.finite_ge(thresh) or not 0.0 < thresh <= 1.0:
         raise ValueError(f"OHEM thresh must be a number in (0, 1] (thresh=None, pure top-k, is not implemented), got {thresh!r}")
     if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 0:
         raise ValueError(f"OHEM min_kept must be an integer >= 0 (pixels per image), got {min_kept!r}")
@@ -121,9 +128,7 @@ class OhemCrossEntropyLoss(CrossEntropyLoss):
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if not self.training:
             return super().forward(input, target)
-        require_cuda(input, "logits")
-        if input.dim() != 4 or target.dim() != 3:
-            raise ValueError("lc2is_amd OhemCrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        self._check_nchw(input, target, "OhemCrossEntropyLoss")
         lg = input.detach().float().contiguous()
         lb = target.contiguous()
         _, _, lpx = ops.ce_nchw_fwd(lg, lb, self.ignore_index, per_pixel=True)   # plain CE per pixel: no weights, no smoothing
@@ -182,38 +187,13 @@ class DiceCrossEntropyLoss(CrossEntropyLoss):
         return self.ce_weight, self.dice_weight, self.smooth, self.present_only
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        require_cuda(input, "logits")
-        if input.dim() != 4 or target.dim() != 3:
-            raise ValueError("lc2is_amd DiceCrossEntropyLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        self._check_nchw(input, target, "DiceCrossEntropyLoss")
         return _DiceFn.apply(input, target, self.ignore_index, check_dice(*self.dice), self)
 
 
 def check_focal(gamma, poly_eps) -> tuple[float, float]:
     """(gamma, poly_eps) of a focal / poly-1 loss, validated: gamma a finite number >= 0, poly_eps a finite number >= -1."""
     return ops.focal_options(gamma, poly_eps)
-
-
-class _FocalFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, ignore_index, weight, focal, reduction):
-        lg = logits.float().contiguous()
-        lb = labels.contiguous()
-        kw = dict(class_weight=weight, gamma=focal[0], poly_eps=focal[1])
-        loss2, lse, *lpx = ops.focal_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
-        ctx.saved = (lg, lb, lse, loss2, ignore_index, kw, reduction)
-        if reduction == "none":
-            return lpx[0]
-        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lg, lb, lse, loss2, ignore_index, kw, reduction = ctx.saved
-        if reduction == "none":
-            d = ops.focal_nchw_bwd(lg, lb, lse, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
-        else:   # device scalar: upstream gradient (over the weighted count for 'mean')
-            scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
-            d = ops.focal_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index, **kw)
-        return d, None, None, None, None, None
 
 
 class FocalLoss(CrossEntropyLoss):
@@ -238,12 +218,12 @@ class FocalLoss(CrossEntropyLoss):
         return self.gamma, self.poly_eps
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        require_cuda(input, "logits")
-        if input.dim() != 4 or target.dim() != 3:
-            raise ValueError("lc2is_amd FocalLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        self._check_nchw(input, target, "FocalLoss")
         if self.label_smoothing != 0.0:
             raise ValueError("FocalLoss: label_smoothing has no agreed definition for a focal / poly-1 loss")
-        return _FocalFn.apply(input, target, self.ignore_index, self.weight, check_focal(*self.focal), self.reduction)
+        gamma, poly_eps = check_focal(*self.focal)
+        return _PixelLossFn.apply(input, target, self.ignore_index, self.reduction, ops.focal_nchw_fwd, ops.focal_nchw_bwd, True,
+                                  dict(class_weight=self.weight, gamma=gamma, poly_eps=poly_eps))
 
 
 class Poly1CrossEntropyLoss(FocalLoss):
@@ -264,31 +244,6 @@ def check_sigmoid(gamma, alpha, normalize="elements"):
     """(gamma, alpha, normalize) of a sigmoid focal / sigmoid cross-entropy loss, validated: gamma a finite number >= 0, alpha None
     or a number in [0, 1], normalize 'elements' or 'pixels'."""
     return ops.sigmoid_options(gamma, alpha, normalize)
-
-
-class _SigmoidFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, ignore_index, weight, sigmoid, reduction):
-        lg = logits.float().contiguous()
-        lb = labels.contiguous()
-        kw = dict(class_weight=weight, gamma=sigmoid[0], alpha=sigmoid[1],
-                  class_scale=ops.sigmoid_class_scale(sigmoid[2], reduction, lg.shape[1]))
-        out = ops.sigmoid_focal_nchw_fwd(lg, lb, ignore_index, per_pixel=reduction == "none", **kw)
-        loss2 = out[0] if reduction == "none" else out
-        ctx.saved = (lg, lb, loss2, ignore_index, kw, reduction)
-        if reduction == "none":
-            return out[1]
-        return loss2[0] / loss2[1] if reduction == "mean" else loss2[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lg, lb, loss2, ignore_index, kw, reduction = ctx.saved
-        if reduction == "none":
-            d = ops.sigmoid_focal_nchw_bwd(lg, lb, None, 1.0, ignore_index, grad_px=g.float().contiguous(), **kw)
-        else:   # device scalar: upstream gradient (over the number of counted pixels for 'mean')
-            scale = (g / loss2[1] if reduction == "mean" else g).reshape(1).float().contiguous()
-            d = ops.sigmoid_focal_nchw_bwd(lg, lb, scale, 1.0, ignore_index, **kw)
-        return d, None, None, None, None, None
 
 
 class SigmoidFocalLoss(CrossEntropyLoss):
@@ -316,12 +271,14 @@ class SigmoidFocalLoss(CrossEntropyLoss):
         return self.gamma, self.alpha, self.normalize
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        require_cuda(input, "logits")
-        if input.dim() != 4 or target.dim() != 3:
-            raise ValueError("lc2is_amd SigmoidFocalLoss expects [B,C,H,W] logits and [B,H,W] labels")
+        self._check_nchw(input, target, "SigmoidFocalLoss")
         if self.label_smoothing != 0.0:
             raise ValueError("SigmoidFocalLoss: label_smoothing is not defined for the sigmoid losses")
-        return _SigmoidFn.apply(input, target, self.ignore_index, self.weight, check_sigmoid(*self.sigmoid), self.reduction)
+        gamma, alpha, normalize = check_sigmoid(*self.sigmoid)
+        return _PixelLossFn.apply(input, target, self.ignore_index, self.reduction, ops.sigmoid_focal_nchw_fwd,
+                                  ops.sigmoid_focal_nchw_bwd, False,
+                                  dict(class_weight=self.weight, gamma=gamma, alpha=alpha,
+                                       class_scale=ops.sigmoid_class_scale(normalize, self.reduction, input.shape[1])))
 
 
 class SigmoidCrossEntropyLoss(SigmoidFocalLoss):

@@ -21,7 +21,9 @@ from .. import ops
 from .base import HipModule, grad_buf, linear_bwd_params, require_cuda, vec_grad
 from .clip import ClipArch, ImageEncoderCLIP, TextEncoderCLIP, TextEncoderCLIPPooler
 from .decoder import DecoderBlock, DecoderLayer
-from .loss import check_dice, check_focal, check_ohem, check_sigmoid
+from .head_loss import HeadCriterion, fused_head_loss, head_criterion
+from .head_loss import (fused_dice_options, fused_focal_options, fused_loss_options,   # noqa: F401  (the pieces of head_criterion:
+                        fused_sigmoid_options, wide_refuse)                            # part of this module's surface)
 
 _DATA = Path(__file__).resolve().parent.parent / "data"
 KPAD = 192  # class dimension padded to a multiple of 64 (MFMA K-step of the dgrad product); past 192 classes: ops.class_pad(K)
@@ -73,70 +75,6 @@ class TextToPatch(HipModule):
         return t_feature, v_feature
 
 
-# ----------------------------------------------------------------------------------------------------------
-def fused_loss_options(weight, label_smoothing: float, reduction: str):
-    """(weight, label_smoothing, reduction) for a fused CE head, or None for the default configuration."""
-    if reduction not in ("mean", "sum", "none"):
-        raise ValueError(f"{reduction} is not a valid value for reduction")
-    if reduction == "none":
-        raise NotImplementedError("lc2is_amd: the fused cross-entropy heads reduce to a scalar ('mean' or 'sum'); "
-                                  "reduction='none' needs the materialised logits (forward + CrossEntropyLoss)")
-    if not 0.0 <= label_smoothing <= 1.0:
-        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
-    if weight is None and label_smoothing == 0.0 and reduction == "mean":
-        return None
-    return weight, float(label_smoothing), reduction
-
-
-def fused_dice_options(dice, opts, ohem):
-    """``dice`` = (ce_weight, dice_weight, smooth, present_only) validated, or None; the Dice term does not combine with class
-    weights, label smoothing, a non-mean reduction (``opts`` of fused_loss_options) or a hard-pixel selection."""
-    if dice is None:
-        return None
-    if opts is not None or ohem is not None:
-        raise ValueError("lc2is_amd: dice= cannot be combined with weight=, label_smoothing, a reduction other than 'mean' "
-                         "or ohem=")
-    return check_dice(*dice)
-
-
-def fused_focal_options(focal, label_smoothing: float, dice):
-    """``focal`` = (gamma, poly_eps) validated, or None; the focal / poly-1 loss keeps weight=, reduction=, ohem=, seg_counts= and
-    accum=, and does not combine with a Dice term or label smoothing."""
-    if focal is None:
-        return None
-    if dice is not None or label_smoothing != 0.0:
-        raise ValueError("lc2is_amd: focal= cannot be combined with dice= or label_smoothing")
-    return check_focal(*focal)
-
-
-def fused_sigmoid_options(sigmoid, label_smoothing: float, dice, focal):
-    """``sigmoid`` = (gamma, alpha, normalize) validated, or None; the sigmoid focal / sigmoid cross-entropy loss keeps weight=,
-    reduction=, ohem=, seg_counts= and accum=, and does not combine with a Dice term, the softmax focal loss or label smoothing."""
-    if sigmoid is None:
-        return None
-    if dice is not None or focal is not None or label_smoothing != 0.0:
-        raise ValueError("lc2is_amd: sigmoid= cannot be combined with dice=, focal= or label_smoothing")
-    return check_sigmoid(*sigmoid)
-
-
-def wide_refuse(who: str, K: int, scale: int, label_smoothing: float, ohem, dice, focal, sigmoid) -> None:
-    """Past 192 classes the fused head is the chunked cross-entropy (``ops.head_upsample_ce_wide``): plain CE with ``weight=``,
-    'mean' / 'sum', ``ignore_index``, ``seg_counts=`` and ``accum=`` at scale 4.  Every other criterion keeps its kernel's 192-class
-    limit and is refused here, before anything is allocated or launched."""
-    if K <= ops.HEAD_CMAX:
-        return
-    if K > ops.HEAD_WIDE_CMAX:
-        raise NotImplementedError(f"lc2is_amd {who}: at most {ops.HEAD_WIDE_CMAX} classes are supported by the fused head, got {K}")
-    for name, on in (("label_smoothing", label_smoothing != 0.0), ("ohem=", ohem is not None), ("dice=", dice is not None),
-                     ("focal=", focal is not None), ("sigmoid=", sigmoid is not None)):
-        if on:
-            raise NotImplementedError(f"lc2is_amd {who}: {name} is limited to {ops.HEAD_CMAX} classes (its fused kernel keeps every "
-                                      f"class of a pixel in registers); {K} classes train with the plain cross-entropy "
-                                      "(weight=, reduction=, ignore_index, seg_counts=, accum=)")
-    if scale != 4:
-        raise NotImplementedError(f"lc2is_amd {who}: past {ops.HEAD_CMAX} classes the fused head upsamples by 4 only, got {scale}")
-
-
 def head_scores_hi(scores, B: int, h: int, w: int, K: int, S: int, mode: int):
     """The materialised [B, K, S h, S w] map of low-resolution scores [B*h*w, ld].  Past 192 classes: contiguous 192-channel slices
     through the same kernel, concatenated (the reference composition of the wide head; the loss and prediction paths never form it)."""
@@ -162,25 +100,12 @@ def head_scores_hi_bwd(gout, B: int, h: int, w: int, K: int, S: int, mode: int, 
     return ds
 
 
-def _reduce(loss2, reduction: str, save: bool):
-    """(loss, gradient multiplier or None) from the head's [sum of losses, weighted count]; a zero count (every pixel ignored)
-    gives torch's NaN mean and a zero gradient, with no host sync."""
-    if reduction == "sum":
-        return loss2[0], None
-    inv = loss2[1].masked_fill(loss2[1] == 0, 1.0).reciprocal() if save else None
-    return loss2[0] / loss2[1], inv
-
-
 class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None,
-                accum=None, focal=None, sigmoid=None):
-        if sigmoid is None:   # (the call as it was)
-            out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal)
-        else:
-            out, saved = model._head_fwd(dec, labels, save, ignore_index, loss_opts, ohem, dice, seg_counts, accum, focal, sigmoid)
+    def forward(ctx, dec, protos, model, labels, save, ignore_index, crit=HeadCriterion(), seg_counts=None, accum=None):
+        out, saved = model._head_fwd(dec, labels, save, ignore_index, crit, seg_counts, accum)
         ctx.model, ctx.saved = model, saved
         return out
 
@@ -188,7 +113,7 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         ddec = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return ddec, None, None, None, None, None, None, None, None, None, None, None, None
+        return (ddec,) + (None,) * 8
 
 
 class BaseModelWithText(HipModule):
@@ -246,71 +171,24 @@ class BaseModelWithText(HipModule):
         _, scores, _ = ops.gemm_nt(fv16, ft16, None, out_bf16=None, out_f32=True)   # [B*P, KPAD]
         return ft16, fv16, scores
 
-    def _head_fwd(self, dec, labels, save, ignore_index, loss_opts=None, ohem=None, dice=None, seg_counts=None, accum=None,
-                  focal=None, sigmoid=None):
+    def _head_fwd(self, dec, labels, save, ignore_index, crit=HeadCriterion(), seg_counts=None, accum=None):
         B, P, C = dec.shape
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
         dec16 = ops.cast_bf16(dec.reshape(B * P, C).float().contiguous())
         ft16, fv16, scores = self._head_scores(dec16)
+        saved = dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None
         if labels is None:
-            hi = head_scores_hi(scores, B, g, g, K, 4, ops.INTERP_BICUBIC)
-            return hi, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None)
-        labels = labels.contiguous()
-        if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
-            ops.seg_counts_add(seg_counts, scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index)
-        if K > ops.HEAD_CMAX:   # the chunked cross-entropy (forward_loss refused every other criterion before the towers ran)
-            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
-            loss2, dlo = ops.head_upsample_ce_wide(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
-                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight)
-            loss, inv_count = _reduce(loss2, reduction, save)
-            if accum is not None:
-                ops.accum_add(accum, loss2)
-                inv_count = None
-            return loss, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=inv_count)
-                          if save else None)
-        if dice is not None:   # CE + soft Dice: statistics pass, coefficients, gradient pass — dlo is the gradient of the scalar loss
-            ce_weight, dice_weight, smooth, present_only = dice
-            loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
-                                                          ignore_index=ignore_index, ce_weight=ce_weight, dice_weight=dice_weight,
-                                                          smooth=smooth, present_only=present_only)
-            self.last_dice = (stats[0], stats[1], stats[2], loss4)
-            return loss4[0], (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=None)
-                              if save else None)
-        if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
-            labels, info = ops.ohem_labels(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index, ohem)
-            self.last_ohem = (labels, info)
-        # the kernel writes the gradient of the SUM of the per-pixel losses and counts the pixels it kept (labels that are
-        # negative, == ignore_index or >= K are skipped, head.hip); the 1/count of nn.CrossEntropyLoss's mean is folded
-        # into the upstream-gradient multiply of _head_bwd, from the device-side count (no host sync, no label pass)
-        if sigmoid is not None:   # sigmoid focal / sigmoid CE: per-class binary terms, [sum, NUMBER of counted pixels]
-            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
-            loss2, dlo = ops.head_upsample_sigmoid(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
-                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight, gamma=sigmoid[0],
-                                                   alpha=sigmoid[1], class_scale=ops.sigmoid_class_scale(sigmoid[2], reduction, K))
-            loss, inv_count = _reduce(loss2, reduction, save)
-        elif focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
-            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
-            loss2, dlo = ops.head_upsample_focal(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC, want_grad=save,
-                                                 ignore_index=ignore_index, grad_scale=1.0, class_weight=weight, gamma=focal[0],
-                                                 poly_eps=focal[1])
-            loss, inv_count = _reduce(loss2, reduction, save)
-        elif loss_opts is None:
-            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
-                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0)
-            loss = loss2[0] / loss2[1]
-            inv_count = (1.0 / loss2[1].clamp_min(1.0)) if save else None
-        else:   # class weights / label smoothing: loss2[1] is the weighted count sum_i w_{y_i}; 'sum' drops the division
-            weight, label_smoothing, reduction = loss_opts
-            loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, g, g, K, 4, ops.INTERP_BICUBIC,
-                                                 want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
-                                                 class_weight=weight, label_smoothing=label_smoothing)
-            loss, inv_count = _reduce(loss2, reduction, save)
-        if accum is not None:   # a micro-batch of an accumulation cycle: its sums join the cycle's on the device, and the backward
-            ops.accum_add(accum, loss2)   # leaves the gradient of the SUM (the 'sum' branch of _head_bwd); the update divides
-            inv_count = None
-        return loss, (dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=dlo, inv_count=inv_count)
-                      if save else None)
+            return head_scores_hi(scores, B, g, g, K, 4, ops.INTERP_BICUBIC), saved
+        loss, dlo, inv_count, dice_stats, ohem_sel = fused_head_loss(scores, labels, B, g, g, K, 4, ops.INTERP_BICUBIC, ignore_index,
+                                                                     crit, save, seg_counts, accum)
+        if dice_stats is not None:
+            self.last_dice = dice_stats
+        if ohem_sel is not None:
+            self.last_ohem = ohem_sel
+        if save:   # the 1/count of the mean is folded into the upstream-gradient multiply of _head_bwd
+            saved.update(fused=dlo, inv_count=inv_count)
+        return loss, saved
 
     def _head_bwd(self, gout, saved):
         B, P, C, g, K = saved["dims"]
@@ -407,7 +285,7 @@ class BaseModelWithText(HipModule):
         pixel in place of the cross-entropy (FocalLoss's definition: 'mean' divides by the sum of w_y), one forward + backward
         launch of the head.  Keeps ``weight``, ``reduction``, ``seg_counts``, ``accum`` (a per-pixel loss: the sums add) and ``ohem``
         (the selection still ranks by the plain CE; the relabelled call is the focal one); not combinable with ``dice=`` or
-        ``label_smoothing``.  None: the call as it was.
+        ``label_smoothing``.  None: the cross-entropy.
         ``sigmoid=(gamma, alpha, normalize)``: the sigmoid focal loss (gamma = 0, alpha None: binary cross-entropy with logits on
         one-hot targets) in place of the cross-entropy — per counted pixel the sum over the K classes of w_c a_t (1 - p_t)^gamma
         (-log p_t) with p = sigmoid(score), no softmax (SigmoidFocalLoss's definition), one forward + backward launch of the head.
@@ -415,29 +293,13 @@ class BaseModelWithText(HipModule):
         torch's and mmseg's rule for binary losses, deliberately different from the softmax losses above.  Keeps ``weight`` (on
         class c's binary term), ``reduction``, ``seg_counts``, ``accum`` and ``ohem`` (the selection still ranks by the plain softmax
         CE; the relabelled call is the sigmoid one); not combinable with ``dice=``, ``focal=`` or ``label_smoothing``
-        (``ValueError`` before the towers run).  None: the call as it was."""
-        if accum is not None and dice is not None:
-            raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
-        sigmoid = fused_sigmoid_options(sigmoid, label_smoothing, dice, focal)
-        focal = fused_focal_options(focal, label_smoothing, dice)
-        opts = fused_loss_options(weight, label_smoothing, reduction)
-        if ohem is not None:
-            ohem = check_ohem(*ohem)
-        dice = fused_dice_options(dice, opts, ohem)
-        if seg_counts is not None:
-            ops.check_seg_counts(seg_counts, self.class_prototypes.shape[0])
-        wide_refuse("BaseModelWithText.forward_loss", self.class_prototypes.shape[0], 4, label_smoothing, ohem, dice, focal, sigmoid)
+        (``ValueError`` before the towers run).  None: the softmax losses above."""
+        crit = head_criterion("BaseModelWithText.forward_loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction,
+                              ohem=ohem, dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
+                              n_classes=lambda: self.class_prototypes.shape[0], scale=4)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
-        if sigmoid is not None:
-            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum,
-                                 None, sigmoid)
-        if focal is not None:
-            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum,
-                                 focal)
-        if accum is None:   # (the call as it was: no new argument reaches the head)
-            return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts)
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, opts, ohem, dice, seg_counts, accum)
+        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, crit, seg_counts, accum)
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:

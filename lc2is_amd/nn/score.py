@@ -17,9 +17,8 @@ from torch import nn
 
 from .. import ops
 from .base import require_cuda
-from .loss import check_ohem
-from .model import (_reduce, fused_dice_options, fused_focal_options, fused_loss_options, fused_sigmoid_options, head_scores_hi,
-                    head_scores_hi_bwd, wide_refuse)
+from .head_loss import HeadCriterion, fused_head_loss, head_criterion
+from .model import head_scores_hi, head_scores_hi_bwd
 
 KPAD = 192   # class pitch up to 192 classes; past them ops.class_pad(K)
 
@@ -64,73 +63,26 @@ def _scores_bwd(ds32, sv):
 
 class _ScoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, visual, text, labels, scale, ignore_index, save, loss_opts=None, ohem=None, owner=None, dice=None, seg_counts=None,
-                accum=None, focal=None, sigmoid=None):
+    def forward(ctx, visual, text, labels, scale, ignore_index, save, crit=HeadCriterion(), owner=None, seg_counts=None, accum=None):
         B, P, C = visual.shape
         K = text.shape[1]
         h = int(round(P ** 0.5))
         scores, sv = _scores_lo(visual, text)
+        ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
         if labels is None:
-            hi = head_scores_hi(scores, B, h, h, K, scale, ops.INTERP_BILINEAR)
-            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), None, (B, h, K, scale)
-            return hi
-        if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
-            ops.seg_counts_add(seg_counts, scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index)
-        if K > ops.HEAD_CMAX:   # the chunked cross-entropy (loss() refused every other criterion before anything ran)
-            weight, _, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
-            loss2, dlo = ops.head_upsample_ce_wide(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, want_grad=save,
-                                                   ignore_index=ignore_index, grad_scale=1.0, class_weight=weight)
-            loss, inv = _reduce(loss2, reduction, save)
-            if accum is not None:
-                ops.accum_add(accum, loss2)
-            elif inv is not None:
-                dlo.mul_(inv)
-            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
-            return loss
-        if dice is not None:   # CE + soft Dice: dlo is the gradient of the scalar loss
-            ce_weight, dice_weight, smooth, present_only = dice
-            loss4, stats, dlo = ops.head_upsample_ce_dice(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                                          want_grad=save, ignore_index=ignore_index, ce_weight=ce_weight,
-                                                          dice_weight=dice_weight, smooth=smooth, present_only=present_only)
-            owner.last_dice = (stats[0], stats[1], stats[2], loss4)
-            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
-            return loss4[0]
-        if ohem is not None:   # hard-pixel selection: per-pixel loss pass, selection, then the same fused call on the new labels
-            labels, info = ops.ohem_labels(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index, ohem)
-            owner.last_ohem = (labels, info)
-        if loss_opts is not None or focal is not None or sigmoid is not None:   # class weights / label smoothing / 'sum' (loss2[1] = sum_i w_{y_i})
-            weight, label_smoothing, reduction = loss_opts if loss_opts is not None else (None, 0.0, "mean")
-            if sigmoid is not None:   # sigmoid focal / sigmoid CE: per-class binary terms, [sum, NUMBER of counted pixels]
-                loss2, dlo = ops.head_upsample_sigmoid(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                                       want_grad=save, ignore_index=ignore_index, grad_scale=1.0, class_weight=weight,
-                                                       gamma=sigmoid[0], alpha=sigmoid[1],
-                                                       class_scale=ops.sigmoid_class_scale(sigmoid[2], reduction, K))
-            elif focal is not None:   # focal / poly-1: the CE gradient times one scalar per pixel, the same [sum, weighted count] pair
-                loss2, dlo = ops.head_upsample_focal(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                                     want_grad=save, ignore_index=ignore_index, grad_scale=1.0, class_weight=weight,
-                                                     gamma=focal[0], poly_eps=focal[1])
-            else:
-                loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                                     want_grad=save, ignore_index=ignore_index, grad_scale=1.0,
-                                                     class_weight=weight, label_smoothing=label_smoothing)
-            loss, inv = _reduce(loss2, reduction, save)
-            if accum is not None:   # accumulation cycle: dlo stays the gradient of the SUM, the cycle's update divides
-                ops.accum_add(accum, loss2)
-            elif inv is not None:
-                dlo.mul_(inv)
-            ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
-            return loss
-        n = float(B * h * scale * h * scale)
-        loss2, dlo, _ = ops.head_upsample_ce(scores, labels.contiguous(), B, h, h, K, scale, ops.INTERP_BILINEAR,
-                                             want_grad=save, ignore_index=ignore_index, grad_scale=1.0 / n)
-        if accum is not None:   # accumulation cycle: undo the kernel's 1/n, dlo is the gradient of the SUM; the update divides
-            ops.accum_add(accum, loss2)
-            if save:
-                dlo.mul_(n)
-        elif save:   # mean over the pixels the kernel counted (negative / ignore_index / out-of-range labels are skipped)
-            dlo.mul_(n / loss2[1].clamp_min(1.0))
-        ctx.sv, ctx.fused, ctx.meta = (sv if save else None), dlo, (B, h, K, scale)
-        return loss2[0] / loss2[1]
+            return head_scores_hi(scores, B, h, h, K, scale, ops.INTERP_BILINEAR)
+        # plain_n: this site's plain cross-entropy has always launched with grad_scale 1/n and rescaled by n/count afterwards
+        loss, dlo, mul, dice_stats, ohem_sel = fused_head_loss(scores, labels, B, h, h, K, scale, ops.INTERP_BILINEAR, ignore_index,
+                                                               crit, save, seg_counts, accum,
+                                                               plain_n=float(B * h * scale * h * scale))
+        if dice_stats is not None:
+            owner.last_dice = dice_stats
+        if ohem_sel is not None:
+            owner.last_ohem = ohem_sel
+        if mul is not None:   # the 1/count of the mean goes into the saved gradient here: the backward is one multiply by gout
+            dlo.mul_(mul)
+        ctx.fused = dlo
+        return loss
 
     @staticmethod
     def backward(ctx, gout):
@@ -141,7 +93,7 @@ class _ScoreFn(torch.autograd.Function):
             ds = head_scores_hi_bwd(gout, B, h, h, K, scale, ops.INTERP_BILINEAR, ops.class_pad(K))
         dv, dt = _scores_bwd(ds, ctx.sv)
         ctx.sv = ctx.fused = None
-        return dv, dt, None, None, None, None, None, None, None, None, None, None, None, None
+        return (dv, dt) + (None,) * 8
 
 
 class ScoreMapTail(nn.Module):
@@ -176,30 +128,13 @@ class ScoreMapTail(nn.Module):
         counted pixel, in place of the cross-entropy (SigmoidFocalLoss's definition: 'mean' divides by a count of elements or of
         pixels, never a weight sum; ``BaseModelWithText.forward_loss`` has the details); keeps ``weight``, ``reduction``, ``ohem``,
         ``seg_counts`` and ``accum``, not combinable with ``dice=``, ``focal=`` or ``label_smoothing``."""
-        if accum is not None and dice is not None:
-            raise ValueError("lc2is_amd: accum= cannot be combined with dice= (the Dice statistics of micro-batches do not add)")
-        sigmoid = fused_sigmoid_options(sigmoid, label_smoothing, dice, focal)
-        focal = fused_focal_options(focal, label_smoothing, dice)
-        opts = fused_loss_options(weight, label_smoothing, reduction)
-        if ohem is not None:
-            ohem = check_ohem(*ohem)
-        dice = fused_dice_options(dice, opts, ohem)
-        if seg_counts is not None:
-            ops.check_seg_counts(seg_counts, text_embeddings.shape[1])
-        wide_refuse("ScoreMapTail.loss", text_embeddings.shape[1], self.scale_factor, label_smoothing, ohem, dice, focal, sigmoid)
+        crit = head_criterion("ScoreMapTail.loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction, ohem=ohem,
+                              dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
+                              n_classes=lambda: text_embeddings.shape[1], scale=self.scale_factor)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
-        if sigmoid is not None:
-            return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
-                                  dice, seg_counts, accum, None, sigmoid)
-        if focal is not None:
-            return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
-                                  dice, seg_counts, accum, focal)
-        if accum is None:
-            return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self,
-                                  dice, seg_counts)
-        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, opts, ohem, self, dice,
-                              seg_counts, accum)
+        return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, crit, self, seg_counts,
+                              accum)
 
     @torch.no_grad()
     def predict(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor) -> torch.Tensor:

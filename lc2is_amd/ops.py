@@ -918,6 +918,68 @@ def swap_f32(a, b):
     _lib.check(_fn("lc2is_swap_f32")(_ptr(a), _ptr(b), a.numel(), _stream()), "swap_f32")
 
 
+def finite_ge(v, lo: float = 0.0) -> bool:
+    """``v`` is a finite number >= lo and not a bool: the test every option validator of the losses applies."""
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v) and v >= lo
+
+
+def _head_front(who: str, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, *, need_labels: bool, scales=None,
+                cmax: int = 0, cmin: int | None = None):
+    """The checks every ``head_upsample_*`` wrapper runs on its tensors, in one order: scores contiguous, labels [B, h S, w S] and
+    contiguous (required or optional), then — where the wrapper names its ``scales``, (4,) or (4, 8, 16) — S among them and scores_lo [B h w, ld] with
+    (cmin <=) C <= ld <= cmax, ld a multiple of 64.  Returns ld."""
+    if scores_lo is None or not scores_lo.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be contiguous")
+    if (need_labels or labels is not None) and (labels is None or tuple(labels.shape) != (B, h * S, w * S)
+                                                or not labels.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.{who}: labels must be contiguous [{B},{h*S},{w*S}]")
+    ld = scores_lo.shape[1]
+    if scales is None:
+        return ld
+    if S not in scales:
+        raise RuntimeError(f"lc2is_amd.{who}: S must be {'4' if scales == (4,) else '4, 8 or 16'}, got {S}")
+    if scores_lo.shape[0] != B * h * w or (cmin is not None and C < cmin) or not C <= ld <= cmax or ld % 64:
+        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be [{B * h * w}, ld] with C <= ld <= {cmax}, ld % 64 == 0, "
+                           f"got {tuple(scores_lo.shape)}")
+    return ld
+
+
+def _head_alloc(who: str, scores_lo, nbytes: int, want_grad: bool, geom, nloss: int = 2):
+    """(loss block, dscores_lo or None, workspace) of a head call whose launches hand partials to a fixed-order finish launch: all
+    overwritten, the workspace per call (its slabs live until the last launch, in stream order).  ``nbytes`` == 0: the C side does
+    not take this geometry."""
+    if nbytes == 0:
+        B, h, w, C, S, mode = geom
+        raise RuntimeError(f"lc2is_amd.{who}: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    dev = scores_lo.device
+    loss = torch.empty(nloss, dtype=torch.float32, device=dev)
+    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
+    return loss, dlo, torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _nchw_front(who: str, logits, labels, *, bwd: bool = False, lse=(), cmax: int | None = None):
+    """The checks of the ``*_nchw_fwd`` / ``*_nchw_bwd`` wrappers on contiguous logits [B,C,H,W] and labels [B,H,W] (a backward: and
+    the forward's ``lse``, given as a 1-tuple, in one message); ``cmax``: the class limit of a forward.  Returns (B, C, H, W)."""
+    if not bwd and (logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.{who}: logits/labels must be contiguous")
+    B, Cc, H, W = logits.shape
+    if not bwd and tuple(labels.shape) != (B, H, W):
+        raise RuntimeError(f"lc2is_amd.{who}: labels must be [{B},{H},{W}]")
+    if bwd and (not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W)
+                or any(tuple(t.shape) != (B, H, W) or not t.is_contiguous() for t in lse)):
+        raise RuntimeError(f"lc2is_amd.{who}: contiguous logits [B,C,H,W] with labels{' / lse' if lse else ''} [{B},{H},{W}] required")
+    if cmax is not None and not 1 <= Cc <= cmax:
+        raise RuntimeError(f"lc2is_amd.{who}: 1 <= C <= {cmax} required, got {Cc}")
+    return B, Cc, H, W
+
+
+def _chk_grad_px(who: str, grad_px, B: int, H: int, W: int) -> None:
+    if grad_px is not None:
+        _chk(grad_px, torch.float32, "grad_px", 3)
+        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
+            raise RuntimeError(f"lc2is_amd.{who}: grad_px must be contiguous [{B},{H},{W}]")
+
+
 def _ce_options(class_weight, label_smoothing: float, C: int, dev):
     """Validate F.cross_entropy's weight / label_smoothing for a C-class call; True when either is set."""
     if not 0.0 <= label_smoothing <= 1.0:
@@ -941,12 +1003,8 @@ def head_upsample_ce(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, 
     the weighted count sum_i w_{y_i}, the denominator of the mean."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
     opts = _ce_options(class_weight, label_smoothing, C, scores_lo.device) and want_loss
-    if not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_ce: scores_lo must be contiguous")
-    ld = scores_lo.shape[1]
+    ld = _head_front("head_upsample_ce", scores_lo, labels, B, h, w, C, S, need_labels=False)
     dev = scores_lo.device
-    if labels is not None and (tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce: labels must be contiguous [{B},{h*S},{w*S}]")
     # S = 4 / 8 / 16: per-block partials in a workspace + a fixed-order second launch (reproducible; outputs overwritten);
     # other S: the atomic path adds into cleared buffers
     nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad)) if want_loss else 0
@@ -972,12 +1030,9 @@ def head_upsample_px(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, 
     """scores_lo fp32 [B*h*w, ld], labels int64 [B, h*S, w*S] -> per-pixel plain CE of the upsampled scores, fp32 [B, h*S, w*S]
     (0 where the pixel is not counted): head_upsample_ce's forward alone (S = 4 / 8 / 16), one launch, no gradient."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
-    if not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_px: scores_lo must be contiguous")
-    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.head_upsample_px: labels must be contiguous [{B},{h*S},{w*S}]")
+    ld = _head_front("head_upsample_px", scores_lo, labels, B, h, w, C, S, need_labels=True)
     lpx = torch.empty((B, h * S, w * S), dtype=torch.float32, device=scores_lo.device)
-    _lib.check(_fn("lc2is_head_upsample_px")(_ptr(scores_lo), scores_lo.shape[1], _ptr(labels), _ptr(lpx), B, h, w, C, S, mode,
+    _lib.check(_fn("lc2is_head_upsample_px")(_ptr(scores_lo), ld, _ptr(labels), _ptr(lpx), B, h, w, C, S, mode,
                                              ignore_index, _stream()), f"head_upsample_px B={B} h={h} w={w} C={C} S={S}")
     return lpx
 
@@ -994,16 +1049,7 @@ def head_upsample_argmax(scores_lo, labels, B: int, h: int, w: int, C: int, S: i
         raise ValueError("lc2is_amd.head_upsample_argmax: want_pred and want_counts are both False")
     if want_counts and labels is None:
         raise ValueError("lc2is_amd.head_upsample_argmax: want_counts needs labels")
-    if scores_lo is None or not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_argmax: scores_lo must be contiguous")
-    if labels is not None and (tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: labels must be contiguous [{B},{h*S},{w*S}]")
-    if S not in (4, 8, 16):
-        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: S must be 4, 8 or 16, got {S}")
-    ld = scores_lo.shape[1]
-    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
-        raise RuntimeError(f"lc2is_amd.head_upsample_argmax: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
-                           f"got {tuple(scores_lo.shape)}")
+    ld = _head_front("head_upsample_argmax", scores_lo, labels, B, h, w, C, S, need_labels=False, scales=(4, 8, 16), cmax=HEAD_CMAX)
     dev = scores_lo.device
     nbytes = 0
     if want_counts:
@@ -1030,21 +1076,6 @@ def class_pad(K: int) -> int:
     return HEAD_CMAX if K <= HEAD_CMAX else (K + 63) // 64 * 64
 
 
-def _wide_front(who: str, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, need_labels: bool):
-    if scores_lo is None or not scores_lo.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be contiguous")
-    if (need_labels or labels is not None) and (labels is None or tuple(labels.shape) != (B, h * S, w * S)
-                                                or not labels.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.{who}: labels must be contiguous [{B},{h*S},{w*S}]")
-    if S != 4:
-        raise RuntimeError(f"lc2is_amd.{who}: S must be 4, got {S}")
-    ld = scores_lo.shape[1]
-    if scores_lo.shape[0] != B * h * w or not 1 <= C <= ld <= HEAD_WIDE_CMAX or ld % 64:
-        raise RuntimeError(f"lc2is_amd.{who}: scores_lo must be [{B * h * w}, ld] with C <= ld <= {HEAD_WIDE_CMAX}, ld % 64 == 0, "
-                           f"got {tuple(scores_lo.shape)}")
-    return ld
-
-
 def head_upsample_ce_wide(scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
                           want_grad: bool = False, ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None):
     """Cross-entropy of the x4-upsampled scores for up to 1024 classes: scores_lo fp32 [B*h*w, ld], labels int64 [B, 4h, 4w].
@@ -1053,15 +1084,11 @@ def head_upsample_ce_wide(scores_lo, labels, B: int, h: int, w: int, C: int, S: 
     axis walked in chunks of 192 channels: an online-softmax sweep, a gradient sweep and the finish launch; nothing syncs, no
     atomics, the same bytes every run, captures into a graph.  C <= 192 is taken too (the narrow call is the faster one there)."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
-    ld = _wide_front("head_upsample_ce_wide", scores_lo, labels, B, h, w, C, S, True)
-    dev = scores_lo.device
-    _ce_options(class_weight, 0.0, C, dev)
+    ld = _head_front("head_upsample_ce_wide", scores_lo, labels, B, h, w, C, S, need_labels=True, scales=(4,), cmax=HEAD_WIDE_CMAX,
+                     cmin=1)
+    _ce_options(class_weight, 0.0, C, scores_lo.device)
     nbytes = _fn("lc2is_head_upsample_ce_wide_workspace_bytes")(B, h, w, C, ld, S, mode, int(want_grad))
-    if nbytes == 0:
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce_wide: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
-    loss = torch.empty(2, dtype=torch.float32, device=dev)
-    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    loss, dlo, ws = _head_alloc("head_upsample_ce_wide", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode))
     _lib.check(_fn("lc2is_head_upsample_ce_wide")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
                                                   ignore_index, grad_scale, _ptr(class_weight), _ptr(ws), nbytes, _stream()),
                f"head_upsample_ce_wide B={B} h={h} w={w} C={C} S={S}")
@@ -1077,7 +1104,8 @@ def head_upsample_argmax_wide(scores_lo, labels, B: int, h: int, w: int, C: int,
         raise ValueError("lc2is_amd.head_upsample_argmax_wide: want_pred and want_counts are both False")
     if want_counts and labels is None:
         raise ValueError("lc2is_amd.head_upsample_argmax_wide: want_counts needs labels")
-    ld = _wide_front("head_upsample_argmax_wide", scores_lo, labels, B, h, w, C, S, False)
+    ld = _head_front("head_upsample_argmax_wide", scores_lo, labels, B, h, w, C, S, need_labels=False, scales=(4,),
+                     cmax=HEAD_WIDE_CMAX, cmin=1)
     dev = scores_lo.device
     nbytes = 0
     if want_counts:
@@ -1171,7 +1199,7 @@ def dice_options(ce_weight, dice_weight, smooth, present_only) -> tuple[float, f
     """(ce_weight, dice_weight, smooth, present_only) of a Dice + CE loss, validated: finite numbers >= 0, the two weights not
     both 0, present_only a bool."""
     for name, v in (("ce_weight", ce_weight), ("dice_weight", dice_weight), ("smooth", smooth)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        if not finite_ge(v):
             raise ValueError(f"Dice + CE: {name} must be a finite number >= 0, got {v!r}")
     if float(ce_weight) == 0.0 and float(dice_weight) == 0.0:
         raise ValueError("Dice + CE: ce_weight and dice_weight must not both be 0")
@@ -1191,24 +1219,10 @@ def head_upsample_ce_dice(scores_lo, labels, B: int, h: int, w: int, C: int, S: 
     ce_weight, dice_weight, smooth, present_only = dice_options(ce_weight, dice_weight, smooth, present_only)
     if not math.isfinite(grad_scale):
         raise ValueError(f"lc2is_amd.head_upsample_ce_dice: grad_scale must be finite, got {grad_scale}")
-    if scores_lo is None or not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_ce_dice: scores_lo must be contiguous")
-    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: labels must be contiguous [{B},{h*S},{w*S}]")
-    if S not in (4, 8, 16):
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: S must be 4, 8 or 16, got {S}")
-    ld = scores_lo.shape[1]
-    if scores_lo.shape[0] != B * h * w or not C <= ld <= DICE_CMAX or ld % 64:
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: scores_lo must be [{B * h * w}, ld] with C <= ld <= {DICE_CMAX}, "
-                           f"ld % 64 == 0, got {tuple(scores_lo.shape)}")
-    dev = scores_lo.device
+    ld = _head_front("head_upsample_ce_dice", scores_lo, labels, B, h, w, C, S, need_labels=True, scales=(4, 8, 16), cmax=DICE_CMAX)
     nbytes = _fn("lc2is_head_upsample_ce_dice_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
-    if nbytes == 0:
-        raise RuntimeError(f"lc2is_amd.head_upsample_ce_dice: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
-    loss = torch.empty(4, dtype=torch.float32, device=dev)
-    stats = torch.empty((3, ld), dtype=torch.float32, device=dev)
-    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: rows, coefficients and slabs live until the last launch)
+    loss, dlo, ws = _head_alloc("head_upsample_ce_dice", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode), nloss=4)
+    stats = torch.empty((3, ld), dtype=torch.float32, device=scores_lo.device)
     _lib.check(_fn("lc2is_head_upsample_ce_dice")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), _ptr(stats), B, h, w,
                                                   C, S, mode, ignore_index, ce_weight, dice_weight, smooth, int(present_only),
                                                   grad_scale, _ptr(ws), nbytes, _stream()),
@@ -1222,13 +1236,7 @@ def ce_dice_nchw_fwd(logits, labels, ignore_index: int = -100, *, ce_weight: flo
     the device coefficient block ``ce_dice_nchw_bwd`` takes."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     ce_weight, dice_weight, smooth, present_only = dice_options(ce_weight, dice_weight, smooth, present_only)
-    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
-        raise RuntimeError("lc2is_amd.ce_dice_nchw_fwd: logits/labels must be contiguous")
-    B, Cc, H, W = logits.shape
-    if tuple(labels.shape) != (B, H, W):
-        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_fwd: labels must be [{B},{H},{W}]")
-    if not 1 <= Cc <= DICE_CMAX:
-        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_fwd: 1 <= C <= {DICE_CMAX} required, got {Cc}")
+    B, Cc, H, W = _nchw_front("ce_dice_nchw_fwd", logits, labels, cmax=DICE_CMAX)
     dev = logits.device
     nbytes = _fn("lc2is_ce_dice_nchw_workspace_bytes")(B, Cc, H * W)
     loss = torch.empty(4, dtype=torch.float32, device=dev)
@@ -1246,10 +1254,7 @@ def ce_dice_nchw_bwd(logits, labels, lse, coef, grad_scale_dev, grad_scale: floa
     """dlogits = grad_scale * grad_scale_dev (device scalar or None) * d loss / d logits, from ``ce_dice_nchw_fwd``'s lse and coef."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     _chk(lse, torch.float32, "lse", 3); _chk(coef, torch.float32, "coef", 1); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
-    B, Cc, H, W = logits.shape
-    if (not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W)
-            or tuple(lse.shape) != (B, H, W) or not lse.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.ce_dice_nchw_bwd: contiguous logits [B,C,H,W] with labels / lse [{B},{H},{W}] required")
+    B, Cc, H, W = _nchw_front("ce_dice_nchw_bwd", logits, labels, bwd=True, lse=(lse,))
     if not 1 <= Cc <= DICE_CMAX or coef.numel() != 2 * ((Cc + 3) // 4 * 4) + 4:
         raise RuntimeError(f"lc2is_amd.ce_dice_nchw_bwd: coef must be ce_dice_nchw_fwd's block for C={Cc} (C <= {DICE_CMAX})")
     d = torch.empty_like(logits)
@@ -1262,7 +1267,7 @@ def ce_dice_nchw_bwd(logits, labels, lse, coef, grad_scale_dev, grad_scale: floa
 def focal_options(gamma, poly_eps) -> tuple[float, float]:
     """(gamma, poly_eps) of a focal / poly-1 loss, validated: gamma a finite number >= 0, poly_eps a finite number >= -1."""
     for name, v, lo in (("gamma", gamma, 0.0), ("poly_eps", poly_eps, -1.0)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < lo:
+        if not finite_ge(v, lo):
             raise ValueError(f"focal loss: {name} must be a finite number >= {lo:g}, got {v!r}")
     return float(gamma), float(poly_eps)
 
@@ -1282,24 +1287,10 @@ def head_upsample_focal(scores_lo, labels, B: int, h: int, w: int, C: int, S: in
     syncs, no atomics, the same bytes every run, captures into a graph."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
     gamma, poly_eps = focal_options(gamma, poly_eps)
-    if scores_lo is None or not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_focal: scores_lo must be contiguous")
-    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.head_upsample_focal: labels must be contiguous [{B},{h*S},{w*S}]")
-    if S not in (4, 8, 16):
-        raise RuntimeError(f"lc2is_amd.head_upsample_focal: S must be 4, 8 or 16, got {S}")
-    ld = scores_lo.shape[1]
-    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
-        raise RuntimeError(f"lc2is_amd.head_upsample_focal: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
-                           f"got {tuple(scores_lo.shape)}")
-    dev = scores_lo.device
-    _focal_weight(class_weight, C, dev)
+    ld = _head_front("head_upsample_focal", scores_lo, labels, B, h, w, C, S, need_labels=True, scales=(4, 8, 16), cmax=HEAD_CMAX)
+    _focal_weight(class_weight, C, scores_lo.device)
     nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
-    if nbytes == 0:
-        raise RuntimeError(f"lc2is_amd.head_upsample_focal: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
-    loss = torch.empty(2, dtype=torch.float32, device=dev)
-    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    loss, dlo, ws = _head_alloc("head_upsample_focal", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode))
     _lib.check(_fn("lc2is_head_upsample_focal")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
                                                 ignore_index, grad_scale, _ptr(class_weight), gamma, poly_eps, _ptr(ws), nbytes,
                                                 _stream()), f"head_upsample_focal B={B} h={h} w={w} C={C} S={S}")
@@ -1312,11 +1303,7 @@ def focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=Non
     tensor: the per-pixel losses [B,H,W] (0 where not counted)."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     gamma, poly_eps = focal_options(gamma, poly_eps)
-    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
-        raise RuntimeError("lc2is_amd.focal_nchw_fwd: logits/labels must be contiguous")
-    B, Cc, H, W = logits.shape
-    if tuple(labels.shape) != (B, H, W):
-        raise RuntimeError(f"lc2is_amd.focal_nchw_fwd: labels must be [{B},{H},{W}]")
+    B, Cc, H, W = _nchw_front("focal_nchw_fwd", logits, labels)
     dev = logits.device
     _focal_weight(class_weight, Cc, dev)
     lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
@@ -1336,15 +1323,9 @@ def focal_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float = 1.0,
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     _chk(lse, torch.float32, "lse", 3); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
     gamma, poly_eps = focal_options(gamma, poly_eps)
-    B, Cc, H, W = logits.shape
-    if (not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W)
-            or tuple(lse.shape) != (B, H, W) or not lse.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.focal_nchw_bwd: contiguous logits [B,C,H,W] with labels / lse [{B},{H},{W}] required")
+    B, Cc, H, W = _nchw_front("focal_nchw_bwd", logits, labels, bwd=True, lse=(lse,))
     _focal_weight(class_weight, Cc, logits.device)
-    if grad_px is not None:
-        _chk(grad_px, torch.float32, "grad_px", 3)
-        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
-            raise RuntimeError(f"lc2is_amd.focal_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    _chk_grad_px("focal_nchw_bwd", grad_px, B, H, W)
     d = torch.empty_like(logits)
     _lib.check(_fn("lc2is_focal_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale, _ptr(grad_px),
                                            _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight), gamma, poly_eps, _stream()),
@@ -1356,9 +1337,9 @@ def focal_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float = 1.0,
 def sigmoid_options(gamma, alpha, normalize: str = "elements"):
     """(gamma, alpha, normalize) of a sigmoid focal / sigmoid cross-entropy loss, validated: gamma a finite number >= 0 (returned as
     a float), alpha None or a number in [0, 1] (returned as None or a float), normalize 'elements' or 'pixels'."""
-    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma) or gamma < 0:
+    if not finite_ge(gamma):
         raise ValueError(f"sigmoid focal loss: gamma must be a finite number >= 0, got {gamma!r}")
-    if alpha is not None and (isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha <= 1.0):
+    if alpha is not None and not (finite_ge(alpha) and alpha <= 1.0):
         raise ValueError(f"sigmoid focal loss: alpha must be None or a number in [0, 1], got {alpha!r}")
     if normalize not in ("elements", "pixels"):
         raise ValueError(f"sigmoid focal loss: normalize must be 'elements' or 'pixels', got {normalize!r}")
@@ -1372,7 +1353,7 @@ def sigmoid_class_scale(normalize: str, reduction: str, C: int) -> float:
 
 def _sigmoid_args(gamma, alpha, class_scale):
     gamma, alpha, _ = sigmoid_options(gamma, alpha)
-    if isinstance(class_scale, bool) or not isinstance(class_scale, (int, float)) or not math.isfinite(class_scale) or class_scale <= 0:
+    if not finite_ge(class_scale) or class_scale == 0:
         raise ValueError(f"sigmoid focal loss: class_scale must be a finite number > 0, got {class_scale!r}")
     return gamma, -1.0 if alpha is None else alpha, float(class_scale)   # (the C entry points read any negative alpha as "none")
 
@@ -1388,24 +1369,10 @@ def head_upsample_sigmoid(scores_lo, labels, B: int, h: int, w: int, C: int, S: 
     bytes every run, captures into a graph."""
     _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
     gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
-    if scores_lo is None or not scores_lo.is_contiguous():
-        raise RuntimeError("lc2is_amd.head_upsample_sigmoid: scores_lo must be contiguous")
-    if labels is None or tuple(labels.shape) != (B, h * S, w * S) or not labels.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: labels must be contiguous [{B},{h*S},{w*S}]")
-    if S not in (4, 8, 16):
-        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: S must be 4, 8 or 16, got {S}")
-    ld = scores_lo.shape[1]
-    if scores_lo.shape[0] != B * h * w or not C <= ld <= 192 or ld % 64:
-        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: scores_lo must be [{B * h * w}, ld] with C <= ld <= 192, ld % 64 == 0, "
-                           f"got {tuple(scores_lo.shape)}")
-    dev = scores_lo.device
-    _focal_weight(class_weight, C, dev)
+    ld = _head_front("head_upsample_sigmoid", scores_lo, labels, B, h, w, C, S, need_labels=True, scales=(4, 8, 16), cmax=HEAD_CMAX)
+    _focal_weight(class_weight, C, scores_lo.device)
     nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
-    if nbytes == 0:
-        raise RuntimeError(f"lc2is_amd.head_upsample_sigmoid: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
-    loss = torch.empty(2, dtype=torch.float32, device=dev)
-    dlo = torch.empty(scores_lo.shape, dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (per call: the slabs live until the second launch, in stream order)
+    loss, dlo, ws = _head_alloc("head_upsample_sigmoid", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode))
     _lib.check(_fn("lc2is_head_upsample_sigmoid")(_ptr(scores_lo), ld, _ptr(labels), _ptr(dlo), _ptr(loss), B, h, w, C, S, mode,
                                                   ignore_index, grad_scale, _ptr(class_weight), gamma, alpha, class_scale, _ptr(ws),
                                                   nbytes, _stream()), f"head_upsample_sigmoid B={B} h={h} w={w} C={C} S={S}")
@@ -1418,11 +1385,7 @@ def sigmoid_focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_we
     per_pixel=True, (loss2, the per-pixel losses [B,H,W], 0 where not counted).  Nothing is saved for the backward."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
-    if logits is None or labels is None or not logits.is_contiguous() or not labels.is_contiguous():
-        raise RuntimeError("lc2is_amd.sigmoid_focal_nchw_fwd: logits/labels must be contiguous")
-    B, Cc, H, W = logits.shape
-    if tuple(labels.shape) != (B, H, W):
-        raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_fwd: labels must be [{B},{H},{W}]")
+    B, Cc, H, W = _nchw_front("sigmoid_focal_nchw_fwd", logits, labels)
     dev = logits.device
     _focal_weight(class_weight, Cc, dev)
     loss = torch.empty(2, dtype=torch.float32, device=dev)   # overwritten: block partials summed in a fixed order
@@ -1441,14 +1404,9 @@ def sigmoid_focal_nchw_bwd(logits, labels, grad_scale_dev, grad_scale: float = 1
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
     gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
-    B, Cc, H, W = logits.shape
-    if not logits.is_contiguous() or not labels.is_contiguous() or tuple(labels.shape) != (B, H, W):
-        raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_bwd: contiguous logits [B,C,H,W] with labels [{B},{H},{W}] required")
+    B, Cc, H, W = _nchw_front("sigmoid_focal_nchw_bwd", logits, labels, bwd=True)
     _focal_weight(class_weight, Cc, logits.device)
-    if grad_px is not None:
-        _chk(grad_px, torch.float32, "grad_px", 3)
-        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
-            raise RuntimeError(f"lc2is_amd.sigmoid_focal_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    _chk_grad_px("sigmoid_focal_nchw_bwd", grad_px, B, H, W)
     d = torch.empty_like(logits)
     _lib.check(_fn("lc2is_sigmoid_focal_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(grad_scale_dev), grad_scale, _ptr(grad_px),
                                                    _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight), gamma, alpha, class_scale,
@@ -1486,10 +1444,7 @@ def ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float, ignore_i
         _lib.check(_fn("lc2is_ce_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
                                             _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_nchw_bwd")
         return d
-    if grad_px is not None:
-        _chk(grad_px, torch.float32, "grad_px", 3)
-        if tuple(grad_px.shape) != (B, H, W) or not grad_px.is_contiguous():
-            raise RuntimeError(f"lc2is_amd.ce_nchw_bwd: grad_px must be contiguous [{B},{H},{W}]")
+    _chk_grad_px("ce_nchw_bwd", grad_px, B, H, W)
     _lib.check(_fn("lc2is_ce_nchw_bwd_opts")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
                                              _ptr(grad_px), _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight),
                                              label_smoothing, _stream()), "ce_nchw_bwd")

@@ -63,40 +63,16 @@ from .nn.base import HipModule, ParamArena
 _DEFAULT_LR = 1e-5
 
 
-def _accepts_ohem(model) -> bool:
+def _accepts(model, keyword: str) -> bool:
+    """Whether ``model.forward_loss`` takes ``keyword`` (a fused-head option the criterion or the step needs)."""
     import inspect
     fl = getattr(model, "forward_loss", None)
-    return fl is not None and "ohem" in inspect.signature(fl).parameters
-
-
-def _accepts_dice(model) -> bool:
-    import inspect
-    fl = getattr(model, "forward_loss", None)
-    return fl is not None and "dice" in inspect.signature(fl).parameters
-
-
-def _accepts_focal(model) -> bool:
-    import inspect
-    fl = getattr(model, "forward_loss", None)
-    return fl is not None and "focal" in inspect.signature(fl).parameters
-
-
-def _accepts_sigmoid(model) -> bool:
-    import inspect
-    fl = getattr(model, "forward_loss", None)
-    return fl is not None and "sigmoid" in inspect.signature(fl).parameters
-
-
-def _accepts_seg_counts(model) -> bool:
-    import inspect
-    fl = getattr(model, "forward_loss", None)
-    return fl is not None and "seg_counts" in inspect.signature(fl).parameters
+    return fl is not None and keyword in inspect.signature(fl).parameters
 
 
 def _accepts_accum(model) -> bool:
-    import inspect
-    fl = getattr(model, "forward_loss", None)
-    return fl is not None and "accum" in inspect.signature(fl).parameters
+    """``_accepts(model, "accum")`` under the name tests/test_accum_cpu.py imports at module level."""
+    return _accepts(model, "accum")
 
 
 def _n_classes(model) -> int | None:
@@ -407,14 +383,14 @@ class TrainStep:
             if isinstance(criterion, _Dice):
                 raise ValueError("TrainStep: a DiceCrossEntropyLoss cannot be trained with accumulate >= 2: its batch statistics "
                                  "do not add across micro-batches")
-            if not _accepts_accum(model):
+            if not _accepts(model, "accum"):
                 raise TypeError("TrainStep: accumulate >= 2 needs a model whose forward_loss takes accum= "
                                 "(BaseModelWithText, PromptFTN)")
         if not isinstance(seg_metrics, bool):
             raise TypeError(f"TrainStep: seg_metrics must be a bool, got {seg_metrics!r}")
         n_seg = None
         if seg_metrics:
-            if not _accepts_seg_counts(model):
+            if not _accepts(model, "seg_counts"):
                 raise TypeError("TrainStep: seg_metrics=True needs a model whose forward_loss takes seg_counts= "
                                 "(BaseModelWithText, PromptFTN)")
             n_seg = _n_classes(model) if seg_classes is None else seg_classes
@@ -450,20 +426,20 @@ class TrainStep:
             self._loss_opts = (criterion.weight is not None or criterion.label_smoothing != 0.0
                                or criterion.reduction != "mean")
             self._ohem = isinstance(criterion, OhemCrossEntropyLoss)
-            if self._ohem and not _accepts_ohem(model):
+            if self._ohem and not _accepts(model, "ohem"):
                 raise TypeError("TrainStep: an OhemCrossEntropyLoss needs a model whose forward_loss takes ohem= "
                                 "(BaseModelWithText); the compose models do not select hard pixels")
             self._dice = isinstance(criterion, DiceCrossEntropyLoss)
-            if self._dice and not _accepts_dice(model):
+            if self._dice and not _accepts(model, "dice"):
                 raise TypeError("TrainStep: a DiceCrossEntropyLoss needs a model whose forward_loss takes dice= "
                                 "(BaseModelWithText); the compose models have no Dice head")
             if isinstance(criterion, FocalLoss):   # rides the options call: weight=, reduction= and focal=(gamma, poly_eps)
-                if not _accepts_focal(model):
+                if not _accepts(model, "focal"):
                     raise TypeError("TrainStep: a FocalLoss / Poly1CrossEntropyLoss needs a model whose forward_loss takes focal= "
                                     "(BaseModelWithText, PromptFTN)")
                 self._loss_opts = True
             if isinstance(criterion, SigmoidFocalLoss):   # rides the options call too: weight=, reduction= and sigmoid=(gamma, alpha, normalize)
-                if not _accepts_sigmoid(model):
+                if not _accepts(model, "sigmoid"):
                     raise TypeError("TrainStep: a SigmoidFocalLoss / SigmoidCrossEntropyLoss needs a model whose forward_loss takes "
                                     "sigmoid= (BaseModelWithText, PromptFTN)")
                 self._loss_opts = True
@@ -509,7 +485,7 @@ class TrainStep:
             # still cache-warm; 401 against 415 us per launch, faster in both repetitions of profiles/ema_cost.txt
             self.ema_reverse_walk = True
             self.ema = self.arena.flat.clone()
-        # accuracy / IoU counts of the training batches: None = forward_loss is called as before, no launch is added
+        # accuracy / IoU counts of the training batches: None = forward_loss gets no seg_counts=, no launch is added
         self._seg_counts = torch.zeros((3, n_seg), dtype=torch.int64, device=dev) if seg_metrics else None
         # gradient accumulation: the cycle's fp64 loss sum and denominator in a device block (lc2is_accum_block); None = no launch
         self._accum_n, self.micro, self._accum = accum_n, 0, None
@@ -746,32 +722,31 @@ class TrainStep:
                 self.reducer.begin_step()
             else:
                 self.reducer.begin_step(sync=last)
-        seg = {} if self._seg_counts is None else {"seg_counts": self._seg_counts}   # (no keyword at all without seg_metrics)
+        # the keywords of the fused head, from the criterion as it is now (its weight buffer: criterion.to(device) replaces it; no
+        # host sync).  Only what is set is passed: a model's forward_loss need not know the options this step does not use.
+        kw = {}
+        ohem = dice = False
+        if self._ohem or self._dice or self._loss_opts:
+            c = self.criterion
+            ohem = self._ohem and c.training   # the selection applies while the criterion is in training mode (as its forward)
+            dice = self._dice and not self._ohem   # CE + soft Dice (deterministic: the training flag does not matter)
+            if dice:
+                kw["dice"] = c.dice
+            else:
+                kw.update(weight=c.weight, label_smoothing=float(c.label_smoothing), reduction=c.reduction)
+                if self._ohem:
+                    kw["ohem"] = c.ohem if ohem else None
+                else:   # a FocalLoss / Poly1CrossEntropyLoss has .focal, a SigmoidFocalLoss / SigmoidCrossEntropyLoss .sigmoid
+                    kw.update({k: getattr(c, k) for k in ("focal", "sigmoid") if getattr(c, k, None) is not None})
+        if self._seg_counts is not None:
+            kw["seg_counts"] = self._seg_counts
         if self._accum is not None:
-            seg["accum"] = self._accum
-        if self._ohem:   # hard-pixel selection in front of the fused head, while the criterion is in training mode (as its forward)
-            c = self.criterion
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
-                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction,
-                                           ohem=c.ohem if c.training else None, **seg)
-            if c.training:
-                c.last_labels, c.last_info = self.model.last_ohem
-        elif self._dice:   # CE + soft Dice on the fused head (deterministic: the criterion's training flag does not matter)
-            c = self.criterion
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index, dice=c.dice, **seg)
+            kw["accum"] = self._accum
+        loss = self.model.forward_loss(inputs, labels, self.ignore_index, **kw)
+        if ohem:
+            c.last_labels, c.last_info = self.model.last_ohem
+        if dice:
             c.last_stats = self.model.last_dice
-        elif self._loss_opts:   # the criterion's weight buffer as it is now (criterion.to(device) replaces it); no host sync
-            c = self.criterion
-            focal = getattr(c, "focal", None)   # a FocalLoss / Poly1CrossEntropyLoss: its (gamma, poly_eps) as they are now
-            if focal is not None:
-                seg["focal"] = focal
-            sigmoid = getattr(c, "sigmoid", None)   # a SigmoidFocalLoss / SigmoidCrossEntropyLoss: (gamma, alpha, normalize) as they are now
-            if sigmoid is not None:
-                seg["sigmoid"] = sigmoid
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index, weight=c.weight,
-                                           label_smoothing=float(c.label_smoothing), reduction=c.reduction, **seg)
-        else:
-            loss = self.model.forward_loss(inputs, labels, self.ignore_index, **seg)
         loss.backward()
         if not last:   # inside a cycle: nothing but the gradient arena, the accumulation block and the metric counts has moved
             self.micro += 1

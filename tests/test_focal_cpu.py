@@ -198,8 +198,16 @@ def test_fused_sites_refuse_combinations_before_running():
         tail.loss(*args, focal=(NAN, 0.0))
     with pytest.raises(RuntimeError):                                          # accepted with weight / sum: the CPU tensors are refused
         tail.loss(*args, focal=f, weight=torch.ones(3), reduction="sum")
-    src = inspect.getsource(N.PromptFTN.forward_loss)
-    assert src.index("fused_focal_options") < src.index("_embeddings")          # refused before the towers run
+    class _Towers:   # a PromptFTN whose towers must not run: a refusal that came after them would be this AssertionError
+        def _embeddings(self, inputs):
+            raise AssertionError("the towers ran before the refusal")
+
+    with pytest.raises(ValueError, match="gamma"):
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, focal=(-1.0, 0.0))
+    with pytest.raises(ValueError, match="cannot be combined"):
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, focal=f, label_smoothing=0.1)
+    with pytest.raises(AssertionError, match="towers ran"):                    # (and an accepted call does reach them)
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, focal=f)
 
 
 class _CpuModel(nn.Module):
@@ -225,9 +233,9 @@ class _NoFocalModel(nn.Module):
 
 
 def test_trainstep_accepts_the_criterion_and_keeps_its_guards():
-    from lc2is_amd.step import TrainStep, _accepts_focal
-    assert _accepts_focal(_CpuModel()) and not _accepts_focal(_NoFocalModel()) and not _accepts_focal(nn.Linear(2, 2))
-    assert _accepts_focal(_tiny_cpu())
+    from lc2is_amd.step import TrainStep, _accepts
+    assert _accepts(_CpuModel(), "focal") and not _accepts(_NoFocalModel(), "focal") and not _accepts(nn.Linear(2, 2), "focal")
+    assert _accepts(_tiny_cpu(), "focal")
     for crit in (N.FocalLoss(2.0, weight=torch.ones(151)), N.Poly1CrossEntropyLoss(1.0), N.FocalLoss(reduction="sum")):
         with pytest.raises(RuntimeError):                       # accepted: the arena is what refuses a CPU model
             TrainStep(_CpuModel(), criterion=crit)

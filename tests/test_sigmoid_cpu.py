@@ -228,8 +228,16 @@ def test_fused_sites_refuse_combinations_before_running():
         tail.loss(*args, sigmoid=(NAN, None, "pixels"))
     with pytest.raises(RuntimeError):                                          # accepted with weight / sum: the CPU tensors are refused
         tail.loss(*args, sigmoid=s, weight=torch.ones(3), reduction="sum")
-    src = inspect.getsource(N.PromptFTN.forward_loss)
-    assert src.index("fused_sigmoid_options") < src.index("_embeddings")        # refused before the towers run
+    class _Towers:   # a PromptFTN whose towers must not run: a refusal that came after them would be this AssertionError
+        def _embeddings(self, inputs):
+            raise AssertionError("the towers ran before the refusal")
+
+    with pytest.raises(ValueError, match="gamma"):
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, sigmoid=(-1.0, 0.25, "elements"))
+    with pytest.raises(ValueError, match="cannot be combined"):
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, sigmoid=s, label_smoothing=0.1)
+    with pytest.raises(AssertionError, match="towers ran"):                    # (and an accepted call does reach them)
+        N.PromptFTN.forward_loss(_Towers(), {}, labels, sigmoid=s)
     with pytest.raises(ValueError, match="cannot be combined"):
         N.PromptFTN.forward_loss(None, {}, labels, sigmoid=s, focal=(2.0, 0.0))   # (before ``self`` is touched)
     with pytest.raises(ValueError, match="cannot be combined"):
@@ -259,9 +267,9 @@ class _NoSigmoidModel(nn.Module):
 
 
 def test_trainstep_accepts_the_criterion_and_keeps_its_guards():
-    from lc2is_amd.step import TrainStep, _accepts_sigmoid
-    assert _accepts_sigmoid(_CpuModel()) and not _accepts_sigmoid(_NoSigmoidModel()) and not _accepts_sigmoid(nn.Linear(2, 2))
-    assert _accepts_sigmoid(_tiny_cpu())
+    from lc2is_amd.step import TrainStep, _accepts
+    assert _accepts(_CpuModel(), "sigmoid") and not _accepts(_NoSigmoidModel(), "sigmoid") and not _accepts(nn.Linear(2, 2), "sigmoid")
+    assert _accepts(_tiny_cpu(), "sigmoid")
     for crit in (N.SigmoidFocalLoss(2.0, weight=torch.ones(151)), N.SigmoidCrossEntropyLoss(), N.SigmoidFocalLoss(reduction="sum"),
                  N.SigmoidFocalLoss(normalize="pixels")):
         with pytest.raises(RuntimeError):                       # accepted: the arena is what refuses a CPU model
