@@ -1018,6 +1018,49 @@ int lc2is_head_upsample_argmax_wide(const float* scores_lo, int ld, const int64_
                                     int h, int w, int C, int S, int mode, long ignore_index, void* workspace,
                                     size_t workspace_bytes, lc2is_stream_t stream);
 
+/* ---- self-training on the fused head: class map + confidence + pseudo-labels, and cross-entropy with a per-pixel weight ------
+ * Both on the fused head of lc2is_head_upsample_ce: scores_lo fp32 [B,h,w,ld] channels-last, 16-byte aligned, C <= ld <= 192,
+ * ld % 64 == 0 (else LC2IS_ERR_SHAPE); S in {4, 8, 16} and a known mode (else LC2IS_ERR_UNSUPPORTED).  Refusals in the order NULL,
+ * SHAPE, UNSUPPORTED, WORKSPACE, from the arguments alone, before any launch.  The xS map is never materialised.  NO
+ * read-modify-write atomics, LDS included: the same bytes every run; both capture into a graph.
+ *
+ * lc2is_head_upsample_conf: forward only.  Per output pixel the class of lc2is_head_upsample_argmax (the same bytes: ties to the
+ * lowest class, the index clamped into [0, C)) and its softmax probability conf = 1 / sum_c exp(z_c - max), formed as the winner's
+ * own exponential over the sum so that a pixel with one dominant class gives exactly 1.  A pixel whose sum is not a number (all
+ * scores -inf, a NaN or a +inf score) gets conf = 1 / C: conf is always finite and in (0, 1].  Each output is optional (NULL = not
+ * written):
+ *   pred   uint8 [B,H,W]: the class map.
+ *   conf   fp32  [B,H,W]: the confidence.
+ *   pseudo int64 [B,H,W]: the class where conf >= thresh, else ignore_index.
+ *   counts int32 [B][2]:  per image {pixels with conf >= thresh, pixels inside the image = H W}.  Needs a 16-byte aligned workspace
+ *          >= lc2is_head_upsample_conf_workspace_bytes(...) (a pure host function; 0 for a call that would be refused): B * tiles * 2
+ *          int32, summed per image in a fixed order by a second launch.
+ * thresh must be in [0, 1] and not a NaN (else LC2IS_ERR_SHAPE); all four outputs NULL: LC2IS_ERR_NULL.  Every pixel of a given
+ * output is written.
+ * replaces: model(inputs)["outputs"].softmax(1).max(1) on the materialised [B,K,H,W] logits of the teacher's forward, the
+ *   thresholding `where(conf >= t, pred, ignore_index)` and the per-image share of confident pixels (FixMatch, ST++, DAFormer).
+ *
+ * lc2is_head_upsample_ce_pw: lc2is_head_upsample_ce_opts with pixel_weight fp32 [B,H,W] (finite and >= 0: documented, not checked on
+ * the device).  Per counted pixel i (label != ignore_index && 0 <= label < C), a1 = 1 - eps, ac = eps / C, W = sum_c w_c:
+ *   loss_i  = pw_i [ a1 w_y (lse - z_y) + ac (W lse - sum_c w_c z_c) ],   count_i = w_y  (NOT multiplied by pw_i)
+ *   dz_k    = grad_scale pw_i [ (a1 w_y + ac W) p_k - a1 w_y [k == y] - ac w_k ]
+ * loss_sum[0] = sum_i loss_i, loss_sum[1] = sum_i w_y: the denominator of the mean stays that of lc2is_head_upsample_ce_opts, so
+ * pixel_weight == 1 is that loss and a per-image weight scales the image's loss instead of cancelling (mmseg's
+ * weight_reduce_loss).  class_weight: device fp32 [C] or NULL (ones); label_smoothing in [0, 1].  dscores_lo (NULL: loss only), all
+ * ld channels overwritten, exactly 0 at and past C.  workspace: 16-byte aligned, >= lc2is_head_upsample_ce_workspace_bytes(B, h, w,
+ * C, S, mode, dscores_lo != NULL).  One forward + backward launch and the fixed-order finish launch of lc2is_head_upsample_ce.
+ * replaces: (F.cross_entropy(model(inputs)["outputs"], labels, weight, reduction='none', label_smoothing) * pixel_weight).sum() /
+ *   sum_i w_y on the materialised logits (DAFormer's pseudo-label weight, confidence weighting, U-Net's boundary-weight maps), plus
+ *   its autograd. */
+size_t lc2is_head_upsample_conf_workspace_bytes(int B, int h, int w, int C, int S, int mode);
+int lc2is_head_upsample_conf(const float* scores_lo, int ld, uint8_t* pred, float* conf, int64_t* pseudo, int32_t* counts, int B,
+                             int h, int w, int C, int S, int mode, float thresh, long ignore_index, void* workspace,
+                             size_t workspace_bytes, lc2is_stream_t stream);
+int lc2is_head_upsample_ce_pw(const float* scores_lo, int ld, const int64_t* labels, const float* pixel_weight, float* dscores_lo,
+                              float* loss_sum, int B, int h, int w, int C, int S, int mode, long ignore_index, float grad_scale,
+                              const float* class_weight, float label_smoothing, void* workspace, size_t workspace_bytes,
+                              lc2is_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

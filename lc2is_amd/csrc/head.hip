@@ -1341,6 +1341,14 @@ int launch_head_finish(int mode, int S, const HeadArgs& a, int nblk, int fgrid, 
 int head_finish_grid(const HeadArgs& a) { return (int)(((a.dlo ? (long)a.B * a.h * a.w : 1) + 3) / 4); }
 }  // namespace
 
+int lc2is_head_finish_launch(const HeadFinishArgs& f, hipStream_t stream) {
+  HeadArgs a{};   // what head_finish_kernel reads
+  a.ld = f.ld; a.dlo = f.dlo; a.loss_sum = f.loss_sum;
+  a.B = f.B; a.h = f.h; a.w = f.w; a.H = f.h * f.S; a.W = f.w * f.S; a.C = f.C; a.S = f.S; a.mode = f.mode;
+  a.ws_loss = f.ws_loss; a.ws_dlo = f.ws_dlo; a.cq = f.cq;
+  return launch_head_finish(f.mode, f.S, a, f.nblk, head_finish_grid(a), stream);
+}
+
 extern "C" size_t lc2is_head_upsample_ce_workspace_bytes(int B, int h, int w, int C, int S, int mode, int want_grad) {
   if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || !(S == 4 || S == 8 || S == 16)) return 0;   // other S: the atomic path, no workspace
   if (mode != LC2IS_INTERP_BICUBIC && mode != LC2IS_INTERP_BILINEAR) return 0;

@@ -338,3 +338,13 @@ int head_grp_launch(int lds_max, int nblk, int lds, hipStream_t stream, A... arg
 }
 
 }  // namespace
+
+// The finish launch of the group kernels that leave [loss, count] partials and gradient slabs (head_finish_kernel, head.hip), for
+// the kernels of other translation units (head_selftrain.hip): loss_sum[2] = the nblk blocks' partials in block order, dlo
+// [B, h, w, ld] = the slabs' cells in the fixed order (null: loss only).  Returns lc2is_check_launch().
+struct HeadFinishArgs {
+  float* dlo; float* loss_sum;
+  float* ws_loss; float* ws_dlo;
+  int B, h, w, C, ld, S, mode, cq, nblk;
+};
+__attribute__((visibility("hidden"))) int lc2is_head_finish_launch(const HeadFinishArgs& a, hipStream_t stream);

@@ -71,16 +71,17 @@ class PromptFTN(nn.Module):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None,
-                     focal=None, sigmoid=None) -> torch.Tensor:
+                     focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
         materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
         {intersection, predicted, labelled} counts (``ScoreMapTail.loss``).  ``accum``: the device block of a gradient-accumulation
         cycle (``ScoreMapTail.loss``; ``TrainStep(accumulate=N)``).  ``focal=(gamma, poly_eps)``: FocalLoss's per-pixel loss in
         place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``.  ``sigmoid=(gamma, alpha,
         normalize)``: SigmoidFocalLoss's per-class binary loss instead (``ScoreMapTail.loss``); not combinable with ``focal=`` or
-        ``label_smoothing``."""
+        ``label_smoothing``.  ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape that multiplies each counted
+        pixel's cross-entropy, not its count (``ScoreMapTail.loss``); not combinable with ``focal=`` or ``sigmoid=``."""
         keywords = dict(weight=weight, label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, accum=accum,
-                        focal=focal, sigmoid=sigmoid)
+                        focal=focal, sigmoid=sigmoid, pixel_weight=pixel_weight)
         head_criterion("PromptFTN.forward_loss", **keywords)   # refused before the towers run; the tail adds what needs the class count
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, **keywords)

@@ -1,7 +1,7 @@
 """The criterion of the fused head as one value: validated in one place (``head_criterion``) and dispatched in one place
 (``fused_head_loss``) for every site that owns low-resolution class scores — ``BaseModelWithText.forward_loss`` (bicubic x4),
 ``ScoreMapTail.loss`` (bilinear) and, through the tail, ``PromptFTN.forward_loss``.  A new criterion or option is added here and
-to the keyword lists of those three methods; nothing else threads it through.
+to the keyword lists of those three methods; nothing else threads it through.  ``pixel_weight=`` (self-training, boundary maps) is such an option: the last field of the criterion.
 """
 from __future__ import annotations
 
@@ -16,7 +16,8 @@ from .loss import check_dice, check_focal, check_ohem, check_sigmoid
 class HeadCriterion(NamedTuple):
     """What the fused head computes; the default is the plain mean cross-entropy.  ``ohem`` = (thresh, min_kept per image),
     ``dice`` = (ce_weight, dice_weight, smooth, present_only), ``focal`` = (gamma, poly_eps), ``sigmoid`` = (gamma, alpha, normalize):
-    validated tuples or None."""
+    validated tuples or None.  ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape (finite, >= 0, no grad) that
+    multiplies each counted pixel's cross-entropy — not its count: the mean still divides by the sum of w_y — or None."""
     weight: torch.Tensor | None = None
     label_smoothing: float = 0.0
     reduction: str = "mean"
@@ -24,12 +25,13 @@ class HeadCriterion(NamedTuple):
     dice: tuple | None = None
     focal: tuple | None = None
     sigmoid: tuple | None = None
+    pixel_weight: torch.Tensor | None = None
 
     @property
     def plain_ce(self) -> bool:
         """No class weights, no smoothing, 'mean': the cross-entropy entry without options (ohem= only relabels in front of it)."""
         return (self.weight is None and self.label_smoothing == 0.0 and self.reduction == "mean" and self.dice is None
-                and self.focal is None and self.sigmoid is None)
+                and self.focal is None and self.sigmoid is None and self.pixel_weight is None)
 
 
 def fused_loss_options(weight, label_smoothing: float, reduction: str):
@@ -77,6 +79,24 @@ def fused_sigmoid_options(sigmoid, label_smoothing: float, dice, focal):
     return check_sigmoid(*sigmoid)
 
 
+def fused_pixel_weight(who: str, pixel_weight, ohem, dice, focal, sigmoid, K):
+    """``pixel_weight`` validated, or None: the per-pixel weight rides the cross-entropy (weight=, label_smoothing, reduction=,
+    seg_counts=, accum=) and is refused with a hard-pixel selection, a Dice term, the focal and the sigmoid losses, and past 192
+    classes (the chunked head has no such kernel yet)."""
+    if pixel_weight is None:
+        return None
+    for name, on in (("ohem=", ohem is not None), ("dice=", dice is not None), ("focal=", focal is not None),
+                     ("sigmoid=", sigmoid is not None)):
+        if on:
+            raise ValueError(f"lc2is_amd {who}: pixel_weight= cannot be combined with {name} (it weights the cross-entropy with "
+                             "weight=, label_smoothing and reduction= only)")
+    ops.check_pixel_weight(who, pixel_weight, None)
+    if K is not None and K > ops.HEAD_CMAX:
+        raise NotImplementedError(f"lc2is_amd {who}: pixel_weight= is limited to {ops.HEAD_CMAX} classes (its fused kernel keeps every "
+                                  f"class of a pixel in registers), got {K}; the chunked head past them takes no pixel weight yet")
+    return pixel_weight
+
+
 def wide_refuse(who: str, K: int, scale: int, label_smoothing: float, ohem, dice, focal, sigmoid) -> None:
     """Past 192 classes the fused head is the chunked cross-entropy (``ops.head_upsample_ce_wide``): plain CE with ``weight=``,
     'mean' / 'sum', ``ignore_index``, ``seg_counts=`` and ``accum=`` at scale 4.  Every other criterion keeps its kernel's 192-class
@@ -96,7 +116,8 @@ def wide_refuse(who: str, K: int, scale: int, label_smoothing: float, ohem, dice
 
 
 def head_criterion(who: str, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                   focal=None, sigmoid=None, seg_counts=None, accum=None, n_classes=None, scale=None) -> HeadCriterion:
+                   focal=None, sigmoid=None, seg_counts=None, accum=None, n_classes=None, scale=None,
+                   pixel_weight=None) -> HeadCriterion:
     """The validated criterion of a ``forward_loss`` / ``ScoreMapTail.loss`` call: every refusal of the fused head, in one order,
     before a tower runs or anything is allocated.  ``n_classes``: the head's class count, or a callable that returns it (read only
     after the combination checks), or None where it is not known yet — the wide refusal then waits for the call that knows it."""
@@ -111,9 +132,10 @@ def head_criterion(who: str, *, weight=None, label_smoothing: float = 0.0, reduc
     K = n_classes() if callable(n_classes) else n_classes
     if seg_counts is not None:
         ops.check_seg_counts(seg_counts, K)
+    pixel_weight = fused_pixel_weight(who, pixel_weight, ohem, dice, focal, sigmoid, K)
     if K is not None:
         wide_refuse(who, K, scale, label_smoothing, ohem, dice, focal, sigmoid)
-    return HeadCriterion(*(opts or (None, 0.0, "mean")), ohem, dice, focal, sigmoid)
+    return HeadCriterion(*(opts or (None, 0.0, "mean")), ohem, dice, focal, sigmoid, pixel_weight)
 
 
 def _reduce(loss2, reduction: str, save: bool):
@@ -141,7 +163,13 @@ def fused_head_loss(scores, labels, B: int, h: int, w: int, K: int, S: int, mode
     if seg_counts is not None:   # accuracy / IoU counts of the batch: the ORIGINAL labels (before OHEM relabels), the loss's scores
         ops.seg_counts_add(seg_counts, scores, labels, *geom, ignore_index)
     dice_stats = ohem_sel = sum_mul = None
-    if K > ops.HEAD_CMAX:   # the chunked cross-entropy (head_criterion refused every other criterion)
+    if crit.pixel_weight is not None:   # cross-entropy with a per-pixel weight: [sum of pw_i l_i, sum of w_y] (the count ignores pw)
+        if K > ops.HEAD_CMAX:   # (head_criterion refuses it where it knows K; a caller that did not say is refused here)
+            raise NotImplementedError(f"lc2is_amd: pixel_weight= is limited to {ops.HEAD_CMAX} classes, got {K}")
+        loss2, dlo = ops.head_upsample_ce_pw(scores, labels, crit.pixel_weight, *geom, grad_scale=1.0, class_weight=crit.weight,
+                                             label_smoothing=crit.label_smoothing, **kw)
+        loss, mul = _reduce(loss2, crit.reduction, save)
+    elif K > ops.HEAD_CMAX:   # the chunked cross-entropy (head_criterion refused every other criterion)
         loss2, dlo = ops.head_upsample_ce_wide(scores, labels, *geom, grad_scale=1.0, class_weight=crit.weight, **kw)
         loss, mul = _reduce(loss2, crit.reduction, save)
     elif crit.dice is not None:   # CE + soft Dice: statistics pass, coefficients, gradient pass — dlo is the gradient of the scalar loss

@@ -265,7 +265,7 @@ class BaseModelWithText(HipModule):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                     seg_counts=None, accum=None, focal=None, sigmoid=None) -> torch.Tensor:
+                     seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
@@ -293,10 +293,18 @@ class BaseModelWithText(HipModule):
         torch's and mmseg's rule for binary losses, deliberately different from the softmax losses above.  Keeps ``weight`` (on
         class c's binary term), ``reduction``, ``seg_counts``, ``accum`` and ``ohem`` (the selection still ranks by the plain softmax
         CE; the relabelled call is the sigmoid one); not combinable with ``dice=``, ``focal=`` or ``label_smoothing``
-        (``ValueError`` before the towers run).  None: the softmax losses above."""
+        (``ValueError`` before the towers run).  None: the softmax losses above.
+        ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape, finite and >= 0 (not checked: no host sync), not
+        requiring grad — each counted pixel's cross-entropy is multiplied by its weight (pseudo-label quality or confidence weights,
+        ``selftrain.PseudoLabeler``; boundary-weight maps), in one forward + backward launch of the head
+        (``ops.head_upsample_ce_pw``).  The pixel's COUNT is not: 'mean' still divides by the sum of w_y over the counted pixels, so
+        an all-ones weight is the plain loss and a per-image weight scales that image's loss (mmseg's ``weight_reduce_loss``) rather
+        than cancelling; ``seg_counts`` and ``accum`` keep their meaning.  Keeps ``weight``, ``label_smoothing`` and ``reduction``;
+        not combinable with ``ohem=``, ``dice=``, ``focal=`` or ``sigmoid=`` (``ValueError``), and limited to 192 classes
+        (``NotImplementedError``).  None: no weight, the calls above."""
         crit = head_criterion("BaseModelWithText.forward_loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction,
                               ohem=ohem, dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
-                              n_classes=lambda: self.class_prototypes.shape[0], scale=4)
+                              n_classes=lambda: self.class_prototypes.shape[0], scale=4, pixel_weight=pixel_weight)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
         return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, crit, seg_counts, accum)
@@ -315,6 +323,27 @@ class BaseModelWithText(HipModule):
         argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
         pred, _ = argmax(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_counts=False)
         return pred
+
+    @torch.no_grad()
+    def predict_confidence(self, inputs: dict, thresh=None, ignore_index: int = -100):
+        """``(pred uint8 [B, out, out], conf fp32 [B, out, out])``: the class map of ``predict`` and its softmax probability,
+        ``forward(inputs)["outputs"].softmax(1).max(1)``, without forming the logits (``ops.head_upsample_conf``).  With ``thresh``
+        (a number in [0, 1]): ``(pred, conf, pseudo, counts)`` — ``pseudo`` int64 = the class where conf >= thresh, else
+        ``ignore_index``; ``counts`` int32 [B, 2] = per image {pixels with conf >= thresh, pixels of the image}.  No host read."""
+        if thresh is not None:
+            thresh = ops.conf_thresh(thresh)
+        K = self.class_prototypes.shape[0]
+        if K > ops.HEAD_CMAX:
+            raise NotImplementedError(f"lc2is_amd BaseModelWithText.predict_confidence: limited to {ops.HEAD_CMAX} classes, got {K} "
+                                      "(the chunked head past them gives the class map only: predict)")
+        dec_v = self._decode(inputs)
+        B, P, C = dec_v.shape
+        g = self.in_size // self.patch_size
+        dec16 = ops.cast_bf16(dec_v.reshape(B * P, C).float().contiguous())
+        _, _, scores = self._head_scores(dec16)
+        out = ops.head_upsample_conf(scores, B, g, g, K, 4, ops.INTERP_BICUBIC, thresh=thresh, ignore_index=ignore_index,
+                                     want_counts=thresh is not None)
+        return out[:2] if thresh is None else out
 
     @torch.no_grad()
     def forward_tuple(self, inputs: dict):

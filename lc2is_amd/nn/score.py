@@ -111,7 +111,7 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None, dice=None, seg_counts=None, accum=None, focal=None, sigmoid=None) -> torch.Tensor:
+             ohem=None, dice=None, seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
         the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
@@ -127,10 +127,14 @@ class ScoreMapTail(nn.Module):
         ``sigmoid=(gamma, alpha, normalize)``: the sigmoid focal / sigmoid cross-entropy loss, summed over the classes of each
         counted pixel, in place of the cross-entropy (SigmoidFocalLoss's definition: 'mean' divides by a count of elements or of
         pixels, never a weight sum; ``BaseModelWithText.forward_loss`` has the details); keeps ``weight``, ``reduction``, ``ohem``,
-        ``seg_counts`` and ``accum``, not combinable with ``dice=``, ``focal=`` or ``label_smoothing``."""
+        ``seg_counts`` and ``accum``, not combinable with ``dice=``, ``focal=`` or ``label_smoothing``.
+        ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape (finite, >= 0, no grad) that multiplies each counted
+        pixel's cross-entropy but not its count — 'mean' still divides by the sum of w_y (``BaseModelWithText.forward_loss`` has the
+        details); keeps ``weight``, ``label_smoothing``, ``reduction``, ``seg_counts`` and ``accum``, not combinable with ``ohem=``,
+        ``dice=``, ``focal=`` or ``sigmoid=``, limited to 192 classes."""
         crit = head_criterion("ScoreMapTail.loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction, ohem=ohem,
                               dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
-                              n_classes=lambda: text_embeddings.shape[1], scale=self.scale_factor)
+                              n_classes=lambda: text_embeddings.shape[1], scale=self.scale_factor, pixel_weight=pixel_weight)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
         return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, crit, self, seg_counts,
@@ -149,3 +153,23 @@ class ScoreMapTail(nn.Module):
         argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
         pred, _ = argmax(scores, None, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, want_counts=False)
         return pred
+
+    @torch.no_grad()
+    def predict_confidence(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, thresh=None,
+                           ignore_index: int = -100):
+        """``(pred, conf)``: the class map of ``predict`` and its softmax probability ``forward(visual, text).softmax(1).max(1)``,
+        fp32 [B, S*h, S*w], without writing the map (``ops.head_upsample_conf``).  With ``thresh``: ``(pred, conf, pseudo, counts)``
+        as ``BaseModelWithText.predict_confidence``.  Limited to 192 classes."""
+        if thresh is not None:
+            thresh = ops.conf_thresh(thresh)
+        K = text_embeddings.shape[1]
+        if K > ops.HEAD_CMAX:
+            raise NotImplementedError(f"lc2is_amd ScoreMapTail.predict_confidence: limited to {ops.HEAD_CMAX} classes, got {K} "
+                                      "(the chunked head past them gives the class map only: predict)")
+        require_cuda(visual_embeddings, "visual_embeddings")
+        B, P, _ = visual_embeddings.shape
+        h = int(round(P ** 0.5))
+        scores, _ = _scores_lo(visual_embeddings, text_embeddings)
+        out = ops.head_upsample_conf(scores, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, thresh=thresh,
+                                     ignore_index=ignore_index, want_counts=thresh is not None)
+        return out[:2] if thresh is None else out

@@ -100,6 +100,9 @@ _ARGTYPES = {
     "lc2is_head_upsample_ce_wide": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _P, _Z, _P],
     "lc2is_head_upsample_argmax_wide_workspace_bytes": [_I, _I, _I, _I, _I, _I],
     "lc2is_head_upsample_argmax_wide": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P, _Z, _P],
+    "lc2is_head_upsample_conf_workspace_bytes": [_I, _I, _I, _I, _I, _I],
+    "lc2is_head_upsample_conf": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _L, _P, _Z, _P],
+    "lc2is_head_upsample_ce_pw": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _P, _Z, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -1119,6 +1122,85 @@ def head_upsample_argmax_wide(scores_lo, labels, B: int, h: int, w: int, C: int,
                                                       mode, ignore_index, _ptr(ws), nbytes, _stream()),
                f"head_upsample_argmax_wide B={B} h={h} w={w} C={C} S={S}")
     return pred, counts
+
+
+# ---- self-training: the teacher's confidence and pseudo-labels, and the cross-entropy with a per-pixel weight (head_selftrain.hip) ----
+def conf_thresh(thresh) -> float:
+    """``thresh`` of a pseudo-labelling call, validated: a number in [0, 1] (a NaN is refused)."""
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 <= thresh <= 1.0:
+        raise ValueError(f"lc2is_amd: the confidence threshold must be a number in [0, 1], got {thresh!r}")
+    return float(thresh)
+
+
+def head_upsample_conf(scores_lo, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *, thresh=None,
+                       ignore_index: int = -100, want_pred: bool = True, want_conf: bool = True, want_counts: bool = False):
+    """scores_lo fp32 [B*h*w, ld] -> (pred uint8 [B, h*S, w*S], conf fp32 [B, h*S, w*S], pseudo int64 [B, h*S, w*S], counts int32
+    [B, 2]), None for what was not asked: the argmax over the C classes of the upsampled scores (S = 4 / 8 / 16; the bytes of
+    ``head_upsample_argmax``) and its softmax probability.  With ``thresh`` (a number in [0, 1]): ``pseudo`` = the class where
+    conf >= thresh, else ``ignore_index``, and (``want_counts``) per image {pixels with conf >= thresh, pixels of the image}.  A
+    pixel whose scores are all -inf or hold a NaN / +inf gets conf = 1 / C: conf is always finite and in (0, 1].  The [B, C, H, W]
+    map is never formed; nothing syncs, no atomics, the same bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo")
+    if thresh is None:
+        if want_counts:
+            raise ValueError("lc2is_amd.head_upsample_conf: want_counts needs thresh")
+        if not want_pred and not want_conf:
+            raise ValueError("lc2is_amd.head_upsample_conf: nothing requested (want_pred and want_conf are False, no thresh)")
+    else:
+        thresh = conf_thresh(thresh)
+    ld = _head_front("head_upsample_conf", scores_lo, None, B, h, w, C, S, need_labels=False, scales=(4, 8, 16), cmax=HEAD_CMAX)
+    dev = scores_lo.device
+    nbytes = 0
+    if want_counts:
+        nbytes = _fn("lc2is_head_upsample_conf_workspace_bytes")(B, h, w, C, S, mode)
+        if nbytes == 0:
+            raise RuntimeError(f"lc2is_amd.head_upsample_conf: unsupported call B={B} h={h} w={w} C={C} S={S} mode={mode}")
+    shape = (B, h * S, w * S)
+    pred = torch.empty(shape, dtype=torch.uint8, device=dev) if want_pred else None
+    conf = torch.empty(shape, dtype=torch.float32, device=dev) if want_conf else None
+    pseudo = torch.empty(shape, dtype=torch.int64, device=dev) if thresh is not None else None
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev) if want_counts else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None   # (per call: the slabs live until the second launch)
+    _lib.check(_fn("lc2is_head_upsample_conf")(_ptr(scores_lo), ld, _ptr(pred), _ptr(conf), _ptr(pseudo), _ptr(counts), B, h, w, C, S,
+                                               mode, 0.0 if thresh is None else thresh, ignore_index, _ptr(ws), nbytes, _stream()),
+               f"head_upsample_conf B={B} h={h} w={w} C={C} S={S}")
+    return pred, conf, pseudo, counts
+
+
+def check_pixel_weight(who: str, pixel_weight, shape, dev=None) -> None:
+    """``pixel_weight`` of a loss call: a contiguous fp32 tensor of the labels' shape that does not require grad (on ``dev`` where
+    given).  Its values must be finite and >= 0, which is documented and not checked (no host sync)."""
+    if not isinstance(pixel_weight, torch.Tensor) or pixel_weight.dtype != torch.float32:
+        raise ValueError(f"lc2is_amd {who}: pixel_weight must be a float32 tensor, got "
+                         f"{getattr(pixel_weight, 'dtype', type(pixel_weight).__name__)}")
+    if pixel_weight.requires_grad:
+        raise ValueError(f"lc2is_amd {who}: pixel_weight must not require grad (the loss is not differentiated with respect to it)")
+    if shape is not None and (tuple(pixel_weight.shape) != tuple(shape) or not pixel_weight.is_contiguous()):
+        raise ValueError(f"lc2is_amd {who}: pixel_weight must be contiguous {list(shape)} (the labels' shape), got "
+                         f"{list(pixel_weight.shape)}")
+    if dev is not None and pixel_weight.device != dev:
+        raise ValueError(f"lc2is_amd {who}: pixel_weight must be on {dev}, got {pixel_weight.device}")
+
+
+def head_upsample_ce_pw(scores_lo, labels, pixel_weight, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                        want_grad: bool = False, ignore_index: int = -100, grad_scale: float = 1.0, class_weight=None,
+                        label_smoothing: float = 0.0):
+    """``head_upsample_ce`` (class_weight / label_smoothing) with a per-pixel weight: scores_lo fp32 [B*h*w, ld], labels int64 and
+    pixel_weight fp32 (contiguous, finite and >= 0: not checked) [B, h*S, w*S].  Returns (loss2, dscores_lo or None): loss2[0] =
+    sum_i pw_i l_i over the counted pixels, loss2[1] = sum_i w_{y_i} — NOT multiplied by pw_i: the denominator of the mean stays the
+    unweighted call's, so pixel_weight == 1 is that loss and a per-image weight scales the image's loss instead of cancelling.
+    dscores_lo = grad_scale * d loss2[0] / d scores_lo.  One forward + backward launch and the finish launch of ``head_upsample_ce``
+    (S = 4 / 8 / 16, C <= 192); nothing syncs, no atomics, the same bytes every run, captures into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    _ce_options(class_weight, label_smoothing, C, scores_lo.device)
+    ld = _head_front("head_upsample_ce_pw", scores_lo, labels, B, h, w, C, S, need_labels=True, scales=(4, 8, 16), cmax=HEAD_CMAX)
+    check_pixel_weight("head_upsample_ce_pw", pixel_weight, labels.shape, scores_lo.device)
+    nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
+    loss, dlo, ws = _head_alloc("head_upsample_ce_pw", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode))
+    _lib.check(_fn("lc2is_head_upsample_ce_pw")(_ptr(scores_lo), ld, _ptr(labels), _ptr(pixel_weight), _ptr(dlo), _ptr(loss), B, h, w,
+                                                C, S, mode, ignore_index, grad_scale, _ptr(class_weight), label_smoothing, _ptr(ws),
+                                                nbytes, _stream()), f"head_upsample_ce_pw B={B} h={h} w={w} C={C} S={S}")
+    return loss, dlo
 
 
 def seg_counts_add(seg_counts, scores_lo, labels, B: int, h: int, w: int, C: int, S: int, mode: int, ignore_index: int):

@@ -1,0 +1,76 @@
+"""Self-training (mean teacher / pseudo-labelling) on the fused head: confident pseudo-labels and their per-pixel loss weights,
+held on the device.
+
+The teacher is the EMA of ``TrainStep(ema_decay=...)``, the views are ``TrainAugment``'s; this module adds the two pieces between
+them: ``PseudoLabeler`` turns the teacher's prediction on the weak view into labels (the class where the max softmax probability
+passes a threshold, ``ignore_index`` elsewhere: FixMatch, ST++, DAFormer) and a per-pixel weight, and ``combine`` forms the
+``(inputs, labels, pixel_weight)`` of one ``TrainStep.step`` from a labelled and a pseudo-labelled batch.  The [B, K, H, W] logits
+are never formed (``model.predict_confidence`` -> ``ops.head_upsample_conf``) and nothing reads the device: the labeler captures
+into a graph.
+
+Recipe (one iteration)::
+
+    step = TrainStep(model, ema_decay=0.999, ...)
+    labeler = PseudoLabeler(model, threshold=0.968, weight="quality")
+    with step.ema_weights():                                   # the teacher's weights
+        labels_u, pw_u, _ = labeler(weak_view)
+    step.step(*labeler.combine(labelled=(inputs, labels), pseudo=(strong_view, labels_u, pw_u)))
+
+Out of scope here: how the strong / weak views are drawn, ClassMix, pooling the confident-pixel counts across ranks, and models
+without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+
+_WEIGHTS = ("quality", "confidence", None)
+
+
+class PseudoLabeler:
+    """``labeler(inputs) -> (labels int64 [B, H, W], pixel_weight fp32 [B, H, W] or None, counts int32 [B, 2])`` from
+    ``model.predict_confidence(inputs, threshold, ignore_index)``: the class where conf >= threshold, ``ignore_index`` elsewhere;
+    ``counts[b]`` = {confident pixels, pixels} of image b.
+
+    ``weight``: "quality" — every pixel of image b weighs ``counts[b, 0] / counts[b, 1]``, the share of its confident pixels
+    (DAFormer); "confidence" — each kept pixel weighs its confidence, the others 0; None — no weight.  The weights multiply the
+    pixel losses and not the pixel counts (``forward_loss(pixel_weight=)``): an image with few confident pixels pulls less.
+    Runs under ``no_grad`` with the weights the model holds when called (inside ``TrainStep.ema_weights()``: the teacher's);
+    torch ops on device tensors after the head's launch pair, no host read."""
+
+    def __init__(self, model, threshold: float = 0.968, weight="quality", ignore_index: int = -100) -> None:
+        if not callable(getattr(model, "predict_confidence", None)):
+            raise TypeError("PseudoLabeler: the model has no predict_confidence (BaseModelWithText has; AuxiliaryLoss, DenseClip and "
+                            "ContrastiveModel are not supported)")
+        if weight not in _WEIGHTS:
+            raise ValueError(f"PseudoLabeler: weight must be 'quality', 'confidence' or None, got {weight!r}")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+            raise TypeError(f"PseudoLabeler: ignore_index must be an int, got {ignore_index!r}")
+        self.model, self.threshold, self.weight, self.ignore_index = model, ops.conf_thresh(threshold), weight, ignore_index
+
+    @torch.no_grad()
+    def __call__(self, inputs):
+        _, conf, labels, counts = self.model.predict_confidence(inputs, self.threshold, self.ignore_index)
+        if self.weight is None:
+            return labels, None, counts
+        if self.weight == "quality":
+            share = counts[:, 0].to(torch.float32) / counts[:, 1].to(torch.float32)
+            return labels, share.view(-1, 1, 1).expand_as(conf).contiguous(), counts
+        return labels, torch.where(conf >= self.threshold, conf, torch.zeros_like(conf)), counts
+
+    @staticmethod
+    def combine(labelled, pseudo):
+        """``labelled = (inputs, labels)`` and ``pseudo = (inputs_u, labels_u, pixel_weight_u or None)`` -> the ``(inputs, labels,
+        pixel_weight)`` of one ``TrainStep.step``: the two batches concatenated along the batch axis, weight 1 on the labelled
+        images (and on the pseudo-labelled ones when they carry none).  ``inputs`` are dicts of tensors with the same keys; a tensor
+        that both hold as the same object (shared prompts) is kept once."""
+        (inputs, labels), (inputs_u, labels_u, pw_u) = labelled, pseudo
+        if set(inputs) != set(inputs_u):
+            raise ValueError(f"PseudoLabeler.combine: the two batches hold different inputs: {sorted(inputs)} and {sorted(inputs_u)}")
+        if labels.shape[1:] != labels_u.shape[1:]:
+            raise ValueError(f"PseudoLabeler.combine: label maps of {tuple(labels.shape[1:])} and {tuple(labels_u.shape[1:])}")
+        both = {k: v if v is inputs_u[k] else torch.cat([v, inputs_u[k]], dim=0) for k, v in inputs.items()}
+        ones = torch.ones(labels.shape, dtype=torch.float32, device=labels.device)
+        pw_u = torch.ones(labels_u.shape, dtype=torch.float32, device=labels.device) if pw_u is None else pw_u
+        return both, torch.cat([labels, labels_u], dim=0), torch.cat([ones, pw_u], dim=0)

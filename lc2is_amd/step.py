@@ -708,9 +708,25 @@ class TrainStep:
             b.copy_(sd[k])
         self.t = int(sd["t"])
 
-    def step(self, inputs: dict, labels: torch.Tensor) -> torch.Tensor:
+    def _check_pixel_weight(self, who: str) -> None:
+        """A per-pixel loss weight needs a model that takes it and a criterion it combines with: refused before anything runs."""
+        if not _accepts(self.model, "pixel_weight"):
+            raise TypeError(f"TrainStep.{who}: pixel_weight needs a model whose forward_loss takes pixel_weight= "
+                            "(BaseModelWithText, PromptFTN)")
+        c = self.criterion
+        if self._ohem or self._dice or getattr(c, "focal", None) is not None or getattr(c, "sigmoid", None) is not None:
+            raise ValueError(f"TrainStep.{who}: pixel_weight weights the cross-entropy (weight, label_smoothing, reduction); it cannot "
+                             "be combined with an OHEM, Dice, focal or sigmoid criterion")
+
+    def step(self, inputs: dict, labels: torch.Tensor, pixel_weight: torch.Tensor | None = None) -> torch.Tensor:
+        """One training step (with ``accumulate=N``: one micro-batch of a cycle).  ``pixel_weight``: a contiguous fp32 device tensor
+        of the labels' shape, finite and >= 0, that multiplies each counted pixel's cross-entropy and not its count — the mean, the
+        accumulation block, a reducer's global count and the seg counts stay those of the unweighted step (``forward_loss``);
+        None: no weight, the keyword is not passed."""
         if self._ema_swapped:
             raise RuntimeError("TrainStep.step: inside ema_weights() the parameters are the EMA; leave the block before training")
+        if pixel_weight is not None:
+            self._check_pixel_weight("step")
         arena = self.arena
         # accumulate=N: N calls are one cycle.  The first overwrites the gradients, the later ones find p.grad set, so every writer
         # accumulates; only the last finalizes, reduces, updates and invalidates the shadows.
@@ -742,6 +758,8 @@ class TrainStep:
             kw["seg_counts"] = self._seg_counts
         if self._accum is not None:
             kw["accum"] = self._accum
+        if pixel_weight is not None:
+            kw["pixel_weight"] = pixel_weight
         loss = self.model.forward_loss(inputs, labels, self.ignore_index, **kw)
         if ohem:
             c.last_labels, c.last_info = self.model.last_ohem
@@ -831,7 +849,7 @@ class TrainStep:
             m.invalidate_shadows()
 
     # -- HIP graph replay ------------------------------------------------------------------------------------
-    def capture(self, inputs: dict, labels: torch.Tensor, warmup: int = 2):
+    def capture(self, inputs: dict, labels: torch.Tensor, warmup: int = 2, pixel_weight=None):
         """Capture one full step (shadow refresh -> forward -> CE -> backward -> optimizer) into a hipGraph over
         static copies of the batch; returns ``replay(inputs, labels) -> loss`` which copies the new batch into the
         static buffers and launches the graph (one host call per step instead of ~800 kernel launches).  ``warmup`` REAL
@@ -842,16 +860,24 @@ class TrainStep:
         Single-process only (the RCCL reduction is not captured).
         With ``accumulate=N`` both arguments are sequences of N batches: the whole cycle (N forward / backward passes and the one
         update) is recorded as ONE graph over N static copies, a warm-up step is a whole cycle, and ``replay`` takes the same two
-        sequences and returns the tuple of the N micro-batch losses."""
+        sequences and returns the tuple of the N micro-batch losses.
+        ``pixel_weight`` (with ``accumulate=N``: a sequence of N): the step is captured with a per-pixel loss weight held in a
+        static buffer, and ``replay`` takes the new weight as its third argument, ``replay(inputs, labels, pixel_weight)``."""
         n_micro = self._accum_n or 1
+        if pixel_weight is not None:
+            self._check_pixel_weight("capture")
         if self._accum_n is not None:
             if isinstance(inputs, dict) or isinstance(labels, torch.Tensor) or len(inputs) != n_micro or len(labels) != n_micro:
                 raise ValueError(f"TrainStep.capture: with accumulate={n_micro} give sequences of {n_micro} inputs and {n_micro} labels")
             if self.micro != 0:
                 raise RuntimeError("TrainStep.capture: an accumulation cycle is open; finish it or flush() first")
             many_in, many_lb = list(inputs), list(labels)
+            if pixel_weight is not None and (isinstance(pixel_weight, torch.Tensor) or len(pixel_weight) != n_micro):
+                raise ValueError(f"TrainStep.capture: with accumulate={n_micro} give a sequence of {n_micro} pixel weights")
+            many_pw = None if pixel_weight is None else list(pixel_weight)
         else:
             many_in, many_lb = [inputs], [labels]
+            many_pw = None if pixel_weight is None else [pixel_weight]
         if self.reducer is not None:
             raise RuntimeError("TrainStep.capture: graph capture is only wired for single-GPU steps")
         if self._ema_swapped:
@@ -865,9 +891,12 @@ class TrainStep:
         static_ins = [{k: v.clone() for k, v in d.items()} for d in many_in]
         static_lbs = [lb.clone() for lb in many_lb]
         static_in, static_lb = static_ins[0], static_lbs[0]
+        static_pws = None if many_pw is None else [pw.clone() for pw in many_pw]
 
         def cycle():
-            return [self.step(d, lb) for d, lb in zip(static_ins, static_lbs)]
+            if static_pws is None:
+                return [self.step(d, lb) for d, lb in zip(static_ins, static_lbs)]
+            return [self.step(d, lb, pw) for d, lb, pw in zip(static_ins, static_lbs, static_pws)]
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -891,12 +920,16 @@ class TrainStep:
         mark1 = ops.captured_tables_mark()   # the pinned descriptor-table images registered in between belong to this graph
         self.t = t_before   # capture records the step; nothing ran
 
-        def replay(new_inputs, new_labels):
+        def replay(new_inputs, new_labels, new_pixel_weight=None):
             if self._ema_swapped:
                 raise RuntimeError("TrainStep replay: inside ema_weights() the parameters are the EMA; leave the block before "
                                    "training")
+            if (new_pixel_weight is None) != (static_pws is None):
+                raise ValueError("TrainStep replay: the step was captured " + ("without a pixel weight: replay(inputs, labels)"
+                                 if static_pws is None else "with a pixel weight: replay(inputs, labels, pixel_weight)"))
             if self._accum_n is None:
                 new_inputs, new_labels = [new_inputs], [new_labels]
+                new_pixel_weight = None if new_pixel_weight is None else [new_pixel_weight]
             elif isinstance(new_inputs, dict) or len(new_inputs) != n_micro or len(new_labels) != n_micro:
                 raise ValueError(f"TrainStep replay: the captured cycle takes sequences of {n_micro} inputs and {n_micro} labels")
             elif self.micro != 0:
@@ -908,6 +941,12 @@ class TrainStep:
             for dst, src in zip(static_lbs, new_labels):
                 if src is not dst:
                     dst.copy_(src, non_blocking=True)
+            if static_pws is not None:
+                if len(new_pixel_weight) != n_micro:
+                    raise ValueError(f"TrainStep replay: the captured cycle takes a sequence of {n_micro} pixel weights")
+                for dst, src in zip(static_pws, new_pixel_weight):
+                    if src is not dst:
+                        dst.copy_(src, non_blocking=True)
             graph.replay()
             self.t += 1
             return static_loss
@@ -928,6 +967,8 @@ class TrainStep:
 
         replay.static_inputs = static_in if self._accum_n is None else static_ins
         replay.static_labels = static_lb if self._accum_n is None else static_lbs
+        if static_pws is not None:
+            replay.static_pixel_weight = static_pws[0] if self._accum_n is None else static_pws
         replay.graph, replay.release = graph, release
         self._captured = replay
         return replay
