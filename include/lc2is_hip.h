@@ -1018,6 +1018,32 @@ int lc2is_head_upsample_argmax_wide(const float* scores_lo, int ld, const int64_
                                     int h, int w, int C, int S, int mode, long ignore_index, void* workspace,
                                     size_t workspace_bytes, lc2is_stream_t stream);
 
+/* ---- distillation on the fused head: per-pixel KL(teacher || student) of two upsampled score maps ---------------------------
+ * On the fused head of lc2is_head_upsample_ce: scores_lo (student) and teacher_lo fp32 [B,h,w,ld] channels-last with the same ld,
+ * both 16-byte aligned, C <= ld <= 192, ld % 64 == 0, temperature T finite and > 0 (else LC2IS_ERR_SHAPE); S in {4, 8, 16} and a
+ * known mode (else LC2IS_ERR_UNSUPPORTED).  Refusals in the order NULL, SHAPE, UNSUPPORTED, WORKSPACE, from the arguments alone,
+ * before any launch.  Neither xS map is materialised.
+ * Counted pixels: labels == NULL: every pixel of the image; else int64 [B,H,W] and the pixels with label != ignore_index &&
+ * 0 <= label < C (the labelled region: crop padding stays out).  pixel_weight: fp32 [B,H,W], finite and >= 0 (documented, not
+ * checked on the device), or NULL (ones).  Per counted pixel i, u = z / T over the C real channels, p = softmax(u):
+ *   loss_i  = pw_i T^2 sum_c p_t,c (log p_t,c - log p_s,c),   count_i = 1  (NOT multiplied by pw_i)
+ *   dz_s,c  = grad_scale pw_i T (p_s,c - p_t,c)               (the teacher gets no gradient)
+ * loss_sum[0] = sum_i loss_i, loss_sum[1] = the number of counted pixels.  The loss is formed in the log domain and both softmaxes
+ * by the same instructions: teacher_lo == scores_lo gives loss_sum[0] == 0.0 and dscores_lo == 0.0 exactly; a class with
+ * p_t == 0 adds exactly 0; finite scores of +-1e4 give finite results.  -inf / NaN scores in the C real channels are unsupported
+ * (not checked).  Channels at and past C of either map are never read into a result.
+ * dscores_lo (NULL: loss only), all ld channels overwritten, exactly 0 at and past C.  loss_sum[2] overwritten.  workspace: 16-byte
+ * aligned, >= lc2is_head_upsample_ce_workspace_bytes(B, h, w, C, S, mode, dscores_lo != NULL), overwritten.  One forward + backward
+ * launch and the fixed-order finish launch of lc2is_head_upsample_ce: NO read-modify-write atomics, LDS included, the same bytes
+ * every run; captures into a graph.
+ * replaces: T*T * F.kl_div(F.log_softmax(student_logits / T, 1), F.softmax(teacher_logits / T, 1), reduction='none').sum(1) on two
+ *   materialised [B,K,H,W] logit maps (Hinton's KD per pixel: mmrazor's KLDivergence, structured KD's pixel-wise term; the soft
+ *   consistency of mean teacher / FixMatch / UniMatch), times pixel_weight, plus autograd through the student's softmax. */
+int lc2is_head_upsample_kd(const float* scores_lo, const float* teacher_lo, int ld, const int64_t* labels /*NULL ok*/,
+                           const float* pixel_weight /*NULL ok*/, float* dscores_lo /*NULL: loss only*/, float* loss_sum,
+                           int B, int h, int w, int C, int S, int mode, long ignore_index, float temperature, float grad_scale,
+                           void* workspace, size_t workspace_bytes, lc2is_stream_t stream);
+
 /* ---- self-training on the fused head: class map + confidence + pseudo-labels, and cross-entropy with a per-pixel weight ------
  * Both on the fused head of lc2is_head_upsample_ce: scores_lo fp32 [B,h,w,ld] channels-last, 16-byte aligned, C <= ld <= 192,
  * ld % 64 == 0 (else LC2IS_ERR_SHAPE); S in {4, 8, 16} and a known mode (else LC2IS_ERR_UNSUPPORTED).  Refusals in the order NULL,

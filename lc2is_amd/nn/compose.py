@@ -71,7 +71,7 @@ class PromptFTN(nn.Module):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", seg_counts=None, accum=None,
-                     focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
+                     focal=None, sigmoid=None, pixel_weight=None, distill=None) -> torch.Tensor:
         """``nn.CrossEntropyLoss(weight, reduction, label_smoothing)(forward(inputs)[1], labels)`` (engine.py:94) without
         materialising the [B,K,512,512] map ('mean' or 'sum').  ``seg_counts``: an int64 [3, K] device tensor that takes the batch's
         {intersection, predicted, labelled} counts (``ScoreMapTail.loss``).  ``accum``: the device block of a gradient-accumulation
@@ -79,9 +79,12 @@ class PromptFTN(nn.Module):
         place of the cross-entropy (``ScoreMapTail.loss``); not combinable with ``label_smoothing``.  ``sigmoid=(gamma, alpha,
         normalize)``: SigmoidFocalLoss's per-class binary loss instead (``ScoreMapTail.loss``); not combinable with ``focal=`` or
         ``label_smoothing``.  ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape that multiplies each counted
-        pixel's cross-entropy, not its count (``ScoreMapTail.loss``); not combinable with ``focal=`` or ``sigmoid=``."""
+        pixel's cross-entropy, not its count (``ScoreMapTail.loss``); not combinable with ``focal=`` or ``sigmoid=``.
+        ``distill``: a ``head_loss.Distill`` — adds weight * the mean per-pixel T^2 KL to a teacher's low-resolution scores
+        (``ScoreMapTail.loss``; the teacher's scores are its tail's ``scores_lo`` on its own embeddings); not combinable with
+        ``accum=``.  Its options and the tensor's dtype are checked before the towers run, its shape by the tail."""
         keywords = dict(weight=weight, label_smoothing=label_smoothing, reduction=reduction, seg_counts=seg_counts, accum=accum,
-                        focal=focal, sigmoid=sigmoid, pixel_weight=pixel_weight)
+                        focal=focal, sigmoid=sigmoid, pixel_weight=pixel_weight, distill=distill)
         head_criterion("PromptFTN.forward_loss", **keywords)   # refused before the towers run; the tail adds what needs the class count
         visual_embeddings, text_embeddings = self._embeddings(inputs)
         return self.tail.loss(visual_embeddings, text_embeddings, labels, ignore_index, **keywords)

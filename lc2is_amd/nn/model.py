@@ -265,7 +265,7 @@ class BaseModelWithText(HipModule):
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
                      label_smoothing: float = 0.0, reduction: str = "mean", ohem=None, dice=None,
-                     seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
+                     seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None, distill=None) -> torch.Tensor:
         """Cross-entropy of the model output against ``labels`` [B,out,out] — CE(engine.py:94) fused with the head; never
         materialises the fp32 logits.  ``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in
         nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept per image)``: the loss over the hard pixels only, selected on the device
@@ -301,10 +301,22 @@ class BaseModelWithText(HipModule):
         an all-ones weight is the plain loss and a per-image weight scales that image's loss (mmseg's ``weight_reduce_loss``) rather
         than cancelling; ``seg_counts`` and ``accum`` keep their meaning.  Keeps ``weight``, ``label_smoothing`` and ``reduction``;
         not combinable with ``ohem=``, ``dice=``, ``focal=`` or ``sigmoid=`` (``ValueError``), and limited to 192 classes
-        (``NotImplementedError``).  None: no weight, the calls above."""
+        (``NotImplementedError``).  None: no weight, the calls above.
+        ``distill``: a ``head_loss.Distill(scores, weight, temperature, region, pixel_weight)`` — ADDS weight * the mean over the
+        counted pixels of pw_i T^2 KL(softmax(teacher / T) || softmax(student / T)) on the upsampled scores to the loss of whatever
+        criterion the other options choose (Hinton's distillation per pixel; the soft consistency of a mean teacher), in one more
+        forward + backward launch of the head on the same low-resolution scores (``ops.head_upsample_kd``): neither logit map is
+        formed.  ``scores`` are the teacher's ``head_scores(inputs)`` (this model under ``TrainStep.ema_weights()``, or another one
+        with the same classes and patch grid), fp32 [B*g*g, class_pad(K)], no grad: nothing flows to the teacher.  ``region``
+        'all': every pixel; 'labelled': the pixels ``labels`` counts (as given: before ``ohem=`` relabels).  The term has its own
+        denominator, the number of pixels it counts, so it is not combinable with ``accum=`` and is limited to 192 classes
+        (``NotImplementedError``); a bad weight, temperature, region or teacher tensor is a ``ValueError`` before the towers run.
+        None: no term, the calls above."""
+        rows = None if distill is None else inputs["pixel_values"].shape[0] * (self.in_size // self.patch_size) ** 2
         crit = head_criterion("BaseModelWithText.forward_loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction,
                               ohem=ohem, dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
-                              n_classes=lambda: self.class_prototypes.shape[0], scale=4, pixel_weight=pixel_weight)
+                              n_classes=lambda: self.class_prototypes.shape[0], scale=4, pixel_weight=pixel_weight, distill=distill,
+                              rows=rows, device=None if distill is None else self.class_prototypes.device)
         dec_v = self._decode(inputs)
         save = torch.is_grad_enabled() and dec_v.requires_grad
         return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, crit, seg_counts, accum)
@@ -323,6 +335,16 @@ class BaseModelWithText(HipModule):
         argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
         pred, _ = argmax(scores, None, B, g, g, K, 4, ops.INTERP_BICUBIC, want_counts=False)
         return pred
+
+    @torch.no_grad()
+    def head_scores(self, inputs: dict) -> torch.Tensor:
+        """The low-resolution class scores of the model output, fp32 [B*g*g, class_pad(K)] (g = in_size // patch_size; channels at
+        and past K are padding): what the fused head upsamples, taken under no_grad as ``predict`` takes them.  This is the layout
+        ``forward_loss(distill=Distill(scores, ...))`` consumes — the teacher's side of a distillation step."""
+        dec_v = self._decode(inputs)
+        B, P, C = dec_v.shape
+        dec16 = ops.cast_bf16(dec_v.reshape(B * P, C).float().contiguous())
+        return self._head_scores(dec16)[2]
 
     @torch.no_grad()
     def predict_confidence(self, inputs: dict, thresh=None, ignore_index: int = -100):

@@ -111,7 +111,8 @@ class ScoreMapTail(nn.Module):
 
     def loss(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, labels: torch.Tensor,
              ignore_index: int = -100, *, weight=None, label_smoothing: float = 0.0, reduction: str = "mean",
-             ohem=None, dice=None, seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None) -> torch.Tensor:
+             ohem=None, dice=None, seg_counts=None, accum=None, focal=None, sigmoid=None, pixel_weight=None,
+             distill=None) -> torch.Tensor:
         """``weight`` / ``label_smoothing`` / ``reduction`` ('mean' or 'sum') as in nn.CrossEntropyLoss.  ``ohem=(thresh, min_kept
         per image)``: the loss over the hard pixels only (OhemCrossEntropyLoss's rule); ``self.last_ohem`` then holds (the labels
         the head saw, the device info block).  ``dice=(ce_weight, dice_weight, smooth, present_only)``: ce_weight * mean CE +
@@ -131,10 +132,16 @@ class ScoreMapTail(nn.Module):
         ``pixel_weight``: a contiguous fp32 device tensor of the labels' shape (finite, >= 0, no grad) that multiplies each counted
         pixel's cross-entropy but not its count — 'mean' still divides by the sum of w_y (``BaseModelWithText.forward_loss`` has the
         details); keeps ``weight``, ``label_smoothing``, ``reduction``, ``seg_counts`` and ``accum``, not combinable with ``ohem=``,
-        ``dice=``, ``focal=`` or ``sigmoid=``, limited to 192 classes."""
+        ``dice=``, ``focal=`` or ``sigmoid=``, limited to 192 classes.
+        ``distill``: a ``head_loss.Distill(scores, weight, temperature, region, pixel_weight)`` — adds weight * the mean per-pixel
+        T^2 KL(teacher || student) of the upsampled scores to the loss of whatever criterion is chosen; ``scores`` are a teacher's
+        ``scores_lo(visual, text)``, fp32 [B*h*w, class_pad(K)], no grad (``BaseModelWithText.forward_loss`` has the details).  Not
+        combinable with ``accum=``, limited to 192 classes."""
+        B, P = visual_embeddings.shape[0], visual_embeddings.shape[1]
         crit = head_criterion("ScoreMapTail.loss", weight=weight, label_smoothing=label_smoothing, reduction=reduction, ohem=ohem,
                               dice=dice, focal=focal, sigmoid=sigmoid, seg_counts=seg_counts, accum=accum,
-                              n_classes=lambda: text_embeddings.shape[1], scale=self.scale_factor, pixel_weight=pixel_weight)
+                              n_classes=lambda: text_embeddings.shape[1], scale=self.scale_factor, pixel_weight=pixel_weight,
+                              distill=distill, rows=B * P, device=visual_embeddings.device)
         require_cuda(visual_embeddings, "visual_embeddings")
         save = torch.is_grad_enabled() and (visual_embeddings.requires_grad or text_embeddings.requires_grad)
         return _ScoreFn.apply(visual_embeddings, text_embeddings, labels, self.scale_factor, ignore_index, save, crit, self, seg_counts,
@@ -153,6 +160,13 @@ class ScoreMapTail(nn.Module):
         argmax = ops.head_upsample_argmax_wide if K > ops.HEAD_CMAX else ops.head_upsample_argmax
         pred, _ = argmax(scores, None, B, h, h, K, self.scale_factor, ops.INTERP_BILINEAR, want_counts=False)
         return pred
+
+    @torch.no_grad()
+    def scores_lo(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor) -> torch.Tensor:
+        """The low-resolution class scores of the score map, fp32 [B*h*w, class_pad(K)] (channels at and past K are padding), under
+        no_grad: what ``loss(distill=Distill(scores, ...))`` consumes as the teacher's side of a distillation step."""
+        require_cuda(visual_embeddings, "visual_embeddings")
+        return _scores_lo(visual_embeddings, text_embeddings)[0]
 
     @torch.no_grad()
     def predict_confidence(self, visual_embeddings: torch.Tensor, text_embeddings: torch.Tensor, thresh=None,

@@ -103,6 +103,7 @@ _ARGTYPES = {
     "lc2is_head_upsample_conf_workspace_bytes": [_I, _I, _I, _I, _I, _I],
     "lc2is_head_upsample_conf": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _L, _P, _Z, _P],
     "lc2is_head_upsample_ce_pw": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _P, _F, _P, _Z, _P],
+    "lc2is_head_upsample_kd": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _F, _F, _P, _Z, _P],
     "lc2is_bilinear_up_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lc2is_bilinear_up_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "lc2is_sr_gather": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -1200,6 +1201,55 @@ def head_upsample_ce_pw(scores_lo, labels, pixel_weight, B: int, h: int, w: int,
     _lib.check(_fn("lc2is_head_upsample_ce_pw")(_ptr(scores_lo), ld, _ptr(labels), _ptr(pixel_weight), _ptr(dlo), _ptr(loss), B, h, w,
                                                 C, S, mode, ignore_index, grad_scale, _ptr(class_weight), label_smoothing, _ptr(ws),
                                                 nbytes, _stream()), f"head_upsample_ce_pw B={B} h={h} w={w} C={C} S={S}")
+    return loss, dlo
+
+
+# ---- distillation: per-pixel KL to a teacher's low-resolution scores (head_distill.hip) ----
+def kd_temperature(temperature) -> float:
+    """``temperature`` of a distillation call, validated: a finite number > 0."""
+    if not finite_ge(temperature) or temperature <= 0:
+        raise ValueError(f"lc2is_amd: the distillation temperature must be a finite number > 0, got {temperature!r}")
+    return float(temperature)
+
+
+def check_teacher_scores(who: str, teacher_lo, shape=None, dev=None) -> None:
+    """``teacher_lo`` of a distillation call: a contiguous fp32 tensor that does not require grad, of the student's low-resolution
+    shape and on its device where those are given."""
+    if not isinstance(teacher_lo, torch.Tensor) or teacher_lo.dtype != torch.float32:
+        raise ValueError(f"lc2is_amd {who}: the teacher's scores must be a float32 tensor, got "
+                         f"{getattr(teacher_lo, 'dtype', type(teacher_lo).__name__)}")
+    if teacher_lo.requires_grad:
+        raise ValueError(f"lc2is_amd {who}: the teacher's scores must not require grad (nothing flows to the teacher; take them "
+                         "under no_grad or detach them)")
+    if not teacher_lo.is_contiguous() or (shape is not None and tuple(teacher_lo.shape) != tuple(shape)):
+        raise ValueError(f"lc2is_amd {who}: the teacher's scores must be contiguous{'' if shape is None else ' ' + str(list(shape))} "
+                         f"(the student's low-resolution scores' shape), got {list(teacher_lo.shape)}")
+    if dev is not None and teacher_lo.device != dev:
+        raise ValueError(f"lc2is_amd {who}: the teacher's scores must be on {dev}, got {teacher_lo.device}")
+
+
+def head_upsample_kd(scores_lo, teacher_lo, B: int, h: int, w: int, C: int, S: int, mode: int = INTERP_BICUBIC, *,
+                     temperature: float = 1.0, labels=None, pixel_weight=None, want_grad: bool = False, ignore_index: int = -100,
+                     grad_scale: float = 1.0):
+    """Per-pixel KL(teacher || student) of the upsampled scores at a temperature T: scores_lo and teacher_lo fp32 [B*h*w, ld]
+    (the teacher contiguous, the student's shape and device, no grad).  Counted pixels: every pixel without ``labels``; with them
+    (int64 [B, h*S, w*S]) the pixels the cross-entropy counts.  ``pixel_weight`` fp32 [B, h*S, w*S] (finite, >= 0: not checked) or
+    None.  Returns (loss2, dscores_lo or None): loss2[0] = sum_i pw_i T^2 KL_i, loss2[1] = the number of counted pixels (NOT
+    multiplied by pw_i), dscores_lo = grad_scale * d loss2[0] / d scores_lo = grad_scale pw_i T (p_s - p_t) pulled through the
+    upsample; the teacher gets no gradient.  teacher_lo == scores_lo gives exactly 0 and 0.  One forward + backward launch and the
+    finish launch of ``head_upsample_ce`` (S = 4 / 8 / 16, C <= 192); nothing syncs, no atomics, the same bytes every run, captures
+    into a graph."""
+    _chk(scores_lo, torch.float32, "scores_lo"); _chk(labels, torch.int64, "labels", 3)
+    temperature = kd_temperature(temperature)
+    ld = _head_front("head_upsample_kd", scores_lo, labels, B, h, w, C, S, need_labels=False, scales=(4, 8, 16), cmax=HEAD_CMAX)
+    check_teacher_scores("head_upsample_kd", teacher_lo, scores_lo.shape, scores_lo.device)
+    if pixel_weight is not None:
+        check_pixel_weight("head_upsample_kd", pixel_weight, (B, h * S, w * S), scores_lo.device)
+    nbytes = _fn("lc2is_head_upsample_ce_workspace_bytes")(B, h, w, C, S, mode, int(want_grad))
+    loss, dlo, ws = _head_alloc("head_upsample_kd", scores_lo, nbytes, want_grad, (B, h, w, C, S, mode))
+    _lib.check(_fn("lc2is_head_upsample_kd")(_ptr(scores_lo), _ptr(teacher_lo), ld, _ptr(labels), _ptr(pixel_weight), _ptr(dlo),
+                                             _ptr(loss), B, h, w, C, S, mode, ignore_index, temperature, grad_scale, _ptr(ws), nbytes,
+                                             _stream()), f"head_upsample_kd B={B} h={h} w={w} C={C} S={S}")
     return loss, dlo
 
 

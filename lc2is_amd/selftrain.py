@@ -16,6 +16,19 @@ Recipe (one iteration)::
         labels_u, pw_u, _ = labeler(weak_view)
     step.step(*labeler.combine(labelled=(inputs, labels), pseudo=(strong_view, labels_u, pw_u)))
 
+The soft-teacher iteration beside it (soft mean teacher, the soft variants of FixMatch / UniMatch): the teacher hands over its
+low-resolution scores instead of hard labels and the step adds the per-pixel KL to them (``forward_loss(distill=...)`` ->
+``ops.head_upsample_kd``; no [B, K, H, W] map of either model)::
+
+    step = TrainStep(model, ema_decay=0.999, distill=(1.0, 1.0, "all"), ...)   # (weight, temperature, region)
+    with step.ema_weights():
+        scores_t = model.head_scores(weak_view)                # fp32 [B*g*g, class_pad(K)], no grad
+    step.step_distill(strong_view, labels, scores_t)          # CE(labels) + weight * mean T^2 KL(teacher || student)
+
+(``labels`` all ``ignore_index`` for an unlabelled batch: the cross-entropy's mean is then NaN by torch's rule, so mix labelled
+images in, as ``combine`` does for the hard recipe; ``teacher_weight=`` takes a per-pixel weight on the KL, e.g. the teacher's
+confidence from ``predict_confidence``.)
+
 Out of scope here: how the strong / weak views are drawn, ClassMix, pooling the confident-pixel counts across ranks, and models
 without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
 """

@@ -364,7 +364,15 @@ class TrainStep:
     collective, call N reduces under its backward and also sums the two fp64 sums over the ranks: for 'mean' the scale is
     1 / (sum over ranks and micro-batches of the count) with no extra 1/world — the GLOBAL-batch mean, which differs from the
     N = 1 behaviour (the mean of the ranks' means) when the ranks' counts differ; 'sum' keeps the 1/world of N = 1.  ``capture``
-    then takes sequences of N inputs and N labels and records the whole cycle as one graph."""
+    then takes sequences of N inputs and N labels and records the whole cycle as one graph.
+    ``distill=(weight, temperature, region)`` (keyword-only; ``None``: today's step, no new launch, no new keyword): every step adds
+    weight * the mean per-pixel T^2 KL(teacher || student) of the upsampled scores to the criterion's loss
+    (``forward_loss(distill=...)``); the teacher's low-resolution scores of the batch come with each call of the step's own
+    entry, ``step_distill(inputs, labels, model.head_scores(view))`` — taken inside ``ema_weights()`` for a soft mean teacher, or
+    another model's — with an optional ``teacher_weight=`` per pixel (``step`` and ``capture`` keep their parameter lists).  Eager,
+    captured (``capture_distill``: static buffers), with ``seg_metrics=True`` and under a reducer; not with ``accumulate >= 2``
+    (``NotImplementedError``: the term has its own denominator); a model whose ``forward_loss`` has no ``distill=`` is refused at
+    construction (``TypeError``), and ``step`` / ``capture`` on such a TrainStep, which bring no teacher scores, with a ``ValueError``."""
 
     def __init__(self, model: nn.Module, *, optimizer: str = "sgd", lr: float = _DEFAULT_LR, momentum: float = 0.0,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, reducer=None,
@@ -372,9 +380,22 @@ class TrainStep:
                  schedule_steps: int | None = None, max_grad_norm: float | None = None, skip_nonfinite: bool = False,
                  device_state: bool = False, param_groups=None, ema_decay: float | None = None, ema_warmup: bool = False,
                  ema_every: int = 1, seg_metrics: bool = False, seg_classes: int | None = None,
-                 accumulate: int | None = None) -> None:
+                 accumulate: int | None = None, distill=None) -> None:
         # (argument checks first: nothing is built or allocated for a step that cannot run)
         _check_ema_args(ema_decay, ema_warmup, ema_every)
+        if distill is not None:
+            from .nn.head_loss import check_distill_options
+            try:
+                d_weight, d_temp, d_region = distill
+            except (TypeError, ValueError):
+                raise ValueError(f"TrainStep: distill must be (weight, temperature, region), got {distill!r}") from None
+            distill = check_distill_options(d_weight, d_temp, d_region)
+            if accumulate not in (None, 1):
+                raise NotImplementedError("TrainStep: distill cannot be combined with accumulate >= 2 (the distillation term has its "
+                                          "own denominator and the accumulation block carries one)")
+            if not _accepts(model, "distill"):
+                raise TypeError("TrainStep: distill needs a model whose forward_loss takes distill= (BaseModelWithText, PromptFTN)")
+        self._distill = distill
         if accumulate is not None and (isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1):
             raise ValueError(f"TrainStep: accumulate must be None or an integer >= 1, got {accumulate!r}")
         accum_n = None if accumulate in (None, 1) else int(accumulate)   # None: today's step, no new launch, no new keyword
@@ -718,15 +739,38 @@ class TrainStep:
             raise ValueError(f"TrainStep.{who}: pixel_weight weights the cross-entropy (weight, label_smoothing, reduction); it cannot "
                              "be combined with an OHEM, Dice, focal or sigmoid criterion")
 
+    def _check_teacher(self, who: str, teacher_scores, teacher_weight) -> None:
+        """The per-step tensors of the distillation term against how the TrainStep was built: refused before anything runs."""
+        if getattr(self, "_distill", None) is None:
+            if teacher_scores is not None or teacher_weight is not None:
+                raise ValueError(f"TrainStep.{who}: teacher_scores / teacher_weight need a TrainStep built with "
+                                 "distill=(weight, temperature, region)")
+        elif teacher_scores is None:
+            raise ValueError(f"TrainStep.{who}: this TrainStep was built with distill=: every step needs teacher_scores — "
+                             "step_distill(inputs, labels, teacher_scores) / capture_distill(...), the teacher's "
+                             "model.head_scores(inputs), e.g. under ema_weights()")
+
     def step(self, inputs: dict, labels: torch.Tensor, pixel_weight: torch.Tensor | None = None) -> torch.Tensor:
         """One training step (with ``accumulate=N``: one micro-batch of a cycle).  ``pixel_weight``: a contiguous fp32 device tensor
         of the labels' shape, finite and >= 0, that multiplies each counted pixel's cross-entropy and not its count — the mean, the
         accumulation block, a reducer's global count and the seg counts stay those of the unweighted step (``forward_loss``);
-        None: no weight, the keyword is not passed."""
+        None: no weight, the keyword is not passed.  A TrainStep built with ``distill=`` steps through ``step_distill``."""
+        return TrainStep._step(self, inputs, labels, pixel_weight, None, None)   # (through the class: a stand-in object has no methods)
+
+    def step_distill(self, inputs: dict, labels: torch.Tensor, teacher_scores: torch.Tensor, teacher_weight: torch.Tensor | None = None,
+                     pixel_weight: torch.Tensor | None = None) -> torch.Tensor:
+        """One training step of a ``TrainStep(distill=(weight, temperature, region))``: ``step`` with the teacher's low-resolution
+        scores of this batch, fp32 [B*g*g, class_pad(K)], no grad — ``model.head_scores(inputs)`` inside ``ema_weights()`` or of
+        another model.  The loss is the criterion's plus weight * the mean per-pixel T^2 KL to them (``forward_loss(distill=...)``).
+        ``teacher_weight``: an optional fp32 tensor of the labels' shape on each pixel's KL."""
+        return self._step(inputs, labels, pixel_weight, teacher_scores, teacher_weight)
+
+    def _step(self, inputs, labels, pixel_weight, teacher_scores, teacher_weight):
         if self._ema_swapped:
             raise RuntimeError("TrainStep.step: inside ema_weights() the parameters are the EMA; leave the block before training")
         if pixel_weight is not None:
-            self._check_pixel_weight("step")
+            TrainStep._check_pixel_weight(self, "step")
+        TrainStep._check_teacher(self, "step", teacher_scores, teacher_weight)
         arena = self.arena
         # accumulate=N: N calls are one cycle.  The first overwrites the gradients, the later ones find p.grad set, so every writer
         # accumulates; only the last finalizes, reduces, updates and invalidates the shadows.
@@ -760,6 +804,9 @@ class TrainStep:
             kw["accum"] = self._accum
         if pixel_weight is not None:
             kw["pixel_weight"] = pixel_weight
+        if getattr(self, "_distill", None) is not None:
+            from .nn.head_loss import Distill
+            kw["distill"] = Distill(teacher_scores, *self._distill, teacher_weight)
         loss = self.model.forward_loss(inputs, labels, self.ignore_index, **kw)
         if ohem:
             c.last_labels, c.last_info = self.model.last_ohem
@@ -862,10 +909,23 @@ class TrainStep:
         update) is recorded as ONE graph over N static copies, a warm-up step is a whole cycle, and ``replay`` takes the same two
         sequences and returns the tuple of the N micro-batch losses.
         ``pixel_weight`` (with ``accumulate=N``: a sequence of N): the step is captured with a per-pixel loss weight held in a
-        static buffer, and ``replay`` takes the new weight as its third argument, ``replay(inputs, labels, pixel_weight)``."""
+        static buffer, and ``replay`` takes the new weight as its third argument, ``replay(inputs, labels, pixel_weight)``.
+        A TrainStep built with ``distill=`` captures through ``capture_distill``."""
+        return self._capture(inputs, labels, warmup, pixel_weight, None, None)
+
+    def capture_distill(self, inputs: dict, labels: torch.Tensor, teacher_scores: torch.Tensor, teacher_weight=None, warmup: int = 2,
+                        pixel_weight=None):
+        """``capture`` for a TrainStep built with ``distill=``: the teacher's scores (and weight) are held in static buffers as the
+        pixel weight is; ``replay(inputs, labels, teacher_scores=..., teacher_weight=...)`` copies the new ones in, and a replay that
+        omits what the capture had (or gives what it had not) is refused.  ``replay.static_teacher_scores`` /
+        ``static_teacher_weight``."""
+        return self._capture(inputs, labels, warmup, pixel_weight, teacher_scores, teacher_weight)
+
+    def _capture(self, inputs, labels, warmup, pixel_weight, teacher_scores, teacher_weight):
         n_micro = self._accum_n or 1
         if pixel_weight is not None:
             self._check_pixel_weight("capture")
+        self._check_teacher("capture", teacher_scores, teacher_weight)
         if self._accum_n is not None:
             if isinstance(inputs, dict) or isinstance(labels, torch.Tensor) or len(inputs) != n_micro or len(labels) != n_micro:
                 raise ValueError(f"TrainStep.capture: with accumulate={n_micro} give sequences of {n_micro} inputs and {n_micro} labels")
@@ -892,8 +952,12 @@ class TrainStep:
         static_lbs = [lb.clone() for lb in many_lb]
         static_in, static_lb = static_ins[0], static_lbs[0]
         static_pws = None if many_pw is None else [pw.clone() for pw in many_pw]
+        static_ts = None if teacher_scores is None else teacher_scores.clone()   # (distill= excludes accumulate: one micro-batch)
+        static_tw = None if teacher_weight is None else teacher_weight.clone()
 
         def cycle():
+            if static_ts is not None:
+                return [self._step(static_in, static_lb, None if static_pws is None else static_pws[0], static_ts, static_tw)]
             if static_pws is None:
                 return [self.step(d, lb) for d, lb in zip(static_ins, static_lbs)]
             return [self.step(d, lb, pw) for d, lb, pw in zip(static_ins, static_lbs, static_pws)]
@@ -920,13 +984,17 @@ class TrainStep:
         mark1 = ops.captured_tables_mark()   # the pinned descriptor-table images registered in between belong to this graph
         self.t = t_before   # capture records the step; nothing ran
 
-        def replay(new_inputs, new_labels, new_pixel_weight=None):
+        def replay(new_inputs, new_labels, new_pixel_weight=None, teacher_scores=None, teacher_weight=None):
             if self._ema_swapped:
                 raise RuntimeError("TrainStep replay: inside ema_weights() the parameters are the EMA; leave the block before "
                                    "training")
             if (new_pixel_weight is None) != (static_pws is None):
                 raise ValueError("TrainStep replay: the step was captured " + ("without a pixel weight: replay(inputs, labels)"
                                  if static_pws is None else "with a pixel weight: replay(inputs, labels, pixel_weight)"))
+            for what, new, held in (("teacher_scores", teacher_scores, static_ts), ("teacher_weight", teacher_weight, static_tw)):
+                if (new is None) != (held is None):
+                    raise ValueError(f"TrainStep replay: the step was captured {'without' if held is None else 'with'} {what}: "
+                                     f"replay(inputs, labels, ...{'' if held is None else ', ' + what + '=...'})")
             if self._accum_n is None:
                 new_inputs, new_labels = [new_inputs], [new_labels]
                 new_pixel_weight = None if new_pixel_weight is None else [new_pixel_weight]
@@ -947,6 +1015,12 @@ class TrainStep:
                 for dst, src in zip(static_pws, new_pixel_weight):
                     if src is not dst:
                         dst.copy_(src, non_blocking=True)
+            for dst, src in ((static_ts, teacher_scores), (static_tw, teacher_weight)):
+                if dst is not None and src is not dst:
+                    if src.shape != dst.shape or src.dtype != dst.dtype:
+                        raise ValueError(f"TrainStep replay: the captured teacher tensor is {dst.dtype} {list(dst.shape)}, got "
+                                         f"{src.dtype} {list(src.shape)}")
+                    dst.copy_(src, non_blocking=True)
             graph.replay()
             self.t += 1
             return static_loss
@@ -969,6 +1043,8 @@ class TrainStep:
         replay.static_labels = static_lb if self._accum_n is None else static_lbs
         if static_pws is not None:
             replay.static_pixel_weight = static_pws[0] if self._accum_n is None else static_pws
+        if static_ts is not None:
+            replay.static_teacher_scores, replay.static_teacher_weight = static_ts, static_tw
         replay.graph, replay.release = graph, release
         self._captured = replay
         return replay
