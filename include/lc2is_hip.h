@@ -72,7 +72,7 @@ int lc2is_get_cu_budget(void);
  * Either or both of out_bf16 / out_f32 may be given.  tile_cfg 0 = auto (the plan: exact rounds of 256x256 or 256x384 tiles over
  * the chip's 256 CUs, persistent form for bf16 outputs, the <= 64 ragged rows of B x 1025-token inputs computed inside the same
  * launch); a non-zero tile_cfg forces one kernel for tests and A/B (1-3 register-staged 128x128 / 256x128 / 64x64, 4 / 6 LDS-DMA
- * 256x256 / 128x128, 13 / 15 persistent 256x256, 16 = 256x384 [N % 384 == 0, no activation, fp32-only or bf16-only output], 17 = row
+ * 256x256 / 128x128, 15 persistent 256x256, 16 = 256x384 [N % 384 == 0, no activation, fp32-only or bf16-only output], 17 = row
  * kernel for M <= 64) and returns LC2IS_ERR_UNSUPPORTED where that kernel does not take the problem.  Every plan gives bitwise the
  * same result as tile_cfg 4.
  * replaces: nn.Linear.forward at hf:CLIPAttention.forward (q/k/v/out_proj), hf:CLIPMLP.forward,
@@ -83,6 +83,21 @@ int lc2is_gemm_nt_bf16(const void* A, int lda, const void* W, int ldw, const flo
                        const float* resid, int ldr, const void* aux_in, int ldx, void* out_bf16, int ldo,
                        float* out_f32, int ldf, void* aux_out, int ldy, int M, int N, int K, int act,
                        int tile_cfg, lc2is_stream_t stream);
+
+/* The plan lc2is_gemm_nt_bf16 runs for the same arguments under the present CU budget, without launching anything (no GPU is
+ * needed; pointers are only tested for NULL).  A plan is one or two launches: kernel `cfg` over rows [row0, row0 + rows) with
+ * `tail_rows` further ragged rows computed inside that launch; the records tile [0, M).  off_* are the bytes by which the
+ * launch's pointers lie past the caller's (0 for an absent one).  Returns the number of records (at most `cap` are written) or
+ * the error code lc2is_gemm_nt_bf16 would return.  All NT kernels give bitwise the same output, so this is the only way a test
+ * can see which one the dispatch picks. */
+typedef struct {
+  int cfg, row0, rows, tail_rows;
+  int staged_epi; /* epilogue through LDS: 0 no, 1 bf16 traffic, 2 fp32-only output */
+  long long off_a, off_resid, off_aux_in, off_out_bf16, off_out_f32, off_aux_out;
+} lc2is_gemm_nt_launch;
+int lc2is_gemm_nt_plan(const void* A, int lda, const void* W, int ldw, const float* bias, const float* resid, int ldr,
+                       const void* aux_in, int ldx, void* out_bf16, int ldo, float* out_f32, int ldf, void* aux_out, int ldy,
+                       int M, int N, int K, int act, int tile_cfg, lc2is_gemm_nt_launch* out, int cap);
 
 /* The residual-stream GEMM and the LayerNorm that follows it in ONE launch (round 5): out_f32 = A.W^T + bias (+ resid) as
  * lc2is_gemm_nt_bf16 writes it, and ln_out = bf16((out_f32 - mean) * rstd * gamma + beta) per row over the N columns (mean, rstd

@@ -206,14 +206,14 @@ __global__ __launch_bounds__(1024) void partials_reduce_kernel(const float* __re
 }
 }  // namespace
 
-// "done once PER DEVICE": hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to a function ON a device, so a process that
-// drives a second GPU must set it there too (a per-process flag let such a launch fail with ~78 KB of dynamic LDS requested)
 // Compute units the tile planners may count on (lc2is_set_cu_budget; 0 = all 256): every large-tile kernel takes a whole CU per block,
 // so a CU held by another queue's kernel (RCCL's channels under data parallelism) turns "exactly one round of tiles" into two.
+// The budget may change between two reads (dp.py sets it during a step): a launcher reads it ONCE and hands the value to its planner.
 extern "C" int lc2is_get_cu_budget(void);
 static inline int lc2is_ncu() { const int b = lc2is_get_cu_budget(); return b > 0 && b < 256 ? b : 256; }
-static inline long lc2is_rounds(long blocks) { const int n = lc2is_ncu(); return (blocks + n - 1) / n; }
 
+// "done once PER DEVICE": hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to a function ON a device, so a process that
+// drives a second GPU must set it there too (a per-process flag let such a launch fail with ~78 KB of dynamic LDS requested)
 static inline int lc2is_cur_dev() {
   int d = 0;
   (void)hipGetDevice(&d);
@@ -224,6 +224,16 @@ struct DevOnce {
   bool need() const { return !((mask.load(std::memory_order_acquire) >> lc2is_cur_dev()) & 1ull); }
   void done() { mask.fetch_or(1ull << lc2is_cur_dev(), std::memory_order_release); }
 };
+// kernel `Kern` may be launched with `bytes` of dynamic LDS on the current device (idempotent; a race only repeats the same call)
+template <auto Kern>
+int set_dyn_lds(int bytes) {
+  static DevOnce once;
+  if (once.need()) {
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return LC2IS_ERR_LAUNCH;
+    once.done();
+  }
+  return LC2IS_OK;
+}
 
 static inline int lc2is_check_launch() {
   hipError_t e = hipGetLastError();

@@ -17,7 +17,7 @@
 // tile t and written to the other LDS buffer after them (one barrier per K step).
 // Block ids are remapped so that each XCD (private L2) owns a contiguous run of tiles.
 #include "gemm_nt_common.h"
-#include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -1232,34 +1232,23 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNtArgs p, int ntile
   }
 }
 
+// ---- host side: the leaf launchers (one kernel each), the plan (pure), the executor, the entry points ----
 template <int ACT>
-int launch_pp_act(const GemmNtArgs& a, hipStream_t stream) {
+int launch_pp_act(const GemmNtArgs& a, int ncu, hipStream_t stream) {
   constexpr int LDS = (256 + 256) * 128 + 8 * 64 * 144;
-  static DevOnce attr_set;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
+  if (set_dyn_lds<gemm_nt_pp_kernel<ACT>>(LDS)) return LC2IS_ERR_LAUNCH;
   const int ntiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  const int grid = ntiles < lc2is_ncu() ? ntiles : lc2is_ncu();   // one block per CU of the budget (common.h)
+  const int grid = ntiles < ncu ? ntiles : ncu;   // one block per CU of the budget the plan counted its rounds with
   hipLaunchKernelGGL(gemm_nt_pp_kernel<ACT>, dim3(grid), dim3(512), LDS, stream, a, ntiles);
   return lc2is_check_launch();
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_cfg(const GemmNtArgs& a, hipStream_t stream, int batch = 1) {
-  constexpr int NT = WAVES_M * WAVES_N * 64;
-  constexpr int LDS = 2 * (BM + BN) * 128;
-  auto kern = gemm_nt_kernel<BM, BN, WAVES_M, WAVES_N>;
-  static DevOnce attr_set;  // idempotent; a race only repeats the same call
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
+  constexpr int NT = WAVES_M * WAVES_N * 64, LDS = 2 * (BM + BN) * 128;
+  if (set_dyn_lds<gemm_nt_kernel<BM, BN, WAVES_M, WAVES_N>>(LDS)) return LC2IS_ERR_LAUNCH;
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(ntm * ntn, batch), dim3(NT), LDS, stream, a);
+  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WAVES_M, WAVES_N>), dim3(ntm * ntn, batch), dim3(NT), LDS, stream, a);
   return lc2is_check_launch();
 }
 
@@ -1268,15 +1257,9 @@ int launch_dma(const GemmNtArgs& a, hipStream_t stream) {
   constexpr int NT = WAVES_M * WAVES_N * 64;
   constexpr int STAGES = 2 * (BM + BN) * 128, PATCHES = EPI == -2 ? WAVES_M * WAVES_N * 64 * 272 : 0;   // fp32 epilogue patches overlay the stages
   constexpr int LDS = STAGES > PATCHES ? STAGES : PATCHES;
-  auto kern = gemm_nt_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI>;
-  static DevOnce attr_set;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
+  if (set_dyn_lds<gemm_nt_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI>>(LDS)) return LC2IS_ERR_LAUNCH;
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(NT), LDS, stream, a);
+  hipLaunchKernelGGL((gemm_nt_dma_kernel<BM, BN, WAVES_M, WAVES_N, EPI>), dim3(ntm * ntn), dim3(NT), LDS, stream, a);
   return lc2is_check_launch();
 }
 
@@ -1296,25 +1279,12 @@ bool w384_bf16_ok(const GemmNtArgs& a) {
 template <int EPI>
 int launch_w384_epi(const GemmNtArgs& a, hipStream_t stream) {
   constexpr int LDS = 2 * (256 + 384) * 128;   // 160 KiB: the whole CU
-  auto kern = gemm_nt_w384_kernel<EPI>;
-  static DevOnce attr_set;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
-  hipLaunchKernelGGL(kern, dim3(((a.M + 255) / 256) * (a.N / 384)), dim3(512), LDS, stream, a);
+  if (set_dyn_lds<gemm_nt_w384_kernel<EPI>>(LDS)) return LC2IS_ERR_LAUNCH;
+  hipLaunchKernelGGL(gemm_nt_w384_kernel<EPI>, dim3(((a.M + 255) / 256) * (a.N / 384)), dim3(512), LDS, stream, a);
   return lc2is_check_launch();
 }
 
-int launch_w384(const GemmNtArgs& a, hipStream_t stream) {
-  if (w384_f32_ok(a)) return launch_w384_epi<-2>(a, stream);
-  if (w384_bf16_ok(a)) return a.act == LC2IS_ACT_ADD_AUX ? launch_w384_epi<1>(a, stream) : launch_w384_epi<0>(a, stream);
-  return LC2IS_ERR_UNSUPPORTED;
-}
-
 int launch_rows(const GemmNtArgs& a, hipStream_t stream) {
-  if (a.M > 64 || a.N % 4) return LC2IS_ERR_UNSUPPORTED;
   if (a.K >= 2048) hipLaunchKernelGGL(gemm_nt_rows_kernel<28>, dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(64), 0, stream, a);   // long K: 56 loads in flight per wave (the 6-bit vmcnt allows 63)
   else hipLaunchKernelGGL(gemm_nt_rows_kernel<16>, dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(64), 0, stream, a);
   return lc2is_check_launch();
@@ -1327,57 +1297,180 @@ bool persist2_ok(const GemmNtArgs& a) {
          (!a.aux_out || (double)a.M * a.ldy * 2.0 < lim) && (!a.aux_in || (double)a.M * a.ldx * 2.0 < lim);
 }
 
-int launch_pp(const GemmNtArgs& a, hipStream_t stream) {
-  if (!persist2_ok(a)) return LC2IS_ERR_UNSUPPORTED;
-  switch (a.act) {
-    case LC2IS_ACT_QUICK_GELU: return launch_pp_act<LC2IS_ACT_QUICK_GELU>(a, stream);
-    case LC2IS_ACT_DQUICK_GELU: return launch_pp_act<LC2IS_ACT_DQUICK_GELU>(a, stream);
-    case LC2IS_ACT_NONE: return launch_pp_act<LC2IS_ACT_NONE>(a, stream);
-    case LC2IS_ACT_ADD_AUX: return launch_pp_act<LC2IS_ACT_ADD_AUX>(a, stream);
-    case LC2IS_ACT_RELU: return launch_pp_act<LC2IS_ACT_RELU>(a, stream);     // (round 5: the decoders' linear1 / its dgrad at >= 2 rounds of tiles)
-    case LC2IS_ACT_DRELU: return launch_pp_act<LC2IS_ACT_DRELU>(a, stream);
-    default: return LC2IS_ERR_UNSUPPORTED;
-  }
+// The one activation dispatch: f(integral_constant<ACT>) for the run-time code `act` if the list names it (rc = its result), else
+// false.  A list IS the set of instantiations of its kernel; what it leaves out falls through at the call site.
+template <int... ACTS> struct ActList {};
+template <int... ACTS> constexpr bool act_in(int act, ActList<ACTS...>) { return ((act == ACTS) || ...); }
+template <class F, int... ACTS> bool for_act(int act, ActList<ACTS...>, int& rc, F&& f) {
+  return ((act == ACTS && (rc = f(std::integral_constant<int, ACTS>{}), true)) || ...);
+}
+using PpActs = ActList<LC2IS_ACT_NONE, LC2IS_ACT_QUICK_GELU, LC2IS_ACT_DQUICK_GELU, LC2IS_ACT_ADD_AUX,
+                       LC2IS_ACT_RELU, LC2IS_ACT_DRELU>;   // (round 5: relu, the decoders' linear1 / its dgrad at >= 2 rounds of tiles)
+using Dma256Acts = ActList<LC2IS_ACT_NONE, LC2IS_ACT_QUICK_GELU, LC2IS_ACT_RELU, LC2IS_ACT_DQUICK_GELU, LC2IS_ACT_DRELU,
+                           LC2IS_ACT_GELU_ERF, LC2IS_ACT_DGELU_ERF, LC2IS_ACT_ADD_AUX>;
+using Dma128Acts = ActList<LC2IS_ACT_NONE, LC2IS_ACT_RELU, LC2IS_ACT_DRELU, LC2IS_ACT_GELU_ERF, LC2IS_ACT_DGELU_ERF,
+                           LC2IS_ACT_ADD_AUX>;   // the activations of the Swin / hierarchical-decoder GEMMs that land on this tile size
+
+// does the kernel behind `cfg` take this (sub-)problem?  (the header lists the codes; 1-4 and 6 take everything)
+bool cfg_takes(const GemmNtArgs& a, int cfg) {
+  if (cfg == 15) return persist2_ok(a) && act_in(a.act, PpActs{});
+  if (cfg == 16) return w384_f32_ok(a) || w384_bf16_ok(a);
+  if (cfg == 17) return a.M <= 64 && a.N % 4 == 0;
+  return (cfg >= 1 && cfg <= 4) || cfg == 6;
 }
 
-int launch_by_cfg(const GemmNtArgs& a_in, int cfg, hipStream_t stream) {
+int launch_by_cfg(const GemmNtArgs& a_in, int cfg, int ncu, hipStream_t stream) {
+  if (!cfg_takes(a_in, cfg)) return LC2IS_ERR_UNSUPPORTED;
   GemmNtArgs a = a_in;
   const bool f32_staged = a.staged_epi == 2;
   if (f32_staged) a.staged_epi = 0;
+  int rc = LC2IS_ERR_UNSUPPORTED;
   switch (cfg) {
     case 1: return launch_cfg<128, 128, 2, 2>(a, stream);
     case 2: return launch_cfg<256, 128, 4, 2>(a, stream);
     case 3: return launch_cfg<64, 64, 2, 2>(a, stream);
     case 4:
       if (f32_staged) return launch_dma<256, 256, 2, 4, -2>(a, stream);
-      switch (a.act) {
-        case LC2IS_ACT_QUICK_GELU: return launch_dma<256, 256, 2, 4, LC2IS_ACT_QUICK_GELU>(a, stream);
-        case LC2IS_ACT_RELU: return launch_dma<256, 256, 2, 4, LC2IS_ACT_RELU>(a, stream);
-        case LC2IS_ACT_DQUICK_GELU: return launch_dma<256, 256, 2, 4, LC2IS_ACT_DQUICK_GELU>(a, stream);
-        case LC2IS_ACT_DRELU: return launch_dma<256, 256, 2, 4, LC2IS_ACT_DRELU>(a, stream);
-        case LC2IS_ACT_GELU_ERF: return launch_dma<256, 256, 2, 4, LC2IS_ACT_GELU_ERF>(a, stream);
-        case LC2IS_ACT_DGELU_ERF: return launch_dma<256, 256, 2, 4, LC2IS_ACT_DGELU_ERF>(a, stream);
-        case LC2IS_ACT_NONE: return launch_dma<256, 256, 2, 4, LC2IS_ACT_NONE>(a, stream);
-        case LC2IS_ACT_ADD_AUX: return launch_dma<256, 256, 2, 4, LC2IS_ACT_ADD_AUX>(a, stream);
-        default: return launch_dma<128, 128, 2, 2>(a, stream);   // codes 5 / 6 (the save-the-derivative experiment): the 128x128 kernel's run-time switch
-                                                                 // (the 256x256 instantiation of it spilled 128 bytes and left the library in round 5)
-      }
+      if (for_act(a.act, Dma256Acts{}, rc, [&](auto act) { return launch_dma<256, 256, 2, 4, decltype(act)::value>(a, stream); })) return rc;
+      return launch_dma<128, 128, 2, 2>(a, stream);   // codes 5 / 6 (the save-the-derivative experiment): the 128x128 kernel's run-time switch
+                                                      // (the 256x256 instantiation of it spilled 128 bytes and left the library in round 5)
     case 6:
       if (f32_staged) return launch_dma<128, 128, 2, 2, -2>(a, stream);
-      switch (a.act) {   // the activations of the Swin / hierarchical-decoder GEMMs that land on this tile size
-        case LC2IS_ACT_RELU: return launch_dma<128, 128, 2, 2, LC2IS_ACT_RELU>(a, stream);
-        case LC2IS_ACT_DRELU: return launch_dma<128, 128, 2, 2, LC2IS_ACT_DRELU>(a, stream);
-        case LC2IS_ACT_GELU_ERF: return launch_dma<128, 128, 2, 2, LC2IS_ACT_GELU_ERF>(a, stream);
-        case LC2IS_ACT_DGELU_ERF: return launch_dma<128, 128, 2, 2, LC2IS_ACT_DGELU_ERF>(a, stream);
-        case LC2IS_ACT_NONE: return launch_dma<128, 128, 2, 2, LC2IS_ACT_NONE>(a, stream);
-        case LC2IS_ACT_ADD_AUX: return launch_dma<128, 128, 2, 2, LC2IS_ACT_ADD_AUX>(a, stream);
-        default: return launch_dma<128, 128, 2, 2>(a, stream);
-      }
-    case 15: return launch_pp(a, stream);
-    case 16: return launch_w384(a, stream);
-    case 17: return launch_rows(a, stream);
-    default: return LC2IS_ERR_UNSUPPORTED;
+      if (for_act(a.act, Dma128Acts{}, rc, [&](auto act) { return launch_dma<128, 128, 2, 2, decltype(act)::value>(a, stream); })) return rc;
+      return launch_dma<128, 128, 2, 2>(a, stream);
+    case 15:
+      for_act(a.act, PpActs{}, rc, [&](auto act) { return launch_pp_act<decltype(act)::value>(a, ncu, stream); });
+      return rc;
+    case 16:
+      if (w384_f32_ok(a)) return launch_w384_epi<-2>(a, stream);
+      return a.act == LC2IS_ACT_ADD_AUX ? launch_w384_epi<1>(a, stream) : launch_w384_epi<0>(a, stream);
+    default: return launch_rows(a, stream);   // 17
   }
+}
+
+// ---- the plan ------------------------------------------------------------------------------------------------------------------
+// Thresholds of the automatic plan (A/B verdicts: DESIGN §6; to A/B a change, build a second library and compare through
+// tile_cfg= and LC2IS_LIB=).
+constexpr int kTailCfg = 17;            // ragged-row tails (<= 64 rows) of the exact-round plans: the one-wave-per-fragment kernel
+constexpr int kTailMaxRows = 64;
+constexpr long kCfg1MinTiles128 = 128;  // below: small problem, 64x64 tiles to fill the chip
+constexpr long kCfg6MinTiles128 = 128;  // 128x128 LDS-DMA tiles, 2 blocks/CU (512 and the register-staged 128x128 kernel below it measured 0.8 % slower on config 5)
+// The large-tile (256-row) family takes a problem from about one round of 256x256 tiles on: >= 1024 tiles of 128x128, or (round 5)
+// >= 7/8 of a round of 256x256 tiles — ViT-L/14 at B = 8 (M = 16 208, N = 1024: 127 x 8 = 1016 small tiles, 64 x 4 = 256 large ones,
+// exactly ONE round) sat a hair under the first rule and ran its N = 1024 GEMMs on 128x128 tiles at 379 TF/s (profiles/r05_config4_*).
+constexpr long kBigMinTiles128 = 1024, kBigMinTiles256 = 224;
+// cfg 16 (256x384 tiles) for bf16-only output without activation (dqkv, dfc1, dout_proj): taken where it saves >= 8 % of the tile
+// time, a 256x384 tile costing 1.5 tiles of 256x256 (qkv, N = 2304: 3 rounds of 384 = 4.5 against 5 tile times: 117 vs 123 us)
+constexpr double kW384TileCost = 1.5, kW384MinGain = 0.92;
+constexpr long kPersistMinTiles = 257;  // the persistent form: more than one round of tiles (A/B 512 -> 257: 907 -> 915 img/s)
+constexpr double kSplitLaunchCost = 65536.0 * 0.3 * 768.0;   // / K: ~8 us for the extra launch of a separate tail, in tile-area units
+constexpr double kSplitTieBreak = 1.03;                      // prefer the plain plan on near-ties
+
+// n records; ncu = the CU count the rounds were counted with (the persistent kernel's grid)
+struct GemmNtPlan { int n, ncu; lc2is_gemm_nt_launch rec[2]; };
+
+// Pure: the whole decision, from the (validated) problem, the caller's tile_cfg and ONE reading of the CU budget.
+GemmNtPlan gemm_nt_plan(const GemmNtArgs& a, int tile_cfg, int ncu) {
+  const int M = a.M, N = a.N, act = a.act, r = M % 256;
+  GemmNtPlan p{0, ncu, {}};
+  auto rounds = [ncu](long blocks) { return (blocks + ncu - 1) / ncu; };
+  // `cfg` over rows [0, mm); rows [mm, M) folded into that launch (fragment jobs after each block's last tile) or as the tail launch
+  auto emit = [&](int cfg, int mm, bool fold) {
+    p.rec[p.n++] = {cfg, 0, mm, fold ? M - mm : 0, a.staged_epi};
+    if (mm < M && !fold) p.rec[p.n++] = {kTailCfg, mm, M - mm, 0, a.staged_epi};
+    return p;
+  };
+  if (tile_cfg != 0) return emit(tile_cfg, M, false);
+  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128), tiles256 = (long)((M + 255) / 256) * (N / 256);
+  if (!((tiles128 >= kBigMinTiles128 || tiles256 >= kBigMinTiles256) && N % 256 == 0))
+    return emit(tiles128 >= kCfg6MinTiles128 ? 6 : tiles128 >= kCfg1MinTiles128 ? 1 : 3, M, false);
+  const bool can_peel = r > 0 && r <= kTailMaxRows && M > 256;   // B x 1025 tokens: 32 ragged rows
+  const int whole = can_peel ? M - r : M;
+  if (w384_bf16_ok(a)) {
+    const long t384 = (long)((whole + 255) / 256) * (N / 384), t256 = (long)((whole + 255) / 256) * (N / 256);
+    if ((double)rounds(t384) * kW384TileCost < kW384MinGain * (double)rounds(t256)) return emit(16, whole, true);
+  }
+  // bf16-output problems of >= 2 rounds of tiles: the persistent form with counted waits across the tile seam (cfg 15, the wave
+  // groups in ping-pong; round 4: 966 -> 975 img/s against the lockstep form, now tools/probes/gemm_nt_persist2/): -4..10 % on the
+  // K = 768 shapes.  One block per CU walks tiles t, t + ncu, ...: the launch lasts ceil(tiles / ncu) tile times.  The ragged rows
+  // (one more row of N / 256 tiles) are peeled off when that saves a whole tile time: fc1 / dfc2 at M = 32 800 walk 1548 tiles =
+  // 6 rounds + 12 tiles, 1536 = exactly 6 without the 32 rows.  Peeled rows are folded into the launch, except behind the
+  // derivative epilogues (see gemm_nt_pp_kernel), which keep the tail launch.
+  if (persist2_ok(a) && tiles256 >= kPersistMinTiles && act_in(act, PpActs{})) {
+    if (!(can_peel && rounds((long)(whole / 256) * (N / 256)) < rounds(tiles256))) return emit(15, M, false);
+    return emit(15, whole, act != LC2IS_ACT_DQUICK_GELU && act != LC2IS_ACT_DRELU);
+  }
+  // Plenty of work: 256x256 LDS-DMA tiles (or 256x384 for fp32-only output; the bf16 form is chosen above), one block per CU, so
+  // time = rounds x tile area; the ragged rows are peeled off when that saves a whole round of tiles.
+  int best_cfg = 4, best_main = M;
+  double best_cost = 1e300;
+  for (int split = 0; split <= (can_peel ? 1 : 0); ++split)
+    for (int c : {4, 16}) {   // (128x384 measured ~45 % slower per flop and left the library)
+      const int bn = c == 16 ? 384 : 256, mm = split ? whole : M;
+      if (c == 16 && !(a.staged_epi == 2 && w384_f32_ok(a))) continue;
+      double cost = (double)rounds((long)((mm + 255) / 256) * (N / bn)) * 256 * bn;
+      if (split) cost = (cost + kSplitLaunchCost / a.K) * kSplitTieBreak;
+      if (cost < best_cost) { best_cost = cost; best_cfg = c; best_main = mm; }
+    }
+  return emit(best_cfg, best_main, best_cfg == 16);
+}
+
+// ---- the executor --------------------------------------------------------------------------------------------------------------
+// rows [row0, row0 + rows) of a problem: EVERY operand and output that is there moves by its own leading dimension
+GemmNtArgs rows_from(const GemmNtArgs& a, int row0, int rows) {
+  GemmNtArgs s = a;
+  const size_t r0 = (size_t)row0;
+  s.M = rows;
+  s.A += r0 * a.lda;
+  if (s.resid) s.resid += r0 * a.ldr;
+  if (s.aux_in) s.aux_in += r0 * a.ldx;
+  if (s.out_bf16) s.out_bf16 += r0 * a.ldo;
+  if (s.out_f32) s.out_f32 += r0 * a.ldf;
+  if (s.aux_out) s.aux_out += r0 * a.ldy;
+  return s;
+}
+
+int run_plan(const GemmNtArgs& a, const GemmNtPlan& p, hipStream_t stream) {
+  for (int i = 0; i < p.n; ++i) {
+    GemmNtArgs s = rows_from(a, p.rec[i].row0, p.rec[i].rows);
+    s.tail_rows = p.rec[i].tail_rows;
+    if (int rc = launch_by_cfg(s, p.rec[i].cfg, p.ncu, stream)) return rc;
+  }
+  return LC2IS_OK;
+}
+
+// ---- validation ----------------------------------------------------------------------------------------------------------------
+// What the three entry points ask of A and W (each reports the two codes at their places in its own refusal order).  SHAPE: K in
+// whole 64-column tiles, rows of >= K elements on 16-byte boundaries.  UNSUPPORTED: 32-bit buffer offsets, the operand panels
+// (plus one tile of overhang) must stay under 2 GiB.
+int operand_check(int M, int N, int K, int lda, int ldw) {
+  if (K % 64 != 0 || lda < K || ldw < K || lda % 8 || ldw % 8) return LC2IS_ERR_SHAPE;
+  if ((double)(M + 256) * lda * 2.0 >= 2147483648.0 || (double)(N + 256) * ldw * 2.0 >= 2147483648.0) return LC2IS_ERR_UNSUPPORTED;
+  return LC2IS_OK;
+}
+
+// lc2is_gemm_nt_bf16's refusals, shared by the launcher and the plan query (no pointer is dereferenced); sets a.staged_epi
+int gemm_nt_check(GemmNtArgs& a) {
+  const int M = a.M, N = a.N, act = a.act;
+  if (!a.A || !a.W || (!a.out_bf16 && !a.out_f32)) return LC2IS_ERR_NULL;
+  if (M <= 0 || N <= 0 || a.K <= 0 || N % 4 != 0) return LC2IS_ERR_SHAPE;
+  const int oc = operand_check(M, N, a.K, a.lda, a.ldw);
+  if (oc == LC2IS_ERR_SHAPE) return oc;
+  if ((a.out_bf16 && (a.ldo < N || a.ldo % 4)) || (a.out_f32 && (a.ldf < N || a.ldf % 4)) || (a.resid && (a.ldr < N || a.ldr % 4)) ||
+      (a.aux_in && (a.ldx < N || a.ldx % 4)) || (a.aux_out && (a.ldy < N || a.ldy % 4)))
+    return LC2IS_ERR_SHAPE;
+  if ((act == LC2IS_ACT_DQUICK_GELU || act == LC2IS_ACT_DRELU || act == LC2IS_ACT_MUL_AUX || act == LC2IS_ACT_DGELU_ERF ||
+       act == LC2IS_ACT_ADD_AUX) && !a.aux_in)
+    return LC2IS_ERR_NULL;
+  if (act < LC2IS_ACT_NONE || act > LC2IS_ACT_ADD_AUX) return LC2IS_ERR_UNSUPPORTED;
+  if (oc) return oc;
+  a.staged_epi = (N % 8 == 0) && (!a.out_bf16 || a.ldo % 8 == 0) && (!a.aux_out || a.ldy % 8 == 0) &&
+                 (!a.aux_in || a.ldx % 8 == 0) && (a.out_bf16 || a.aux_out || a.aux_in);
+  // fp32-only output leaves through LDS as well (whole-line stores instead of the MFMA layout's half lines)
+  if (a.out_f32 && !a.out_bf16 && !a.aux_out && !a.aux_in && act == LC2IS_ACT_NONE &&
+      (double)M * a.ldf * 4.0 < 2147483648.0 && (!a.resid || (double)M * a.ldr * 4.0 < 2147483648.0))
+    a.staged_epi = 2;
+  return LC2IS_OK;
 }
 
 }  // namespace
@@ -1386,133 +1479,33 @@ extern "C" int lc2is_gemm_nt_bf16(const void* A, int lda, const void* W, int ldw
                                   const float* resid, int ldr, const void* aux_in, int ldx, void* out_bf16,
                                   int ldo, float* out_f32, int ldf, void* aux_out, int ldy, int M, int N,
                                   int K, int act, int tile_cfg, lc2is_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!A || !W) return LC2IS_ERR_NULL;
-  if (!out_bf16 && !out_f32) return LC2IS_ERR_NULL;
-  if (M <= 0 || N <= 0 || K <= 0) return LC2IS_ERR_SHAPE;
-  if (K % 64 != 0 || N % 4 != 0) return LC2IS_ERR_SHAPE;
-  if (lda < K || ldw < K || lda % 8 || ldw % 8) return LC2IS_ERR_SHAPE;
-  if ((out_bf16 && (ldo < N || ldo % 4)) || (out_f32 && (ldf < N || ldf % 4)) || (resid && (ldr < N || ldr % 4)) ||
-      (aux_in && (ldx < N || ldx % 4)) || (aux_out && (ldy < N || ldy % 4)))
-    return LC2IS_ERR_SHAPE;
-  if ((act == LC2IS_ACT_DQUICK_GELU || act == LC2IS_ACT_DRELU || act == LC2IS_ACT_MUL_AUX || act == LC2IS_ACT_DGELU_ERF ||
-       act == LC2IS_ACT_ADD_AUX) && !aux_in)
-    return LC2IS_ERR_NULL;
-  if (act < LC2IS_ACT_NONE || act > LC2IS_ACT_ADD_AUX) return LC2IS_ERR_UNSUPPORTED;
-  // 32-bit buffer offsets: operand panels (plus one tile of overhang) must stay under 2 GiB
-  if ((double)(M + 256) * lda * 2.0 >= 2147483648.0 || (double)(N + 256) * ldw * 2.0 >= 2147483648.0)
-    return LC2IS_ERR_UNSUPPORTED;
   GemmNtArgs a{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, resid, ldr, (const bf16_t*)aux_in, ldx,
                (bf16_t*)out_bf16, ldo, out_f32, ldf, (bf16_t*)aux_out, ldy, M, N, K, act, 0};
-  a.staged_epi = (N % 8 == 0) && (!out_bf16 || ldo % 8 == 0) && (!aux_out || ldy % 8 == 0) &&
-                 (!aux_in || ldx % 8 == 0) && (out_bf16 || aux_out || aux_in);
-  static const bool f32_lds = !(getenv("LC2IS_F32_STAGED") && atoi(getenv("LC2IS_F32_STAGED")) == 0);
-  if (f32_lds && out_f32 && !out_bf16 && !aux_out && !aux_in && act == LC2IS_ACT_NONE &&
-      (double)M * ldf * 4.0 < 2147483648.0 && (!resid || (double)M * ldr * 4.0 < 2147483648.0))
-    a.staged_epi = 2;
-  int cfg = tile_cfg;
-  if (cfg != 0) return launch_by_cfg(a, cfg, stream);
-  // ragged-row tails (<= 64 rows) of the exact-round plans: the one-wave-per-fragment kernel (cfg 17); LC2IS_GEMM_ROWS_TAIL=0: 64x64 tiles
-  static const int tail_cfg = (getenv("LC2IS_GEMM_ROWS_TAIL") && atoi(getenv("LC2IS_GEMM_ROWS_TAIL")) == 0) ? 3 : 17;
-  // ... and behind a 256x384 launch they are folded into it (fragment jobs after each block's own tile); LC2IS_GEMM_TAIL_FOLD=0: separate launch
-  static const bool fold_tail = tail_cfg == 17 && !(getenv("LC2IS_GEMM_TAIL_FOLD") && atoi(getenv("LC2IS_GEMM_TAIL_FOLD")) == 0);
-  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  static const long cfg6_min = getenv("LC2IS_GEMM_CFG6_MIN") ? atol(getenv("LC2IS_GEMM_CFG6_MIN")) : 128;   // (512 and the register-staged 128x128 kernel below it measured 0.8 % slower on config 5)
-  // The large-tile (256-row) family takes a problem from about one round of 256x256 tiles on: >= 1024 tiles of 128x128, or (round 5)
-  // >= 7/8 of a round of 256x256 tiles — ViT-L/14 at B = 8 (M = 16 208, N = 1024: 127 x 8 = 1016 small tiles, 64 x 4 = 256 large ones,
-  // exactly ONE round) sat a hair under the first rule and ran its N = 1024 GEMMs on 128x128 tiles at 379 TF/s (profiles/r05_config4_*).
-  static const long big_min256 = getenv("LC2IS_GEMM_BIG_MIN256") ? atol(getenv("LC2IS_GEMM_BIG_MIN256")) : 224;
-  const long tiles256 = (long)((M + 255) / 256) * (N / 256);
-  if (!((tiles128 >= 1024 || tiles256 >= big_min256) && N % 256 == 0)) {
-    if (tiles128 >= cfg6_min) cfg = 6;              // 128x128 LDS-DMA tiles, 2 blocks/CU
-    else if (tiles128 >= 128) cfg = 1;
-    else cfg = 3;                                        // small problem: 64x64 tiles to fill the chip
-    return launch_by_cfg(a, cfg, stream);
+  if (int rc = gemm_nt_check(a)) return rc;
+  return run_plan(a, gemm_nt_plan(a, tile_cfg, lc2is_ncu()), (hipStream_t)stream_);   // ONE read of the CU budget
+}
+
+// The plan lc2is_gemm_nt_bf16 would run for these arguments under the present CU budget, without launching: the launcher's own
+// refusals, then its records (at most `cap` of them are written) with the byte offsets rows_from() gives each launch's pointers.
+extern "C" int lc2is_gemm_nt_plan(const void* A, int lda, const void* W, int ldw, const float* bias, const float* resid, int ldr,
+                                  const void* aux_in, int ldx, void* out_bf16, int ldo, float* out_f32, int ldf, void* aux_out,
+                                  int ldy, int M, int N, int K, int act, int tile_cfg, lc2is_gemm_nt_launch* out, int cap) {
+  GemmNtArgs a{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, resid, ldr, (const bf16_t*)aux_in, ldx,
+               (bf16_t*)out_bf16, ldo, out_f32, ldf, (bf16_t*)aux_out, ldy, M, N, K, act, 0};
+  if (int rc = gemm_nt_check(a)) return rc;
+  if (!out && cap > 0) return LC2IS_ERR_NULL;
+  const GemmNtPlan p = gemm_nt_plan(a, tile_cfg, lc2is_ncu());
+  for (int i = 0; i < p.n; ++i) {
+    const GemmNtArgs s = rows_from(a, p.rec[i].row0, p.rec[i].rows);
+    if (!cfg_takes(s, p.rec[i].cfg)) return LC2IS_ERR_UNSUPPORTED;
+    if (i >= cap) continue;
+    auto bytes = [](const void* sub, const void* whole) { return (long long)((const char*)sub - (const char*)whole); };
+    out[i] = p.rec[i];
+    out[i].off_a = bytes(s.A, a.A);                    out[i].off_resid = bytes(s.resid, a.resid);
+    out[i].off_aux_in = bytes(s.aux_in, a.aux_in);     out[i].off_out_bf16 = bytes(s.out_bf16, a.out_bf16);
+    out[i].off_out_f32 = bytes(s.out_f32, a.out_f32);  out[i].off_aux_out = bytes(s.aux_out, a.aux_out);
   }
-  // cfg 16 (256x384 tiles): N = 768 at M = 128 x 256 is exactly one round instead of 1.5 (LC2IS_GEMM_W384=0: off)
-  static const bool use_w384 = !(getenv("LC2IS_GEMM_W384") && atoi(getenv("LC2IS_GEMM_W384")) == 0);
-  static const bool use_w384_bf16 = !(getenv("LC2IS_GEMM_W384_BF16") && atoi(getenv("LC2IS_GEMM_W384_BF16")) == 0);
-  if (use_w384 && use_w384_bf16 && w384_bf16_ok(a)) {   // bf16-only, no activation (dqkv, dfc1, dout_proj): take it where it saves >= 8 % of the tile time
-    const int r = M % 256;
-    const bool can_peel = r > 0 && r <= 64 && M > 256;
-    const int mm = can_peel ? M - r : M;
-    const long t384 = (long)((mm + 255) / 256) * (N / 384), t256 = (long)((mm + 255) / 256) * (N / 256);
-    if ((double)lc2is_rounds(t384) * 1.5 < 0.92 * (double)lc2is_rounds(t256)) {   // (qkv, N = 2304: 3 rounds of 384 = 4.5 against 5 tile times: 117 vs 123 us)
-      GemmNtArgs main_part = a, tail = a;
-      main_part.M = mm;
-      if (fold_tail) main_part.tail_rows = M - mm;   // the ragged rows ride in the same launch (rows M .. follow in the same buffers)
-      int rc = launch_by_cfg(main_part, 16, stream);
-      if (rc || mm == M || fold_tail) return rc;
-      tail.M = M - mm;
-      tail.A = a.A + (size_t)mm * lda;
-      tail.out_bf16 = a.out_bf16 + (size_t)mm * ldo;
-      if (a.aux_in) tail.aux_in = a.aux_in + (size_t)mm * ldx;
-      return launch_by_cfg(tail, tail_cfg, stream);
-    }
-  }
-  // bf16-output problems of >= 2 rounds of tiles: the persistent form with counted waits across the tile seam (cfg 13; ragged
-  // rows stay in the launch — its blocks walk the tiles, there is no round to save): -4..10 % on the K = 768 shapes
-  static const bool use_persist = !(getenv("LC2IS_GEMM_PERSIST") && atoi(getenv("LC2IS_GEMM_PERSIST")) == 0);
-  static const long persist_min = getenv("LC2IS_GEMM_PERSIST_MIN") ? atol(getenv("LC2IS_GEMM_PERSIST_MIN")) : 257;   // more than one round of tiles (A/B 512 -> 257: 907 -> 915 img/s)
-  if (use_persist && persist2_ok(a) && (long)((M + 255) / 256) * (N / 256) >= persist_min &&
-      (act == LC2IS_ACT_NONE || act == LC2IS_ACT_QUICK_GELU || act == LC2IS_ACT_DQUICK_GELU || act == LC2IS_ACT_ADD_AUX ||
-       act == LC2IS_ACT_RELU || act == LC2IS_ACT_DRELU)) {
-    // One block per CU walks tiles t, t + 256, ...: the launch lasts ceil(tiles / 256) tile times.  The ragged last <= 64 rows
-    // (B x 1025 tokens: 32 rows, i.e. one more row of N / 256 tiles) are peeled off into a small-tile launch when that saves a
-    // whole tile time: fc1 / dfc2 at M = 32 800 walk 1548 tiles = 6 rounds + 12 tiles, 1536 = exactly 6 without the 32 rows.
-    static const bool peel = !(getenv("LC2IS_GEMM_PERSIST_PEEL") && atoi(getenv("LC2IS_GEMM_PERSIST_PEEL")) == 0);
-    constexpr int pcfg = 15;   // the wave groups in ping-pong (round 4: 966 -> 975 img/s against cfg 13, the lockstep persistent form — now tools/probes/gemm_nt_persist2/)
-    const int r = M % 256;
-    const long tiles_all = (long)((M + 255) / 256) * (N / 256), tiles_main = (long)(M / 256) * (N / 256);
-    if (peel && r > 0 && r <= 64 && M > 256 && lc2is_rounds(tiles_main) < lc2is_rounds(tiles_all)) {
-      GemmNtArgs main_part = a, tail = a;
-      main_part.M = M - r;
-      if (fold_tail && pcfg == 15 && N % 16 == 0 && act != LC2IS_ACT_DQUICK_GELU && act != LC2IS_ACT_DRELU) main_part.tail_rows = r;
-      int rc = launch_by_cfg(main_part, pcfg, stream);
-      if (rc || main_part.tail_rows) return rc;
-      const size_t m0 = (size_t)(M - r);
-      tail.M = r;
-      tail.A = a.A + m0 * lda;
-      if (a.aux_in) tail.aux_in = a.aux_in + m0 * ldx;
-      if (a.out_bf16) tail.out_bf16 = a.out_bf16 + m0 * ldo;
-      if (a.aux_out) tail.aux_out = a.aux_out + m0 * ldy;
-      return launch_by_cfg(tail, tail_cfg, stream);
-    }
-    return launch_by_cfg(a, pcfg, stream);
-  }
-  // Plenty of work: 256x256 LDS-DMA tiles, one block per CU, so time = rounds x tile cost; the ragged last <= 64 rows
-  // (B x 1025 tokens: 32 rows) are peeled off into a small-tile launch when that saves a whole round of tiles.
-  int best_cfg = 0, best_main = M;
-  double best_cost = 1e300;
-  for (int split = 0; split < 2; ++split)
-    for (int c : {4, 16}) {   // (128x384 measured ~45 % slower per flop and left the library)
-      const int bm = 256, bn = c == 16 ? 384 : 256;
-      if (c == 16 && !(use_w384 && a.staged_epi == 2 && w384_f32_ok(a))) continue;   // (fp32-only output here; the bf16 form is chosen above)
-      if (N % bn) continue;
-      const int r = M % bm;
-      if (split && (r == 0 || r > 64 || M <= bm)) continue;
-      const int mm = split ? M - r : M;
-      const long tiles = (long)((mm + bm - 1) / bm) * (N / bn);
-      double cost = (double)lc2is_rounds(tiles) * bm * bn;
-      if (split) cost += 65536.0 * 0.3 * 768.0 / K;                                      // ~8 us for the extra launch
-      if (split) cost *= 1.03;                                                            // prefer the plain plan on near-ties
-      if (cost < best_cost) { best_cost = cost; best_cfg = c; best_main = mm; }
-    }
-  if (best_main == M) return launch_by_cfg(a, best_cfg, stream);
-  GemmNtArgs main_part = a, tail = a;
-  main_part.M = best_main;
-  if (best_cfg == 16 && fold_tail) main_part.tail_rows = M - best_main;
-  int rc = launch_by_cfg(main_part, best_cfg, stream);
-  if (rc || main_part.tail_rows) return rc;
-  const size_t m0 = (size_t)best_main;
-  tail.M = M - best_main;
-  tail.A = a.A + m0 * lda;
-  if (a.resid) tail.resid = a.resid + m0 * ldr;
-  if (a.aux_in) tail.aux_in = a.aux_in + m0 * ldx;
-  if (a.out_bf16) tail.out_bf16 = a.out_bf16 + m0 * ldo;
-  if (a.out_f32) tail.out_f32 = a.out_f32 + m0 * ldf;
-  if (a.aux_out) tail.aux_out = a.aux_out + m0 * ldy;
-  return launch_by_cfg(tail, tail_cfg, stream);
+  return p.n;
 }
 
 // out_f32 = A.W^T + bias (+ resid) AND ln_out = bf16(LayerNorm(out_f32) * gamma + beta) (+ mean / rstd) in ONE launch of the
@@ -1528,13 +1521,12 @@ extern "C" int lc2is_gemm_nt_ln_bf16(const void* A, int lda, const void* W, int 
   hipStream_t stream = (hipStream_t)stream_;
   if (!A || !W || !out_f32 || !ln_out || !gamma) return LC2IS_ERR_NULL;
   if (M <= 0 || N <= 0 || K <= 0) return LC2IS_ERR_SHAPE;
-  if (K % 64 != 0 || lda < K || ldw < K || lda % 8 || ldw % 8) return LC2IS_ERR_SHAPE;
+  const int oc = operand_check(M, N, K, lda, ldw);
+  if (oc == LC2IS_ERR_SHAPE) return oc;
   if (ldf < N || ldf % 4 || (resid && (ldr < N || ldr % 4)) || ldl < N || ldl % 8) return LC2IS_ERR_SHAPE;
-  if (N != 384 && N != 768) return LC2IS_ERR_UNSUPPORTED;
-  if (M < 256) return LC2IS_ERR_UNSUPPORTED;
+  if ((N != 384 && N != 768) || M < 256) return LC2IS_ERR_UNSUPPORTED;
   const double lim = 2147483648.0;
-  if ((double)(M + 256) * lda * 2.0 >= lim || (double)(N + 256) * ldw * 2.0 >= lim || (double)M * ldf * 4.0 >= lim ||
-      (resid && (double)M * ldr * 4.0 >= lim) || (double)M * ldl * 2.0 >= lim)
+  if (oc || (double)M * ldf * 4.0 >= lim || (resid && (double)M * ldr * 4.0 >= lim) || (double)M * ldl * 2.0 >= lim)
     return LC2IS_ERR_UNSUPPORTED;
   if (N == 768 && (!xchg || xchg_bytes < lc2is_gemm_nt_ln_xchg_bytes(M, N) || ((uintptr_t)xchg & 7))) return LC2IS_ERR_WORKSPACE;
   const int r = M % 256;
@@ -1562,15 +1554,13 @@ extern "C" int lc2is_gemm_nt_bf16_batched(const void* A, int lda, long stride_a,
                                           void* out_bf16, int ldo, long stride_ob, float* out_f32, int ldf,
                                           long stride_of, int M, int N, int K, int batch, lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!A || !W) return LC2IS_ERR_NULL;
-  if (!out_bf16 && !out_f32) return LC2IS_ERR_NULL;
+  if (!A || !W || (!out_bf16 && !out_f32)) return LC2IS_ERR_NULL;
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535) return LC2IS_ERR_SHAPE;
-  if (K % 64 != 0 || N % 4 != 0) return LC2IS_ERR_SHAPE;
-  if (lda < K || ldw < K || lda % 8 || ldw % 8 || stride_a % 8 || stride_w % 8) return LC2IS_ERR_SHAPE;
+  const int oc = operand_check(M, N, K, lda, ldw);
+  if (oc == LC2IS_ERR_SHAPE || N % 4 != 0 || stride_a % 8 || stride_w % 8) return LC2IS_ERR_SHAPE;
   if ((out_bf16 && (ldo < N || ldo % 4 || stride_ob % 4)) || (out_f32 && (ldf < N || ldf % 4 || stride_of % 4)))
     return LC2IS_ERR_SHAPE;
-  if ((double)(M + 256) * lda * 2.0 >= 2147483648.0 || (double)(N + 256) * ldw * 2.0 >= 2147483648.0)
-    return LC2IS_ERR_UNSUPPORTED;
+  if (oc) return oc;
   GemmNtArgs a{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, nullptr, nullptr, 0, nullptr, 0,
                (bf16_t*)out_bf16, ldo, out_f32, ldf, nullptr, 0, M, N, K, LC2IS_ACT_NONE, 0,
                stride_a, stride_w, stride_ob, stride_of};

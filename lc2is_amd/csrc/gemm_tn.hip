@@ -618,20 +618,7 @@ extern "C" int lc2is_gemm_tn_bf16(const void* dY, int ldy, const void* X, int ld
   const TnPlan p = tn_plan(M, N, K, lc2is_ncu());   // ONE read of the CU budget: the launch and its workspace need come from this plan
   const size_t need = tn_plan_bytes(p, N, K);
   if (need && (!workspace || workspace_bytes < need)) return LC2IS_ERR_WORKSPACE;
-  static DevOnce attr_set;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TN_STAGE) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
-  static DevOnce attr_big_set;
-  if (p.big && attr_big_set.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_tn_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TD_STAGE) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_big_set.done();
-  }
+  if (set_dyn_lds<gemm_tn_kernel>(2 * TN_STAGE) || (p.big && set_dyn_lds<gemm_tn_dma_kernel>(2 * TD_STAGE))) return LC2IS_ERR_LAUNCH;
   const int grid = p.ntn * p.ntk * p.splits;
   auto launch = [&](float* o, int ldo, size_t o_stride, float* b, size_t b_stride, int acc_flag) {
     if (p.big)
@@ -886,19 +873,9 @@ extern "C" int lc2is_gemm_tn_grouped(const lc2is_tn_problem* problems, int n, vo
     t.blk_end[k] = blk;
     t.red_end[k] = red;
   }
-  static DevOnce attr_set;
-  if (attr_set.need()) {
-    if (hipFuncSetAttribute((const void*)gemm_tn_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TD_STAGE) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_tn_grouped_tbl_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TD_STAGE) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_tn_grouped_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TN_STAGE) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_tn_grouped_small_tbl_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * TN_STAGE) != hipSuccess)
-      return LC2IS_ERR_LAUNCH;
-    attr_set.done();
-  }
+  if (set_dyn_lds<gemm_tn_grouped_kernel>(2 * TD_STAGE) || set_dyn_lds<gemm_tn_grouped_tbl_kernel>(2 * TD_STAGE) ||
+      set_dyn_lds<gemm_tn_grouped_small_kernel>(2 * TN_STAGE) || set_dyn_lds<gemm_tn_grouped_small_tbl_kernel>(2 * TN_STAGE))
+    return LC2IS_ERR_LAUNCH;
   if (tbl) {
     if (hipMemcpyAsync(workspace, &t, sizeof(TnGroupTbl), hipMemcpyHostToDevice, stream) != hipSuccess) return LC2IS_ERR_LAUNCH;
     if (slot) {

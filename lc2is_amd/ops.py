@@ -21,6 +21,7 @@ ACT_GELU_ERF, ACT_DGELU_ERF, ACT_ADD_AUX = 7, 8, 9
 _P, _I, _F, _Z, _L, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long, C.c_ulonglong
 _ARGTYPES = {
     "lc2is_gemm_nt_bf16": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
+    "lc2is_gemm_nt_plan": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I],
     "lc2is_gemm_nt_ln_xchg_bytes": [_I, _I],
     "lc2is_gemm_nt_ln_bf16": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _P, _P, _Z, _I, _I, _I, _P],
     "lc2is_gemm_nt_bf16_batched": [_P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _I, _L, _I, _I, _I, _I, _P],
@@ -153,7 +154,7 @@ def _fn(name: str):
         f = getattr(_lib.load(), name)
         if name in _ARGTYPES:
             f.argtypes = _ARGTYPES[name]
-        if name.endswith("_workspace_bytes"):
+        if name.endswith("_bytes"):
             f.restype = C.c_size_t
         _bound[name] = f
     return f
@@ -237,6 +238,27 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, 
                                    _ld(ao), M, N, K, act, tile_cfg, _stream())
     _lib.check(rc, f"gemm_nt M={M} N={N} K={K}")
     return ob, of, ao
+
+
+class _GemmNtLaunch(C.Structure):   # lc2is_gemm_nt_launch
+    _fields_ = [(n, _I) for n in ("cfg", "row0", "rows", "tail_rows", "staged_epi")] + \
+               [(n, C.c_longlong) for n in ("off_a", "off_resid", "off_aux_in", "off_out_bf16", "off_out_f32", "off_aux_out")]
+
+
+def gemm_nt_plan(M: int, N: int, K: int, *, act: int = ACT_NONE, resid: bool = False, aux_in: bool = False, out_bf16: bool = True,
+                 out_f32: bool = False, aux_out: bool = False, tile_cfg: int = 0, ld: int | None = None):
+    """The launches gemm_nt runs for this problem under the present CU budget: a list of (cfg, row0, rows, tail_rows, staged_epi,
+    offsets) tuples, offsets = the bytes by which that launch's (a, resid, aux_in, out_bf16, out_f32, aux_out) pointers lie past the
+    caller's.  ``ld`` = leading dimension of resid / aux_in / the outputs (default N).  Nothing is launched and no GPU is needed;
+    raises what gemm_nt would raise for arguments the library refuses."""
+    ld = N if ld is None else ld
+    opt = [v for on in (resid, aux_in, out_bf16, out_f32, aux_out) for v in ((1 << 40 if on else None), (ld if on else 0))]
+    recs = (_GemmNtLaunch * 2)()   # (pointers are only tested for NULL)
+    n = _fn("lc2is_gemm_nt_plan")(1 << 40, K, 1 << 40, K, None, *opt, M, N, K, act, tile_cfg, recs, 2)
+    if n < 0:
+        _lib.check(n, f"gemm_nt_plan M={M} N={N} K={K}")
+    return [(r.cfg, r.row0, r.rows, r.tail_rows, r.staged_epi,
+             (r.off_a, r.off_resid, r.off_aux_in, r.off_out_bf16, r.off_out_f32, r.off_aux_out)) for r in recs[:n]]
 
 
 _xchg_cache = {}

@@ -202,8 +202,9 @@ def test_gemm_nt_rows_tail_is_bitwise_equal(dev, M, N, K):
 
 
 def test_gemm_nt_auto_plan_picks_exact_round_and_matches(dev):
-    """M = 32 800, N = 768 (the residual-stream GEMMs of the headline step): the automatic plan is 256 tiles of 256x384 + the row
-    tail; bitwise equal to the single-launch 256x256 plan, residual updated in place as the modules do."""
+    """M = 32 800, N = 768 (the residual-stream GEMMs of the headline step; the plans themselves are pinned in
+    test_gemm_nt_plan_cpu.py): the automatic plan is bitwise equal to the single-launch 256x256 plan, residual updated in place as
+    the modules do."""
     from lc2is_amd import ops
     g = torch.Generator(device="cpu").manual_seed(5)
     M, N, K = 32800, 768, 768
@@ -215,17 +216,16 @@ def test_gemm_nt_auto_plan_picks_exact_round_and_matches(dev):
     x = resid.clone()
     ops.gemm_nt(a, w, bias, resid=x, out_bf16=False, out_f32=x, tile_cfg=0)
     assert torch.equal(x, f4)
-    b4, _, _ = ops.gemm_nt(a, w, None, tile_cfg=4)   # bf16-only: 256 tiles of 256x384 + the row tail as well
+    b4, _, _ = ops.gemm_nt(a, w, None, tile_cfg=4)   # bf16-only output
     b0, _, _ = ops.gemm_nt(a, w, None, tile_cfg=0)
     assert torch.equal(b4, b0)
 
 
 @pytest.mark.parametrize("N,K", [(3072, 128), (3072, 768), (2304, 192)])
 def test_gemm_nt_auto_plan_persistent_with_folded_tail(dev, N, K):
-    """M = 64*256 + 32 rows with bf16 outputs: the automatic plan is the persistent ping-pong kernel (or 256x384 tiles for N = 2304)
-    over the whole tiles with the 32 ragged rows FOLDED into the same launch (fragment jobs after each block's last tile; the
-    derivative epilogue keeps a separate tail launch) — bitwise equal to the single-launch 256x256 plan for the three epilogues of
-    the tower: bias, quick_gelu + saved pre-activation, x quick_gelu'(saved)."""
+    """M = 64*256 + 32 rows with bf16 outputs (plans: test_gemm_nt_plan_cpu.py — ragged rows folded into the persistent launch, a
+    separate tail launch behind the derivative epilogue, one whole launch at N = 2304): bitwise equal to the single-launch 256x256
+    plan for the three epilogues of the tower: bias, quick_gelu + saved pre-activation, x quick_gelu'(saved)."""
     from lc2is_amd import ops
     g = torch.Generator(device="cpu").manual_seed(N + K)
     M = 64 * 256 + 32
@@ -247,8 +247,8 @@ def test_gemm_nt_auto_plan_persistent_with_folded_tail(dev, N, K):
 
 @pytest.mark.parametrize("N,K", [(3072, 128), (768, 192), (2304, 128)])
 def test_gemm_nt_auto_plan_ragged_rows(dev, N, K):
-    """M = 64*256 + 32 rows (the B x 1025-token shape): the automatic plan peels the ragged rows into a small-tile
-    launch and / or picks 128x384 tiles; every output must match the single-launch 256x256 plan."""
+    """M = 64*256 + 32 rows (the B x 1025-token shape) with every output at once and the saved-derivative pair of epilogues: every
+    output of the automatic plan (test_gemm_nt_plan_cpu.py) must match the single-launch 256x256 plan."""
     from lc2is_amd import ops
     g = torch.Generator(device="cpu").manual_seed(N + K)
     M = 64 * 256 + 32
@@ -267,6 +267,33 @@ def test_gemm_nt_auto_plan_ragged_rows(dev, N, K):
     ref = a[-40:].double() @ w.double().T + bias.double()
     sg = torch.sigmoid(1.702 * ref)
     assert _rel(outs[0][1][-40:], ref * sg + resid[-40:].double()) < 1e-5      # the peeled rows themselves
+
+
+@pytest.mark.parametrize("K,budget", [(64, 0), (64, 224), (256, 0)])
+def test_gemm_nt_auto_plan_separate_f32_tail(dev, K, budget):
+    """M = 64*256 + 32, N = 1024, fp32 output + residual: no 256x384 form (N % 384), so from K = 256 on the plan is 256x256 tiles
+    over 16 384 rows and a SEPARATE rows-kernel launch whose resid and out_f32 pointers must have moved with A (at K = 64 the
+    extra launch costs more than the round it saves, and 224 CUs leave no round to save: one launch).  Bitwise equal to
+    tile_cfg=4, residual added in place."""
+    from lc2is_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(K + budget)
+    M, N = 64 * 256 + 32, 1024
+    a = _bf(torch.randn(M, K, generator=g)).to(dev)
+    w = _bf(torch.randn(N, K, generator=g) * 0.1).to(dev)
+    bias = torch.randn(N, generator=g).to(dev)
+    resid = torch.randn(M, N, generator=g).to(dev)
+    _, f4, _ = ops.gemm_nt(a, w, bias, resid=resid, out_bf16=False, out_f32=True, tile_cfg=4)
+    try:
+        ops.set_cu_budget(budget)
+        plan = ops.gemm_nt_plan(M, N, K, resid=True, out_bf16=False, out_f32=True)
+        assert [r[:4] for r in plan] == ([(4, 0, 16384, 0), (17, 16384, 32, 0)] if (K, budget) == (256, 0) else [(4, 0, M, 0)])
+        x = resid.clone()
+        ops.gemm_nt(a, w, bias, resid=x, out_bf16=False, out_f32=x)
+    finally:
+        ops.set_cu_budget(0)
+    assert torch.equal(x, f4)
+    ref = a[-32:].double() @ w.double().T + bias.double() + resid[-32:].double()
+    assert _rel(x[-32:], ref) < 2e-6 * (K ** 0.5)
 
 
 @pytest.mark.parametrize("cfg", [0, 3, 4])
