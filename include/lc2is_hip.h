@@ -131,13 +131,29 @@ int lc2is_gemm_tn_bf16(const void* dY, int ldy, const void* X, int ldx, float* d
                        int N, int K, int accumulate, void* workspace, size_t workspace_bytes,
                        lc2is_stream_t stream);
 
+/* The plan lc2is_gemm_tn_bf16 runs for densely packed operands of this shape under the present CU budget and overrides
+ * (LC2IS_GEMM_TN_CFG), without launching anything: no GPU is needed.  The split count fixes the order of the fp32 partial sums,
+ * so this plan decides result bits, not only speed.  Returns the code the launcher would return for the shape. */
+typedef struct {
+  int big;        /* kernel form: 1 = 256x256 LDS-DMA tiles, 0 = 128x128 register-staged tiles */
+  int ntn, ntk;   /* output tiles along N and K */
+  int splits;     /* ranges the M rows are cut into; > 1: each writes a slab, a second launch sums them in order */
+  int chunk;      /* rows per range, a multiple of 64 */
+  int grid;       /* blocks of the main launch = ntn * ntk * splits */
+  int red_grid;   /* slab blocks of the reduce launch, 0 when splits == 1 (a db adds ceil(N / 256) blocks behind them) */
+  long long workspace_bytes;   /* = lc2is_gemm_tn_workspace_bytes(M, N, K) */
+} lc2is_tn_plan;
+int lc2is_gemm_tn_plan(int M, int N, int K, lc2is_tn_plan* out);
+
 /* Grouped form: up to LC2IS_TN_GROUP_MAX weight gradients (one transformer layer — q, k, v, out-proj, fc1, fc2, each the
  * autograd of an nn.Linear call listed above — or a whole tower's: 12 layers = 72 problems = 1296 output tiles, scheduled as
  * full-length blocks plus a few finely split problems that fill the last round of CUs) in ONE grid and one ordered-reduce
- * launch.  More than 16 problems: the descriptor table is uploaded into the front of the workspace (one small H2D copy on
- * `stream`; such a call cannot be captured into a hipGraph).  N and K multiples of 8; a group whose N and K are all
- * multiples of 256 runs on the 256x256 LDS-DMA tiles, any other (the Swin blocks) on 128x128 tiles.  Same results contract: fp32, bitwise
- * reproducible, db (optional) = column sums of dY, `accumulate` adds to dW / db. */
+ * launch.  Up to 16 problems travel as kernel arguments.  More than 16: the descriptor table is uploaded into the front of the
+ * workspace (one small H2D copy on `stream` from a pinned host image).  Such a call can be captured into a hipGraph: the copy
+ * becomes a memcpy node that re-reads its host image at every replay, so a captured call gets an image of its own that the
+ * library keeps for the graph (see lc2is_release_captured_tables below).  N and K multiples of 8; a group whose N and K are all
+ * multiples of 256 runs on the 256x256 LDS-DMA tiles, any other (the Swin blocks) on 128x128 tiles.  Same results contract: fp32,
+ * bitwise reproducible, db (optional) = column sums of dY, `accumulate` adds to dW / db. */
 #define LC2IS_TN_GROUP_MAX 128
 typedef struct lc2is_tn_problem {
   const void* dY; const void* X; float* dW; float* db;
@@ -146,8 +162,29 @@ typedef struct lc2is_tn_problem {
 size_t lc2is_gemm_tn_grouped_workspace_bytes(const lc2is_tn_problem* problems, int n);
 int lc2is_gemm_tn_grouped(const lc2is_tn_problem* problems, int n, void* workspace, size_t workspace_bytes,
                           lc2is_stream_t stream);
-/* A lc2is_gemm_tn_grouped call of more than 128 problems made under stream capture uploads its descriptor table through a
-   memcpy node that re-reads a pinned host image at every replay; the image belongs to the graph that captured it.  This frees
+
+/* The plan lc2is_gemm_tn_grouped runs for the same problems under the present CU budget, without launching anything (no GPU is
+ * needed; pointers are only tested for NULL): a summary and one record per problem in GRID order (at most `cap` are written).
+ * Returns the code the launcher would return for the problems (LC2IS_ERR_NULL also for a missing `summary` / `recs`). */
+typedef struct {
+  int small;      /* 1: 128x128 register-staged body (some N or K off the 256 grid), 0: 256x256 LDS-DMA body */
+  int table;      /* 1: descriptors uploaded into the front of the workspace (n > 16), 0: passed as kernel arguments */
+  int grid, red_grid;          /* blocks of the main and of the reduce launch (0: no reduce launch) */
+  long long workspace_bytes;   /* = lc2is_gemm_tn_grouped_workspace_bytes(problems, n), table_bytes included */
+  long long table_bytes;
+} lc2is_tn_group_plan;
+typedef struct {
+  int index;                    /* of the problem in the caller's list */
+  int ntn, ntk, splits, chunk;  /* as in lc2is_tn_plan */
+  int blk_end, red_end;         /* exclusive ends of the problem's block ranges in the main and the reduce grid */
+  int red_blocks;               /* slab blocks among its reduce blocks (the rest sum the bias partials) */
+  long long slab_offset, bias_offset;   /* bytes from the start of the workspace; -1: written straight to dW / db (or no db) */
+} lc2is_tn_group_rec;
+int lc2is_gemm_tn_grouped_plan(const lc2is_tn_problem* problems, int n, lc2is_tn_group_plan* summary, lc2is_tn_group_rec* recs,
+                               int cap);
+
+/* The pinned host image of a CAPTURED lc2is_gemm_tn_grouped call of more than 16 problems belongs to the graph that captured it
+   and must outlive it; the library holds it until told otherwise.  lc2is_release_captured_tables frees
    every such image (returns how many): call it once ALL graphs captured so far have been destroyed.  Per-graph ownership:
    lc2is_captured_tables_mark() before and after a capture brackets the images that capture registered, and
    lc2is_release_captured_tables_range(first, last) frees exactly those once that graph is destroyed (lc2is_amd.step.TrainStep

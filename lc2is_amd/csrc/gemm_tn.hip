@@ -12,6 +12,8 @@
 // fp32 slab and a second launch sums the slabs in a fixed order (bitwise reproducible, no atomics).
 #include "common.h"
 #include "lc2is_hip.h"
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
@@ -23,55 +25,53 @@ constexpr int TN_BN = 128, TN_BK = 128, TN_BM = 64;
 constexpr int TN_TILE_BYTES = TN_BM * 256;  // one operand tile: 64 rows x 256 B
 constexpr int TN_STAGE = 2 * TN_TILE_BYTES;
 
+// ---- planning: pure functions of their arguments (no HIP call, no environment, no static state) ----------------------
+constexpr int TN_TARGET_BLOCKS = 1024;    // 128x128 tiles: blocks aimed at (two 256-thread blocks per CU, the chip twice over)
+constexpr int TN_FULL_GRID = 512;         // ... from this many blocks on a block runs at least TN_LONG_ROWS rows
+constexpr int TN_MIN_ROWS = 512, TN_LONG_ROWS = 2048;   // rows per block: at least 8 steps of 64, 32 once the grid is full
+constexpr int TN_BIG_MIN_BLOCKS = 128;    // fewer 256x256 blocks than this: the 128x128 form fills the chip better
+constexpr int TN_RED_GRID_MAX = 2048, TG_RED_GRID_MAX = 1024;   // slab blocks of the single / the grouped reduce grid
+constexpr int TG_MAX_SPLITS = 32;         // 256x256 groups: M-split cap
+constexpr double TG_BLOCK_STEPS = 13.0;   // prologue + 256-KiB epilogue of a 256x256 block, in 64-row steps (~1.65 us each)
+constexpr double TG_SLAB_UNIT = 2.0 / 4.0e12 / 1.65e-6;   // steps per byte of slab written and read back (4 TB/s, 1.65 us per step)
+
+struct TnSplit { int chunk, splits; };   // the ONE rounding rule of an M split: rows per block rounded up to whole 64-row steps, then as many blocks as that needs
+inline TnSplit tn_chunk(int M, int want_splits) {
+  const int chunk = ((M + want_splits - 1) / want_splits + TN_BM - 1) / TN_BM * TN_BM;
+  return {chunk, (M + chunk - 1) / chunk};
+}
+inline int tn_clamp_splits(int splits, int max_splits) { return std::max(1, std::min(splits, max_splits)); }
+// 128x128 tiles: at least 8 steps of 64 rows per block; once the grid covers the chip twice over at least 32, so that a
+// few-tile gradient over hundreds of thousands of rows (Swin stage 1) is not all prologue and slab traffic
+inline int tn_small_max_splits(int M, long tiles) {
+  const int long_splits = (M + TN_LONG_ROWS - 1) / TN_LONG_ROWS;
+  return tiles * long_splits >= TN_FULL_GRID ? long_splits : (M + TN_MIN_ROWS - 1) / TN_MIN_ROWS;
+}
+inline int tn_target_splits_floor(long tiles) { return (int)(TN_TARGET_BLOCKS / tiles); }   // single form: rounds DOWN (the grouped form rounds to nearest)
+inline int tg_target_splits_nearest(long tiles) { return (int)((TN_TARGET_BLOCKS + tiles / 2) / tiles); }   // grouped form: rounds to NEAREST (the single form rounds down)
+
 struct TnPlan {
   int ntn, ntk, splits, chunk;
   int big;  // 1: 256x256 LDS-DMA kernel, 0: 128x128 register-staged kernel
+  int grid() const { return ntn * ntk * splits; }
+  // slab blocks of the reduce launch (a bias gradient adds ceil(N / 256) blocks behind them)
+  int red_grid(int N, int K) const { return splits == 1 ? 0 : (int)std::min<size_t>(((size_t)N * K / 4 + 255) / 256, TN_RED_GRID_MAX); }
+  size_t bytes(int N, int K) const { return splits > 1 ? (size_t)splits * N * ((size_t)K + 1) * sizeof(float) : 0; }
 };
 
-inline int tn_forced_cfg() {  // LC2IS_GEMM_TN_CFG=1|2 pins the kernel choice (tests / tools); default 0 = by shape
-  static int cfg = -1;
-  if (cfg < 0) {
-    const char* e = getenv("LC2IS_GEMM_TN_CFG");
-    cfg = e ? atoi(e) : 0;
+// `ncu`: the CU budget; `force`: LC2IS_GEMM_TN_CFG (1 | 2 pins the 128x128 | 256x256 form for tests and tools, 0 = by shape).  Both
+// are read ONCE per call by the entry point (tn_env): a planner that re-read them could see two values within one call.
+inline TnPlan tn_plan(int M, int N, int K, int ncu, int force) {
+  if (N % 256 == 0 && K % 256 == 0 && force != 1) {
+    const int tiles = (N / 256) * (K / 256);
+    const int splits = tn_clamp_splits((ncu + tiles / 2) / tiles, (M + TN_MIN_ROWS - 1) / TN_MIN_ROWS);   // about one block per CU of the budget
+    const TnSplit s = tn_chunk(M, splits);
+    if (tiles * splits >= TN_BIG_MIN_BLOCKS || force == 2) return {N / 256, K / 256, s.splits, s.chunk, 1};
   }
-  return cfg;
-}
-
-// `ncu`: the CU budget, read ONCE per call by the entry point (a planner that re-read the process-wide atomic could see two values)
-inline TnPlan tn_plan(int M, int N, int K, int ncu) {
-  TnPlan p;
-  p.big = 0;
-  if (N % 256 == 0 && K % 256 == 0 && tn_forced_cfg() != 1) {
-    const int ntn = N / 256, ntk = K / 256, tiles = ntn * ntk;
-    int splits = (ncu + tiles / 2) / tiles;   // about one block per CU of the budget (common.h)
-    const int max_splits = (M + 511) / 512;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (tiles * splits >= 128 || tn_forced_cfg() == 2) {
-      int chunk = (M + splits - 1) / splits;
-      chunk = (chunk + TN_BM - 1) / TN_BM * TN_BM;
-      p.ntn = ntn; p.ntk = ntk; p.chunk = chunk;
-      p.splits = (M + chunk - 1) / chunk;
-      p.big = 1;
-      return p;
-    }
-  }
-  p.ntn = (N + TN_BN - 1) / TN_BN;
-  p.ntk = (K + TN_BK - 1) / TN_BK;
-  const int tiles = p.ntn * p.ntk;
-  int splits = 1024 / tiles;
-  // at least 8 steps of 64 rows per block; once the grid covers the chip twice over (>= 512 blocks) at least 32, so
-  // that a few-tile gradient over hundreds of thousands of rows (Swin stage 1) is not all prologue and slab traffic
-  int max_splits = (M + 511) / 512;
-  const int long_splits = (M + 2047) / 2048;
-  if ((long)tiles * long_splits >= 512) max_splits = long_splits;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int chunk = (M + splits - 1) / splits;
-  chunk = (chunk + TN_BM - 1) / TN_BM * TN_BM;
-  p.splits = (M + chunk - 1) / chunk;
-  p.chunk = chunk;
-  return p;
+  const int ntn = (N + TN_BN - 1) / TN_BN, ntk = (K + TN_BK - 1) / TN_BK;
+  const long tiles = (long)ntn * ntk;
+  const TnSplit s = tn_chunk(M, tn_clamp_splits(tn_target_splits_floor(tiles), tn_small_max_splits(M, tiles)));
+  return {ntn, ntk, s.splits, s.chunk, 0};
 }
 
 __device__ __forceinline__ int tn_swz(int row, int ch) {
@@ -419,70 +419,70 @@ struct TnGroupTbl {
 };
 constexpr size_t TG_TBL_BYTES = (sizeof(TnGroupTbl) + 255) / 256 * 256;
 
+// The ONE range search of the six grouped kernels: declares `i` = the problem whose block range holds `bid` and `begin` = the start of
+// that range; END(j) = exclusive end of problem j's range, n problems.  A macro, not a __forceinline__ function: the function form
+// compiled to a slightly different scalar prologue, which moved the K loop of the 256x256 kernels by two instructions and cost the
+// training step 0.4 % in a three-way A/B (profiles/gemm_tn_plan_ab.txt); this form leaves their device code identical to what it was.
+#define TBL_BLK_END(j) t->blk_end[j]
+#define TBL_RED_END(j) t->red_end[j]
+#define ARG_BLK_END(j) g.p[j].blk_end
+#define ARG_RED_END(j) g.p[j].red_end
+#define TN_LOCATE(i, begin, END, n, bid) \
+  int i = 0, begin = 0;                  \
+  _Pragma("unroll 1") while (i < (n) - 1 && (bid) >= END(i)) { begin = END(i); ++i; }
+
+// (a POINTER to the descriptor, not a reference: a reference promises that every field may be read ahead of time, which turns the
+// accumulate test into a select and loses the epilogue specialised for accumulate == 0)
+__device__ __forceinline__ void tn_dma_prob(const TnGroupProb* q, int block, char* smem) {
+  tn_dma_body(q->dY, q->ldy, q->X, q->ldx, q->out, q->ldo, q->split_stride, q->bias_out, q->bias_split_stride, q->M, q->N,
+              q->K, q->ntn, q->ntk, q->chunk, q->splits == 1 ? q->accumulate : 0, block, smem);
+}
+__device__ __forceinline__ void tn_small_prob(const TnGroupProb* q, int block, char* smem) {
+  tn_small_body(q->dY, q->ldy, q->X, q->ldx, q->out, q->ldo, q->split_stride, q->bias_out, q->bias_split_stride, q->M, q->N,
+                q->K, q->ntn, q->ntk, q->chunk, q->splits == 1 ? q->accumulate : 0, block, smem);
+}
+__device__ __forceinline__ void slab_reduce_grouped_body(const TnGroupProb& q, int b);
+
 // XCD-aware block order (t->pad_[0] / g.remap): blocks b, b+8, ... share an XCD and its L2, but neighbouring LOGICAL blocks are the
 // tiles of one problem, which share operand panels (a 256-column panel of dY serves K/256 tiles, one of X serves N/256): with the
 // plain order every tile streamed both of its panels from the Infinity Cache / HBM by itself — rocprofv3 FETCH_SIZE 38 GB per
 // whole-tower launch, 7.3 TB/s over its 5.2 ms.
 __global__ __launch_bounds__(512, 2) void gemm_tn_grouped_tbl_kernel(const TnGroupTbl* __restrict__ t) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int i = 0, begin = 0;
   const int n = t->n;
   const int bid = t->pad_[0] ? xcd_round_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-#pragma unroll 1
-  while (i < n - 1 && bid >= t->blk_end[i]) { begin = t->blk_end[i]; ++i; }
-  const TnGroupProb* q = &t->p[i];
-  tn_dma_body(q->dY, q->ldy, q->X, q->ldx, q->out, q->ldo, q->split_stride, q->bias_out, q->bias_split_stride, q->M, q->N,
-              q->K, q->ntn, q->ntk, q->chunk, q->splits == 1 ? q->accumulate : 0, bid - begin, smem);
+  TN_LOCATE(i, begin, TBL_BLK_END, n, bid)
+  tn_dma_prob(&t->p[i], bid - begin, smem);
+}
+
+__global__ __launch_bounds__(512, 2) void gemm_tn_grouped_kernel(TnGroup g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int bid = g.remap ? xcd_round_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  TN_LOCATE(i, begin, ARG_BLK_END, g.n, bid)
+  tn_dma_prob(&g.p[i], bid - begin, smem);
 }
 
 // groups whose N / K are not all multiples of 256 (the Swin blocks: 96 .. 768 channels and their 4x MLPs) run the 128x128
 // register-staged body of gemm_tn_kernel per block instead: one grid + one ordered reduce per layer, not two launches per weight
 __global__ __launch_bounds__(256) void gemm_tn_grouped_small_kernel(TnGroup g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int i = 0, begin = 0;
-#pragma unroll 1
-  while (i < g.n - 1 && (int)blockIdx.x >= g.p[i].blk_end) { begin = g.p[i].blk_end; ++i; }
-  const TnGroupProb& q = g.p[i];
-  tn_small_body(q.dY, q.ldy, q.X, q.ldx, q.out, q.ldo, q.split_stride, q.bias_out, q.bias_split_stride, q.M, q.N, q.K, q.ntn,
-                q.ntk, q.chunk, q.splits == 1 ? q.accumulate : 0, (int)blockIdx.x - begin, smem);
+  TN_LOCATE(i, begin, ARG_BLK_END, g.n, (int)blockIdx.x)
+  tn_small_prob(&g.p[i], (int)blockIdx.x - begin, smem);
 }
 
 __global__ __launch_bounds__(256) void gemm_tn_grouped_small_tbl_kernel(const TnGroupTbl* __restrict__ t) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int i = 0, begin = 0;
-  const int n = t->n;
-#pragma unroll 1
-  while (i < n - 1 && (int)blockIdx.x >= t->blk_end[i]) { begin = t->blk_end[i]; ++i; }
-  const TnGroupProb* q = &t->p[i];
-  tn_small_body(q->dY, q->ldy, q->X, q->ldx, q->out, q->ldo, q->split_stride, q->bias_out, q->bias_split_stride, q->M, q->N,
-                q->K, q->ntn, q->ntk, q->chunk, q->splits == 1 ? q->accumulate : 0, (int)blockIdx.x - begin, smem);
+  TN_LOCATE(i, begin, TBL_BLK_END, t->n, (int)blockIdx.x)
+  tn_small_prob(&t->p[i], (int)blockIdx.x - begin, smem);
 }
-
-__global__ __launch_bounds__(512, 2) void gemm_tn_grouped_kernel(TnGroup g) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int i = 0, begin = 0;
-  const int bid = g.remap ? xcd_round_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
-#pragma unroll 1
-  while (i < g.n - 1 && bid >= g.p[i].blk_end) { begin = g.p[i].blk_end; ++i; }
-  const TnGroupProb& q = g.p[i];
-  tn_dma_body(q.dY, q.ldy, q.X, q.ldx, q.out, q.ldo, q.split_stride, q.bias_out, q.bias_split_stride, q.M, q.N, q.K, q.ntn,
-              q.ntk, q.chunk, q.splits == 1 ? q.accumulate : 0, bid - begin, smem);
-}
-
-__device__ __forceinline__ void slab_reduce_grouped_body(const TnGroupProb& q, int b);
 
 __global__ __launch_bounds__(256) void slab_reduce_grouped_kernel(TnGroup g) {
-  int i = 0, begin = 0;
-#pragma unroll 1
-  while (i < g.n - 1 && (int)blockIdx.x >= g.p[i].red_end) { begin = g.p[i].red_end; ++i; }
+  TN_LOCATE(i, begin, ARG_RED_END, g.n, (int)blockIdx.x)
   slab_reduce_grouped_body(g.p[i], (int)blockIdx.x - begin);
 }
 
 __global__ __launch_bounds__(256) void slab_reduce_grouped_tbl_kernel(const TnGroupTbl* __restrict__ t) {
-  int i = 0, begin = 0;
-  const int n = t->n;
-#pragma unroll 1
-  while (i < n - 1 && (int)blockIdx.x >= t->red_end[i]) { begin = t->red_end[i]; ++i; }
+  TN_LOCATE(i, begin, TBL_RED_END, t->n, (int)blockIdx.x)
   slab_reduce_grouped_body(t->p[i], (int)blockIdx.x - begin);
 }
 
@@ -596,51 +596,66 @@ inline int colsum_parts(int M) {
 
 }  // namespace
 
-static size_t tn_plan_bytes(const TnPlan& p, int N, int K) {
-  return p.splits > 1 ? (size_t)p.splits * N * ((size_t)K + 1) * sizeof(float) : 0;
+// ---- host side: validate -> plan -> (build) -> launch ------------------------------------------------------------------
+namespace {
+// What an entry point reads ONCE per call and hands down: the CU budget (it may change between two reads: common.h) and the two overrides,
+// read from the environment once per process: LC2IS_GEMM_TN_CFG (1 | 2 pins the single form's kernel) and LC2IS_TN_XCD (0 = plain block order)
+struct TnEnv { int ncu, force, xcd; };
+inline TnEnv tn_env() {
+  static const int force = [] { const char* e = getenv("LC2IS_GEMM_TN_CFG"); return e ? atoi(e) : 0; }();
+  static const int xcd = [] { const char* e = getenv("LC2IS_TN_XCD"); return !(e && atoi(e) == 0); }();
+  return {lc2is_ncu(), force, xcd};
 }
+
+// The operand rules of one problem, in the order both forms refuse in.  `dims_code`: what the caller returns for an empty shape or
+// an N / K off the 8-element grid (LC2IS_ERR_SHAPE from the single form, LC2IS_ERR_UNSUPPORTED from the grouped one).
+inline int tn_operand_check(const void* dY, int ldy, const void* X, int ldx, const float* dW, int ldw, int M, int N, int K,
+                            int dims_code) {
+  if (!dY || !X || !dW) return LC2IS_ERR_NULL;
+  if (M <= 0 || N <= 0 || K <= 0 || N % 8 || K % 8) return dims_code;
+  if (ldy < N || ldx < K || ldw < K || ldy % 8 || ldx % 8 || ldw % 4) return LC2IS_ERR_SHAPE;
+  const bool past_2gib = (double)(M + 64) * ldy * 2.0 >= 2147483648.0 || (double)(M + 64) * ldx * 2.0 >= 2147483648.0;
+  return past_2gib ? LC2IS_ERR_UNSUPPORTED : LC2IS_OK;
+}
+}  // namespace
 
 extern "C" size_t lc2is_gemm_tn_workspace_bytes(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const TnPlan p = tn_plan(M, N, K, lc2is_ncu());
-  return tn_plan_bytes(p, N, K);
+  const TnEnv env = tn_env();
+  return tn_plan(M, N, K, env.ncu, env.force).bytes(N, K);
+}
+
+extern "C" int lc2is_gemm_tn_plan(int M, int N, int K, lc2is_tn_plan* out) {
+  if (!out) return LC2IS_ERR_NULL;
+  if (const int rc = tn_operand_check(out, N, out, K, (const float*)out, K, M, N, K, LC2IS_ERR_SHAPE)) return rc;   // (densely packed operands)
+  const TnEnv env = tn_env();
+  const TnPlan p = tn_plan(M, N, K, env.ncu, env.force);
+  *out = {p.big, p.ntn, p.ntk, p.splits, p.chunk, p.grid(), p.red_grid(N, K), (long long)p.bytes(N, K)};
+  return LC2IS_OK;
 }
 
 extern "C" int lc2is_gemm_tn_bf16(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, float* db,
                                   int M, int N, int K, int accumulate, void* workspace, size_t workspace_bytes,
                                   lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!dY || !X || !dW) return LC2IS_ERR_NULL;
-  if (M <= 0 || N <= 0 || K <= 0 || N % 8 || K % 8) return LC2IS_ERR_SHAPE;
-  if (ldy < N || ldx < K || ldw < K || ldy % 8 || ldx % 8 || ldw % 4) return LC2IS_ERR_SHAPE;
-  if ((double)(M + 64) * ldy * 2.0 >= 2147483648.0 || (double)(M + 64) * ldx * 2.0 >= 2147483648.0)
-    return LC2IS_ERR_UNSUPPORTED;
-  const TnPlan p = tn_plan(M, N, K, lc2is_ncu());   // ONE read of the CU budget: the launch and its workspace need come from this plan
-  const size_t need = tn_plan_bytes(p, N, K);
+  int rc = tn_operand_check(dY, ldy, X, ldx, dW, ldw, M, N, K, LC2IS_ERR_SHAPE);
+  if (rc) return rc;
+  const TnEnv env = tn_env();
+  const TnPlan p = tn_plan(M, N, K, env.ncu, env.force);   // the launch and its workspace need come from this one plan
+  const size_t need = p.bytes(N, K);
   if (need && (!workspace || workspace_bytes < need)) return LC2IS_ERR_WORKSPACE;
   if (set_dyn_lds<gemm_tn_kernel>(2 * TN_STAGE) || (p.big && set_dyn_lds<gemm_tn_dma_kernel>(2 * TD_STAGE))) return LC2IS_ERR_LAUNCH;
-  const int grid = p.ntn * p.ntk * p.splits;
-  auto launch = [&](float* o, int ldo, size_t o_stride, float* b, size_t b_stride, int acc_flag) {
-    if (p.big)
-      hipLaunchKernelGGL(gemm_tn_dma_kernel, dim3(grid), dim3(512), 2 * TD_STAGE, stream, (const bf16_t*)dY, ldy,
-                         (const bf16_t*)X, ldx, o, ldo, o_stride, b, b_stride, M, N, K, p.ntn, p.ntk, p.chunk, acc_flag);
-    else
-      hipLaunchKernelGGL(gemm_tn_kernel, dim3(grid), dim3(256), 2 * TN_STAGE, stream, (const bf16_t*)dY, ldy,
-                         (const bf16_t*)X, ldx, o, ldo, o_stride, b, b_stride, M, N, K, p.ntn, p.ntk, p.chunk, acc_flag);
-  };
-  if (p.splits == 1) {
-    launch(dW, ldw, (size_t)0, db, (size_t)0, accumulate);
+  auto launch = [&](float* o, int ldo, size_t o_stride, float* b, size_t b_stride, int acc_flag) {   // (the two kernels share a signature)
+    hipLaunchKernelGGL(p.big ? gemm_tn_dma_kernel : gemm_tn_kernel, dim3(p.grid()), dim3(p.big ? 512 : 256), 2 * (p.big ? TD_STAGE : TN_STAGE),
+                       stream, (const bf16_t*)dY, ldy, (const bf16_t*)X, ldx, o, ldo, o_stride, b, b_stride, M, N, K, p.ntn, p.ntk, p.chunk, acc_flag);
     return lc2is_check_launch();
-  }
+  };
+  if (p.splits == 1) return launch(dW, ldw, (size_t)0, db, (size_t)0, accumulate);
   float* bias_ws = db ? (float*)workspace + (size_t)p.splits * N * K : nullptr;
-  launch((float*)workspace, K, (size_t)N * K, bias_ws, (size_t)N, 0);
-  int rc = lc2is_check_launch();
+  rc = launch((float*)workspace, K, (size_t)N * K, bias_ws, (size_t)N, 0);
   if (rc) return rc;
-  const size_t total4 = (size_t)N * K / 4;
-  int rgrid = (int)((total4 + 255) / 256);
-  if (rgrid > 2048) rgrid = 2048;
   const int bias_blocks = db ? (N + 255) / 256 : 0;
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(rgrid + bias_blocks), dim3(256), 0, stream, (const float*)workspace,
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(p.red_grid(N, K) + bias_blocks), dim3(256), 0, stream, (const float*)workspace,
                      p.splits, (size_t)N * K, dW, ldw, N, K, accumulate, (const float*)bias_ws, db, bias_blocks);
   return lc2is_check_launch();
 }
@@ -652,51 +667,24 @@ struct TgPlan {
   int order[TG_TBL_MAX];    // problem indices in grid order (split problems last: their short blocks fill the last round)
   size_t ws_floats;         // slab floats (after the descriptor table when n > TG_MAX)
   bool small;               // some N or K is not a multiple of 256: 128x128 tiles, register-staged body
+  size_t bytes(int n) const { return ws_floats * sizeof(float) + (n > TG_MAX ? TG_TBL_BYTES : 0); }
 };
 
 inline int tg_valid(const lc2is_tn_problem* pr, int n) {
   if (!pr || n <= 0 || n > TG_TBL_MAX) return LC2IS_ERR_UNSUPPORTED;
-  for (int i = 0; i < n; ++i) {
-    const lc2is_tn_problem& q = pr[i];
-    if (!q.dY || !q.X || !q.dW) return LC2IS_ERR_NULL;
-    if (q.M <= 0 || q.N <= 0 || q.K <= 0 || q.N % 8 || q.K % 8) return LC2IS_ERR_UNSUPPORTED;
-    if (q.ldy < q.N || q.ldx < q.K || q.ldw < q.K || q.ldy % 8 || q.ldx % 8 || q.ldw % 4) return LC2IS_ERR_SHAPE;
-    if ((double)(q.M + 64) * q.ldy * 2.0 >= 2147483648.0 || (double)(q.M + 64) * q.ldx * 2.0 >= 2147483648.0)
-      return LC2IS_ERR_UNSUPPORTED;
-  }
+  for (const lc2is_tn_problem* q = pr; q < pr + n; ++q)
+    if (const int rc = tn_operand_check(q->dY, q->ldy, q->X, q->ldx, q->dW, q->ldw, q->M, q->N, q->K, LC2IS_ERR_UNSUPPORTED)) return rc;
   return LC2IS_OK;
 }
 
-// Cost in units of one 64-row step of a 256x256 tile (~1.65 us); 13 steps ~ prologue + 256-KiB epilogue of a block; one
-// block per CU, so time = rounds x block length.  Two candidate plans:
+// 256x256 groups.  Cost in units of one 64-row step of a 256x256 tile (~1.65 us); TG_BLOCK_STEPS ~ prologue + 256-KiB epilogue of a
+// block; one block per CU, so time = rounds x block length.  Two candidate plans:
 //  (uniform) one M-split count for the whole group: rounds x (longest block + 13) + slab traffic — the right shape for a
 //            single layer (108 tiles: 2 splits, 216 blocks in one round);
 //  (tail)    every tile a full-length block except a few small problems that are split so finely that their blocks fill
 //            the last, partly empty round (a whole tower, 1296 tiles: 1278 full blocks in 5 rounds + 18 tiles x 14 splits)
 //            — no slabs for the bulk and ~97 % of the CUs busy instead of 84 %.
-inline void tg_plan(const lc2is_tn_problem* pr, int n, TgPlan& pl, const int ncu) {
-  pl.small = false;
-  for (int i = 0; i < n; ++i)
-    if (pr[i].N % 256 || pr[i].K % 256) pl.small = true;
-  if (pl.small) {
-    // 128x128 tiles, two 256-thread blocks per CU (64 KB of LDS each): aim at ~1024 blocks for the group, at least 8 steps
-    // of 64 rows per block (at least 32 once the grid is that full anyway: Swin stage 1 has few tiles over 260k rows)
-    long tiles = 0;
-    for (int i = 0; i < n; ++i) tiles += (long)((pr[i].N + TN_BN - 1) / TN_BN) * ((pr[i].K + TN_BK - 1) / TN_BK);
-    pl.ws_floats = 0;
-    for (int i = 0; i < n; ++i) {
-      int sp = (int)((1024 + tiles / 2) / tiles);
-      int max_sp = (pr[i].M + 511) / 512;
-      const int long_sp = (pr[i].M + 2047) / 2048;
-      if (tiles * long_sp >= 512) max_sp = long_sp;
-      if (sp > max_sp) sp = max_sp;
-      if (sp < 1) sp = 1;
-      pl.splits[i] = sp;
-      pl.order[i] = i;
-      if (sp > 1) pl.ws_floats += (size_t)sp * pr[i].N * ((size_t)pr[i].K + 1);
-    }
-    return;
-  }
+inline void tg_plan_big(const lc2is_tn_problem* pr, int n, int ncu, TgPlan& pl) {
   long tiles = 0;
   double wbytes = 0;
   int max_steps = 0, max_splits = 1 << 30;
@@ -707,86 +695,182 @@ inline void tg_plan(const lc2is_tn_problem* pr, int n, TgPlan& pl, const int ncu
     wbytes += 4.0 * pr[i].N * pr[i].K;
     const int steps = (pr[i].M + TN_BM - 1) / TN_BM;
     if (steps > max_steps) max_steps = steps;
-    const int ms = (pr[i].M + 511) / 512;
+    const int ms = (pr[i].M + TN_MIN_ROWS - 1) / TN_MIN_ROWS;
     if (ms < max_splits) max_splits = ms;
   }
-  if (max_splits > 32) max_splits = 32;
-  if (max_splits < 1) max_splits = 1;
-  const double slab_unit = 2.0 / 4.0e12 / 1.65e-6;   // steps per byte of slab written and read back
+  max_splits = tn_clamp_splits(max_splits, TG_MAX_SPLITS);
   int best = 1;
   double best_t = 1e300;
   for (int sp = 1; sp <= max_splits; ++sp) {
     const long blocks = tiles * sp;
     const double rounds = (double)((blocks + ncu - 1) / ncu);
-    const double t = rounds * ((max_steps + sp - 1) / sp + 13.0) + (sp > 1 ? sp * wbytes * slab_unit : 0.0);
+    const double t = rounds * ((max_steps + sp - 1) / sp + TG_BLOCK_STEPS) + (sp > 1 ? sp * wbytes * TG_SLAB_UNIT : 0.0);
     if (t < best_t) { best_t = t; best = sp; }
   }
-  for (int i = 0; i < n; ++i) { pl.splits[i] = best; pl.order[i] = i; }
-  // (ncu: 256, or the budget set while another queue's kernels hold CUs: common.h)
+  for (int i = 0; i < n; ++i) pl.splits[i] = best;
   const int rem = (int)(tiles % ncu);
-  if (n > 1 && tiles > ncu && rem != 0 && max_splits >= 2) {
-    bool in_tail[TG_TBL_MAX] = {};
-    int ts = 0;
-    double tail_bytes = 0;
-    while (ts < rem) {   // smallest problems first (later index on ties)
-      int pick = -1;
-      for (int i = 0; i < n; ++i)
-        if (!in_tail[i] && (pick < 0 || ptiles[i] <= ptiles[pick])) pick = i;
-      if (pick < 0) break;
-      in_tail[pick] = true;
-      ts += ptiles[pick];
-      tail_bytes += 4.0 * pr[pick].N * pr[pick].K;
-    }
-    int sp = ts > 0 ? ncu / ts : 0;
-    if (sp > max_splits) sp = max_splits;
-    if (ts >= rem && sp >= 2) {
-      const double rounds = (double)((tiles - ts + ncu - 1) / ncu);
-      const double t = rounds * (max_steps + 13.0) + ((max_steps + sp - 1) / sp + 13.0) + sp * tail_bytes * slab_unit;
-      if (t < best_t) {
-        int k = 0;
-        for (int i = 0; i < n; ++i) if (!in_tail[i]) { pl.order[k++] = i; pl.splits[i] = 1; }
-        for (int i = 0; i < n; ++i) if (in_tail[i]) { pl.order[k++] = i; pl.splits[i] = sp; }
-      }
-    }
+  if (!(n > 1 && tiles > ncu && rem != 0 && max_splits >= 2)) return;
+  bool in_tail[TG_TBL_MAX] = {};
+  int ts = 0;
+  double tail_bytes = 0;
+  while (ts < rem) {   // smallest problems first (later index on ties)
+    int pick = -1;
+    for (int i = 0; i < n; ++i)
+      if (!in_tail[i] && (pick < 0 || ptiles[i] <= ptiles[pick])) pick = i;
+    if (pick < 0) break;
+    in_tail[pick] = true;
+    ts += ptiles[pick];
+    tail_bytes += 4.0 * pr[pick].N * pr[pick].K;
   }
+  int sp = ts > 0 ? ncu / ts : 0;
+  if (sp > max_splits) sp = max_splits;
+  if (ts < rem || sp < 2) return;
+  const double rounds = (double)((tiles - ts + ncu - 1) / ncu);
+  const double t = rounds * (max_steps + TG_BLOCK_STEPS) + ((max_steps + sp - 1) / sp + TG_BLOCK_STEPS) + sp * tail_bytes * TG_SLAB_UNIT;
+  if (t >= best_t) return;
+  int k = 0;
+  for (int i = 0; i < n; ++i) if (!in_tail[i]) { pl.order[k++] = i; pl.splits[i] = 1; }
+  for (int i = 0; i < n; ++i) if (in_tail[i]) { pl.order[k++] = i; pl.splits[i] = sp; }
+}
+
+inline TgPlan tg_plan(const lc2is_tn_problem* pr, int n, int ncu) {
+  TgPlan pl;
+  pl.small = false;
+  for (int i = 0; i < n; ++i) {
+    pl.order[i] = i;
+    if (pr[i].N % 256 || pr[i].K % 256) pl.small = true;
+  }
+  long tiles = 0;   // 128x128 tiles, two 256-thread blocks per CU (64 KB of LDS each): ~TN_TARGET_BLOCKS blocks for the whole group
+  for (int i = 0; i < n; ++i) tiles += (long)((pr[i].N + TN_BN - 1) / TN_BN) * ((pr[i].K + TN_BK - 1) / TN_BK);
+  for (int i = 0; i < n; ++i) pl.splits[i] = tn_clamp_splits(tg_target_splits_nearest(tiles), tn_small_max_splits(pr[i].M, tiles));
+  if (!pl.small) tg_plan_big(pr, n, ncu, pl);   // (all on the 256 grid: the 256x256 plan replaces those counts)
   pl.ws_floats = 0;
   for (int i = 0; i < n; ++i)
     if (pl.splits[i] > 1) pl.ws_floats += (size_t)pl.splits[i] * pr[i].N * ((size_t)pr[i].K + 1);
+  return pl;
+}
+
+// The descriptors of a planned group in grid order and the two grid sizes; `workspace` is only added to (slabs behind the table, if any)
+inline void tg_build(const lc2is_tn_problem* pr, int n, const TgPlan& pl, int xcd, void* workspace, TnGroupTbl& t, int& grid,
+                     int& red_grid) {
+  t.n = n; t.pad_[0] = xcd;
+  float* ws = (float*)((char*)workspace + (n > TG_MAX ? TG_TBL_BYTES : 0));
+  grid = red_grid = 0;
+  for (int k = 0; k < n; ++k) {
+    const int i = pl.order[k];
+    const lc2is_tn_problem& q = pr[i];
+    TnGroupProb& d = t.p[k];
+    d.dY = (const bf16_t*)q.dY; d.X = (const bf16_t*)q.X; d.dW = q.dW; d.db = q.db;
+    d.ldy = q.ldy; d.ldx = q.ldx; d.ldw = q.ldw; d.M = q.M; d.N = q.N; d.K = q.K; d.accumulate = q.accumulate;
+    d.ntn = pl.small ? (q.N + TN_BN - 1) / TN_BN : q.N / 256;
+    d.ntk = pl.small ? (q.K + TN_BK - 1) / TN_BK : q.K / 256;
+    const TnSplit s = tn_chunk(q.M, pl.splits[i]);
+    d.chunk = s.chunk; d.splits = s.splits;
+    if (d.splits > 1) {
+      d.out = ws; d.ldo = q.K; d.split_stride = (size_t)q.N * q.K;
+      d.bias_out = q.db ? ws + (size_t)d.splits * q.N * q.K : nullptr; d.bias_split_stride = (size_t)q.N;
+    } else {
+      d.out = q.dW; d.ldo = q.ldw; d.split_stride = 0; d.bias_out = q.db; d.bias_split_stride = 0;
+    }
+    if (pl.splits[i] > 1) ws += (size_t)pl.splits[i] * q.N * ((size_t)q.K + 1);   // reserved for the PLANNED count even where the rounded chunk needs fewer
+    d.red_blocks = d.splits > 1 ? (int)std::min<size_t>(((size_t)q.N * q.K / 4 + 255) / 256, TG_RED_GRID_MAX) : 0;
+    grid += d.ntn * d.ntk * d.splits;
+    red_grid += d.splits > 1 ? d.red_blocks + (q.db ? (q.N + 255) / 256 : 0) : 0;
+    d.blk_end = t.blk_end[k] = grid;
+    d.red_end = t.red_end[k] = red_grid;
+  }
+}
+
+// ---- host images of the descriptor table ------------------------------------------------------------------------------
+// <= TG_MAX problems travel as kernel arguments: plain host memory.  More are uploaded, from a ring of PINNED slots, each guarded by
+// an event recorded behind its upload, so a slot is never rewritten while an asynchronous H2D copy may still be reading it
+// (whatever the runtime does with pageable memory).  Under stream capture the upload becomes a memcpy node that re-reads its host
+// source at EVERY replay, so a captured call gets a pinned image of its own that is never reused; it belongs to the graph being
+// captured and is freed with it through the three entry points below.
+struct TblSlot { TnGroupTbl* host; hipEvent_t done; bool in_flight; };
+std::mutex g_captured_mu;
+std::vector<void*> g_captured_tables;   // the table never shrinks and never reuses a slot: marks held by other captured steps stay valid indices
+
+// the image to fill (nullptr: a HIP call failed); `slot` is set when it is a ring slot, for tg_image_upload to guard
+TnGroupTbl* tg_image_acquire(bool tbl, hipStream_t stream, TblSlot*& slot) {
+  static thread_local TblSlot ring[4] = {};
+  static thread_local unsigned ring_pos = 0;
+  static thread_local TnGroupTbl small_tbl;
+  slot = nullptr;
+  if (!tbl) return &small_tbl;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) return nullptr;
+  if (cap != hipStreamCaptureStatusNone) {
+    // (an allocation is an "unsafe" call under the default global capture mode: relax this thread's mode around it)
+    TnGroupTbl* image = nullptr;
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    if (hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) return nullptr;
+    const hipError_t e = hipHostMalloc((void**)&image, sizeof(TnGroupTbl), hipHostMallocDefault);
+    if (hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess || e != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(g_captured_mu);
+    g_captured_tables.push_back(image);
+    return image;
+  }
+  slot = &ring[ring_pos++ & 3];
+  if (!slot->host && (hipHostMalloc((void**)&slot->host, sizeof(TnGroupTbl), hipHostMallocDefault) != hipSuccess ||
+                      hipEventCreateWithFlags(&slot->done, hipEventDisableTiming) != hipSuccess))
+    return nullptr;
+  if (slot->in_flight && hipEventSynchronize(slot->done) != hipSuccess) return nullptr;
+  slot->in_flight = false;
+  return slot->host;
+}
+
+int tg_image_upload(const TnGroupTbl* image, TblSlot* slot, void* dst, hipStream_t stream) {
+  if (hipMemcpyAsync(dst, image, sizeof(TnGroupTbl), hipMemcpyHostToDevice, stream) != hipSuccess) return LC2IS_ERR_LAUNCH;
+  if (slot) {
+    if (hipEventRecord(slot->done, stream) != hipSuccess) return LC2IS_ERR_LAUNCH;
+    slot->in_flight = true;
+  }
+  return LC2IS_OK;
+}
+
+int tg_release_captured(int first, int last) {
+  std::lock_guard<std::mutex> lock(g_captured_mu);
+  first = std::max(first, 0); last = std::min(last, (int)g_captured_tables.size());
+  int n = 0;
+  for (int i = first; i < last; ++i)
+    if (g_captured_tables[i]) { (void)hipHostFree(g_captured_tables[i]); g_captured_tables[i] = nullptr; ++n; }   // (slots keep their index)
+  return n;
 }
 }  // namespace
 
-static std::mutex g_captured_mu;
-static std::vector<void*> g_captured_tables;   // pinned descriptor-table images of captured grouped launches
-
-extern "C" int lc2is_release_captured_tables(void) {
-  std::lock_guard<std::mutex> lock(g_captured_mu);
-  int n = 0;
-  for (void*& p : g_captured_tables)   // the table never shrinks: marks held by other captured steps stay valid indices (their slots
-    if (p) { (void)hipHostFree(p); p = nullptr; ++n; }   // are simply empty afterwards; a later capture appends, it never reuses a slot)
-  return n;
-}
-
+extern "C" int lc2is_release_captured_tables(void) { return tg_release_captured(0, 1 << 30); }
+extern "C" int lc2is_release_captured_tables_range(int first, int last) { return tg_release_captured(first, last); }
 // Per-graph ownership: the images registered between two marks belong to the graph captured in between.
 extern "C" int lc2is_captured_tables_mark(void) {
   std::lock_guard<std::mutex> lock(g_captured_mu);
   return (int)g_captured_tables.size();
 }
 
-extern "C" int lc2is_release_captured_tables_range(int first, int last) {
-  std::lock_guard<std::mutex> lock(g_captured_mu);
-  if (first < 0) first = 0;
-  if (last > (int)g_captured_tables.size()) last = (int)g_captured_tables.size();
-  int n = 0;
-  for (int i = first; i < last; ++i)
-    if (g_captured_tables[i]) { (void)hipHostFree(g_captured_tables[i]); g_captured_tables[i] = nullptr; ++n; }   // (slots keep their index)
-  return n;
-}
-
 extern "C" size_t lc2is_gemm_tn_grouped_workspace_bytes(const lc2is_tn_problem* problems, int n) {
   if (tg_valid(problems, n) != LC2IS_OK) return 0;
-  TgPlan pl;
-  tg_plan(problems, n, pl, lc2is_ncu());
-  return pl.ws_floats * sizeof(float) + (n > TG_MAX ? TG_TBL_BYTES : 0);
+  return tg_plan(problems, n, lc2is_ncu()).bytes(n);
+}
+
+extern "C" int lc2is_gemm_tn_grouped_plan(const lc2is_tn_problem* problems, int n, lc2is_tn_group_plan* summary,
+                                          lc2is_tn_group_rec* recs, int cap) {
+  const int rc = tg_valid(problems, n);
+  if (rc) return rc;
+  if (!summary || (!recs && cap > 0)) return LC2IS_ERR_NULL;
+  const TnEnv env = tn_env();
+  const TgPlan pl = tg_plan(problems, n, env.ncu);
+  char* const base = (char*)((uintptr_t)1 << 40);   // a workspace that is never touched: slab pointers go back out as offsets from it
+  TnGroupTbl t;
+  int grid, red_grid;
+  tg_build(problems, n, pl, env.xcd, base, t, grid, red_grid);
+  *summary = {pl.small, n > TG_MAX, grid, red_grid, (long long)pl.bytes(n), n > TG_MAX ? (long long)TG_TBL_BYTES : 0};
+  for (int k = 0; k < n && k < cap; ++k) {
+    const TnGroupProb& d = t.p[k];
+    const bool slabs = d.splits > 1;
+    recs[k] = {pl.order[k], d.ntn, d.ntk, d.splits, d.chunk, d.blk_end, d.red_end, d.red_blocks,
+               slabs ? (long long)((char*)d.out - base) : -1, slabs && d.bias_out ? (long long)((char*)d.bias_out - base) : -1};
+  }
+  return LC2IS_OK;
 }
 
 extern "C" int lc2is_gemm_tn_grouped(const lc2is_tn_problem* problems, int n, void* workspace, size_t workspace_bytes,
@@ -794,116 +878,33 @@ extern "C" int lc2is_gemm_tn_grouped(const lc2is_tn_problem* problems, int n, vo
   hipStream_t stream = (hipStream_t)stream_;
   int rc = tg_valid(problems, n);
   if (rc) return rc;
-  TgPlan pl;
-  tg_plan(problems, n, pl, lc2is_ncu());
+  const TnEnv env = tn_env();
+  const TgPlan pl = tg_plan(problems, n, env.ncu);
   const bool tbl = n > TG_MAX;
-  const size_t need = pl.ws_floats * sizeof(float) + (tbl ? TG_TBL_BYTES : 0);
+  const size_t need = pl.bytes(n);
   if (need && (!workspace || workspace_bytes < need)) return LC2IS_ERR_WORKSPACE;
-  // Host image of the table: a ring of PINNED slots, each guarded by an event recorded behind its upload, so a slot is
-  // never rewritten while an asynchronous H2D copy may still be reading it (whatever the runtime does with pageable memory).
-  // Under stream capture the upload becomes a memcpy node that re-reads its host source at EVERY replay, so a captured
-  // call gets a pinned image of its own that is never reused; it lives as long as its graph (lc2is_release_captured_tables).
-  struct TblSlot { TnGroupTbl* host; hipEvent_t done; bool in_flight; };
-  static thread_local TblSlot ring[4] = {};
-  static thread_local unsigned ring_pos = 0;
-  static thread_local TnGroupTbl small_tbl;     // <= TG_MAX problems travel as kernel arguments: plain host memory
-  TblSlot* slot = nullptr;
-  TnGroupTbl* captured_tbl = nullptr;
-  if (tbl) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) return LC2IS_ERR_LAUNCH;
-    if (cap != hipStreamCaptureStatusNone) {
-      // (an allocation is an "unsafe" call under the default global capture mode: relax this thread's mode around it)
-      hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-      if (hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) return LC2IS_ERR_LAUNCH;
-      const hipError_t e = hipHostMalloc((void**)&captured_tbl, sizeof(TnGroupTbl), hipHostMallocDefault);
-      if (hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess || e != hipSuccess) return LC2IS_ERR_LAUNCH;
-      {   // owned by the graph being captured: remembered so that lc2is_release_captured_tables() can free it with the graph
-        std::lock_guard<std::mutex> lock(g_captured_mu);
-        g_captured_tables.push_back(captured_tbl);
-      }
-    } else {
-      slot = &ring[ring_pos++ & 3];
-      if (!slot->host) {
-        if (hipHostMalloc((void**)&slot->host, sizeof(TnGroupTbl), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&slot->done, hipEventDisableTiming) != hipSuccess)
-          return LC2IS_ERR_LAUNCH;
-      }
-      if (slot->in_flight && hipEventSynchronize(slot->done) != hipSuccess) return LC2IS_ERR_LAUNCH;
-      slot->in_flight = false;
-    }
-  }
-  TnGroupTbl& t = captured_tbl ? *captured_tbl : (tbl ? *slot->host : small_tbl);
-  static const int xcd_order = !(getenv("LC2IS_TN_XCD") && atoi(getenv("LC2IS_TN_XCD")) == 0);
-  t.n = n;
-  t.pad_[0] = xcd_order;
-  float* ws = (float*)((char*)workspace + (tbl ? TG_TBL_BYTES : 0));
-  int blk = 0, red = 0;
-  for (int k = 0; k < n; ++k) {
-    const int i = pl.order[k];
-    const lc2is_tn_problem& q = problems[i];
-    TnGroupProb& d = t.p[k];
-    d.dY = (const bf16_t*)q.dY; d.X = (const bf16_t*)q.X; d.dW = q.dW; d.db = q.db;
-    d.ldy = q.ldy; d.ldx = q.ldx; d.ldw = q.ldw; d.M = q.M; d.N = q.N; d.K = q.K; d.accumulate = q.accumulate;
-    d.ntn = pl.small ? (q.N + TN_BN - 1) / TN_BN : q.N / 256;
-    d.ntk = pl.small ? (q.K + TN_BK - 1) / TN_BK : q.K / 256;
-    int chunk = (q.M + pl.splits[i] - 1) / pl.splits[i];
-    chunk = (chunk + TN_BM - 1) / TN_BM * TN_BM;
-    d.chunk = chunk;
-    d.splits = (q.M + chunk - 1) / chunk;
-    if (pl.splits[i] > 1) {   // (slab space is reserved for the planned count even if the rounded chunk needs fewer)
-      float* base = ws;
-      ws += (size_t)pl.splits[i] * q.N * ((size_t)q.K + 1);
-      if (d.splits > 1) {
-        d.out = base; d.ldo = q.K; d.split_stride = (size_t)q.N * q.K;
-        d.bias_out = q.db ? base + (size_t)d.splits * q.N * q.K : nullptr; d.bias_split_stride = (size_t)q.N;
-      }
-    }
-    if (d.splits <= 1) {
-      d.out = q.dW; d.ldo = q.ldw; d.split_stride = 0; d.bias_out = q.db; d.bias_split_stride = 0;
-    }
-    blk += d.ntn * d.ntk * d.splits;
-    d.blk_end = blk;
-    const size_t total4 = (size_t)q.N * q.K / 4;
-    int rb = (int)((total4 + 255) / 256);
-    if (rb > 1024) rb = 1024;
-    d.red_blocks = d.splits > 1 ? rb : 0;
-    red += d.splits > 1 ? rb + (q.db ? (q.N + 255) / 256 : 0) : 0;
-    d.red_end = red;
-    t.blk_end[k] = blk;
-    t.red_end[k] = red;
-  }
+  TblSlot* slot;
+  TnGroupTbl* t = tg_image_acquire(tbl, stream, slot);
+  if (!t) return LC2IS_ERR_LAUNCH;
+  int grid, red_grid;
+  tg_build(problems, n, pl, env.xcd, workspace, *t, grid, red_grid);
   if (set_dyn_lds<gemm_tn_grouped_kernel>(2 * TD_STAGE) || set_dyn_lds<gemm_tn_grouped_tbl_kernel>(2 * TD_STAGE) ||
       set_dyn_lds<gemm_tn_grouped_small_kernel>(2 * TN_STAGE) || set_dyn_lds<gemm_tn_grouped_small_tbl_kernel>(2 * TN_STAGE))
     return LC2IS_ERR_LAUNCH;
-  if (tbl) {
-    if (hipMemcpyAsync(workspace, &t, sizeof(TnGroupTbl), hipMemcpyHostToDevice, stream) != hipSuccess) return LC2IS_ERR_LAUNCH;
-    if (slot) {
-      if (hipEventRecord(slot->done, stream) != hipSuccess) return LC2IS_ERR_LAUNCH;
-      slot->in_flight = true;
-    }
-    const TnGroupTbl* dt = (const TnGroupTbl*)workspace;
-    if (pl.small)
-      hipLaunchKernelGGL(gemm_tn_grouped_small_tbl_kernel, dim3(blk), dim3(256), 2 * TN_STAGE, stream, dt);
-    else
-      hipLaunchKernelGGL(gemm_tn_grouped_tbl_kernel, dim3(blk), dim3(512), 2 * TD_STAGE, stream, dt);
-    rc = lc2is_check_launch();
-    if (rc || red == 0) return rc;
-    hipLaunchKernelGGL(slab_reduce_grouped_tbl_kernel, dim3(red), dim3(256), 0, stream, dt);
+  auto launch = [&](auto small_kernel, auto big_kernel, auto reduce_kernel, const auto& arg) {
+    hipLaunchKernelGGL(pl.small ? small_kernel : big_kernel, dim3(grid), dim3(pl.small ? 256 : 512), 2 * (pl.small ? TN_STAGE : TD_STAGE), stream, arg);
+    const int lrc = lc2is_check_launch();
+    if (lrc || red_grid == 0) return lrc;
+    hipLaunchKernelGGL(reduce_kernel, dim3(red_grid), dim3(256), 0, stream, arg);
     return lc2is_check_launch();
+  };
+  if (tbl) {
+    if (tg_image_upload(t, slot, workspace, stream)) return LC2IS_ERR_LAUNCH;
+    return launch(gemm_tn_grouped_small_tbl_kernel, gemm_tn_grouped_tbl_kernel, slab_reduce_grouped_tbl_kernel, (const TnGroupTbl*)workspace);
   }
-  TnGroup g{};
-  g.n = n;
-  g.remap = xcd_order;
-  for (int k = 0; k < n; ++k) g.p[k] = t.p[k];
-  if (pl.small)
-    hipLaunchKernelGGL(gemm_tn_grouped_small_kernel, dim3(blk), dim3(256), 2 * TN_STAGE, stream, g);
-  else
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(blk), dim3(512), 2 * TD_STAGE, stream, g);
-  rc = lc2is_check_launch();
-  if (rc || red == 0) return rc;
-  hipLaunchKernelGGL(slab_reduce_grouped_kernel, dim3(red), dim3(256), 0, stream, g);
-  return lc2is_check_launch();
+  TnGroup g{n, env.xcd, {}};
+  for (int k = 0; k < n; ++k) g.p[k] = t->p[k];
+  return launch(gemm_tn_grouped_small_kernel, gemm_tn_grouped_kernel, slab_reduce_grouped_kernel, g);
 }
 
 extern "C" size_t lc2is_colsum_workspace_bytes(int M, int N) {

@@ -28,6 +28,8 @@ _ARGTYPES = {
     "lc2is_transpose_bf16_batched": [_P, _I, _L, _P, _I, _L, _I, _I, _I, _P],
     "lc2is_gemm_tn_workspace_bytes": [_I, _I, _I],
     "lc2is_gemm_tn_bf16": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _Z, _P],
+    "lc2is_gemm_tn_plan": [_I, _I, _I, _P],
+    "lc2is_gemm_tn_grouped_plan": [_P, _I, _P, _P, _I],
     "lc2is_colsum_workspace_bytes": [_I, _I],
     "lc2is_colsum_bf16": [_P, _I, _P, _I, _I, _I, _P, _Z, _P],
     "lc2is_layernorm_fwd": [_P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _F, _P],
@@ -361,6 +363,18 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor | None = None, a
     return dw
 
 
+class _TnPlan(C.Structure):   # lc2is_tn_plan
+    _fields_ = [(n, _I) for n in ("big", "ntn", "ntk", "splits", "chunk", "grid", "red_grid")] + [("workspace_bytes", C.c_longlong)]
+
+
+def gemm_tn_plan(M: int, N: int, K: int) -> dict:
+    """The plan gemm_tn runs for densely packed [M,N] / [M,K] operands under the present CU budget: dict(big, ntn, ntk, splits,
+    chunk, grid, red_grid, workspace_bytes).  Nothing is launched and no GPU is needed; raises what gemm_tn would raise."""
+    rec = _TnPlan()
+    _lib.check(_fn("lc2is_gemm_tn_plan")(M, N, K, C.addressof(rec)), f"gemm_tn_plan M={M} N={N} K={K}")
+    return {n: getattr(rec, n) for n, _ in _TnPlan._fields_}
+
+
 class TnProblem(C.Structure):
     _fields_ = [("dY", C.c_void_p), ("X", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p), ("ldy", C.c_int),
                 ("ldx", C.c_int), ("ldw", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("accumulate", C.c_int)]
@@ -394,6 +408,30 @@ def gemm_tn_grouped(problems):
     ws = workspace(nbytes, problems[0][0].device, "gemm_tn_grouped")
     rc = _fn("lc2is_gemm_tn_grouped")(arr, len(problems), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, f"gemm_tn_grouped n={len(problems)}")
+
+
+class _TnGroupPlan(C.Structure):   # lc2is_tn_group_plan
+    _fields_ = [(n, _I) for n in ("small", "table", "grid", "red_grid")] + [(n, C.c_longlong) for n in ("workspace_bytes", "table_bytes")]
+
+
+class _TnGroupRec(C.Structure):   # lc2is_tn_group_rec
+    _fields_ = [(n, _I) for n in ("index", "ntn", "ntk", "splits", "chunk", "blk_end", "red_end", "red_blocks")] + \
+               [(n, C.c_longlong) for n in ("slab_offset", "bias_offset")]
+
+
+def gemm_tn_grouped_plan(shapes, M: int, lds=None, db=True):
+    """The plan gemm_tn_grouped runs for problems of ``shapes`` = [(N, K), ...] over M rows each under the present CU budget:
+    (summary dict, [record dict per problem, in grid order]).  ``lds`` = [(ldy, ldx, ldw), ...] (default: densely packed), ``db``:
+    with bias gradients (one bool, or one per problem).  Nothing is launched and no GPU is needed; raises what gemm_tn_grouped would raise."""
+    n = len(shapes)
+    arr = (TnProblem * max(n, 1))()
+    for i, (N, K) in enumerate(shapes):
+        ldy, ldx, ldw = lds[i] if lds is not None else (N, K, K)
+        arr[i] = TnProblem(1 << 40, 1 << 40, 1 << 40, (1 << 40) if (db[i] if isinstance(db, (list, tuple)) else db) else None, ldy, ldx, ldw, M, N, K, 0)   # (only tested for NULL)
+    summary, recs = _TnGroupPlan(), (_TnGroupRec * max(n, 1))()
+    _lib.check(_fn("lc2is_gemm_tn_grouped_plan")(arr, n, C.addressof(summary), recs, n), f"gemm_tn_grouped_plan n={n}")
+    return ({f: getattr(summary, f) for f, _ in _TnGroupPlan._fields_},
+            [{f: getattr(r, f) for f, _ in _TnGroupRec._fields_} for r in recs[:n]])
 
 
 def release_captured_tables() -> int:

@@ -321,10 +321,17 @@ def test_gemm_nt_gelu_derivative_pair(dev, cfg):
         ops.gemm_nt(dy, w, None, act=ops.ACT_MUL_AUX, tile_cfg=cfg)                    # aux_in is required
 
 
-@pytest.mark.parametrize("M,N,K", [(300, 128, 128), (1025, 768, 768), (4100, 2304, 768), (2050, 152, 512),
-                                   (64, 64, 64), (5000, 3072, 768), (33, 8, 8)])
+# (300, 3072, 3072): 144 tiles of 256x256 in ONE split — the direct accumulate + db epilogue of gemm_tn_dma_kernel, with a ragged
+# last 64-row step; no other row takes that form (test_gemm_tn_rows_cover_both_kernels_with_and_without_slabs)
+TN_ROWS = [(300, 128, 128), (1025, 768, 768), (4100, 2304, 768), (2050, 152, 512), (64, 64, 64), (5000, 3072, 768), (33, 8, 8),
+           (300, 3072, 3072)]
+
+
+@pytest.mark.parametrize("M,N,K", TN_ROWS)
 def test_gemm_tn(dev, M, N, K):
     from lc2is_amd import ops
+    plan = ops.gemm_tn_plan(M, N, K)
+    assert plan["workspace_bytes"] == ops._fn("lc2is_gemm_tn_workspace_bytes")(M, N, K)      # the query the launcher sizes its workspace by
     g = torch.Generator(device="cpu").manual_seed(M + N + K)
     dy = _bf(torch.randn(M, N, generator=g)).to(dev)
     x = _bf(torch.randn(M, K, generator=g)).to(dev)
@@ -342,6 +349,14 @@ def test_gemm_tn(dev, M, N, K):
     db2 = db.clone()
     ops.gemm_tn(dy, x, dw3, accumulate=True, db=db2)
     assert _rel(db2, 2 * dy.double().sum(0)) < 1e-5
+
+
+def test_gemm_tn_rows_cover_both_kernels_with_and_without_slabs(dev):
+    """The rows of test_gemm_tn together run {128x128, 256x256} x {one split, several splits}."""
+    from lc2is_amd import ops
+    plans = [ops.gemm_tn_plan(M, N, K) for M, N, K in TN_ROWS]
+    assert {(p["big"], p["splits"] > 1) for p in plans} == {(0, False), (0, True), (1, False), (1, True)}
+    assert [(p["big"], p["splits"]) for p in plans if p["big"] and p["splits"] == 1] == [(1, 1)]      # (300, 3072, 3072) alone
 
 
 def test_gemm_tn_asymmetric(dev):
@@ -612,7 +627,8 @@ def test_gemm_tn_grouped_small_tiles(dev):
 def test_gemm_tn_grouped_whole_tower_table_and_tail_split(dev):
     """More than 16 problems go through the device-side descriptor table; with > 256 output tiles and a ragged last round
     the planner keeps the bulk as full-length blocks and splits the smallest problems (slabs + ordered reduce for those
-    only).  59 problems x (1..6 tiles) = 297 tiles, 41 past one round: the smallest problems are split, the rest run full length."""
+    only).  59 problems x (1..6 tiles) = 279 tiles, 23 past one round: the 14 smallest problems (24 tiles) are split 9-way into
+    216 blocks that fill the last round, the other 45 run full length (ops.gemm_tn_grouped_plan, asserted below)."""
     from lc2is_amd import ops
     g = torch.Generator(device="cpu").manual_seed(23)
     M = 4160
@@ -629,6 +645,12 @@ def test_gemm_tn_grouped_whole_tower_table_and_tail_split(dev):
         db = torch.full((N,), 3.0, device=dev) if i % 4 != 2 else None
         probs.append((dy, x, dw, db, acc))
         refs.append((dy.double().T @ x.double() + (2.0 if acc else 0.0), dy.double().sum(0) + (3.0 if acc else 0.0)))
+    summary, recs = ops.gemm_tn_grouped_plan(shapes, M=M, db=[p[3] is not None for p in probs])
+    splits = [r["splits"] for r in recs]
+    n_whole = splits.count(1)
+    assert summary["table"] and not summary["small"] and sum(r["ntn"] * r["ntk"] for r in recs) == 279
+    assert 0 < n_whole < len(shapes) and splits[:n_whole] == [1] * n_whole and min(splits[n_whole:]) > 1      # the split problems come last
+    assert (n_whole, set(splits[n_whole:]), sum(r["ntn"] * r["ntk"] for r in recs[n_whole:])) == (45, {9}, 24)
     ops.gemm_tn_grouped(probs)
     for (dy, x, dw, db, acc), (rw, rb) in zip(probs, refs):
         assert _rel(dw, rw) < 1e-5
@@ -640,6 +662,37 @@ def test_gemm_tn_grouped_whole_tower_table_and_tail_split(dev):
         assert torch.equal(a[2], b[2]) and (a[3] is None or torch.equal(a[3], b[3]))   # bitwise reproducible
     with pytest.raises(RuntimeError):
         ops.gemm_tn_grouped(probs * 3)      # 177 problems > LC2IS_TN_GROUP_MAX
+
+
+def test_gemm_tn_grouped_small_tiles_table(dev):
+    """17 problems off the 256 grid: the descriptor table with the 128x128 body and the table form of the ordered reduce
+    (gemm_tn_grouped_small_tbl_kernel, slab_reduce_grouped_tbl_kernel), every problem split; strided dy, mixed accumulate, some
+    without a bias gradient."""
+    from lc2is_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(31)
+    M = 1100
+    shapes = [[(96, 96), (200, 136), (288, 96)][i % 3] for i in range(17)]
+    summary, recs = ops.gemm_tn_grouped_plan(shapes, M=M, lds=[(N + 8, K, K) for N, K in shapes], db=[i % 4 != 1 for i in range(17)])
+    assert summary["table"] and summary["small"] and summary["red_grid"] > 0 and all(r["splits"] > 1 for r in recs)
+    x_by_k = {K: _bf(torch.randn(M, K, generator=g)).to(dev) for K in (96, 136)}
+    probs, refs = [], []
+    for i, (N, K) in enumerate(shapes):
+        dy = _bf(torch.randn(M, N + 8, generator=g)).to(dev)[:, :N]
+        x = x_by_k[K]
+        acc = i % 2 == 0
+        dw = torch.full((N, K), 2.0, device=dev)
+        db = torch.full((N,), 3.0, device=dev) if i % 4 != 1 else None
+        probs.append((dy, x, dw, db, acc))
+        refs.append((dy.double().T @ x.double() + (2.0 if acc else 0.0), dy.double().sum(0) + (3.0 if acc else 0.0)))
+    ops.gemm_tn_grouped(probs)
+    for (dy, x, dw, db, acc), (rw, rb) in zip(probs, refs):
+        assert _rel(dw, rw) < 1e-5
+        if db is not None:
+            assert _rel(db, rb) < 1e-5
+    again = [(dy, x, torch.full_like(dw, 2.0), None if db is None else torch.full_like(db, 3.0), acc) for dy, x, dw, db, acc in probs]
+    ops.gemm_tn_grouped(again)
+    for a, b in zip(again, probs):
+        assert torch.equal(a[2], b[2]) and (a[3] is None or torch.equal(a[3], b[3]))   # a second launch gives the same bits
 
 
 def test_cu_budget_changes_plans_not_results(dev):
