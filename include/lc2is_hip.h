@@ -858,6 +858,74 @@ int lc2is_aug_crop_select(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_
 int lc2is_label_histogram(const uint8_t* lab, size_t lab_bytes, const lc2is_aug_image* desc, long n_images, const int64_t* slots,
                           int B, int32_t* counts, lc2is_stream_t stream);
 
+/* ---- mixed-sample augmentation on the device: ClassMix and CutMix of two batches, two launches ------------------------
+ * Output sample b < B is destination sample b with the masked region replaced by source sample s = src_index[b] (NULL: s = b) of a
+ * source batch of Bs samples; a batch is pixels fp32 [.,3,S,S], labels int64 [.,L,L] and per-pixel loss weights fp32 [.,L,L] or NULL
+ * (= ones).  S % 4 == 0, S % L == 0, r = S / L >= 1, S <= LC2IS_AUG_MAX_SIDE.  The mask lives on the L x L label cells; pixel (y, x)
+ * belongs to cell (y / r, x / r).  The outputs are SELECTS, never blends:
+ *   out_px = mask ? src_px : dst_px (all three channels), out_lab = mask ? src_lab : dst_lab, out_pw = mask ? src_pw : dst_pw,
+ * only the chosen side of an element is read, so a NaN / infinity on the other side does not reach the output.  The outputs may
+ * alias neither input; the source batch may be the destination batch itself (ClassMix within a batch, src_index = a roll).
+ * Random numbers: h = the sample hash of lc2is_aug_params for (cfg's seed, *epoch, keys[b]) XOR LC2IS_MIX_STREAM, u24(k) as there:
+ * a mixer and a TrainAugment with the same seed share no draw, a sample's mask depends on (seed, epoch, key, its source label map)
+ * only, and a captured launch pair draws again on replay from the DEVICE epoch / keys / src_index.
+ * Mask, by cfg->mode:
+ *   LC2IS_MIX_CLASSMIX: the classes PRESENT in the source map src_lab[s] are the labels v with 0 <= v < n_classes, v != ignore_index,
+ *     v != exclude_label (-1: none; ADE20K's label 0, the pad label, is the usual value); 1 <= n_classes <= LC2IS_MIX_MAX_CLASSES.
+ *     With n present, the CHOSEN set is the ceil(n / 2) present classes c with the smallest pairs (u24(16 + c), c) - ties of the
+ *     24-bit draw break by class id: a uniformly random subset of fixed size, DACS's randperm(n)[:(n + n % 2) / 2].  A cell is
+ *     masked iff its source label is chosen; n = 0 gives the empty mask.
+ *   LC2IS_MIX_CUTMIX, one box, integers only (64-bit products):
+ *     a = area_lo1024 + ((u24(0) * (area_hi1024 - area_lo1024 + 1)) >> 24)      the box's share of the area in 1/1024 units
+ *     hmin = max(1, ceil(a * L / 1024));  bh = hmin + ((u24(1) * (L - hmin + 1)) >> 24)
+ *     bw = clamp((2 * a * L * L + 1024 * bh) / (2 * 1024 * bh), 1, L)            a * L * L / (1024 * bh), rounded
+ *     top = (u24(2) * (L - bh + 1)) >> 24;  left = (u24(3) * (L - bw + 1)) >> 24
+ *     cell (i, j) is masked iff top <= i < top + bh && left <= j < left + bw.  1 <= area_lo1024 <= area_hi1024 <= 1024 (default
+ *     256, 512).  The aspect is uniform in the box HEIGHT; CutMix-Seg's is log-uniform in the aspect ratio.
+ *   LC2IS_MIX_NONE: the empty mask.
+ * replaces: DACS / DAFormer's ClassMix (torch.unique per image - a host read -, randperm, a broadcast compare, three blends by a
+ *   float mask) and the CutMix of CPS / UniMatch / French et al. (numpy box draws on the host, slice assignment per image). */
+#define LC2IS_MIX_NONE 0
+#define LC2IS_MIX_CLASSMIX 1
+#define LC2IS_MIX_CUTMIX 2
+#define LC2IS_MIX_MAX_CLASSES 1024
+#define LC2IS_MIX_STREAM 0x4D495831u /* "MIX1" */
+#define LC2IS_MIX_PLAN_WORDS 40      /* one plan row, int32: {mode, source row, top, left, bh, bw, classes present, classes chosen}, */
+#define LC2IS_MIX_BITMAP 8           /*   then the chosen-class bitmap: class c is bit c % 32 of word LC2IS_MIX_BITMAP + c / 32     */
+typedef struct {
+  uint32_t seed_lo, seed_hi;          /* the 64-bit seed                                              */
+  int32_t mode;                       /* LC2IS_MIX_*                                                  */
+  int32_t n_classes;                  /* classmix: 1 .. LC2IS_MIX_MAX_CLASSES                         */
+  int64_t ignore_index, exclude_label;/* classmix: labels that are never present (exclude: -1 = none) */
+  int32_t area_lo1024, area_hi1024;   /* cutmix: the box's area share in 1/1024 units                 */
+} lc2is_mix_config;
+
+/* mix_select_kernel, one block of 1024 lanes per output sample b < B: writes row b of plan int32 [B][LC2IS_MIX_PLAN_WORDS] and of
+ * info int32 [B][4] = {classes present, classes chosen, masked cells, L * L}.  Classmix: presence is recorded as flags in LDS
+ * (same-value plain stores), a class's rank is the count of smaller pairs among the present classes, the bitmap words are wave
+ * ballots, the masked cells are counted by ballot + popcount and summed in a fixed order; top .. bw are 0.  Cutmix: the box, the two
+ * class counts and the bitmap are 0, masked cells = bh * bw.  NO read-modify-write atomics, LDS included; bitwise reproducible.
+ * A source row outside [0, Bs): the plan row is all zeros (mode NONE: the empty mask, nothing of the source is read, by
+ * lc2is_mix_apply neither) and info = {-1, 0, 0, 0}.
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (src_lab, keys, epoch, cfg, plan, info); LC2IS_ERR_SHAPE (B, Bs < 1,
+ * L outside 1 .. LC2IS_AUG_MAX_SIDE, n_classes or the area range out of range, src_lab / keys / src_index not 8-byte, plan / info /
+ * epoch not 4-byte aligned); LC2IS_ERR_UNSUPPORTED (a mode that is none of the three). */
+int lc2is_mix_select(const int64_t* src_lab, int Bs, const int64_t* src_index, const int64_t* keys, int B, const int32_t* epoch,
+                     const lc2is_mix_config* cfg /* HOST */, int L, int32_t* plan, int32_t* info, lc2is_stream_t stream);
+
+/* mix_apply_kernel, ONE launch for pixels, labels and weights: grid.y = B samples, grid.x = pixel blocks followed by label-cell
+ * blocks (256 lanes; a pixel lane makes 4 consecutive x of all 3 channels with 16-byte loads and stores and ONE mask lookup when
+ * r % 4 == 0; otherwise a float4 can straddle two cells and the lane selects per element, with 16-byte loads where its four masks
+ * agree).  Reads the plan rows lc2is_mix_select wrote; a row whose mode is none of CLASSMIX / CUTMIX or whose source row lies outside
+ * [0, Bs) gives the destination sample, and whatever a row holds nothing outside the batches is read.  dst_pw / src_pw may be NULL
+ * (ones).  Ideal traffic: one read and one write of [B,3,S,S] plus the label and weight maps.  No atomics; bitwise reproducible.
+ * Errors, in this order: LC2IS_ERR_NULL (dst_px, dst_lab, src_px, src_lab, plan, out_px, out_lab, out_pw); LC2IS_ERR_SHAPE (B outside
+ * 1 .. 65535, Bs < 1, S outside 4 .. LC2IS_AUG_MAX_SIDE, S % 4, L < 1, S % L, pixels not 16-byte, labels not 8-byte, weights / plan
+ * not 4-byte aligned, an output that overlaps an input). */
+int lc2is_mix_apply(const float* dst_px, const int64_t* dst_lab, const float* dst_pw, const float* src_px, const int64_t* src_lab,
+                    const float* src_pw, int Bs, const int32_t* plan, int B, int S, int L, float* out_px, int64_t* out_lab,
+                    float* out_pw, lc2is_stream_t stream);
+
 /* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
  * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
  * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with

@@ -11,25 +11,15 @@
 //     per sample counts the label cells aug_apply would write for each candidate origin and replaces the row's (top, left).
 //   * label_hist_kernel: per-image class counts of the pool's label maps, for class weights.  Both count with label_hist.h.
 // The exact definition is in include/lc2is_hip.h; tests/augment_ref.py and tests/catcrop_ref.py restate it in numpy (integers bit
-// for bit).
+// for bit).  The counter RNG (aug_key, aug_u24, aug_range) and aug_div live in aug_rng.h, shared with mix.hip.
 #include "common.h"
+#include "aug_rng.h"
 #include "label_hist.h"
 #include "lc2is_hip.h"
 
 namespace {
 
 constexpr int AUG_P = LC2IS_AUG_PARAM_WORDS;
-constexpr unsigned AUG_GOLD = 0x9E3779B9u;
-
-__device__ __forceinline__ unsigned aug_key(unsigned seed_lo, unsigned seed_hi, int epoch, long long key) {
-  unsigned h = mix32((unsigned)key + seed_lo);
-  h = mix32(h ^ ((unsigned)((unsigned long long)key >> 32) + seed_hi));
-  return mix32(h ^ ((unsigned)epoch * AUG_GOLD + 0x85EBCA6Bu));
-}
-__device__ __forceinline__ unsigned aug_u24(unsigned h, unsigned k) { return mix32(h + k * AUG_GOLD) >> 8; }
-__device__ __forceinline__ float aug_range(unsigned u24, float lo, float hi) {
-  return lo + (hi - lo) * ((float)u24 * (1.0f / 16777216.0f));
-}
 
 // (M, o) = A (M, o)
 __device__ __forceinline__ void aug_left_mul(const float (&A)[9], float (&M)[9], float (&o)[3]) {
@@ -112,16 +102,6 @@ __global__ __launch_bounds__(64) void aug_params_kernel(const int64_t* __restric
   for (int e = LC2IS_AUG_O + 3; e < AUG_P; ++e) row[e] = 0;
 }
 
-// n / d and the remainder for 0 <= n < 2^31, 1 <= d < 2^24, n / d <= 4096, rcp_d = v_rcp_f32(d) (1 ulp): the fp32 estimate is off
-// by less than 4097 * 2^-22 < 1, so its floor is the quotient or one next to it and one integer correction makes it exact.
-__device__ __forceinline__ int aug_div(int n, int d, float rcp_d, int& rem) {
-  int q = (int)((float)n * rcp_d);
-  int r = (int)((unsigned)n - (unsigned)q * (unsigned)d);
-  if (r < 0) { q -= 1; r += d; }
-  else if (r >= d) { q += 1; r -= d; }
-  rem = r;
-  return q;
-}
 __device__ __forceinline__ int aug_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct AugSample {   // block-uniform: one sample per blockIdx.y

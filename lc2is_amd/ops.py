@@ -141,6 +141,8 @@ _ARGTYPES = {
     "lc2is_aug_apply": [_P, _Z, _P, _Z, _P, _L, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P],
     "lc2is_aug_crop_select": [_P, _Z, _P, _L, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "lc2is_label_histogram": [_P, _Z, _P, _L, _P, _I, _P, _P],
+    "lc2is_mix_select": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P],
+    "lc2is_mix_apply": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -2348,6 +2350,100 @@ def label_histogram(lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, 
     rc = _fn("lc2is_label_histogram")(_ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), B, _ptr(out), _stream())
     _lib.check(rc, f"label_histogram B={B}")
     return out
+
+
+# ---- mixed-sample augmentation (ClassMix / CutMix) -------------------------------------------------------------------
+MIX_NONE, MIX_CLASSMIX, MIX_CUTMIX = 0, 1, 2       # LC2IS_MIX_*
+MIX_MAX_CLASSES, MIX_PLAN_WORDS, MIX_BITMAP, MIX_STREAM = 1024, 40, 8, 0x4D495831
+
+
+class MixConfig(C.Structure):
+    """lc2is_mix_config (include/lc2is_hip.h): host struct, passed by value into mix_select_kernel."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("mode", C.c_int32), ("n_classes", C.c_int32),
+                ("ignore_index", C.c_int64), ("exclude_label", C.c_int64), ("area_lo1024", C.c_int32), ("area_hi1024", C.c_int32)]
+
+
+def _mix_batch(px, lab, pw, name):
+    _chk(px, torch.float32, f"{name} pixels", 4); _chk(lab, torch.int64, f"{name} labels", 3); _chk(pw, torch.float32, f"{name} weights", 3)
+    n, S, L = px.shape[0], px.shape[2], lab.shape[1]
+    if n < 1 or tuple(px.shape) != (n, 3, S, S) or tuple(lab.shape) != (n, L, L) or (pw is not None and pw.shape != lab.shape) \
+            or not (px.is_contiguous() and lab.is_contiguous() and (pw is None or pw.is_contiguous())):
+        raise RuntimeError(f"lc2is_amd.mix_apply: the {name} batch must be contiguous pixels [n, 3, S, S], labels [n, L, L] and "
+                           "weights [n, L, L] or None")
+    return n, S, L
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor | None) -> bool:
+    if b is None:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def mix_select(src_lab: torch.Tensor, keys: torch.Tensor, epoch: torch.Tensor, cfg: MixConfig, *,
+               src_index: torch.Tensor | None = None, plan: torch.Tensor | None = None, info: torch.Tensor | None = None):
+    """Draw one mixing plan per output sample (lc2is_mix_select): plan int32 [B, MIX_PLAN_WORDS] = mode, source row, cutmix box (top,
+    left, bh, bw), classes present, classes chosen, and the chosen-class bitmap; info int32 [B, 4] = classes present, classes chosen,
+    masked cells, L * L ({-1, 0, 0, 0}: the source row lies outside the source batch; that sample keeps its destination).  src_lab
+    int64 [Bs, L, L]: the source batch's label maps; keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE
+    int32 scalar; src_index int64 [B] or None (row b).  Nothing but device memory decides the result: a captured call draws again."""
+    _chk(src_lab, torch.int64, "src_lab", 3); _chk(keys, torch.int64, "keys", 1); _chk(src_index, torch.int64, "src_index", 1)
+    _chk(epoch, torch.int32, "epoch", None)
+    Bs, L, B = src_lab.shape[0], src_lab.shape[1], keys.numel()
+    if Bs < 1 or B < 1 or src_lab.shape[2] != L or not src_lab.is_contiguous() or epoch.numel() != 1 or \
+            (src_index is not None and src_index.numel() != B):
+        raise RuntimeError("lc2is_amd.mix_select: src_lab must be contiguous int64 [Bs, L, L], epoch one int32, keys and src_index "
+                           "one int64 per output sample")
+    if not 1 <= L <= AUG_MAX_SIDE:
+        raise ValueError(f"lc2is_amd.mix_select: label size {L} must be 1..{AUG_MAX_SIDE}")
+    if cfg.mode not in (MIX_NONE, MIX_CLASSMIX, MIX_CUTMIX) or not 1 <= cfg.n_classes <= MIX_MAX_CLASSES or \
+            not 1 <= cfg.area_lo1024 <= cfg.area_hi1024 <= 1024:
+        raise ValueError(f"lc2is_amd.mix_select: mode {cfg.mode} must be MIX_NONE / MIX_CLASSMIX / MIX_CUTMIX, n_classes {cfg.n_classes} "
+                         f"1..{MIX_MAX_CLASSES} and the area range ({cfg.area_lo1024}, {cfg.area_hi1024}) ordered inside 1..1024")
+    if plan is None:
+        plan = torch.empty((B, MIX_PLAN_WORDS), dtype=torch.int32, device=keys.device)
+    if info is None:
+        info = torch.empty((B, 4), dtype=torch.int32, device=keys.device)
+    _chk(plan, torch.int32, "plan"); _chk(info, torch.int32, "info")
+    if tuple(plan.shape) != (B, MIX_PLAN_WORDS) or tuple(info.shape) != (B, 4) or not (plan.is_contiguous() and info.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.mix_select: plan / info must be contiguous int32 [{B}, {MIX_PLAN_WORDS}] / [{B}, 4]")
+    rc = _fn("lc2is_mix_select")(_ptr(src_lab), Bs, _ptr(src_index), _ptr(keys), B, _ptr(epoch), C.addressof(cfg), L, _ptr(plan),
+                                 _ptr(info), _stream())
+    _lib.check(rc, f"mix_select B={B} Bs={Bs} L={L}")
+    return plan, info
+
+
+def mix_apply(dst, src, plan: torch.Tensor, out=None):
+    """One launch (lc2is_mix_apply): out = mask ? src[plan's source row] : dst for pixels fp32 [B, 3, S, S], labels int64 [B, L, L] and
+    per-pixel weights fp32 [B, L, L], the mask on the L x L cells from `plan` (mix_select).  dst / src: (pixels, labels, weights or
+    None = ones); the source batch may hold another number of samples and may be the destination batch itself.  out: (pixels,
+    labels, weights) to write into; an output that overlaps an input is refused.  A select, never a blend: bit for bit the chosen
+    side, whatever the other side holds."""
+    (dpx, dlab, dpw), (spx, slab, spw) = dst, src
+    B, S, L = _mix_batch(dpx, dlab, dpw, "destination")
+    Bs, S2, L2 = _mix_batch(spx, slab, spw, "source")
+    if (S2, L2) != (S, L):
+        raise RuntimeError(f"lc2is_amd.mix_apply: the destination is {S} px / {L} cells a side, the source {S2} / {L2}")
+    if S < 4 or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
+        raise ValueError(f"lc2is_amd.mix_apply: the size {S} must be a multiple of 4 and of the label size {L}, at most {AUG_MAX_SIDE}")
+    if not 1 <= B <= 65535:
+        raise ValueError(f"lc2is_amd.mix_apply: at most 65535 samples per call, got {B}")
+    _chk(plan, torch.int32, "plan")
+    if tuple(plan.shape) != (B, MIX_PLAN_WORDS) or not plan.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.mix_apply: plan must be contiguous int32 [{B}, {MIX_PLAN_WORDS}]")
+    if out is None:
+        out = (torch.empty_like(dpx), torch.empty_like(dlab), torch.empty(dlab.shape, dtype=torch.float32, device=dlab.device))
+    opx, olab, opw = out
+    _chk(opx, torch.float32, "out pixels", 4); _chk(olab, torch.int64, "out labels", 3); _chk(opw, torch.float32, "out weights", 3)
+    if opx.shape != dpx.shape or olab.shape != dlab.shape or opw.shape != dlab.shape or \
+            not (opx.is_contiguous() and olab.is_contiguous() and opw.is_contiguous()):
+        raise RuntimeError(f"lc2is_amd.mix_apply: outputs must be contiguous [{B}, 3, {S}, {S}] fp32, [{B}, {L}, {L}] int64 and fp32")
+    if any(_overlap(o, i) for o, ins in ((opx, (dpx, spx)), (olab, (dlab, slab)), (opw, (dpw, spw))) for i in ins):
+        raise RuntimeError("lc2is_amd.mix_apply: an output may not alias an input (the source batch may be the destination batch)")
+    rc = _fn("lc2is_mix_apply")(_ptr(dpx), _ptr(dlab), _ptr(dpw), _ptr(spx), _ptr(slab), _ptr(spw), Bs, _ptr(plan), B, S, L,
+                                _ptr(opx), _ptr(olab), _ptr(opw), _stream())
+    _lib.check(rc, f"mix_apply B={B} Bs={Bs} S={S} L={L}")
+    return opx, olab, opw
 
 
 def set_cu_budget(ncu: int) -> None:

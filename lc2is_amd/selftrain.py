@@ -29,7 +29,15 @@ low-resolution scores instead of hard labels and the step adds the per-pixel KL 
 images in, as ``combine`` does for the hard recipe; ``teacher_weight=`` takes a per-pixel weight on the KL, e.g. the teacher's
 confidence from ``predict_confidence``.)
 
-Out of scope here: how the strong / weak views are drawn, ClassMix, pooling the confident-pixel counts across ranks, and models
+The mixed-sample step of DACS / DAFormer (ClassMix) and of CPS / UniMatch (CutMix) goes between the two: the labelled batch is the
+source, ``(strong_view, labels_u, pw_u)`` the destination, and the mixed batch is the step's (``lc2is_amd.data.SampleMix``, two
+launches, no host read; ``mixed`` is the helper)::
+
+    mix = SampleMix("classmix", n_classes=151, exclude_label=0, seed=1234)
+    px, labels_m, pw_m, _ = mix((strong_view["pixel_values"], labels_u, pw_u), (inputs["pixel_values"], labels, None), keys, epoch)
+    step.step({**strong_view, "pixel_values": px}, labels_m, pw_m)          # = step.step(*labeler.mixed(...))
+
+Out of scope here: how the strong / weak views are drawn, pooling the confident-pixel counts across ranks, and models
 without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
 """
 from __future__ import annotations
@@ -87,3 +95,14 @@ class PseudoLabeler:
         ones = torch.ones(labels.shape, dtype=torch.float32, device=labels.device)
         pw_u = torch.ones(labels_u.shape, dtype=torch.float32, device=labels.device) if pw_u is None else pw_u
         return both, torch.cat([labels, labels_u], dim=0), torch.cat([ones, pw_u], dim=0)
+
+    @staticmethod
+    def mixed(labelled, pseudo, mix, keys, epoch, src_index=None):
+        """``labelled = (inputs, labels)`` as the source and ``pseudo = (inputs_u, labels_u, pixel_weight_u or None)`` as the
+        destination of ``mix`` (a ``lc2is_amd.data.SampleMix``) -> the ``(inputs, labels, pixel_weight)`` of one ``TrainStep.step``:
+        ``inputs_u`` with the mixed ``pixel_values``, the mixed labels and weights (weight 1 on what comes from the labelled
+        images).  ``keys`` / ``epoch`` / ``src_index`` as ``SampleMix`` takes them; ``mix.last_info`` holds the call's statistics."""
+        (inputs, labels), (inputs_u, labels_u, pw_u) = labelled, pseudo
+        px, labels_m, pw_m, _ = mix((inputs_u["pixel_values"], labels_u, pw_u), (inputs["pixel_values"], labels, None), keys, epoch,
+                                    src_index=src_index)
+        return {**inputs_u, "pixel_values": px}, labels_m, pw_m
