@@ -753,9 +753,32 @@ def patchify(pixels: torch.Tensor, patch: int, kpad: int | None = None):
     return out
 
 
+def _chk_rows(who: str, t, name: str, rows: int, what: str):
+    """The row-streaming kernels index a tensor by their integer arguments alone: a tensor with another row count is read or
+    written out of bounds, so it is refused here, before any launch."""
+    if t.shape[0] != rows:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must have {what} = {rows} rows, got shape {tuple(t.shape)}")
+
+
+def _chk_table(who: str, t, name: str, like, min_rows: int | None, Cc: int):
+    """A parameter or gradient table the kernels address as dense fp32 [rows, C] (a [C] vector when ``min_rows`` is None)."""
+    _chk(t, torch.float32, name, 1 if min_rows is None else 2)
+    if t.device != like.device:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} is on {t.device}, the data on {like.device}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous")
+    if t.shape[-1] != Cc:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must have C = {Cc} columns, got shape {tuple(t.shape)}")
+    if min_rows is not None and t.shape[0] < min_rows:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must have at least {min_rows} rows, got shape {tuple(t.shape)}")
+
+
 def vit_embed_fwd(patch_f32, cls, pos, B: int, P: int):
-    _chk(patch_f32, torch.float32, "patch"); _chk(cls, torch.float32, "cls", 1); _chk(pos, torch.float32, "pos")
+    _chk(patch_f32, torch.float32, "patch")
     Cc = patch_f32.shape[1]
+    _chk_rows("vit_embed_fwd", patch_f32, "patch", B * P, "B*P")
+    _chk_table("vit_embed_fwd", cls, "cls", patch_f32, None, Cc)
+    _chk_table("vit_embed_fwd", pos, "pos", patch_f32, P + 1, Cc)
     x = torch.empty((B * (P + 1), Cc), dtype=torch.float32, device=patch_f32.device)
     _lib.check(_fn("lc2is_vit_embed_fwd")(_ptr(patch_f32), _ld(patch_f32), _ptr(cls), _ptr(pos), _ptr(x), Cc, B,
                                           P, Cc, _stream()), "vit_embed_fwd")
@@ -763,8 +786,11 @@ def vit_embed_fwd(patch_f32, cls, pos, B: int, P: int):
 
 
 def vit_embed_bwd(dx, dpos, dcls, B: int, P: int, accumulate: bool = False):
-    _chk(dx, torch.float32, "dx"); _chk(dpos, torch.float32, "dpos"); _chk(dcls, torch.float32, "dcls", 1)
+    _chk(dx, torch.float32, "dx")
     Cc = dx.shape[1]
+    _chk_rows("vit_embed_bwd", dx, "dx", B * (P + 1), "B*(P+1)")
+    _chk_table("vit_embed_bwd", dcls, "dcls", dx, None, Cc)
+    _chk_table("vit_embed_bwd", dpos, "dpos", dx, P + 1, Cc)
     dpatch = torch.empty((B * P, Cc), dtype=torch.bfloat16, device=dx.device)
     _lib.check(_fn("lc2is_vit_embed_bwd")(_ptr(dx), _ld(dx), _ptr(dpos), _ptr(dcls), _ptr(dpatch), Cc, B, P, Cc,
                                           int(accumulate), _stream()), "vit_embed_bwd")
@@ -772,11 +798,13 @@ def vit_embed_bwd(dx, dpos, dcls, B: int, P: int, accumulate: bool = False):
 
 
 def text_embed_fwd(ids, tok, pos):
-    _chk(ids, torch.int64, "input_ids"); _chk(tok, torch.float32, "tok"); _chk(pos, torch.float32, "pos")
+    _chk(ids, torch.int64, "input_ids"); _chk(tok, torch.float32, "tok")
     if not ids.is_contiguous():
         raise RuntimeError("lc2is_amd.text_embed_fwd: input_ids must be contiguous")
     B, L = ids.shape
     V, Cc = tok.shape
+    _chk_table("text_embed_fwd", tok, "tok", ids, 1, Cc)
+    _chk_table("text_embed_fwd", pos, "pos", ids, L, Cc)
     x = torch.empty((B * L, Cc), dtype=torch.float32, device=tok.device)
     _lib.check(_fn("lc2is_text_embed_fwd")(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(x), Cc, B, L, Cc, V, _stream()),
                "text_embed_fwd")
@@ -786,8 +814,16 @@ def text_embed_fwd(ids, tok, pos):
 def text_embed_bwd(ids, dx, dtok, dpos, accumulate: bool = False):
     """dtok must already hold the running gradient (or zeros); per-token sums in row order, no atomics (reproducible)."""
     _chk(ids, torch.int64, "input_ids"); _chk(dx, torch.float32, "dx")
+    if not ids.is_contiguous():
+        raise RuntimeError("lc2is_amd.text_embed_bwd: input_ids must be contiguous")
     B, L = ids.shape
-    V, Cc = dtok.shape
+    Cc = dx.shape[1]
+    _chk_rows("text_embed_bwd", dx, "dx", B * L, "B*L")
+    if dx.device != ids.device:
+        raise RuntimeError(f"lc2is_amd.text_embed_bwd: dx is on {dx.device}, input_ids on {ids.device}")
+    _chk_table("text_embed_bwd", dtok, "dtok", ids, 1, Cc)
+    _chk_table("text_embed_bwd", dpos, "dpos", ids, L, Cc)
+    V = dtok.shape[0]
     _lib.check(_fn("lc2is_text_embed_bwd")(_ptr(ids), _ptr(dx), _ld(dx), _ptr(dtok), _ptr(dpos), B, L, Cc, V,
                                            int(accumulate), _stream()), "text_embed_bwd")
 
@@ -1666,6 +1702,7 @@ def bilinear_up_fwd(x, B: int, h: int, w: int, S: int, *, want_f32: bool = True,
     """x fp32 [B*h*w, C] channels-last tokens -> ([B*h*S*w*S, C] fp32 or None, bf16 twin or None)."""
     _dense(x, torch.float32, "x")
     Cc = x.shape[1]
+    _chk_rows("bilinear_up_fwd", x, "x", B * h * w, "B*h*w")
     n = B * h * S * w * S
     of = torch.empty((n, Cc), dtype=torch.float32, device=x.device) if want_f32 else None
     ob = torch.empty((n, Cc), dtype=torch.bfloat16, device=x.device) if want_bf16 else None
@@ -1676,10 +1713,14 @@ def bilinear_up_fwd(x, B: int, h: int, w: int, S: int, *, want_f32: bool = True,
 def bilinear_up_bwd(dout, B: int, h: int, w: int, S: int, *, din=None, accumulate: bool = False, want_bf16: bool = False):
     _dense(dout, torch.float32, "dout")
     Cc = dout.shape[1]
+    _chk_rows("bilinear_up_bwd", dout, "dout", B * h * S * w * S, "B*h*S*w*S")
     if din is None:
         din = torch.empty((B * h * w, Cc), dtype=torch.float32, device=dout.device)
         accumulate = False
     _dense(din, torch.float32, "din")
+    if tuple(din.shape) != (B * h * w, Cc) or din.device != dout.device:
+        raise RuntimeError(f"lc2is_amd.bilinear_up_bwd: din must be [B*h*w, C] = [{B * h * w}, {Cc}] on {dout.device}, got shape "
+                           f"{tuple(din.shape)} on {din.device}")
     d16 = torch.empty((B * h * w, Cc), dtype=torch.bfloat16, device=dout.device) if want_bf16 else None
     _lib.check(_fn("lc2is_bilinear_up_bwd")(_ptr(dout), _ptr(din), _ptr(d16), B, h, w, Cc, S, int(accumulate), _stream()),
                "bilinear_up_bwd")
@@ -1689,10 +1730,16 @@ def bilinear_up_bwd(dout, B: int, h: int, w: int, S: int, *, din=None, accumulat
 def sr_gather(x16, B: int, h: int, w: int, scatter: bool = False):
     """gather: bf16 [B*h*w, C] -> [B*h*w/4, 4C];  scatter: bf16 [B*h*w/4, 4C] -> [B*h*w, C]."""
     _dense(x16, torch.bfloat16, "x")
+    if h % 2 or w % 2:
+        raise RuntimeError(f"lc2is_amd.sr_gather: h and w must be even, got {h} x {w}")
     if scatter:
+        _chk_rows("sr_gather", x16, "x", B * h * w // 4, "B*h*w/4")
+        if x16.shape[1] % 4:
+            raise RuntimeError(f"lc2is_amd.sr_gather: scatter rows hold 4 pixels of C, got shape {tuple(x16.shape)}")
         Cc = x16.shape[1] // 4
         out = torch.empty((B * h * w, Cc), dtype=torch.bfloat16, device=x16.device)
     else:
+        _chk_rows("sr_gather", x16, "x", B * h * w, "B*h*w")
         Cc = x16.shape[1]
         out = torch.empty((B * h * w // 4, 4 * Cc), dtype=torch.bfloat16, device=x16.device)
     _lib.check(_fn("lc2is_sr_gather")(_ptr(x16), _ptr(out), B, h, w, Cc, int(scatter), _stream()), "sr_gather")
@@ -1712,6 +1759,12 @@ def l2norm_fwd(x, eps: float = 1e-12, *, want_f32: bool = True, want_bf16: bool 
 def l2norm_bwd(dy, x, inv, eps: float = 1e-12):
     _dense(dy, torch.float32, "dy"); _dense(x, torch.float32, "x")
     M, Cc = x.shape
+    if dy.shape != x.shape or dy.device != x.device:
+        raise RuntimeError(f"lc2is_amd.l2norm_bwd: dy must match x {tuple(x.shape)} on {x.device}, got {tuple(dy.shape)} on {dy.device}")
+    _chk(inv, torch.float32, "inv", None)
+    if inv.numel() != M or not inv.is_contiguous() or inv.device != x.device:
+        raise RuntimeError(f"lc2is_amd.l2norm_bwd: inv must hold M = {M} contiguous values on {x.device}, got shape "
+                           f"{tuple(inv.shape)} on {inv.device}")
     dx = torch.empty_like(x)
     _lib.check(_fn("lc2is_l2norm_bwd")(_ptr(dy), _ptr(x), _ptr(inv), _ptr(dx), M, Cc, eps, _stream()), "l2norm_bwd")
     return dx
@@ -1736,6 +1789,12 @@ def sr_scatter_add(src16, dst32, B: int, h: int, w: int):
     """dst32 [B*h*w, C] fp32 += scatter(src16 [B*h*w/4, 4C] bf16)."""
     _dense(src16, torch.bfloat16, "src"); _dense(dst32, torch.float32, "dst")
     Cc = dst32.shape[1]
+    if h % 2 or w % 2:
+        raise RuntimeError(f"lc2is_amd.sr_scatter_add: h and w must be even, got {h} x {w}")
+    _chk_rows("sr_scatter_add", dst32, "dst", B * h * w, "B*h*w")
+    if tuple(src16.shape) != (B * h * w // 4, 4 * Cc) or src16.device != dst32.device:
+        raise RuntimeError(f"lc2is_amd.sr_scatter_add: src must be [B*h*w/4, 4C] = [{B * h * w // 4}, {4 * Cc}] on {dst32.device}, "
+                           f"got shape {tuple(src16.shape)} on {src16.device}")
     _lib.check(_fn("lc2is_sr_scatter_add_f32")(_ptr(src16), _ptr(dst32), B, h, w, Cc, _stream()), "sr_scatter_add")
 
 
