@@ -41,6 +41,19 @@ extern "C" {
 
 typedef void* lc2is_stream_t; /* hipStream_t */
 
+/* Base addresses of the dense hot-path operands (lc2is_gemm_nt_* / gemm_tn_* / colsum, layernorm, attention, dropout_rows, swin_attn).
+ * The kernels issue 8- and 16-byte accesses; the `ld %` rules of an entry point make every ROW as aligned as the first, so the
+ * base has to be:
+ *   - bf16 rows with ld % 8 == 0: 16 bytes;  bf16 rows of an entry that admits ld % 4 == 0, with such an ld: 8 bytes;
+ *   - fp32 rows (ld % 4 == 0): 16 bytes;
+ *   - vectors without an ld: 16 bytes where the kernel reads them as float4 (bias of the NT GEMMs, gamma / beta), else 4 (db,
+ *     dgamma / dbeta, mean / rstd, lse, delta, kbias, the Swin bias tables).
+ * A pointer below its rule is refused with LC2IS_ERR_SHAPE, next to the ld checks, before any launch.  NULL passes (optional
+ * operands are tested for NULL elsewhere). */
+#define LC2IS_MISALIGNED(p, bytes) ((p) != NULL && ((uintptr_t)(p) & ((uintptr_t)(bytes) - 1u)) != 0)
+#define LC2IS_MISALIGNED_BF16(p, ld) LC2IS_MISALIGNED(p, ((ld) % 8) ? 8 : 16)
+#define LC2IS_MISALIGNED_F32(p) LC2IS_MISALIGNED(p, 16)
+
 /* One fp32 master weight [N,K] (contiguous) and its bf16 shadows; see lc2is_shadow_refresh. */
 typedef struct {
   const void* src; /* fp32 [N,K]                                               */
@@ -242,7 +255,8 @@ int lc2is_ln_partials_reduce(const lc2is_ln_partials* items, int n, lc2is_stream
 /* ---- attention -----------------------------------------------------------------------------------
  * O[b,s,h,:] = softmax_k( scale * Q[b,s,h,:]·K[b,k,h,:] + kbias[b,k] (+ causal) ) · V[b,k,h,:]
  * Q/K/V/O are token-major 2-D views: row (b*S + s), head h in columns [h*D,(h+1)*D), row stride ld*
- * (elements) — Q, K, V may alias one packed projection buffer.  D in {64, 96, 128}.
+ * (elements) — Q, K, V may alias one packed projection buffer.  D in {64, 96, 128}.  Every ld* is a multiple of 8 (16-byte
+ * row chunks: the operands by LDS-DMA, O and dQ by 16-byte stores), except lddk / lddv, which may be multiples of 4 (8-byte stores).
  * kbias: fp32 [B,Sk] additive key bias in natural-log units, NULL = none.  Per key it is any finite value or -inf
  * (masked); 0 / -inf is key_padding_mask / attention_mask, and the masked keys may be any subset, not only a suffix.
  * +inf and NaN are not allowed.  causal != 0 adds the lower-triangular mask (requires Sq == Sk).

@@ -738,8 +738,13 @@ static int attention_bwd_impl(const void* Q, int ldq, const void* K, int ldk, co
   const int hd = H * D;
   if (ldq < hd || ldk < hd || ldv < hd || ldo < hd || lddo < hd || lddq < hd || lddk < hd || lddv < hd)
     return LC2IS_ERR_SHAPE;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 4 || lddk % 4 || lddv % 4)
+  // (dQ leaves as whole 16-byte chunks, raw_buffer_store_b128 with no narrower path: ld % 8; dK / dV leave as 8-byte stores: ld % 4)
+  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 8 || lddk % 4 || lddv % 4)
     return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED(Q, 16) || LC2IS_MISALIGNED(K, 16) || LC2IS_MISALIGNED(V, 16) || LC2IS_MISALIGNED(O, 16) ||
+      LC2IS_MISALIGNED(dO, 16) || LC2IS_MISALIGNED(dQ, 16) || LC2IS_MISALIGNED_BF16(dK, lddk) || LC2IS_MISALIGNED_BF16(dV, lddv) ||
+      LC2IS_MISALIGNED(lse2, 4) || LC2IS_MISALIGNED(delta, 4) || LC2IS_MISALIGNED(kbias, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (causal && Sq != Sk) return LC2IS_ERR_UNSUPPORTED;
   if (!(p_drop >= 0.f && p_drop < 1.f)) return LC2IS_ERR_UNSUPPORTED;
   const double lim = 2147483648.0;

@@ -413,8 +413,12 @@ static int attention_fwd_impl(const void* Q, int ldq, const void* K, int ldk, co
   hipStream_t stream = (hipStream_t)stream_;
   if (!Q || !K || !V || !O) return LC2IS_ERR_NULL;
   if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return LC2IS_ERR_SHAPE;
-  if (ldq < H * D || ldk < H * D || ldv < H * D || ldo < H * D || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4)
+  // (O leaves as whole 16-byte chunks, raw_buffer_store_b128 with no narrower path: its rows need ld % 8 like the operands')
+  if (ldq < H * D || ldk < H * D || ldv < H * D || ldo < H * D || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8)
     return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED(Q, 16) || LC2IS_MISALIGNED(K, 16) || LC2IS_MISALIGNED(V, 16) || LC2IS_MISALIGNED(O, 16) ||
+      LC2IS_MISALIGNED(lse2, 4) || LC2IS_MISALIGNED(kbias, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (causal && Sq != Sk) return LC2IS_ERR_UNSUPPORTED;
   if (!(p_drop >= 0.f && p_drop < 1.f)) return LC2IS_ERR_UNSUPPORTED;
   if ((double)B * Sq * ldq * 2.0 >= 2147483648.0 || (double)B * (Sk + 64) * ldk * 2.0 >= 2147483648.0 ||

@@ -77,6 +77,8 @@ extern "C" int lc2is_dropout_rows_f32(const float* x, int ldx, const float* resi
   if (M <= 0 || C <= 0 || C % 4 || ldx < C || ldx % 4 || (resid && (ldr < C || ldr % 4)) || (y32 && (ldy < C || ldy % 4)) ||
       (y16 && (ldy16 < C || ldy16 % 4)) || rows_per_sample < 0)
     return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_F32(x) || LC2IS_MISALIGNED_F32(resid) || LC2IS_MISALIGNED_F32(y32) || LC2IS_MISALIGNED_BF16(y16, ldy16))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (!(p >= 0.f && p < 1.f)) return LC2IS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(dropout_rows_f32_kernel, dim3(dr_grid((size_t)M * C / 4)), dim3(256), 0, stream, x, ldx, resid, ldr, y32,
                      ldy, (bf16_t*)y16, ldy16, M, C, rows_per_sample, make_drop_cfg(p, seed));
@@ -88,6 +90,7 @@ extern "C" int lc2is_dropout_rows_bf16(const void* x, int ldx, void* y, int ldy,
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !y) return LC2IS_ERR_NULL;
   if (M <= 0 || C <= 0 || C % 4 || ldx < C || ldx % 4 || ldy < C || ldy % 4) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_BF16(x, ldx) || LC2IS_MISALIGNED_BF16(y, ldy)) return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (!(p >= 0.f && p < 1.f)) return LC2IS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(dropout_rows_bf16_kernel, dim3(dr_grid((size_t)M * C / 4)), dim3(256), 0, stream, (const bf16_t*)x, ldx,
                      (bf16_t*)y, ldy, M, C, make_drop_cfg(p, seed));

@@ -1459,6 +1459,11 @@ int gemm_nt_check(GemmNtArgs& a) {
   if ((a.out_bf16 && (a.ldo < N || a.ldo % 4)) || (a.out_f32 && (a.ldf < N || a.ldf % 4)) || (a.resid && (a.ldr < N || a.ldr % 4)) ||
       (a.aux_in && (a.ldx < N || a.ldx % 4)) || (a.aux_out && (a.ldy < N || a.ldy % 4)))
     return LC2IS_ERR_SHAPE;
+  // base addresses (the rule of lc2is_hip.h): with them, the ld checks above make every row as aligned as its accesses need
+  if (LC2IS_MISALIGNED_BF16(a.A, a.lda) || LC2IS_MISALIGNED_BF16(a.W, a.ldw) || LC2IS_MISALIGNED(a.bias, 16) ||
+      LC2IS_MISALIGNED_F32(a.resid) || LC2IS_MISALIGNED_BF16(a.aux_in, a.ldx) || LC2IS_MISALIGNED_BF16(a.out_bf16, a.ldo) ||
+      LC2IS_MISALIGNED_F32(a.out_f32) || LC2IS_MISALIGNED_BF16(a.aux_out, a.ldy))
+    return LC2IS_ERR_SHAPE;
   if ((act == LC2IS_ACT_DQUICK_GELU || act == LC2IS_ACT_DRELU || act == LC2IS_ACT_MUL_AUX || act == LC2IS_ACT_DGELU_ERF ||
        act == LC2IS_ACT_ADD_AUX) && !a.aux_in)
     return LC2IS_ERR_NULL;
@@ -1524,6 +1529,10 @@ extern "C" int lc2is_gemm_nt_ln_bf16(const void* A, int lda, const void* W, int 
   const int oc = operand_check(M, N, K, lda, ldw);
   if (oc == LC2IS_ERR_SHAPE) return oc;
   if (ldf < N || ldf % 4 || (resid && (ldr < N || ldr % 4)) || ldl < N || ldl % 8) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_BF16(A, lda) || LC2IS_MISALIGNED_BF16(W, ldw) || LC2IS_MISALIGNED(bias, 16) || LC2IS_MISALIGNED_F32(resid) ||
+      LC2IS_MISALIGNED_F32(out_f32) || LC2IS_MISALIGNED(gamma, 16) || LC2IS_MISALIGNED(beta, 16) || LC2IS_MISALIGNED_BF16(ln_out, ldl) ||
+      LC2IS_MISALIGNED(mean, 4) || LC2IS_MISALIGNED(rstd, 4))
+    return LC2IS_ERR_SHAPE;
   if ((N != 384 && N != 768) || M < 256) return LC2IS_ERR_UNSUPPORTED;
   const double lim = 2147483648.0;
   if (oc || (double)M * ldf * 4.0 >= lim || (resid && (double)M * ldr * 4.0 >= lim) || (double)M * ldl * 2.0 >= lim)
@@ -1559,6 +1568,10 @@ extern "C" int lc2is_gemm_nt_bf16_batched(const void* A, int lda, long stride_a,
   const int oc = operand_check(M, N, K, lda, ldw);
   if (oc == LC2IS_ERR_SHAPE || N % 4 != 0 || stride_a % 8 || stride_w % 8) return LC2IS_ERR_SHAPE;
   if ((out_bf16 && (ldo < N || ldo % 4 || stride_ob % 4)) || (out_f32 && (ldf < N || ldf % 4 || stride_of % 4)))
+    return LC2IS_ERR_SHAPE;
+  // (lc2is_hip.h: base addresses; the bf16 output's rows sit on 16-byte boundaries only if ldo AND the batch stride are multiples of 8)
+  if (LC2IS_MISALIGNED_BF16(A, lda) || LC2IS_MISALIGNED_BF16(W, ldw) || LC2IS_MISALIGNED_BF16(out_bf16, ldo | (int)(stride_ob & 7)) ||
+      LC2IS_MISALIGNED_F32(out_f32))
     return LC2IS_ERR_SHAPE;
   if (oc) return oc;
   GemmNtArgs a{(const bf16_t*)A, lda, (const bf16_t*)W, ldw, nullptr, nullptr, 0, nullptr, 0,

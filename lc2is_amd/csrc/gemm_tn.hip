@@ -609,11 +609,12 @@ inline TnEnv tn_env() {
 
 // The operand rules of one problem, in the order both forms refuse in.  `dims_code`: what the caller returns for an empty shape or
 // an N / K off the 8-element grid (LC2IS_ERR_SHAPE from the single form, LC2IS_ERR_UNSUPPORTED from the grouped one).
-inline int tn_operand_check(const void* dY, int ldy, const void* X, int ldx, const float* dW, int ldw, int M, int N, int K,
+inline int tn_operand_check(const void* dY, int ldy, const void* X, int ldx, const float* dW, int ldw, const float* db, int M, int N, int K,
                             int dims_code) {
   if (!dY || !X || !dW) return LC2IS_ERR_NULL;
   if (M <= 0 || N <= 0 || K <= 0 || N % 8 || K % 8) return dims_code;
   if (ldy < N || ldx < K || ldw < K || ldy % 8 || ldx % 8 || ldw % 4) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_BF16(dY, ldy) || LC2IS_MISALIGNED_BF16(X, ldx) || LC2IS_MISALIGNED_F32(dW) || LC2IS_MISALIGNED(db, 4)) return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   const bool past_2gib = (double)(M + 64) * ldy * 2.0 >= 2147483648.0 || (double)(M + 64) * ldx * 2.0 >= 2147483648.0;
   return past_2gib ? LC2IS_ERR_UNSUPPORTED : LC2IS_OK;
 }
@@ -627,7 +628,8 @@ extern "C" size_t lc2is_gemm_tn_workspace_bytes(int M, int N, int K) {
 
 extern "C" int lc2is_gemm_tn_plan(int M, int N, int K, lc2is_tn_plan* out) {
   if (!out) return LC2IS_ERR_NULL;
-  if (const int rc = tn_operand_check(out, N, out, K, (const float*)out, K, M, N, K, LC2IS_ERR_SHAPE)) return rc;   // (densely packed operands)
+  const void* dense = (const void*)(uintptr_t)4096;   // (densely packed, aligned operands: no pointer is dereferenced)
+  if (const int rc = tn_operand_check(dense, N, dense, K, (const float*)dense, K, nullptr, M, N, K, LC2IS_ERR_SHAPE)) return rc;
   const TnEnv env = tn_env();
   const TnPlan p = tn_plan(M, N, K, env.ncu, env.force);
   *out = {p.big, p.ntn, p.ntk, p.splits, p.chunk, p.grid(), p.red_grid(N, K), (long long)p.bytes(N, K)};
@@ -638,7 +640,7 @@ extern "C" int lc2is_gemm_tn_bf16(const void* dY, int ldy, const void* X, int ld
                                   int M, int N, int K, int accumulate, void* workspace, size_t workspace_bytes,
                                   lc2is_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = tn_operand_check(dY, ldy, X, ldx, dW, ldw, M, N, K, LC2IS_ERR_SHAPE);
+  int rc = tn_operand_check(dY, ldy, X, ldx, dW, ldw, db, M, N, K, LC2IS_ERR_SHAPE);
   if (rc) return rc;
   const TnEnv env = tn_env();
   const TnPlan p = tn_plan(M, N, K, env.ncu, env.force);   // the launch and its workspace need come from this one plan
@@ -673,7 +675,7 @@ struct TgPlan {
 inline int tg_valid(const lc2is_tn_problem* pr, int n) {
   if (!pr || n <= 0 || n > TG_TBL_MAX) return LC2IS_ERR_UNSUPPORTED;
   for (const lc2is_tn_problem* q = pr; q < pr + n; ++q)
-    if (const int rc = tn_operand_check(q->dY, q->ldy, q->X, q->ldx, q->dW, q->ldw, q->M, q->N, q->K, LC2IS_ERR_UNSUPPORTED)) return rc;
+    if (const int rc = tn_operand_check(q->dY, q->ldy, q->X, q->ldx, q->dW, q->ldw, q->db, q->M, q->N, q->K, LC2IS_ERR_UNSUPPORTED)) return rc;
   return LC2IS_OK;
 }
 
@@ -917,6 +919,7 @@ extern "C" int lc2is_colsum_bf16(const void* dY, int ldy, float* db, int M, int 
   hipStream_t stream = (hipStream_t)stream_;
   if (!dY || !db) return LC2IS_ERR_NULL;
   if (M <= 0 || N <= 0 || N % 8 || ldy < N || ldy % 8) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_BF16(dY, ldy) || LC2IS_MISALIGNED(db, 4)) return LC2IS_ERR_SHAPE;
   if (!workspace || workspace_bytes < lc2is_colsum_workspace_bytes(M, N)) return LC2IS_ERR_WORKSPACE;
   const int parts = colsum_parts(M);
   hipLaunchKernelGGL(colsum_kernel, dim3((N / 8 + 63) / 64, parts), dim3(256), 0, stream, (const bf16_t*)dY,

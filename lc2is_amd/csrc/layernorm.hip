@@ -357,6 +357,9 @@ extern "C" int lc2is_layernorm_fwd(const void* x, int ldx, int x_is_bf16, const 
   if (M <= 0 || C <= 0 || C % 4 || C > LN_MAXV * 256) return LC2IS_ERR_SHAPE;
   if (ldx < C || ldx % 4 || (y_bf16 && (ldy < C || ldy % 4)) || (y_f32 && (ldyf < C || ldyf % 4)))
     return LC2IS_ERR_SHAPE;
+  if ((x_is_bf16 ? LC2IS_MISALIGNED_BF16(x, ldx) : LC2IS_MISALIGNED_F32(x)) || LC2IS_MISALIGNED(gamma, 16) || LC2IS_MISALIGNED(beta, 16) ||
+      LC2IS_MISALIGNED_BF16(y_bf16, ldy) || LC2IS_MISALIGNED_F32(y_f32) || LC2IS_MISALIGNED(mean, 4) || LC2IS_MISALIGNED(rstd, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
 #define LN_FWD(NV_)                                                                                  \
   hipLaunchKernelGGL(ln_fwd_kernel<NV_>, dim3(ln_fwd_blocks(M)), dim3(256), 0, stream, xf, xb, ldx, gamma, beta, \
                      (bf16_t*)y_bf16, ldy, y_f32, ldyf, mean, rstd, M, C, eps)
@@ -390,6 +393,11 @@ extern "C" int lc2is_layernorm_bwd(const void* dy_bf16, int lddy, const float* d
   if ((dres && (lddres < C || lddres % 4)) || (dx_f32 && (lddx < C || lddx % 4)) ||
       (dx_bf16 && (lddxb < C || lddxb % 4)))
     return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED_BF16(dy_bf16, lddy) || LC2IS_MISALIGNED_F32(dy_f32) || (x_is_bf16 ? LC2IS_MISALIGNED_BF16(x, ldx) : LC2IS_MISALIGNED_F32(x)) ||
+      LC2IS_MISALIGNED(gamma, 16) || LC2IS_MISALIGNED(mean, 4) || LC2IS_MISALIGNED(rstd, 4) ||
+      (dres_is_bf16 ? LC2IS_MISALIGNED_BF16(dres, lddres) : LC2IS_MISALIGNED_F32(dres)) || LC2IS_MISALIGNED_F32(dx_f32) ||
+      LC2IS_MISALIGNED_BF16(dx_bf16, lddxb) || LC2IS_MISALIGNED(dgamma, 4) || LC2IS_MISALIGNED(dbeta, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (!workspace || workspace_bytes < lc2is_layernorm_bwd_workspace_bytes(M, C)) return LC2IS_ERR_WORKSPACE;
   const int nblk = ln_bwd_blocks(M, C);
   const int nv = (C / 4 + 63) / 64;

@@ -452,6 +452,8 @@ extern "C" int lc2is_swin_attn_fwd(const void* qkv, int ld, void* out, int ldo, 
   int rc = sw_check(nwin, win_per_img, nwx, Hp, Wp, ws, shift, nH, C);
   if (rc) return rc;
   if (ld < 3 * C || ldo < C || ld % 8 || ldo % 8) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED(qkv, 16) || LC2IS_MISALIGNED(out, 16) || LC2IS_MISALIGNED(lse, 4) || LC2IS_MISALIGNED(bias, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   SwinAttnArgs a{};
   a.qkv = (const bf16_t*)qkv; a.ld = ld; a.out = (bf16_t*)out; a.ldo = ldo; a.lse = lse; a.bias = bias;
   a.nwin = nwin; a.win_per_img = win_per_img; a.nwx = nwx; a.Hp = Hp; a.Wp = Wp; a.ws = ws; a.shift = shift; a.nH = nH;
@@ -482,6 +484,9 @@ extern "C" int lc2is_swin_attn_bwd(const void* qkv, int ld, const void* o, int l
   int rc = sw_check(nwin, win_per_img, nwx, Hp, Wp, ws, shift, nH, C);
   if (rc) return rc;
   if (ld < 3 * C || lddq < 3 * C || ld_o < C || lddo < C || ld % 8 || lddq % 8 || ld_o % 8 || lddo % 8) return LC2IS_ERR_SHAPE;
+  if (LC2IS_MISALIGNED(qkv, 16) || LC2IS_MISALIGNED(o, 16) || LC2IS_MISALIGNED(dout, 16) || LC2IS_MISALIGNED(dqkv, 16) ||
+      LC2IS_MISALIGNED(lse, 4) || LC2IS_MISALIGNED(bias, 4) || LC2IS_MISALIGNED(dbias, 4))
+    return LC2IS_ERR_SHAPE;   // (lc2is_hip.h: base addresses)
   if (dbias && (!workspace || workspace_bytes < lc2is_swin_attn_bwd_workspace_bytes(nwin, ws, nH))) return LC2IS_ERR_WORKSPACE;
   int nchunk = sw_chunks(nwin, nH);
   {   // the kernel holds 34 KB of LDS and ~300 registers: four single-wave blocks per CU, one round of them

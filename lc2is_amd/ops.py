@@ -181,6 +181,63 @@ def _chk(t: torch.Tensor | None, dtype, name: str, ndim: int | None = 2):
         raise RuntimeError(f"lc2is_amd: {name} must have unit stride in its last dimension")
 
 
+def _dims(who: str, t: torch.Tensor, name: str, ndim: int = 2, dtype=None):
+    """The shape of an operand that DEFINES sizes of the call.  With ``dtype``: the call's first operand, which also gives the device
+    every other operand is held to — it has to be on the GPU and passes everything _chk_op asks of rows (its shape being its own)."""
+    if t.dim() == ndim:
+        if dtype is None:
+            return t.shape
+        if t.is_cuda and t.dtype is dtype:
+            st = t.stride()
+            if st[-1] == 1 and t.data_ptr() % (8 if dtype is torch.bfloat16 and st[-2] % 8 else 16) == 0:
+                return t.shape
+    if dtype is not None and not t.is_cuda:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be a CUDA(HIP) tensor; there is no CPU path")
+    if t.dim() != ndim:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be {ndim}-D, got shape {tuple(t.shape)}")
+    _chk_op(who, t, name, dtype, t.shape, t.device)      # (raises: names the rule)
+    raise AssertionError("unreachable")
+
+
+def _chk_op(who: str, t: torch.Tensor | None, name: str, dtype, shape, dev, vec: int = 0):
+    """One operand of a dense hot-path launcher.  The kernels index every tensor by the call's integers alone and issue 8- and
+    16-byte accesses, so a tensor on another device, of another dtype or shape, or with a base below the alignment rule of
+    include/lc2is_hip.h is refused here, before any launch.  ``vec`` = 0: rows with a leading dimension (unit inner stride;
+    16-byte base, 8 for bf16 rows whose ld is only a multiple of 4).  ``vec`` > 0: a tensor the kernel takes no ld for — it must be
+    contiguous with a ``vec``-byte base (16 where the kernel reads it as float4, else 4)."""
+    if t is None:
+        return
+    if t.device == dev and t.dtype is dtype and t.shape == shape:
+        if vec:
+            if t.is_contiguous() and t.data_ptr() % vec == 0:
+                return
+        else:
+            st = t.stride()   # (one call: cheaper than two stride(i))
+            if st[-1] == 1 and t.data_ptr() % (8 if dtype is torch.bfloat16 and st[-2] % 8 else 16) == 0:
+                return
+    # the slow path: which rule it was
+    if t.device != dev:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} is on {t.device}, the first operand on {dev}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be {dtype}, got {t.dtype}")
+    if t.shape != shape:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if vec and not t.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous (the kernel takes no leading dimension for it)")
+    if not vec and t.stride(-1) != 1:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must have unit stride in its last dimension")
+    raise RuntimeError(f"lc2is_amd.{who}: {name} has a base address below the alignment its accesses need "
+                       f"(data_ptr % 16 = {t.data_ptr() % 16}, strides {tuple(t.stride())})")
+
+
+def _chk_ld8(who: str, t: torch.Tensor, name: str):
+    """bf16 rows the attention kernels store as whole 16-byte chunks and have no narrower path for: every row has to begin on a
+    16-byte boundary, i.e. ld % 8 == 0 (the launchers refuse the same)."""
+    if t.stride(0) % 8:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} needs a leading dimension that is a multiple of 8 (16-byte stores), "
+                           f"got {t.stride(0)}")
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
@@ -220,23 +277,27 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, 
     residual stream: the add runs as the ACT_ADD_AUX epilogue, needs act == ACT_NONE and no other aux_in).
     ``out_bf16`` / ``out_f32`` / ``aux_out``: True = allocate, tensor = write into it, None/False = skip.
     Returns (out_bf16, out_f32, aux_out) with None for skipped outputs."""
-    _chk(a, torch.bfloat16, "a"); _chk(w, torch.bfloat16, "w")
-    if resid is not None and resid.dtype == torch.bfloat16:
-        if act != ACT_NONE or aux_in is not None:
-            raise RuntimeError("lc2is_amd.gemm_nt: a bf16 residual needs act == ACT_NONE and no aux_in")
-        act, aux_in, resid = ACT_ADD_AUX, resid, None
-    _chk(bias, torch.float32, "bias", 1); _chk(resid, torch.float32, "resid"); _chk(aux_in, torch.bfloat16, "aux_in")
-    M, K = a.shape
-    N, K2 = w.shape
-    if K2 != K:
-        raise RuntimeError(f"lc2is_amd.gemm_nt: K mismatch {K} vs {K2}")
-    if bias is not None and bias.numel() != N:
-        raise RuntimeError("lc2is_amd.gemm_nt: bias length != N")
+    who, bf, f32, aux_name = "gemm_nt", torch.bfloat16, torch.float32, "aux_in"
+    M, K = _dims(who, a, "a", 2, bf)
     dev = a.device
-    ob = _out(out_bf16, (M, N), torch.bfloat16, dev)
-    of = _out(out_f32, (M, N), torch.float32, dev)
-    ao = _out(aux_out, (M, N), torch.bfloat16, dev)
-    _chk(ob, torch.bfloat16, "out_bf16"); _chk(of, torch.float32, "out_f32"); _chk(ao, torch.bfloat16, "aux_out")
+    N = _dims(who, w, "w")[0]
+    mn = (M, N)
+    _chk_op(who, w, "w", bf, (N, K), dev)
+    if resid is not None and resid.dtype == bf:
+        if act != ACT_NONE or aux_in is not None:
+            raise RuntimeError("lc2is_amd.gemm_nt: resid in bf16 needs act == ACT_NONE and no aux_in")
+        act, aux_in, resid, aux_name = ACT_ADD_AUX, resid, None, "resid"
+    _chk_op(who, bias, "bias", f32, (N,), dev, 16); _chk_op(who, resid, "resid", f32, mn, dev)
+    _chk_op(who, aux_in, aux_name, bf, mn, dev)
+    ob = _out(out_bf16, mn, bf, dev)
+    of = _out(out_f32, mn, f32, dev)
+    ao = _out(aux_out, mn, bf, dev)
+    if out_bf16 is not True:   # (what _out allocated above needs no check)
+        _chk_op(who, ob, "out_bf16", bf, mn, dev)
+    if out_f32 is not True:
+        _chk_op(who, of, "out_f32", f32, mn, dev)
+    if aux_out is not True:
+        _chk_op(who, ao, "aux_out", bf, mn, dev)
     rc = _fn("lc2is_gemm_nt_bf16")(_ptr(a), _ld(a), _ptr(w), _ld(w), _ptr(bias), _ptr(resid), _ld(resid),
                                    _ptr(aux_in), _ld(aux_in), _ptr(ob), _ld(ob), _ptr(of), _ld(of), _ptr(ao),
                                    _ld(ao), M, N, K, act, tile_cfg, _stream())
@@ -288,15 +349,18 @@ def gemm_nt_ln(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, resi
     """x = a @ w.T + bias (+ resid) in fp32 AND h = bf16(LayerNorm(x) * gamma + beta) in ONE launch (256x384 tiles, the two column
     tiles of a row tile exchange row statistics).  a [M,K] bf16, w [N,K] bf16 with N in (384, 768), resid fp32 [M,N].
     Returns (x_f32, h_bf16, mean, rstd) — what gemm_nt(..., out_f32=True) followed by layernorm_fwd returns."""
-    _chk(a, torch.bfloat16, "a"); _chk(w, torch.bfloat16, "w"); _chk(bias, torch.float32, "bias", 1)
-    _chk(resid, torch.float32, "resid"); _chk(gamma, torch.float32, "gamma", 1); _chk(beta, torch.float32, "beta", 1)
-    M, K = a.shape
-    N, K2 = w.shape
-    if K2 != K or gamma.numel() != N or (bias is not None and bias.numel() != N) or (beta is not None and beta.numel() != N):
-        raise RuntimeError("lc2is_amd.gemm_nt_ln: shape mismatch")
+    who, bf, f32 = "gemm_nt_ln", torch.bfloat16, torch.float32
+    M, K = _dims(who, a, "a", 2, bf)
     dev = a.device
-    xf = _out(out_f32 if out_f32 is not None else True, (M, N), torch.float32, dev)
-    h = _out(ln_out if ln_out is not None else True, (M, N), torch.bfloat16, dev)
+    N = _dims(who, w, "w")[0]
+    _chk_op(who, w, "w", bf, (N, K), dev); _chk_op(who, bias, "bias", f32, (N,), dev, 16)
+    _chk_op(who, resid, "resid", f32, (M, N), dev)
+    if gamma is None:
+        raise RuntimeError("lc2is_amd.gemm_nt_ln: gamma is required")
+    _chk_op(who, gamma, "gamma", f32, (N,), dev, 16); _chk_op(who, beta, "beta", f32, (N,), dev, 16)
+    xf = _out(out_f32 if out_f32 is not None else True, (M, N), f32, dev)
+    h = _out(ln_out if ln_out is not None else True, (M, N), bf, dev)
+    _chk_op(who, out_f32, "out_f32", f32, (M, N), dev); _chk_op(who, ln_out, "ln_out", bf, (M, N), dev)
     mean = torch.empty((M,), dtype=torch.float32, device=dev) if save_stats else None
     rstd = torch.empty((M,), dtype=torch.float32, device=dev) if save_stats else None
     nb = _fn("lc2is_gemm_nt_ln_xchg_bytes")(M, N)
@@ -318,14 +382,16 @@ def gemm_nt_batched(a: torch.Tensor, w: torch.Tensor, *, out_bf16: torch.Tensor 
                     out_f32: torch.Tensor | bool | None = True):
     """out[b] = a[b] @ w[b].T for every b in ONE launch.  a [B,M,K] bf16, w [B,N,K] bf16 (unit inner stride; any row /
     batch strides that are multiples of 8 elements).  Returns (out_bf16 [B,M,N] or None, out_f32 [B,M,N] or None)."""
-    _chk(a, torch.bfloat16, "a", 3); _chk(w, torch.bfloat16, "w", 3)
-    Bn, M, K = a.shape
-    if w.shape[0] != Bn or w.shape[2] != K:
-        raise RuntimeError(f"lc2is_amd.gemm_nt_batched: shape mismatch {tuple(a.shape)} vs {tuple(w.shape)}")
-    N = w.shape[1]
-    ob = _out(out_bf16, (Bn, M, N), torch.bfloat16, a.device)
-    of = _out(out_f32, (Bn, M, N), torch.float32, a.device)
-    _chk(ob, torch.bfloat16, "out_bf16", 3); _chk(of, torch.float32, "out_f32", 3)
+    who, dev = "gemm_nt_batched", a.device
+    Bn, M, K = _dims(who, a, "a", 3, torch.bfloat16)
+    N = _dims(who, w, "w", 3)[1]
+    _chk_op(who, w, "w", torch.bfloat16, (Bn, N, K), dev)
+    ob = _out(out_bf16, (Bn, M, N), torch.bfloat16, dev)
+    of = _out(out_f32, (Bn, M, N), torch.float32, dev)
+    if out_bf16 is not True:
+        _chk_op(who, ob, "out_bf16", torch.bfloat16, (Bn, M, N), dev)
+    if out_f32 is not True:
+        _chk_op(who, of, "out_f32", torch.float32, (Bn, M, N), dev)
     st = lambda t: (0, 0) if t is None else (t.stride(1), t.stride(0))  # noqa: E731
     rc = _fn("lc2is_gemm_nt_bf16_batched")(_ptr(a), a.stride(1), a.stride(0), _ptr(w), w.stride(1), w.stride(0),
                                            _ptr(ob), *st(ob), _ptr(of), *st(of), M, N, K, Bn, _stream())
@@ -346,17 +412,16 @@ def transpose_bf16_batched(x: torch.Tensor) -> torch.Tensor:
 def gemm_tn(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor | None = None, accumulate: bool = False,
             db: torch.Tensor | None = None):
     """dw[N,K] (fp32) = dy[M,N]^T @ x[M,K]; optional fused bias gradient db[N] = dy.sum(0) (same accumulate flag)."""
-    _chk(dy, torch.bfloat16, "dy"); _chk(x, torch.bfloat16, "x")
-    M, N = dy.shape
-    M2, K = x.shape
-    if M2 != M:
-        raise RuntimeError("lc2is_amd.gemm_tn: M mismatch")
+    who, dev = "gemm_tn", dy.device
+    M, N = _dims(who, dy, "dy", 2, torch.bfloat16)
+    K = _dims(who, x, "x")[1]
+    _chk_op(who, x, "x", torch.bfloat16, (M, K), dev)
     if dw is None:
-        dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+        dw = torch.empty((N, K), dtype=torch.float32, device=dev)
         accumulate = False
-    _chk(dw, torch.float32, "dw"); _chk(db, torch.float32, "db", 1)
-    if db is not None and db.numel() != N:
-        raise RuntimeError("lc2is_amd.gemm_tn: db length != N")
+    else:
+        _chk_op(who, dw, "dw", torch.float32, (N, K), dev)
+    _chk_op(who, db, "db", torch.float32, (N,), dev, 4)
     nbytes = _fn("lc2is_gemm_tn_workspace_bytes")(M, N, K)
     ws = workspace(nbytes, dy.device, "gemm_tn")
     rc = _fn("lc2is_gemm_tn_bf16")(_ptr(dy), _ld(dy), _ptr(x), _ld(x), _ptr(dw), _ld(dw), _ptr(db), M, N, K,
@@ -400,12 +465,20 @@ def gemm_tn_grouped(problems):
     if not 1 <= len(problems) <= GROUP_MAX:
         raise RuntimeError(f"lc2is_amd.gemm_tn_grouped: 1..{GROUP_MAX} problems per launch")
     arr = (TnProblem * len(problems))()
+    who, dev = "gemm_tn_grouped", problems[0][0].device
     for i, (dy, x, dw, db, acc) in enumerate(problems):
-        _chk(dy, torch.bfloat16, "dy"); _chk(x, torch.bfloat16, "x"); _chk(dw, torch.float32, "dw"); _chk(db, torch.float32, "db", 1)
-        M, N = dy.shape
-        if x.shape[0] != M or tuple(dw.shape) != (N, x.shape[1]) or (db is not None and db.numel() != N):
-            raise RuntimeError("lc2is_amd.gemm_tn_grouped: shape mismatch")
-        arr[i] = TnProblem(_ptr(dy), _ptr(x), _ptr(dw), _ptr(db), _ld(dy), _ld(x), _ld(dw), M, N, x.shape[1], int(acc))
+        try:
+            M, N = _dims(who, dy, "dy", 2, torch.bfloat16)
+            K = _dims(who, x, "x")[1]
+            if i:
+                _chk_op(who, dy, "dy", torch.bfloat16, (M, N), dev)      # (on the first problem's device)
+            _chk_op(who, x, "x", torch.bfloat16, (M, K), dev)
+            if dw is None:
+                raise RuntimeError("lc2is_amd.gemm_tn_grouped: dw is required")
+            _chk_op(who, dw, "dw", torch.float32, (N, K), dev); _chk_op(who, db, "db", torch.float32, (N,), dev, 4)
+        except RuntimeError as e:
+            raise RuntimeError(f"{e} (problem {i})") from None
+        arr[i] = TnProblem(_ptr(dy), _ptr(x), _ptr(dw), _ptr(db), _ld(dy), _ld(x), _ld(dw), M, N, K, int(acc))
     nbytes = _fn("lc2is_gemm_tn_grouped_workspace_bytes")(arr, len(problems))
     ws = workspace(nbytes, problems[0][0].device, "gemm_tn_grouped")
     rc = _fn("lc2is_gemm_tn_grouped")(arr, len(problems), _ptr(ws), ws.numel(), _stream())
@@ -456,12 +529,12 @@ def release_captured_tables_range(first: int, last: int) -> int:
 
 def colsum(dy: torch.Tensor, db: torch.Tensor | None = None, accumulate: bool = False):
     """db[N] (fp32) = dy[M,N].sum(0)."""
-    _chk(dy, torch.bfloat16, "dy")
-    M, N = dy.shape
+    M, N = _dims("colsum", dy, "dy", 2, torch.bfloat16)
     if db is None:
         db = torch.empty((N,), dtype=torch.float32, device=dy.device)
         accumulate = False
-    _chk(db, torch.float32, "db", 1)
+    else:
+        _chk_op("colsum", db, "db", torch.float32, (N,), dy.device, 4)
     nbytes = _fn("lc2is_colsum_workspace_bytes")(M, N)
     ws = workspace(nbytes, dy.device, "colsum")
     rc = _fn("lc2is_colsum_bf16")(_ptr(dy), _ld(dy), _ptr(db), M, N, int(accumulate), _ptr(ws), ws.numel(),
@@ -474,12 +547,19 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor | Non
                   save_stats: bool = True, out_bf16: torch.Tensor | bool | None = True,
                   out_f32: torch.Tensor | bool | None = None):
     """x fp32 or bf16 [M,C] (the residual stream) -> (y_bf16, y_f32, mean, rstd)."""
-    xb = x.dtype == torch.bfloat16
-    _chk(x, torch.bfloat16 if xb else torch.float32, "x"); _chk(gamma, torch.float32, "gamma", 1); _chk(beta, torch.float32, "beta", 1)
-    M, Cc = x.shape
+    who, bf, f32 = "layernorm_fwd", torch.bfloat16, torch.float32
+    xb = x.dtype == bf
+    M, Cc = _dims(who, x, "x", 2, bf if xb else f32)
     dev = x.device
-    yb = _out(out_bf16, (M, Cc), torch.bfloat16, dev)
-    yf = _out(out_f32, (M, Cc), torch.float32, dev)
+    if gamma is None:
+        raise RuntimeError("lc2is_amd.layernorm_fwd: gamma is required")
+    _chk_op(who, gamma, "gamma", f32, (Cc,), dev, 16); _chk_op(who, beta, "beta", f32, (Cc,), dev, 16)
+    yb = _out(out_bf16, (M, Cc), bf, dev)
+    yf = _out(out_f32, (M, Cc), f32, dev)
+    if out_bf16 is not True:
+        _chk_op(who, yb, "out_bf16", bf, (M, Cc), dev)
+    if out_f32 is not True:
+        _chk_op(who, yf, "out_f32", f32, (M, Cc), dev)
     mean = torch.empty((M,), dtype=torch.float32, device=dev) if save_stats else None
     rstd = torch.empty((M,), dtype=torch.float32, device=dev) if save_stats else None
     rc = _fn("lc2is_layernorm_fwd")(_ptr(x), _ld(x), int(xb), _ptr(gamma), _ptr(beta), _ptr(yb), _ld(yb), _ptr(yf),
@@ -494,16 +574,21 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, mean: 
                   want_bf16: bool = True, need_param_grads: bool = True):
     """Returns (dx_f32, dx_bf16, dgamma, dbeta).  dy, x (the residual stream the forward normalised) and dres (the gradient
     arriving over the residual path) are each bf16 or fp32 [M,C]."""
-    M, Cc = x.shape
+    who, bf, f32 = "layernorm_bwd", torch.bfloat16, torch.float32
+    xb = x.dtype == bf
+    M, Cc = _dims(who, x, "x", 2, bf if xb else f32)
     dev = x.device
-    dyb = dy if dy.dtype == torch.bfloat16 else None
-    dyf = dy if dy.dtype == torch.float32 else None
+    dyb = dy if dy.dtype == bf else None
+    dyf = dy if dy.dtype == f32 else None
     if dyb is None and dyf is None:
         raise RuntimeError("lc2is_amd.layernorm_bwd: dy must be bf16 or fp32")
-    xb = x.dtype == torch.bfloat16
-    rb = dres is not None and dres.dtype == torch.bfloat16
-    _chk(dyb, torch.bfloat16, "dy"); _chk(dyf, torch.float32, "dy"); _chk(x, torch.bfloat16 if xb else torch.float32, "x")
-    _chk(dres, torch.bfloat16 if rb else torch.float32, "dres")
+    rb = dres is not None and dres.dtype == bf
+    _chk_op(who, dy, "dy", dy.dtype, (M, Cc), dev)
+    _chk_op(who, dres, "dres", bf if rb else f32, (M, Cc), dev)
+    if gamma is None or mean is None or rstd is None:
+        raise RuntimeError("lc2is_amd.layernorm_bwd: gamma, mean and rstd are required")
+    _chk_op(who, gamma, "gamma", f32, (Cc,), dev, 16); _chk_op(who, mean, "mean", f32, (M,), dev, 4); _chk_op(who, rstd, "rstd", f32, (M,), dev, 4)
+    _chk_op(who, dgamma, "dgamma", f32, (Cc,), dev, 4); _chk_op(who, dbeta, "dbeta", f32, (Cc,), dev, 4)
     dxf = torch.empty((M, Cc), dtype=torch.float32, device=dev) if want_f32 else None
     dxb = torch.empty((M, Cc), dtype=torch.bfloat16, device=dev) if want_bf16 else None
     if need_param_grads:
@@ -589,14 +674,17 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, H: 
     kbias: fp32 contiguous [B,Sk] additive key bias, per key any finite value or -inf (masked); any subset of the keys may be
     masked.  A query row with no visible key gives O = 0 and lse2 = -inf (torch gives NaN).  The K / V rows of masked keys
     do not matter as long as they are finite."""
-    _chk(q, torch.bfloat16, "q"); _chk(k, torch.bfloat16, "k"); _chk(v, torch.bfloat16, "v")
-    _chk(kbias, torch.float32, "kbias")
-    if q.shape != (B * Sq, H * D) or k.shape != (B * Sk, H * D) or v.shape != (B * Sk, H * D):
-        raise RuntimeError("lc2is_amd.attention_fwd: q/k/v shapes do not match B,H,S,D")
-    if kbias is not None and (kbias.shape != (B, Sk) or not kbias.is_contiguous()):
-        raise RuntimeError("lc2is_amd.attention_fwd: kbias must be contiguous [B,Sk]")
-    o = out if out is not None else torch.empty((B * Sq, H * D), dtype=torch.bfloat16, device=q.device)
-    _chk(o, torch.bfloat16, "out")
+    who, bf = "attention_fwd", torch.bfloat16
+    dev, qs, ks = q.device, (B * Sq, H * D), (B * Sk, H * D)
+    if _dims(who, q, "q", 2, bf) != qs:
+        raise RuntimeError(f"lc2is_amd.attention_fwd: q must have shape {qs}, got {tuple(q.shape)}")
+    _chk_op(who, k, "k", bf, ks, dev); _chk_op(who, v, "v", bf, ks, dev)
+    _chk_op(who, kbias, "kbias", torch.float32, (B, Sk), dev, 4)
+    o = out
+    if o is None:
+        o = torch.empty(qs, dtype=bf, device=dev)
+    else:
+        _chk_op(who, o, "out", bf, qs, dev); _chk_ld8(who, o, "out")
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if save_lse else None
     if dropout_p > 0.0:
         rc = _fn("lc2is_attention_fwd_dropout")(_ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(o), _ld(o),
@@ -616,15 +704,24 @@ def attention_bwd(q, k, v, o, do, lse2, B: int, H: int, Sq: int, Sk: int, D: int
     """Returns (dq, dk, dv) bf16; dq/dk/dv may be preallocated 2-D views (e.g. slices of a packed dQKV).
     kbias / causal / dropout_p / seed as passed to attention_fwd.  A row whose lse2 is -inf (no visible key) gets dq = 0 and
     gives nothing to dk / dv; the dk / dv rows of masked keys are 0."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        _chk(t, torch.bfloat16, n)
-    _chk(lse2, torch.float32, "lse2", 3); _chk(kbias, torch.float32, "kbias")
-    dev = q.device
-    dq = dq if dq is not None else torch.empty((B * Sq, H * D), dtype=torch.bfloat16, device=dev)
-    dk = dk if dk is not None else torch.empty((B * Sk, H * D), dtype=torch.bfloat16, device=dev)
-    dv = dv if dv is not None else torch.empty((B * Sk, H * D), dtype=torch.bfloat16, device=dev)
-    for t, n in ((dq, "dq"), (dk, "dk"), (dv, "dv")):
-        _chk(t, torch.bfloat16, n)
+    who, bf = "attention_bwd", torch.bfloat16
+    dev, qs, ks = q.device, (B * Sq, H * D), (B * Sk, H * D)
+    if _dims(who, q, "q", 2, bf) != qs:
+        raise RuntimeError(f"lc2is_amd.attention_bwd: q must have shape {qs}, got {tuple(q.shape)}")
+    for t, n, s in ((k, "k", ks), (v, "v", ks), (o, "o", qs), (do, "do", qs)):
+        if t is None:
+            raise RuntimeError(f"lc2is_amd.attention_bwd: {n} is required")
+        _chk_op(who, t, n, bf, s, dev)
+    _chk_op(who, dq, "dq", bf, qs, dev); _chk_op(who, dk, "dk", bf, ks, dev); _chk_op(who, dv, "dv", bf, ks, dev)
+    if dq is None:
+        dq = torch.empty(qs, dtype=bf, device=dev)
+    else:
+        _chk_ld8(who, dq, "dq")   # (dk / dv leave as 8-byte stores: ld % 4 is enough for them)
+    dk = dk if dk is not None else torch.empty(ks, dtype=bf, device=dev)
+    dv = dv if dv is not None else torch.empty(ks, dtype=bf, device=dev)
+    if lse2 is None:
+        raise RuntimeError("lc2is_amd.attention_bwd: lse2 is required")
+    _chk_op(who, lse2, "lse2", torch.float32, (B, H, Sq), dev, 4); _chk_op(who, kbias, "kbias", torch.float32, (B, Sk), dev, 4)
     delta = torch.empty((B, H, Sq), dtype=torch.float32, device=dev)
     args = (_ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(o), _ld(o), _ptr(do), _ld(do), _ptr(dq), _ld(dq),
             _ptr(dk), _ld(dk), _ptr(dv), _ld(dv), _ptr(lse2), _ptr(delta), _ptr(kbias), B, H, Sq, Sk, D, float(scale),
@@ -643,11 +740,15 @@ def dropout_rows_f32(x: torch.Tensor, p: float, seed: int, *, resid: torch.Tenso
     """y = resid + keep * x / (1 - p) on fp32 rows [M,C]; one decision per element, or per sample of `rows_per_sample` rows
     (drop-path).  Returns (y_f32 or None, y_bf16 or None).  Applied to a gradient with the forward's (p, seed) it is the
     backward of the same site."""
-    _chk(x, torch.float32, "x"); _chk(resid, torch.float32, "resid")
-    M, Cc = x.shape
-    yf = _out(out_f32, (M, Cc), torch.float32, x.device)
-    yb = _out(out_bf16, (M, Cc), torch.bfloat16, x.device)
-    _chk(yf, torch.float32, "out_f32"); _chk(yb, torch.bfloat16, "out_bf16")
+    who, dev = "dropout_rows_f32", x.device
+    M, Cc = _dims(who, x, "x", 2, torch.float32)
+    _chk_op(who, resid, "resid", torch.float32, (M, Cc), dev)
+    yf = _out(out_f32, (M, Cc), torch.float32, dev)
+    yb = _out(out_bf16, (M, Cc), torch.bfloat16, dev)
+    if out_f32 is not True:
+        _chk_op(who, yf, "out_f32", torch.float32, (M, Cc), dev)
+    if out_bf16 is not True:
+        _chk_op(who, yb, "out_bf16", torch.bfloat16, (M, Cc), dev)
     rc = _fn("lc2is_dropout_rows_f32")(_ptr(x), _ld(x), _ptr(resid), _ld(resid), _ptr(yf), _ld(yf), _ptr(yb), _ld(yb), M, Cc,
                                        int(rows_per_sample), float(p), int(seed), _stream())
     _lib.check(rc, f"dropout_rows_f32 M={M} C={Cc}")
@@ -656,10 +757,9 @@ def dropout_rows_f32(x: torch.Tensor, p: float, seed: int, *, resid: torch.Tenso
 
 def dropout_rows_bf16(x: torch.Tensor, p: float, seed: int, out: torch.Tensor | None = None):
     """bf16 [M,C] -> keep * x / (1 - p), in place unless `out` is given."""
-    _chk(x, torch.bfloat16, "x")
+    M, Cc = _dims("dropout_rows_bf16", x, "x", 2, torch.bfloat16)
     y = x if out is None else out
-    _chk(y, torch.bfloat16, "out")
-    M, Cc = x.shape
+    _chk_op("dropout_rows_bf16", out, "out", torch.bfloat16, (M, Cc), x.device)
     rc = _fn("lc2is_dropout_rows_bf16")(_ptr(x), _ld(x), _ptr(y), _ld(y), M, Cc, float(p), int(seed), _stream())
     _lib.check(rc, f"dropout_rows_bf16 M={M} C={Cc}")
     return y
@@ -2181,14 +2281,15 @@ def rows_gather(src: torch.Tensor, index_map: torch.Tensor, *, out: torch.Tensor
 def swin_attn_fwd(qkv: torch.Tensor, bias: torch.Tensor, nwin: int, win_per_img: int, nwx: int, Hp: int, Wp: int,
                   ws: int, shift: int, nH: int, scale: float, *, save_lse: bool = True, out: torch.Tensor | None = None):
     """qkv bf16 [nwin*ws*ws, 3C]; bias fp32 [nH, S, S].  Returns (o bf16 [nwin*S, C], lse [nwin, nH, S])."""
-    _chk(qkv, torch.bfloat16, "qkv"); _dense(bias, torch.float32, "bias") if bias.dim() == 2 else _chk(bias, torch.float32, "bias", 3)
-    S, Cc = ws * ws, qkv.shape[1] // 3
-    if qkv.shape[0] != nwin * S or tuple(bias.shape) != (nH, S, S) or not bias.is_contiguous():
-        raise RuntimeError("lc2is_amd.swin_attn_fwd: shape mismatch")
-    o = out if out is not None else torch.empty((nwin * S, Cc), dtype=torch.bfloat16, device=qkv.device)
-    _chk(o, torch.bfloat16, "out")
-    if tuple(o.shape) != (nwin * S, Cc):
-        raise RuntimeError("lc2is_amd.swin_attn_fwd: out shape mismatch")
+    who, dev = "swin_attn_fwd", qkv.device
+    S, Cc = ws * ws, _dims(who, qkv, "qkv", 2, torch.bfloat16)[1] // 3
+    if qkv.shape != (nwin * S, 3 * Cc):
+        raise RuntimeError(f"lc2is_amd.swin_attn_fwd: qkv must have shape {(nwin * S, 3 * Cc)}, got {tuple(qkv.shape)}")
+    if bias is None:
+        raise RuntimeError("lc2is_amd.swin_attn_fwd: bias is required")
+    _chk_op(who, bias, "bias", torch.float32, (nH, S, S), dev, 4)
+    _chk_op(who, out, "out", torch.bfloat16, (nwin * S, Cc), dev)
+    o = out if out is not None else torch.empty((nwin * S, Cc), dtype=torch.bfloat16, device=dev)
     lse = torch.empty((nwin, nH, S), dtype=torch.float32, device=qkv.device)
     rc = _fn("lc2is_swin_attn_fwd")(_ptr(qkv), _ld(qkv), _ptr(o), _ld(o), _ptr(lse), _ptr(bias), nwin, win_per_img, nwx,
                                     Hp, Wp, ws, shift, nH, Cc, float(scale), _stream())
@@ -2200,15 +2301,22 @@ def swin_attn_bwd(qkv, o, do, lse, bias, nwin: int, win_per_img: int, nwx: int, 
                   nH: int, scale: float, *, dbias: torch.Tensor | None = None, accumulate_dbias: bool = False,
                   dqkv: torch.Tensor | None = None):
     """Returns dqkv bf16 [nwin*S, 3C]; dbias fp32 [nH,S,S] is written (or accumulated) when given."""
-    for t, n in ((qkv, "qkv"), (o, "o"), (do, "do")):
-        _chk(t, torch.bfloat16, n)
-    _chk(lse, torch.float32, "lse", 3); _chk(bias, torch.float32, "bias", 3); _chk(dbias, torch.float32, "dbias", 3)
-    Cc = qkv.shape[1] // 3
+    who, dev, bf, f32 = "swin_attn_bwd", qkv.device, torch.bfloat16, torch.float32
+    S, Cc = ws * ws, _dims(who, qkv, "qkv", 2, bf)[1] // 3
+    rows = nwin * S
+    if qkv.shape != (rows, 3 * Cc):
+        raise RuntimeError(f"lc2is_amd.swin_attn_bwd: qkv must have shape {(rows, 3 * Cc)}, got {tuple(qkv.shape)}")
+    _chk_op(who, dqkv, "dqkv", bf, (rows, 3 * Cc), dev)
     if dqkv is None:
-        dqkv = torch.empty(qkv.shape, dtype=torch.bfloat16, device=qkv.device)
-    _chk(dqkv, torch.bfloat16, "dqkv")
-    if dqkv.shape != qkv.shape:
-        raise RuntimeError("lc2is_amd.swin_attn_bwd: dqkv shape mismatch")
+        dqkv = torch.empty((rows, 3 * Cc), dtype=bf, device=dev)
+    for t, n, s in ((o, "o", (rows, Cc)), (do, "do", (rows, Cc))):
+        if t is None:
+            raise RuntimeError(f"lc2is_amd.swin_attn_bwd: {n} is required")
+        _chk_op(who, t, n, bf, s, dev)
+    if lse is None or bias is None:
+        raise RuntimeError("lc2is_amd.swin_attn_bwd: lse and bias are required")
+    _chk_op(who, lse, "lse", f32, (nwin, nH, S), dev, 4); _chk_op(who, bias, "bias", f32, (nH, S, S), dev, 4)
+    _chk_op(who, dbias, "dbias", f32, (nH, S, S), dev, 4)
     ws_b = None
     if dbias is not None:
         nbytes = _fn("lc2is_swin_attn_bwd_workspace_bytes")(nwin, ws, nH)
