@@ -216,7 +216,8 @@ __global__ __launch_bounds__(256) void text_embed_fwd_kernel(const int64_t* __re
 // last bits run-dependent): block r owns token row r.  It first scans ids[0..r) for an earlier occurrence of its id — if there is
 // one, the block that owns the FIRST occurrence does the work and this one leaves — then sums the rows r' >= r that carry the id
 // in row order and adds the sum to dtok[id] with a plain read-modify-write (the id has exactly one owner).  B*L is a few
-// hundred to a few thousand rows: the scans are L2-resident integer reads.
+// hundred to a few thousand rows: the scans are L2-resident integer reads.  The clamp of ids into [0, vocab) is relied on: with the
+// token table frozen the caller passes a one-row scratch (vocab = 1), every id lands on row 0 and only dpos is kept.
 __global__ __launch_bounds__(256) void text_embed_dtok_kernel(const int64_t* __restrict__ ids, const float* __restrict__ dx,
                                                                int ldx, float* dtok, int R, int C, int vocab) {
   const int r = blockIdx.x;

@@ -164,6 +164,10 @@ class HipModule(nn.Module):
         self._sh_versions = None
         self._sh_device = None
         self._sh_ptrs = []
+        self._gp = None           # what _grad_params() returned (False: the version list), kept until the shadows are rebuilt
+        self._rg_flags = None     # requires_grad of those parameters at the last _ensure_ready
+        self._anchor = [None]     # [first of them that requires grad, or None: all frozen] (in a list: not registered as a
+                                  # parameter of this module); see _anchor_save
         self._grad_ready_cb = None  # set by dp.GradReducer: called when this module's backward is complete
         self._part_ready_cb = None  # set by dp.GradReducer: called when a sub-module's (a layer's) gradients are complete
 
@@ -173,6 +177,22 @@ class HipModule(nn.Module):
 
     def _params_for_version(self):
         return list(self.parameters(recurse=True))
+
+    def _grad_params(self):
+        """The parameters whose gradients this module's backward writes, when that is not the list the version check
+        walks (a composition that drives sub-modules' layers itself; a tower with a parameter its graph never reaches);
+        None: the same list.  Called when the shadows are (re)built — .to(), a replaced Parameter of the version list — and
+        the list is kept until then."""
+        return None
+
+    def _anchor_save(self, *inputs):
+        """(anchor, save) of a forward, after _ensure_ready: the module saves for backward when grad mode is on and ANY of
+        its parameters or of the float `inputs` requires grad; `anchor` is a parameter that requires grad (None when all
+        are frozen) — handed to the autograd.Function so that its output requires grad whichever parameters are frozen."""
+        a = self._anchor[0]
+        if not torch.is_grad_enabled():
+            return a, False
+        return a, a is not None or any(t is not None and t.requires_grad for t in inputs)
 
     def _ensure_ready(self):
         ps = self._params_for_version()
@@ -185,12 +205,23 @@ class HipModule(nn.Module):
             self._sh_device = dev
             self._sh_ptrs = [p.data_ptr() for p in ps]
             self._sh_versions = None
+            self._gp = self._rg_flags = None
         vers = [p._version for p in ps]
         if vers != self._sh_versions:
             if self._sh_table is not None:
                 self._sh_table.refresh()
             self._post_refresh()
             self._sh_versions = vers
+        # requires_grad_() moves no version counter, so what is cached here is the anchor, not the look: EVERY call reads
+        # requires_grad of every gradient parameter (one more pass like the two above; for a pyramid that is all its blocks'
+        # parameters, not only the six weights of its version list) and the anchor is chosen again only when a flag moved.
+        if self._gp is None:
+            self._gp = self._grad_params() or False
+        gp = self._gp or ps
+        flags = [p.requires_grad for p in gp]
+        if flags != self._rg_flags:
+            self._rg_flags = flags
+            self._anchor = [next((p for p in gp if p.requires_grad), None)]
         return self._sh
 
     def _post_refresh(self):
@@ -295,6 +326,34 @@ def vec_grad(p: nn.Parameter | None):
     if p is None or not p.requires_grad:
         return None, False
     return grad_buf(p)
+
+
+def put_grad(buf: torch.Tensor | None, acc: bool, value: torch.Tensor) -> None:
+    """A gradient computed into a temporary goes to its buffer: overwrite or accumulate by the buffer's own state."""
+    if buf is not None:
+        buf.add_(value) if acc else buf.copy_(value)
+
+
+def layernorm_bwd_params(dy, x, weight: nn.Parameter, bias: nn.Parameter | None, mean, rstd, **kw):
+    """ops.layernorm_bwd with dgamma / dbeta going to the gradient buffers of `weight` / `bias`: each is computed iff its
+    own parameter requires grad, and each overwrites or accumulates by its own ``.grad`` state.  Returns (dx_f32, dx_bf16).
+    The kernel has ONE accumulate flag and computes both sums or none, so a pair in different states (bias trainable under
+    a frozen weight, one ``.grad`` set and the other None) takes the sums into temporaries, outside a deferral scope, and
+    adds or copies them afterwards."""
+    dg, accg = vec_grad(weight)
+    db, accb = vec_grad(bias)
+    if dg is None and db is None:
+        return ops.layernorm_bwd(dy, x, weight, mean, rstd, need_param_grads=False, **kw)[:2]
+    if dg is not None and (db is None or accb == accg):
+        return ops.layernorm_bwd(dy, x, weight, mean, rstd, dgamma=dg, dbeta=db, accumulate=accg, **kw)[:2]
+    prev, ops._ln_defer = ops._ln_defer, None
+    try:
+        d32, d16, tg, tb = ops.layernorm_bwd(dy, x, weight, mean, rstd, **kw)
+    finally:
+        ops._ln_defer = prev
+    put_grad(dg, accg, tg)
+    put_grad(db, accb, tb)
+    return d32, d16
 
 
 GROUP_SKIP = 255   # granule id of a parameter the grouped optimizers leave alone (ops.GROUP_SKIP)

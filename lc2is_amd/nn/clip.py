@@ -25,7 +25,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .base import HipModule, WgradBatch, grad_buf, linear_bwd_params, require_cuda, vec_grad
+from .base import HipModule, WgradBatch, layernorm_bwd_params, linear_bwd_params, put_grad, require_cuda, vec_grad
 
 
 @dataclass
@@ -258,11 +258,8 @@ def _stack_bwd(g32, g16, stack: _Stack, sh, saved, a: ClipArch, B: int, S: int, 
             dz, _, _ = ops.gemm_nt(g16, s["w2T"], None, act=ops.ACT_DQUICK_GELU, aux_in=z)
             linear_bwd_params(dz, h2, mlp.fc1.weight, mlp.fc1.bias)
             dh2, _, _ = ops.gemm_nt(dz, s["w1T"], None)
-            dg, accg = vec_grad(layer.layer_norm2.weight)
-            db, _ = vec_grad(layer.layer_norm2.bias)
-            gm32, gm16, _, _ = ops.layernorm_bwd(dh2, x_mid, layer.layer_norm2.weight, m2, r2, dres=g16 if lean else g32,
-                                                 dgamma=dg, dbeta=db, accumulate=accg, want_f32=not lean,
-                                                 need_param_grads=dg is not None)
+            gm32, gm16 = layernorm_bwd_params(dh2, x_mid, layer.layer_norm2.weight, layer.layer_norm2.bias, m2, r2,
+                                              dres=g16 if lean else g32, want_f32=not lean)
             # x_mid = x + out_proj(attn(qkv(LN1(x))))
             linear_bwd_params(gm16, o, at.out_proj.weight, at.out_proj.bias)
             do, _, _ = ops.gemm_nt(gm16, s["woT"], None)
@@ -272,12 +269,9 @@ def _stack_bwd(g32, g16, stack: _Stack, sh, saved, a: ClipArch, B: int, S: int, 
             for j, proj in enumerate((at.q_proj, at.k_proj, at.v_proj)):
                 linear_bwd_params(dqkv[:, j * C:(j + 1) * C], h, proj.weight, proj.bias)
             dh, _, _ = ops.gemm_nt(dqkv, s["wqkvT"], None)
-            dg, accg = vec_grad(layer.layer_norm1.weight)
-            db, _ = vec_grad(layer.layer_norm1.bias)
-            g32, g16, _, _ = ops.layernorm_bwd(dh, x, layer.layer_norm1.weight, m1, r1, dres=gm16 if lean else gm32,
-                                               dgamma=dg, dbeta=db, accumulate=accg,
-                                               want_f32=(not lean) or (final_f32 and layer is first),
-                                               need_param_grads=dg is not None)
+            g32, g16 = layernorm_bwd_params(dh, x, layer.layer_norm1.weight, layer.layer_norm1.bias, m1, r1,
+                                            dres=gm16 if lean else gm32,
+                                            want_f32=(not lean) or (final_f32 and layer is first))
             waiting.append(layer)
             if len(waiting) >= pair:
                 batch.flush()
@@ -378,6 +372,11 @@ class ImageEncoderCLIP(HipModule):
             state_dict[key] = self.pos_emebedding_interpolate(self.in_size // self.patch_size, weight=state_dict[key])
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
+    def _grad_params(self):
+        """Everything but post_layernorm, which the tokens never pass: trainable alone it starts no backward."""
+        skip = {id(p) for p in self.enc.post_layernorm.parameters()}
+        return [p for p in self.parameters() if id(p) not in skip]
+
     def _build_shadows(self, device):
         a = self.arch
         per, entries = _stack_shadows(self.enc.encoder, a, device)
@@ -389,7 +388,7 @@ class ImageEncoderCLIP(HipModule):
 
     def _fwd(self, pixel_values, keep_cls, save):
         require_cuda(pixel_values, "pixel_values")
-        a, sh = self.arch, self._ensure_ready()
+        a, sh = self.arch, self._sh     # (forward has called _ensure_ready)
         B = pixel_values.shape[0]
         G = self.in_size // self.patch_size
         P = G * G
@@ -431,29 +430,38 @@ class ImageEncoderCLIP(HipModule):
         g32, g16 = _stack_bwd(g32, g16, self.enc.encoder, sh["layers"], saved["layers"], a, B, P + 1, None, False,
                               on_layer_done=self._part_grads_ready if self._part_ready_cb is not None else None,
                               final_f32=False)
-        dg, accg = vec_grad(self.enc.pre_layrnorm.weight)
-        db, _ = vec_grad(self.enc.pre_layrnorm.bias)
-        dx0, _, _, _ = ops.layernorm_bwd(g32 if g32 is not None else g16, saved["x0"], self.enc.pre_layrnorm.weight, saved["m0"], saved["r0"],
-                                         dgamma=dg, dbeta=db, accumulate=accg, want_bf16=False,
-                                         need_param_grads=dg is not None)
         emb = self.enc.embeddings
-        gpos, accp = grad_buf(emb.position_embedding.weight)
-        gcls, accc = grad_buf(emb.class_embedding)
-        if accp != accc:
-            raise RuntimeError("lc2is_amd: inconsistent gradient state of the ViT embeddings")
-        dpatch = ops.vit_embed_bwd(dx0, gpos, gcls, B, P, accumulate=accp)
-        gw, accw = grad_buf(emb.patch_embedding.weight)
-        k = 3 * self.patch_size ** 2
-        if sh["kpad"] == k:
-            ops.gemm_tn(dpatch, saved["cols"], gw.view(C, k), accumulate=accw)
-        else:
-            tmp = ops.gemm_tn(dpatch, saved["cols"])
-            gw.view(C, k).copy_(tmp[:, :k]) if not accw else gw.view(C, k).add_(tmp[:, :k])
+        pre = self.enc.pre_layrnorm
+        gpos, accp = vec_grad(emb.position_embedding.weight)
+        gcls, accc = vec_grad(emb.class_embedding)
+        gw, accw = vec_grad(emb.patch_embedding.weight)
+        if gpos is None and gcls is None and gw is None and not (pre.weight.requires_grad or pre.bias.requires_grad):
+            self._grads_ready()          # a frozen stem: nothing below the first layer is wanted (pixels carry no gradient)
+            return
+        dx0, _ = layernorm_bwd_params(g32 if g32 is not None else g16, saved["x0"], pre.weight, pre.bias, saved["m0"], saved["r0"],
+                                      want_bf16=False)
+        if gpos is not None and gcls is not None and accp == accc:
+            dpatch = ops.vit_embed_bwd(dx0, gpos, gcls, B, P, accumulate=accp)
+        elif gpos is not None or gcls is not None or gw is not None:
+            # the kernel writes both tables under one accumulate flag: a frozen table, or two in different states, go
+            # through temporaries
+            tpos, tcls = torch.empty_like(emb.position_embedding.weight), torch.empty_like(emb.class_embedding)
+            dpatch = ops.vit_embed_bwd(dx0, tpos, tcls, B, P, accumulate=False)
+            put_grad(gpos, accp, tpos)
+            put_grad(gcls, accc, tcls)
+        if gw is not None:
+            k = 3 * self.patch_size ** 2
+            if sh["kpad"] == k:
+                ops.gemm_tn(dpatch, saved["cols"], gw.view(C, k), accumulate=accw)
+            else:
+                tmp = ops.gemm_tn(dpatch, saved["cols"])
+                gw.view(C, k).copy_(tmp[:, :k]) if not accw else gw.view(C, k).add_(tmp[:, :k])
         self._grads_ready()
 
     def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
-        anchor = self.enc.pre_layrnorm.weight
-        return _VisionFn.apply(pixel_values, anchor, self, self.keep_cls, torch.is_grad_enabled() and anchor.requires_grad)
+        self._ensure_ready()
+        anchor, save = self._anchor_save()
+        return _VisionFn.apply(pixel_values, anchor, self, self.keep_cls, save)
 
 
 class ImageEncoderCLIPFull(ImageEncoderCLIP):
@@ -510,7 +518,7 @@ class TextEncoderCLIP(HipModule):
 
     def _fwd(self, input_ids, attention_mask, save):
         require_cuda(input_ids, "input_ids")
-        a, sh = self.arch, self._ensure_ready()
+        a, sh = self.arch, self._sh     # (forward has called _ensure_ready)
         B, L = input_ids.shape
         if L > a.max_pos:
             raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: "
@@ -534,27 +542,29 @@ class TextEncoderCLIP(HipModule):
         a, sh = self.arch, self._sh
         B, L, C = saved["B"], saved["L"], a.hidden
         fl = self.enc.final_layer_norm
-        dg, accg = vec_grad(fl.weight)
-        db, _ = vec_grad(fl.bias)
-        g32, g16, _, _ = ops.layernorm_bwd(gout.reshape(B * L, C).float().contiguous(), saved["xf"], fl.weight,
-                                           saved["mf"], saved["rf"], dgamma=dg, dbeta=db, accumulate=accg,
-                                           need_param_grads=dg is not None)
+        g32, g16 = layernorm_bwd_params(gout.reshape(B * L, C).float().contiguous(), saved["xf"], fl.weight, fl.bias,
+                                        saved["mf"], saved["rf"])
         g32, _ = _stack_bwd(g32, g16, self.enc.encoder, sh["layers"], saved["layers"], a, B, L, saved["kbias"], True,
                             on_layer_done=self._part_grads_ready if self._part_ready_cb is not None else None)
         emb = self.enc.embeddings
-        if emb.token_embedding.weight.requires_grad:
-            gtok, acct = grad_buf(emb.token_embedding.weight)
-            gpos, accp = grad_buf(emb.position_embedding.weight)
-            if not acct:
-                gtok.zero_()  # the scatter uses atomics
-            if not accp:
-                gpos.zero_()
+        gtok, acct = vec_grad(emb.token_embedding.weight)
+        gpos, accp = vec_grad(emb.position_embedding.weight)
+        if gtok is not None or gpos is not None:
+            if gtok is None:      # frozen token table: a one-row scratch takes the sums (ops.text_embed_bwd: ids are clamped
+                gtok = torch.empty(1, C, dtype=torch.float32, device=g32.device)     # to the rows of dtok, documented there)
+            elif not acct:
+                gtok.zero_()      # the kernel adds to what the table holds
+            if gpos is None:      # frozen position table: a zeroed scratch of the L rows the kernel adds to
+                gpos = torch.zeros(L, C, dtype=torch.float32, device=g32.device)
+            elif not accp:
+                gpos.zero_()      # rows past L get no gradient: the whole table is defined
             ops.text_embed_bwd(saved["ids"], g32, gtok, gpos, accumulate=True)
         self._grads_ready()
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
-        anchor = self.enc.final_layer_norm.weight
-        return _TextFn.apply(input_ids, attention_mask, anchor, self, torch.is_grad_enabled() and anchor.requires_grad)
+        self._ensure_ready()
+        anchor, save = self._anchor_save()
+        return _TextFn.apply(input_ids, attention_mask, anchor, self, save)
 
 
 class TextEncoderCLIPPooler(TextEncoderCLIP):
@@ -562,7 +572,8 @@ class TextEncoderCLIPPooler(TextEncoderCLIP):
     (hf:modeling_clip.py:572-581); the gather is plain indexing on top of the HIP last_hidden_state."""
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor = None) -> torch.Tensor:
-        anchor = self.enc.final_layer_norm.weight
-        hidden = _TextFn.apply(input_ids, attention_mask, anchor, self, torch.is_grad_enabled() and anchor.requires_grad)
+        self._ensure_ready()
+        anchor, save = self._anchor_save()
+        hidden = _TextFn.apply(input_ids, attention_mask, anchor, self, save)
         eos = (input_ids == self.arch.eos_token_id).int().argmax(dim=-1)
         return hidden[torch.arange(hidden.shape[0], device=hidden.device), eos]

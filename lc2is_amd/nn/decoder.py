@@ -25,8 +25,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .base import (DropSites, HipModule, WgradBatch, drop_branch_add, drop_branch_grad16, grad_buf, linear_bwd_params,
-                   require_cuda, vec_grad)
+from .base import (DropSites, HipModule, WgradBatch, drop_branch_add, drop_branch_grad16, layernorm_bwd_params,
+                   linear_bwd_params, require_cuda, vec_grad)
 
 
 class _SelfAttnParams(nn.Module):
@@ -201,11 +201,7 @@ def _layer_bwd_impl(g32, g16, dmem32, mem16, layer: DecoderLayer, s, sv, B, Sq, 
     def ln_bwd(i, dy, dres):
         n = getattr(layer, f"norm{i}")
         t, m, r = sv[f"ln{i}"]
-        dg, accg = vec_grad(n.weight)
-        db, _ = vec_grad(n.bias)
-        a32, a16, _, _ = ops.layernorm_bwd(dy, t, n.weight, m, r, dres=dres, dgamma=dg, dbeta=db, accumulate=accg,
-                                           need_param_grads=dg is not None)
-        return a32, a16
+        return layernorm_bwd_params(dy, t, n.weight, n.bias, m, r, dres=dres)
 
     ds = sv.get("ds")
     pd = ds.p if ds is not None else 0.0
@@ -235,13 +231,10 @@ def _layer_bwd_impl(g32, g16, dmem32, mem16, layer: DecoderLayer, s, sv, B, Sq, 
                       dk=dkv[:, :C], dv=dkv[:, C:], dropout_p=pd, seed=ds.seeds["ca_p"] if ds else 0)
     # packed in_proj_bias [3C] = (q, k, v): write the three slices
     gb, accb = vec_grad(ca.in_proj_bias)
-    if ca.q_proj_weight.requires_grad:
-        gw, acc = grad_buf(ca.q_proj_weight)
-        ops.gemm_tn(dq, sv["h2"], gw, accumulate=acc)
-        gw, acc = grad_buf(ca.k_proj_weight)
-        ops.gemm_tn(dkv[:, :C], mem16, gw, accumulate=acc)
-        gw, acc = grad_buf(ca.v_proj_weight)
-        ops.gemm_tn(dkv[:, C:], mem16, gw, accumulate=acc)
+    for w, dy, xin in ((ca.q_proj_weight, dq, sv["h2"]), (ca.k_proj_weight, dkv[:, :C], mem16), (ca.v_proj_weight, dkv[:, C:], mem16)):
+        gw, acc = vec_grad(w)
+        if gw is not None:
+            ops.gemm_tn(dy, xin, gw, accumulate=acc)
     if gb is not None:
         ops.colsum(dq, gb[:C], accumulate=accb)
         ops.colsum(dkv, gb[C:], accumulate=accb)
@@ -307,7 +300,7 @@ class DecoderBlock(HipModule):
         l0 = self.layers[0]
         if not l0.batch_first:
             raise NotImplementedError("lc2is_amd DecoderBlock: only batch_first=True is implemented (the reference's use)")
-        sh = self._ensure_ready()
+        sh = self._sh     # (forward has called _ensure_ready)
         B, Sq, C = tgt.shape
         Sk, Ckv = memory.shape[1], memory.shape[2]
         x = tgt.reshape(B * Sq, C).float().contiguous()
@@ -336,10 +329,7 @@ class DecoderBlock(HipModule):
         g32 = gout.reshape(B * Sq, C).float().contiguous()
         if saved["fin"] is not None:
             xin, m, r = saved["fin"]
-            dg, accg = vec_grad(self.norm.weight)
-            db, _ = vec_grad(self.norm.bias)
-            g32, g16, _, _ = ops.layernorm_bwd(g32, xin, self.norm.weight, m, r, dgamma=dg, dbeta=db, accumulate=accg,
-                                               need_param_grads=dg is not None)
+            g32, g16 = layernorm_bwd_params(g32, xin, self.norm.weight, self.norm.bias, m, r)
         else:
             g16 = ops.cast_bf16(g32)
         dmem = torch.zeros(B * Sk, Ckv, dtype=torch.float32, device=gout.device)
@@ -353,8 +343,9 @@ class DecoderBlock(HipModule):
         if tgt_mask is not None or memory_mask is not None or tgt_key_padding_mask is not None:
             raise NotImplementedError("lc2is_amd DecoderBlock: only memory_key_padding_mask is implemented "
                                       "(the one mask the reference passes, model/model.py:38)")
-        anchor = self.layers[0].norm1.weight
-        save = torch.is_grad_enabled() and (anchor.requires_grad or tgt.requires_grad or memory.requires_grad)
+        require_cuda(tgt, "tgt")
+        self._ensure_ready()
+        anchor, save = self._anchor_save(tgt, memory)
         return _DecoderFn.apply(tgt, memory, anchor, self, memory_key_padding_mask, save)
 
 

@@ -25,9 +25,9 @@ import torch
 from torch import nn
 
 from .. import ops
-from .base import (DropSites, HipModule, assign_rng_names, WgradBatch, drop_branch_add, drop_branch_grad16, grad_buf, linear_bwd_params,
-                   require_cuda, vec_grad)
-from .hier import _PackedAttnParams, _packed_param_grads, _split_bias
+from .base import (DropSites, HipModule, assign_rng_names, WgradBatch, drop_branch_add, drop_branch_grad16, layernorm_bwd_params,
+                   linear_bwd_params, require_cuda)
+from .hier import _PackedAttnParams, _packed_param_grads, _split_bias, sr_conv_grads
 
 
 class _StdLayerParams(nn.Module):
@@ -128,11 +128,7 @@ def _std_layer_bwd_impl(g32, dmem32, mem16, layer: _StdLayerParams, s, tag, sv, 
 
     def ln_bwd(norm, dy, saved):
         t, m, r = saved
-        dg, accg = vec_grad(norm.weight)
-        db, _ = vec_grad(norm.bias)
-        a32, a16, _, _ = ops.layernorm_bwd(dy, t, norm.weight, m, r, dgamma=dg, dbeta=db, accumulate=accg,
-                                           need_param_grads=dg is not None)
-        return a32, a16
+        return layernorm_bwd_params(dy, t, norm.weight, norm.bias, m, r)
 
     ds = sv.get("ds")
     pd = ds.p if ds is not None else 0.0
@@ -263,17 +259,8 @@ class Transformer(HipModule):
                 g32, _ = ops.bilinear_up_bwd(g32, B, h, cur // h, 2)
             g32 = _std_layer_bwd(g32, dmem, mem16, self._layer(r), s, f"l{r}.", svl, B, cur, K)
         if self.sr_ratio == 2:
-            dg, accg = vec_grad(self.norm.weight)
-            db, _ = vec_grad(self.norm.bias)
-            _, dr16, _, _ = ops.layernorm_bwd(dmem, sv["r32"], self.norm.weight, sv["mr"], sv["rr"], dgamma=dg, dbeta=db,
-                                              accumulate=accg, want_f32=False, need_param_grads=dg is not None)
-            if self.sr.weight.requires_grad:
-                gw, acc = grad_buf(self.sr.weight)
-                gb, accb = grad_buf(self.sr.bias)
-                tmp = ops.gemm_tn(dr16, sv["g"])
-                ops.colsum(dr16, gb, accumulate=accb)
-                perm = tmp.view(C, 4, C).transpose(1, 2).reshape(C, C, 2, 2)
-                gw.add_(perm) if acc else gw.copy_(perm)
+            _, dr16 = layernorm_bwd_params(dmem, sv["r32"], self.norm.weight, self.norm.bias, sv["mr"], sv["rr"], want_f32=False)
+            sr_conv_grads(self.sr, dr16, sv["g"], C)
             dg16, _, _ = ops.gemm_nt(dr16, s["w_srT"], None)
             ops.sr_scatter_add(dg16, g32, B, h, h)
         else:
@@ -293,8 +280,9 @@ class Transformer(HipModule):
         return self._bwd(gout.reshape(-1, C).float().contiguous(), sv, B).view(B, P, C)
 
     def forward(self, x, h):
-        anchor = self.norm.weight
-        save = torch.is_grad_enabled() and (anchor.requires_grad or x.requires_grad)
+        require_cuda(x, "x")
+        self._ensure_ready()
+        anchor, save = self._anchor_save(x)
         return _TransformerFn.apply(x, anchor, self, int(h), save)
 
 
@@ -335,6 +323,10 @@ class Decoder(HipModule):
     def _params_for_version(self):
         return [m.weight for m in self.linears] + [m.weight for m in self.linears2]
 
+    def _grad_params(self):
+        """The Linears' weights and biases and every stage's Transformer: this module's backward drives them itself."""
+        return list(self.parameters())
+
     def _build_shadows(self, device):
         s, e = {}, []
         for grp, mods in (("lin", self.linears), ("lin2", self.linears2)):
@@ -348,8 +340,7 @@ class Decoder(HipModule):
     def _fwd(self, xs, save):
         if len(xs) != 4:
             raise ValueError("lc2is_amd ftn.Decoder: expects the 4 backbone stages")
-        require_cuda(xs[0], "x")
-        s = self._ensure_ready()
+        s = self._sh     # (forward has called _ensure_ready)
         B = xs[0].shape[0]
         x32, x16 = [], []
         for i, x in enumerate(xs):
@@ -403,6 +394,7 @@ class Decoder(HipModule):
         return [dx[i].view(B, self.H[i] ** 2, self.dim_in[i]) for i in range(4)]
 
     def forward(self, x):
-        anchor = self.linears2[0].weight
-        save = torch.is_grad_enabled() and (anchor.requires_grad or any(t.requires_grad for t in x))
+        require_cuda(x[0], "x")
+        self._ensure_ready()
+        anchor, save = self._anchor_save(*x)
         return _DecoderFn.apply(x[0], x[1], x[2], x[3], anchor, self, save)

@@ -25,8 +25,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .base import (DropSites, HipModule, assign_rng_names, WgradBatch, drop_branch_add, drop_branch_grad16, grad_buf, linear_bwd_params,
-                   require_cuda, vec_grad)
+from .base import (DropSites, HipModule, assign_rng_names, WgradBatch, drop_branch_add, drop_branch_grad16, layernorm_bwd_params,
+                   linear_bwd_params, put_grad, require_cuda, vec_grad)
 
 
 def _isqrt(p: int) -> int:
@@ -182,15 +182,27 @@ def _sr_layer_fwd(x32, x16, mem16, layer: _SRLayer, s, B, P, K, save, ds=None):
 
 def _packed_param_grads(attn: _PackedAttnParams, dq16, x_q16, dkv16, x_kv16, C):
     """in_proj_weight [3C,C] rows: q from (dq, x_q), k|v from (dkv, x_kv); packed bias likewise."""
-    if not attn.in_proj_weight.requires_grad:
-        return
-    gw, acc = grad_buf(attn.in_proj_weight)
+    gw, acc = vec_grad(attn.in_proj_weight)
     gb, accb = vec_grad(attn.in_proj_bias)
-    ops.gemm_tn(dq16, x_q16, gw[:C], accumulate=acc, db=gb[:C] if gb is not None and accb == acc else None)
-    ops.gemm_tn(dkv16, x_kv16, gw[C:], accumulate=acc, db=gb[C:] if gb is not None and accb == acc else None)
-    if gb is not None and accb != acc:
+    fused = gw is not None and gb is not None and accb == acc     # the bias gradient rides on the weight-gradient launch
+    if gw is not None:
+        ops.gemm_tn(dq16, x_q16, gw[:C], accumulate=acc, db=gb[:C] if fused else None)
+        ops.gemm_tn(dkv16, x_kv16, gw[C:], accumulate=acc, db=gb[C:] if fused else None)
+    if gb is not None and not fused:
         ops.colsum(dq16, gb[:C], accumulate=accb)
         ops.colsum(dkv16, gb[C:], accumulate=accb)
+
+
+def sr_conv_grads(sr: nn.Conv2d, dr16, g16, C):
+    """Gradients of the 2x2 / stride-2 reduction conv from its GEMM form: the weight gradient is permuted back from the
+    gathered operand's [Co, (2i+j)*Ci + ci] order to the [Co,Ci,2,2] parameter order."""
+    gw, acc = vec_grad(sr.weight)
+    gb, accb = vec_grad(sr.bias)
+    if gw is not None:
+        tmp = ops.gemm_tn(dr16, g16)
+        put_grad(gw, acc, tmp.view(C, 4, C).transpose(1, 2).reshape(C, C, 2, 2))
+    if gb is not None:
+        ops.colsum(dr16, gb, accumulate=accb)
 
 
 def _sr_layer_bwd(g32, dmem32, mem16, layer, s, sv, B, P, K):
@@ -210,11 +222,7 @@ def _sr_layer_bwd_impl(g32, dmem32, mem16, layer: _SRLayer, s, sv, B, P, K):
 
     def ln_bwd(norm, dy, saved):
         t, m, r = saved
-        dg, accg = vec_grad(norm.weight)
-        db, _ = vec_grad(norm.bias)
-        a32, a16, _, _ = ops.layernorm_bwd(dy, t, norm.weight, m, r, dgamma=dg, dbeta=db, accumulate=accg,
-                                           need_param_grads=dg is not None)
-        return a32, a16
+        return layernorm_bwd_params(dy, t, norm.weight, norm.bias, m, r)
 
     ds = sv.get("ds")
     pd = ds.p if ds is not None else 0.0
@@ -250,17 +258,8 @@ def _sr_layer_bwd_impl(g32, dmem32, mem16, layer: _SRLayer, s, sv, B, P, K):
                       dv=dkv[:, C:], dropout_p=pd, seed=ds.seeds["sa_p"] if ds else 0)
     _packed_param_grads(sa, dq, sv["x16"], dkv, sv["rn16"], C)
     drn16, _, _ = ops.gemm_nt(dkv, s["w_inT"][:, C:], None)
-    dg, accg = vec_grad(layer.norm.weight)
-    db, _ = vec_grad(layer.norm.bias)
-    _, dr16, _, _ = ops.layernorm_bwd(drn16, sv["r32"], layer.norm.weight, sv["mr"], sv["rr"], dgamma=dg, dbeta=db,
-                                      accumulate=accg, want_f32=False, need_param_grads=dg is not None)
-    if layer.sr.weight.requires_grad:      # conv weight grad, permuted back to the [Co,Ci,2,2] parameter order
-        gw, acc = grad_buf(layer.sr.weight)
-        gb, accb = grad_buf(layer.sr.bias)
-        tmp = ops.gemm_tn(dr16, sv["g"])                                   # [C, (2i+j)*C + ci]
-        ops.colsum(dr16, gb, accumulate=accb)
-        perm = tmp.view(C, 4, C).transpose(1, 2).reshape(C, C, 2, 2)
-        gw.add_(perm) if acc else gw.copy_(perm)
+    _, dr16 = layernorm_bwd_params(drn16, sv["r32"], layer.norm.weight, layer.norm.bias, sv["mr"], sv["rr"], want_f32=False)
+    sr_conv_grads(layer.sr, dr16, sv["g"], C)
     dg16, _, _ = ops.gemm_nt(dr16, s["w_srT"], None)                       # [B*P/4, 4C]
     _, dx32, _ = ops.gemm_nt(dq, s["w_inT"][:, :C], None, resid=d32, out_bf16=None, out_f32=True)
     ops.sr_scatter_add(dg16, dx32, B, hw, hw)
@@ -344,8 +343,8 @@ class _SRBlock(HipModule):
         return dx.view(B, P, C), (dmem.view(B, K, C) if K else None)
 
     def _apply_block(self, x, memory):
-        anchor = self._l.norm1.weight
-        save = torch.is_grad_enabled() and (anchor.requires_grad or x.requires_grad)
+        self._ensure_ready()
+        anchor, save = self._anchor_save(x, memory)
         return _BlockFn.apply(x, memory, anchor, self, save)
 
 
@@ -420,6 +419,10 @@ class _Pyramid(HipModule):
     def _params_for_version(self):
         return [getattr(self, n).weight for n in self._LIN]
 
+    def _grad_params(self):
+        """The six Linears' weights and biases and every block's layer: this module's backward drives the blocks itself."""
+        return list(self.parameters())
+
     def _build_shadows(self, device):
         s, e = {}, []
         for n in self._LIN:
@@ -458,11 +461,12 @@ class _Pyramid(HipModule):
         if Kp == Kk:
             linear_bwd_params(dy16, x16, lin.weight, lin.bias)
         else:
-            gw, acc = grad_buf(lin.weight)
-            gb, accb = grad_buf(lin.bias)
-            tmp = ops.gemm_tn(dy16, x16)
-            gw.add_(tmp[:, :Kk]) if acc else gw.copy_(tmp[:, :Kk])
-            ops.colsum(dy16, gb, accumulate=accb)
+            gw, acc = vec_grad(lin.weight)
+            gb, accb = vec_grad(lin.bias)
+            if gw is not None:
+                put_grad(gw, acc, ops.gemm_tn(dy16, x16)[:, :Kk])
+            if gb is not None:
+                ops.colsum(dy16, gb, accumulate=accb)
         ob, of, _ = ops.gemm_nt(dy16, self._sh[name + "T"], None, resid=resid, out_bf16=True if want_bf16 else None,
                                 out_f32=True if want_f32 else None)
         return of, ob
@@ -472,7 +476,7 @@ class _Pyramid(HipModule):
         for blk in self._blocks():
             if not isinstance(blk, _SRBlock):
                 raise TypeError("lc2is_amd pyramid: attention stages must be lc2is_amd SR blocks")
-        sh = self._ensure_ready()
+        sh = self._sh     # (_run has called _ensure_ready)
         B, P0, C0 = v0.shape
         P3, C3 = v3.shape[1], v3.shape[2]
         h3 = _isqrt(P3)
@@ -552,9 +556,10 @@ class _Pyramid(HipModule):
         return dv0.view(B, P0, C0), dv3.view(B, P3, C3), (dmem.view(B, K, dim) if K else None)
 
     def _run(self, visual, textual):
-        anchor = self.linear2_stage_1.weight
         v0, v3 = visual[0], visual[3]   # visual[1], visual[2] are never read by the reference
-        save = torch.is_grad_enabled() and (anchor.requires_grad or v0.requires_grad or v3.requires_grad)
+        require_cuda(v0, "visual")
+        self._ensure_ready()
+        anchor, save = self._anchor_save(v0, v3, textual)
         return _PyramidFn.apply(v0, v3, textual, anchor, self, save)
 
 

@@ -104,7 +104,7 @@ class _HeadFn(torch.autograd.Function):
     """dec_v [B,P,C] (+ class prototypes) -> NCHW logits [B,K,4g,4g]  or, with labels, the mean CE loss."""
 
     @staticmethod
-    def forward(ctx, dec, protos, model, labels, save, ignore_index, crit=HeadCriterion(), seg_counts=None, accum=None):
+    def forward(ctx, dec, anchor, model, labels, save, ignore_index, crit=HeadCriterion(), seg_counts=None, accum=None):
         out, saved = model._head_fwd(dec, labels, save, ignore_index, crit, seg_counts, accum)
         ctx.model, ctx.saved = model, saved
         return out
@@ -156,14 +156,19 @@ class BaseModelWithText(HipModule):
     def _params_for_version(self):
         return [self.class_prototypes]
 
+    def _grad_params(self):
+        """What the head's backward writes: the prototypes and TextToPatch's two Linears (the towers and the decoder are
+        modules of their own)."""
+        return [self.class_prototypes, *self.pixel_patch.parameters()]
+
     def _build_shadows(self, device):
         K, Ct = self.class_prototypes.shape
         p16 = torch.zeros(ops.class_pad(K), Ct, dtype=torch.bfloat16, device=device)
         return dict(p16=p16, K=K), [(self.class_prototypes, p16[:K], None)]
 
     # -- head ------------------------------------------------------------------------------------------------
-    def _head_scores(self, dec16):
-        sh = self._ensure_ready()
+    def _head_scores(self, dec16, ready: bool = False):
+        sh = self._sh if ready else self._ensure_ready()     # ready: the caller has just made the check (forward, forward_loss)
         pp = self.pixel_patch
         psh = pp._ensure_ready()
         ft16, _, _ = ops.gemm_nt(sh["p16"], psh["wt"], pp.textual.bias)            # [KPAD, out]
@@ -176,7 +181,7 @@ class BaseModelWithText(HipModule):
         g = self.in_size // self.patch_size
         K = self.class_prototypes.shape[0]
         dec16 = ops.cast_bf16(dec.reshape(B * P, C).float().contiguous())
-        ft16, fv16, scores = self._head_scores(dec16)
+        ft16, fv16, scores = self._head_scores(dec16, ready=True)
         saved = dict(dec16=dec16, ft16=ft16, fv16=fv16, dims=(B, P, C, g, K), fused=None) if save else None
         if labels is None:
             return head_scores_hi(scores, B, g, g, K, 4, ops.INTERP_BICUBIC), saved
@@ -259,8 +264,9 @@ class BaseModelWithText(HipModule):
 
     def forward(self, inputs: dict) -> dict:
         dec_v = self._decode(inputs)
-        save = torch.is_grad_enabled() and dec_v.requires_grad
-        logits = _HeadFn.apply(dec_v, self.class_prototypes, self, None, save, -100)
+        self._ensure_ready()
+        anchor, save = self._anchor_save(dec_v)
+        logits = _HeadFn.apply(dec_v, anchor, self, None, save, -100)
         return dict(outputs=logits)
 
     def forward_loss(self, inputs: dict, labels: torch.Tensor, ignore_index: int = -100, *, weight=None,
@@ -318,8 +324,9 @@ class BaseModelWithText(HipModule):
                               n_classes=lambda: self.class_prototypes.shape[0], scale=4, pixel_weight=pixel_weight, distill=distill,
                               rows=rows, device=None if distill is None else self.class_prototypes.device)
         dec_v = self._decode(inputs)
-        save = torch.is_grad_enabled() and dec_v.requires_grad
-        return _HeadFn.apply(dec_v, self.class_prototypes, self, labels, save, ignore_index, crit, seg_counts, accum)
+        self._ensure_ready()
+        anchor, save = self._anchor_save(dec_v)
+        return _HeadFn.apply(dec_v, anchor, self, labels, save, ignore_index, crit, seg_counts, accum)
 
     @torch.no_grad()
     def predict(self, inputs: dict) -> torch.Tensor:
@@ -396,7 +403,7 @@ class _ContrastiveHeadFn(torch.autograd.Function):
     ONE bicubic x4 of the Nt class channels)."""
 
     @staticmethod
-    def forward(ctx, enc_v, enc_t, model, save):
+    def forward(ctx, enc_v, enc_t, anchor, model, save):
         logits, saved = model._head_fwd(enc_v, enc_t, save)
         ctx.model, ctx.saved = model, saved
         return logits
@@ -405,7 +412,7 @@ class _ContrastiveHeadFn(torch.autograd.Function):
     def backward(ctx, gout):
         dv, dt = ctx.model._head_bwd(gout, ctx.saved)
         ctx.saved = None
-        return dv, dt, None, None
+        return dv, dt, None, None, None
 
 
 class ContrastiveModel(HipModule):
@@ -472,8 +479,9 @@ class ContrastiveModel(HipModule):
         enc_t = self.text_encoder(**text_inputs)                                                # model.py:77
         enc_v = self.vision_encoder(**vision_inputs)                                            # model.py:80
         require_cuda(enc_v, "pixel_values")
-        save = torch.is_grad_enabled() and (enc_v.requires_grad or enc_t.requires_grad)
-        logits = _ContrastiveHeadFn.apply(enc_v, enc_t, self, save)
+        self.pixel_patch._ensure_ready()
+        anchor, save = self.pixel_patch._anchor_save(enc_v, enc_t)     # the head's own parameters are TextToPatch's
+        logits = _ContrastiveHeadFn.apply(enc_v, enc_t, anchor, self, save)
         feature_t = feature_v = None
         if self.return_features:
             with torch.no_grad():

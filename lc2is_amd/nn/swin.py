@@ -26,7 +26,8 @@ import torch
 from torch import nn
 
 from .. import ops
-from .base import DropoutRng, HipModule, WgradBatch, grad_buf, linear_bwd_params, require_cuda, vec_grad
+from .base import (DropoutRng, HipModule, WgradBatch, grad_buf, layernorm_bwd_params, linear_bwd_params, put_grad, require_cuda,
+                   vec_grad)
 
 
 @dataclass(frozen=True)
@@ -318,13 +319,12 @@ class SwinTransformer(HipModule):
             linear_bwd_params(dy16, x16p, weight, bias)
             return
         gb, accb = vec_grad(bias)
-        if weight.requires_grad:
-            gw, acc = grad_buf(weight)
+        gw, acc = vec_grad(weight)
+        if gw is not None:
             tmp_b = torch.empty_like(gb) if gb is not None else None
             tmp = ops.gemm_tn(dy16, x16p, db=tmp_b)                     # bias gradient rides on the same launch
-            gw.add_(tmp[:, :C_in]) if acc else gw.copy_(tmp[:, :C_in])
-            if gb is not None:
-                gb.add_(tmp_b) if accb else gb.copy_(tmp_b)
+            put_grad(gw, acc, tmp[:, :C_in])
+            put_grad(gb, accb, tmp_b)
         elif gb is not None:
             ops.colsum(dy16, gb, accumulate=accb)
 
@@ -390,10 +390,8 @@ class SwinTransformer(HipModule):
         dz, _, _ = ops.gemm_nt(g16, s["w2T"], None, act=ops.ACT_DGELU_ERF, aux_in=sv["z"])         # [M, F]
         self._wgrad_padded(dz, sv["h2"], mlp.fc1.weight, mlp.fc1.bias, C)
         dh2, _, _ = ops.gemm_nt(dz, s["w1T"], None)                                               # [M, C]
-        dg, accg = vec_grad(blk.layernorm_after.weight)
-        db, _ = vec_grad(blk.layernorm_after.bias)
-        gm32, _, _, _ = ops.layernorm_bwd(dh2, sv["x_mid"], blk.layernorm_after.weight, sv["m2"], sv["r2"], dres=g32, dgamma=dg,
-                                          dbeta=db, accumulate=accg, want_bf16=False, need_param_grads=dg is not None)
+        gm32, _ = layernorm_bwd_params(dh2, sv["x_mid"], blk.layernorm_after.weight, blk.layernorm_after.bias, sv["m2"], sv["r2"],
+                                       dres=g32, want_bf16=False)
         # x_mid = x + unwindow(o_proj(attn(qkv(window(LN_before(x))))))
         Mw = mp["fwd"].numel()
         dy16 = self._padded(Mw, C, Cp, g32.device)
@@ -416,10 +414,8 @@ class SwinTransformer(HipModule):
         self._qkv_wgrad(dqkv[:, :3 * C], sv["win16"], at, C)
         dwin16, _, _ = ops.gemm_nt(dqkv, s["wqkvT"][:C], None)                                     # [Mw, C]
         dh16 = ops.rows_gather(dwin16, mp["inv"])                                                 # [M, C] bf16
-        dg, accg = vec_grad(blk.layernorm_before.weight)
-        db, _ = vec_grad(blk.layernorm_before.bias)
-        gx32, _, _, _ = ops.layernorm_bwd(dh16, sv["x"], blk.layernorm_before.weight, sv["m1"], sv["r1"], dres=gm32, dgamma=dg,
-                                          dbeta=db, accumulate=accg, want_bf16=False, need_param_grads=dg is not None)
+        gx32, _ = layernorm_bwd_params(dh16, sv["x"], blk.layernorm_before.weight, blk.layernorm_before.bias, sv["m1"], sv["r1"],
+                                       dres=gm32, want_bf16=False)
         return gx32
 
     # ---- patch merging ----------------------------------------------------------------------------------------------------
@@ -438,10 +434,7 @@ class SwinTransformer(HipModule):
         g16 = ops.cast_bf16(g32)
         linear_bwd_params(g16, sv["mn16"], mg.reduction.weight, None)
         dmn16, _, _ = ops.gemm_nt(g16, ss["wredT"], None)                                         # [M2, 4C]
-        dg, accg = vec_grad(mg.norm.weight)
-        db, _ = vec_grad(mg.norm.bias)
-        dm32, _, _, _ = ops.layernorm_bwd(dmn16, sv["m32"], mg.norm.weight, sv["mm"], sv["rm"], dgamma=dg, dbeta=db,
-                                          accumulate=accg, want_bf16=False, need_param_grads=dg is not None)
+        dm32, _ = layernorm_bwd_params(dmn16, sv["m32"], mg.norm.weight, mg.norm.bias, sv["mm"], sv["rm"], want_bf16=False)
         return ops.rows_gather(dm32.view(-1, C), mp["inv"], add=gskip)                            # [M, C] (+ this level's own grad)
 
     # ---- whole backbone ----------------------------------------------------------------------------------------------------
@@ -454,7 +447,7 @@ class SwinTransformer(HipModule):
         G = Hi // a.patch
         if G // 4 <= a.window:
             raise NotImplementedError("lc2is_amd SwinTransformer: stage-3 grids no larger than the window are outside the path")
-        sh = self._ensure_ready()
+        sh = self._sh     # (forward has called _ensure_ready)
         emb = self.encoder.embeddings
         cols = ops.patchify(pixel_values.float().contiguous(), a.patch, sh["kpad"])
         _, pe, _ = ops.gemm_nt(cols, sh["wp"], emb.patch_embeddings.projection.bias, out_bf16=None, out_f32=True)
@@ -506,10 +499,7 @@ class SwinTransformer(HipModule):
             if gskip is not None:
                 g = g + gskip
         emb = self.encoder.embeddings
-        dg, accg = vec_grad(emb.norm.weight)
-        db, _ = vec_grad(emb.norm.bias)
-        _, dpe16, _, _ = ops.layernorm_bwd(g, saved["pe"], emb.norm.weight, saved["m0"], saved["r0"], dgamma=dg, dbeta=db,
-                                           accumulate=accg, want_f32=False, need_param_grads=dg is not None)
+        _, dpe16 = layernorm_bwd_params(g, saved["pe"], emb.norm.weight, emb.norm.bias, saved["m0"], saved["r0"], want_f32=False)
         proj = emb.patch_embeddings.projection
         k = 3 * a.patch ** 2
         if proj.weight.requires_grad:
@@ -522,6 +512,7 @@ class SwinTransformer(HipModule):
         self._grads_ready()
 
     def forward(self, pixel_values: torch.Tensor):
-        anchor = self.encoder.embeddings.norm.weight
-        save = torch.is_grad_enabled() and anchor.requires_grad
+        require_cuda(pixel_values, "pixel_values")
+        self._ensure_ready()
+        anchor, save = self._anchor_save()
         return _SwinFn.apply(pixel_values, anchor, self, save)

@@ -912,7 +912,9 @@ def text_embed_fwd(ids, tok, pos):
 
 
 def text_embed_bwd(ids, dx, dtok, dpos, accumulate: bool = False):
-    """dtok must already hold the running gradient (or zeros); per-token sums in row order, no atomics (reproducible)."""
+    """dtok must already hold the running gradient (or zeros); per-token sums in row order, no atomics (reproducible).
+    ids outside [0, rows of dtok) are clamped into it, as the forward clamps them — and callers rely on it: a tower whose token
+    table is frozen hands a ONE-row scratch as dtok, every id then lands on row 0 and only dpos is kept (nn/clip.py)."""
     _chk(ids, torch.int64, "input_ids"); _chk(dx, torch.float32, "dx")
     if not ids.is_contiguous():
         raise RuntimeError("lc2is_amd.text_embed_bwd: input_ids must be contiguous")
