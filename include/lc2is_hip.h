@@ -940,6 +940,87 @@ int lc2is_mix_apply(const float* dst_px, const int64_t* dst_lab, const float* ds
                     const float* src_pw, int Bs, const int32_t* plan, int B, int S, int L, float* out_px, int64_t* out_lab,
                     float* out_pw, lc2is_stream_t stream);
 
+/* ---- strong photometric views on the device: colour jitter, random greyscale, Gaussian blur; two launches --------------
+ * The student's view in self-training (FixMatch, UniMatch, CPS, DACS, DAFormer): the SAME geometry as the view the teacher
+ * labelled, another and stronger colour, made from the normalised fp32 batch [B,3,S,S] (before or after the mix).  Per sample b, from
+ * row b of a parameter table int32 [B][LC2IS_STRONG_PARAM_WORDS] (fp32 fields as bit patterns):
+ *   word LC2IS_STRONG_FLAGS   bit 0 (LC2IS_STRONG_COLOUR): the colour map (M, o) is not the identity and is applied;
+ *                             bit 1 (LC2IS_STRONG_GREY): greyscale was drawn (recorded; it is folded into M, o, and implies bit 0);
+ *                             bit 2 (LC2IS_STRONG_BLUR): the blur is applied
+ *   word LC2IS_STRONG_R       int32 R, the blur's radius, 0 .. LC2IS_STRONG_MAX_RADIUS
+ *   word LC2IS_STRONG_SIGMA   fp32 sigma
+ *   words LC2IS_STRONG_M ..   fp32 M[3][3] row-major, then LC2IS_STRONG_O .. fp32 o[3]: rgb' = clamp(M rgb + o, 0, 255), 0..255 scale
+ *   words LC2IS_STRONG_W ..   fp32 w[0 .. 8], the blur's taps (w[k] weighs the pixels at distance k); entries past R are 0
+ *   words 24 .. 31            0
+ * Random numbers: h = the sample hash of lc2is_aug_params for (cfg's seed, *epoch, keys[b]) XOR LC2IS_STRONG_STREAM, u24(k) as there: a
+ * StrongAugment, a TrainAugment and a SampleMix with one seed share no draw; a sample's view depends on (seed, epoch, key) only, and a
+ * captured launch pair draws again on replay from the DEVICE epoch / keys.  Draws (a value is drawn whether its switch is on or not):
+ *   k=0  jitter group on iff u24 < jitter_thr
+ *   k=1..4  brightness b in [-brightness_delta, brightness_delta] (0..255 scale), contrast c, saturation s, hue h (radians), each
+ *           lo + (hi - lo) * (u24 * 2^-24) in fp32
+ *   k=5  grey on iff u24 < gray_thr        k=6  blur on iff u24 < blur_thr
+ *   k=7  sigma = fma(sigma_hi - sigma_lo, u24 * 2^-24, sigma_lo) in fp32 (the difference rounded, then ONE rounding), 0 < sigma_lo <=
+ *        sigma_hi <= 2.0;  R = min(LC2IS_STRONG_MAX_RADIUS, ceil(4 * sigma))
+ * Colour: M = I, o = 0; with the jitter group on ALL FOUR steps of lc2is_aug_params in its order and linear form: brightness o += b;
+ * contrast M, o *= c; saturation (M, o) = A (M, o), A = s I + (1 - s) 1 w^T; hue (M, o) = R (M, o), R the rotation by h about
+ * (1, 1, 1) / sqrt(3).  Grey on then applies (M, o) = A (M, o) with A = 1 w^T, w = (0.299, 0.587, 0.114).  ONE clamp to [0, 255]
+ * follows in strong_apply, none between the steps: intermediate values outside the range are carried, not cut - the project's
+ * deliberate difference from torchvision's ColorJitter, which clips after every step.
+ * Blur taps: w_k = exp(-k^2 / (2 sigma^2)) / (w_0 + 2 sum_{k=1..R} w_k) for k = 0 .. R, formed in fp32 in the params kernel. */
+#define LC2IS_STRONG_MAX_RADIUS 8
+#define LC2IS_STRONG_STREAM 0x53545231u /* "STR1" */
+#define LC2IS_STRONG_PARAM_WORDS 32
+#define LC2IS_STRONG_FLAGS 0
+#define LC2IS_STRONG_R 1
+#define LC2IS_STRONG_SIGMA 2
+#define LC2IS_STRONG_M 3
+#define LC2IS_STRONG_O 12
+#define LC2IS_STRONG_W 15
+#define LC2IS_STRONG_COLOUR 1
+#define LC2IS_STRONG_GREY 2
+#define LC2IS_STRONG_BLUR 4
+typedef struct {
+  uint32_t seed_lo, seed_hi;                /* the 64-bit seed                                                           */
+  uint32_t jitter_thr, gray_thr, blur_thr;  /* round(p * 2^24): on iff u24 < thr                                         */
+  float brightness_delta;                   /* b in [-delta, delta], added on the 0..255 scale                           */
+  float contrast_lo, contrast_hi;           /* c: every channel is multiplied by c                                       */
+  float saturation_lo, saturation_hi;       /* s: rgb' = s rgb + (1 - s) grey                                            */
+  float hue_delta;                          /* h in [-delta, delta] RADIANS                                              */
+  float sigma_lo, sigma_hi;                 /* 0 < sigma_lo <= sigma_hi <= 2.0                                           */
+  float mean[3], std[3], inv_std[3];        /* the batch's normalisation; inv_std_c = 1 / std_c rounded to fp32 once     */
+} lc2is_strong_config;
+
+/* strong_params_kernel, one thread per sample b < B: writes row b of params as defined above.  No atomics.
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (keys, epoch, cfg, params); LC2IS_ERR_SHAPE (B < 1, a threshold above
+ * 2^24, a sigma range that is not 0 < lo <= hi <= 2.0, keys not 8-byte, epoch / params not 4-byte aligned).
+ * replaces: the host-side draws of torchvision's ColorJitter.get_params / RandomGrayscale / GaussianBlur.get_params (torch.rand,
+ *   torch.empty(1).uniform_(sigma_min, sigma_max) per image) and the Gaussian kernel each image's sigma is turned into. */
+int lc2is_strong_params(const int64_t* keys, int B, const int32_t* epoch, const lc2is_strong_config* cfg /* HOST */, int32_t* params,
+                        lc2is_stream_t stream);
+
+/* strong_apply_kernel, ONE launch for the batch: grid.y = B samples, grid.x = tiles of 32 rows x 64 columns; in / out fp32
+ * [B][3][S][S].  Sample b, as row b of params says (only the words named here are read; bit 1 of the flags is not acted on):
+ *   flags == 0: out = in BIT FOR BIT (NaN payloads included): no de-normalise / re-normalise round trip.
+ *   colour (bit 0):  v_c = 255 * (x_c * std_c + mean_c);  v' = clamp(M v + o, 0, 255)  (fminf(fmaxf(., 0), 255): a NaN becomes 0);
+ *     after the blur, if any:  out_c = (v'_c * (1/255) - mean_c) * inv_std_c   (lc2is_aug_apply's last line).
+ *   blur (bit 2):  a separable blur with the row's w[0 .. R] on v' (directly on x when colour is off), rows first, then columns:
+ *     t(y, x) = w_0 v'(y, x) + sum_{k=1..R} w_k (v'(y, rho(x - k)) + v'(y, rho(x + k))),  u(y, x) the same over y on t, with the
+ *     border reflected without repeating the edge: rho(i) = -i for i < 0, 2 (S - 1) - i for i >= S (torch's "reflect"; S >= 12 > R).
+ *     Taps past R are not read, whatever the row's w holds there.
+ *   A row whose R lies outside 0 .. LC2IS_STRONG_MAX_RADIUS or whose flag word has a bit above bit 2 is rendered as the copy.  Every
+ *   index is reflected and then clamped into the image: whatever a row holds, nothing outside `in` is read.
+ * Samples without blur stream: 16-byte loads and stores, no LDS traffic.  With blur the colour-mapped tile plus a halo of R is staged
+ * in LDS once per block (colour at staging time, not per tap) and both passes run from LDS; 57 KB of LDS per block, two blocks per
+ * CU.  The branch is block-uniform (one sample per grid.y).  No atomics, no scratch; bitwise reproducible; a sample's output does not
+ * depend on B or on its position in the batch.  Ideal traffic: one read and one write of [B,3,S,S].
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (in, params, cfg, out); LC2IS_ERR_SHAPE (B outside 1 .. 65535, S
+ * outside 12 .. LC2IS_AUG_MAX_SIDE, S % 4, in / out not 16-byte or params not 4-byte aligned, in and out overlapping: the blur reads a
+ * halo, so the call cannot run in place).
+ * replaces: ColorJitter + RandomGrayscale + GaussianBlur applied to the normalised batch: de-normalise, a per-sample 3x3 product
+ *   (einsum), clamp, F.pad(mode="reflect") + a grouped conv2d with per-sample kernels, re-normalise - several passes over the batch. */
+int lc2is_strong_apply(const float* in, const int32_t* params, const lc2is_strong_config* cfg /* HOST */, int B, int S, float* out,
+                       lc2is_stream_t stream);
+
 /* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
  * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
  * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with

@@ -1,6 +1,6 @@
-// The counter-based RNG of the data-path kernels (augment.hip, mix.hip) and their exact small-quotient division.  Every random
-// number is a pure function of (seed, epoch, key, draw number); the definition is in include/lc2is_hip.h (lc2is_aug_params) and
-// tests/augment_ref.py restates it in numpy, bit for bit.
+// The counter-based RNG of the data-path kernels (augment.hip, mix.hip, strong.hip), their exact small-quotient division and the
+// composition of colour maps (aug_left_mul).  Every random number is a pure function of (seed, epoch, key, draw number); the
+// definition is in include/lc2is_hip.h (lc2is_aug_params) and tests/augment_ref.py restates it in numpy, bit for bit.
 #pragma once
 #include "common.h"
 
@@ -27,6 +27,21 @@ __device__ __forceinline__ int aug_div(int n, int d, float rcp_d, int& rem) {
   else if (r >= d) { q += 1; r -= d; }
   rem = r;
   return q;
+}
+
+// (M, o) = A (M, o)
+__device__ __forceinline__ void aug_left_mul(const float (&A)[9], float (&M)[9], float (&o)[3]) {
+  float N[9], p[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) N[3 * r + c] = A[3 * r] * M[c] + A[3 * r + 1] * M[3 + c] + A[3 * r + 2] * M[6 + c];
+    p[r] = A[3 * r] * o[0] + A[3 * r + 1] * o[1] + A[3 * r + 2] * o[2];
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) M[e] = N[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) o[e] = p[e];
 }
 
 }  // namespace

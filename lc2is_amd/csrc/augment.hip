@@ -11,7 +11,7 @@
 //     per sample counts the label cells aug_apply would write for each candidate origin and replaces the row's (top, left).
 //   * label_hist_kernel: per-image class counts of the pool's label maps, for class weights.  Both count with label_hist.h.
 // The exact definition is in include/lc2is_hip.h; tests/augment_ref.py and tests/catcrop_ref.py restate it in numpy (integers bit
-// for bit).  The counter RNG (aug_key, aug_u24, aug_range) and aug_div live in aug_rng.h, shared with mix.hip.
+// for bit).  The counter RNG (aug_key, aug_u24, aug_range), aug_div and aug_left_mul live in aug_rng.h, shared with mix.hip and strong.hip.
 #include "common.h"
 #include "aug_rng.h"
 #include "label_hist.h"
@@ -20,21 +20,6 @@
 namespace {
 
 constexpr int AUG_P = LC2IS_AUG_PARAM_WORDS;
-
-// (M, o) = A (M, o)
-__device__ __forceinline__ void aug_left_mul(const float (&A)[9], float (&M)[9], float (&o)[3]) {
-  float N[9], p[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) N[3 * r + c] = A[3 * r] * M[c] + A[3 * r + 1] * M[3 + c] + A[3 * r + 2] * M[6 + c];
-    p[r] = A[3 * r] * o[0] + A[3 * r + 1] * o[1] + A[3 * r + 2] * o[2];
-  }
-#pragma unroll
-  for (int e = 0; e < 9; ++e) M[e] = N[e];
-#pragma unroll
-  for (int e = 0; e < 3; ++e) o[e] = p[e];
-}
 
 __global__ __launch_bounds__(64) void aug_params_kernel(const int64_t* __restrict__ slots, const int64_t* __restrict__ keys, int B,
                                                          const int32_t* __restrict__ epoch, const lc2is_aug_image* __restrict__ desc,

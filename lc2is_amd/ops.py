@@ -143,6 +143,8 @@ _ARGTYPES = {
     "lc2is_label_histogram": [_P, _Z, _P, _L, _P, _I, _P, _P],
     "lc2is_mix_select": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P],
     "lc2is_mix_apply": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    "lc2is_strong_params": [_P, _I, _P, _P, _P, _P],
+    "lc2is_strong_apply": [_P, _P, _P, _I, _I, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -2613,6 +2615,79 @@ def mix_apply(dst, src, plan: torch.Tensor, out=None):
                                 _ptr(opx), _ptr(olab), _ptr(opw), _stream())
     _lib.check(rc, f"mix_apply B={B} Bs={Bs} S={S} L={L}")
     return opx, olab, opw
+
+
+# ---- strong photometric views (colour jitter, greyscale, Gaussian blur) ----------------------------------------------
+STRONG_MAX_RADIUS, STRONG_PARAM_WORDS, STRONG_STREAM = 8, 32, 0x53545231      # LC2IS_STRONG_*
+STRONG_FLAGS, STRONG_R, STRONG_SIGMA, STRONG_M, STRONG_O, STRONG_W = 0, 1, 2, 3, 12, 15
+STRONG_COLOUR, STRONG_GREY, STRONG_BLUR = 1, 2, 4
+STRONG_MIN_SIDE, STRONG_MAX_SIGMA = 12, 2.0
+
+
+class StrongConfig(C.Structure):
+    """lc2is_strong_config (include/lc2is_hip.h): host struct, passed by value into both kernels."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("jitter_thr", C.c_uint32), ("gray_thr", C.c_uint32),
+                ("blur_thr", C.c_uint32), ("brightness_delta", C.c_float), ("contrast_lo", C.c_float), ("contrast_hi", C.c_float),
+                ("saturation_lo", C.c_float), ("saturation_hi", C.c_float), ("hue_delta", C.c_float), ("sigma_lo", C.c_float),
+                ("sigma_hi", C.c_float), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("inv_std", C.c_float * 3)]
+
+
+def strong_params(keys: torch.Tensor, epoch: torch.Tensor, cfg: StrongConfig, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Draw one row of strong-view parameters per sample (lc2is_strong_params): int32 [B, STRONG_PARAM_WORDS] = flags (bit 0 colour,
+    bit 1 grey, bit 2 blur), the blur radius R, then fp32 bit patterns: sigma, the colour matrix M[3][3] and offset o[3], the blur taps
+    w[0..8]; the rest 0.  keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE int32 scalar.  Nothing but
+    device memory decides the result: a captured call draws again on replay."""
+    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
+    B = keys.numel()
+    if B < 1 or epoch.numel() != 1:
+        raise RuntimeError("lc2is_amd.strong_params: epoch must hold one int32 and keys at least one int64")
+    if max(cfg.jitter_thr, cfg.gray_thr, cfg.blur_thr) > 1 << 24 or not 0.0 < cfg.sigma_lo <= cfg.sigma_hi <= STRONG_MAX_SIGMA:
+        raise ValueError(f"lc2is_amd.strong_params: thresholds must be at most 2^24 and the sigma range ({cfg.sigma_lo}, {cfg.sigma_hi}) "
+                         f"ordered inside (0, {STRONG_MAX_SIGMA}]")
+    if out is None:
+        out = torch.empty((B, STRONG_PARAM_WORDS), dtype=torch.int32, device=keys.device)
+    _chk(out, torch.int32, "out")
+    if tuple(out.shape) != (B, STRONG_PARAM_WORDS) or not out.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.strong_params: out must be contiguous int32 [{B}, {STRONG_PARAM_WORDS}]")
+    rc = _fn("lc2is_strong_params")(_ptr(keys), B, _ptr(epoch), C.addressof(cfg), _ptr(out), _stream())
+    _lib.check(rc, f"strong_params B={B}")
+    return out
+
+
+def _strong_batch(x: torch.Tensor, out: torch.Tensor | None):
+    """Everything strong_apply asks of its input and output, before any device work; returns (B, S, out), out allocated if None."""
+    _chk(x, torch.float32, "pixel_values", 4)
+    B, S = x.shape[0], x.shape[2]
+    if B < 1 or tuple(x.shape) != (B, 3, S, S) or not x.is_contiguous() or x.data_ptr() % 16:
+        raise RuntimeError(f"lc2is_amd.strong_apply: pixel_values must be contiguous fp32 [B, 3, S, S] with a 16-byte base, got shape "
+                           f"{tuple(x.shape)}, strides {tuple(x.stride())}")
+    if S < STRONG_MIN_SIDE or S > AUG_MAX_SIDE or S % 4:
+        raise ValueError(f"lc2is_amd.strong_apply: the size {S} must be a multiple of 4 in {STRONG_MIN_SIDE}..{AUG_MAX_SIDE}")
+    if B > 65535:
+        raise ValueError(f"lc2is_amd.strong_apply: at most 65535 samples per call, got {B}")
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(out, torch.float32, "out", 4)
+    if out.shape != x.shape or not out.is_contiguous() or out.data_ptr() % 16:
+        raise RuntimeError(f"lc2is_amd.strong_apply: out must be contiguous fp32 [{B}, 3, {S}, {S}] with a 16-byte base")
+    if _overlap(out, x):
+        raise RuntimeError("lc2is_amd.strong_apply: out may not overlap the input (the blur reads a halo: no in-place form)")
+    return B, S, out
+
+
+def strong_apply(x: torch.Tensor, params: torch.Tensor, cfg: StrongConfig, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One launch (lc2is_strong_apply): the strong view of a normalised batch fp32 [B, 3, S, S] as the rows of `params`
+    (strong_params) say: colour map on the 0..255 scale with one clamp, separable Gaussian blur with reflected borders, re-normalise;
+    a row with no flag gives the input bit for bit.  S % 4 == 0, 12 <= S <= 4096.  x must be contiguous with a 16-byte base (a batch
+    slice x[i:j] is; a strided or permuted view is refused, not copied); out: a tensor to write into, which may not overlap x (the
+    blur reads a halo)."""
+    _chk(params, torch.int32, "params")
+    B, S, out = _strong_batch(x, out)
+    if tuple(params.shape) != (B, STRONG_PARAM_WORDS) or not params.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.strong_apply: params must be contiguous int32 [{B}, {STRONG_PARAM_WORDS}]")
+    rc = _fn("lc2is_strong_apply")(_ptr(x), _ptr(params), C.addressof(cfg), B, S, _ptr(out), _stream())
+    _lib.check(rc, f"strong_apply B={B} S={S}")
+    return out
 
 
 def set_cu_budget(ncu: int) -> None:

@@ -1,8 +1,8 @@
 """Self-training (mean teacher / pseudo-labelling) on the fused head: confident pseudo-labels and their per-pixel loss weights,
 held on the device.
 
-The teacher is the EMA of ``TrainStep(ema_decay=...)``, the views are ``TrainAugment``'s; this module adds the two pieces between
-them: ``PseudoLabeler`` turns the teacher's prediction on the weak view into labels (the class where the max softmax probability
+The teacher is the EMA of ``TrainStep(ema_decay=...)``, the weak view is ``TrainAugment``'s and the strong view ``StrongAugment``'s
+(``lc2is_amd.data``); this module adds the two pieces between them: ``PseudoLabeler`` turns the teacher's prediction on the weak view into labels (the class where the max softmax probability
 passes a threshold, ``ignore_index`` elsewhere: FixMatch, ST++, DAFormer) and a per-pixel weight, and ``combine`` forms the
 ``(inputs, labels, pixel_weight)`` of one ``TrainStep.step`` from a labelled and a pseudo-labelled batch.  The [B, K, H, W] logits
 are never formed (``model.predict_confidence`` -> ``ops.head_upsample_conf``) and nothing reads the device: the labeler captures
@@ -12,8 +12,12 @@ Recipe (one iteration)::
 
     step = TrainStep(model, ema_decay=0.999, ...)
     labeler = PseudoLabeler(model, threshold=0.968, weight="quality")
+    strong = StrongAugment(seed=1234)                          # colour jitter, greyscale, Gaussian blur: two launches
+    batch_u = TrainAugment(photometric=False, seed=1234)(pool_u, keys, epoch)             # geometry only
+    weak = {**prompts, "pixel_values": batch_u["pixel_values"]}
     with step.ema_weights():                                   # the teacher's weights
-        labels_u, pw_u, _ = labeler(weak_view)
+        labels_u, pw_u, _ = labeler(weak)
+    strong_view = strong.view(weak, keys, epoch)               # the same geometry, another and stronger colour
     step.step(*labeler.combine(labelled=(inputs, labels), pseudo=(strong_view, labels_u, pw_u)))
 
 The soft-teacher iteration beside it (soft mean teacher, the soft variants of FixMatch / UniMatch): the teacher hands over its
@@ -37,7 +41,11 @@ launches, no host read; ``mixed`` is the helper)::
     px, labels_m, pw_m, _ = mix((strong_view["pixel_values"], labels_u, pw_u), (inputs["pixel_values"], labels, None), keys, epoch)
     step.step({**strong_view, "pixel_values": px}, labels_m, pw_m)          # = step.step(*labeler.mixed(...))
 
-Out of scope here: how the strong / weak views are drawn, pooling the confident-pixel counts across ranks, and models
+``strong.view`` goes before the mix, as above (CPS, UniMatch), or after it on the mixed batch, as DACS and DAFormer do: mix
+``(weak, labels_u, pw_u)`` first and call ``strong.view(mixed_inputs, keys, epoch)`` on the result - it takes any normalised fp32
+``pixel_values``.
+
+Out of scope here: geometric strong augmentation (the labels would have to follow), pooling the confident-pixel counts across ranks, and models
 without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
 """
 from __future__ import annotations
