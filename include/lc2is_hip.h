@@ -1021,6 +1021,109 @@ int lc2is_strong_params(const int64_t* keys, int B, const int32_t* epoch, const 
 int lc2is_strong_apply(const float* in, const int32_t* params, const lc2is_strong_config* cfg /* HOST */, int B, int S, float* out,
                        lc2is_stream_t stream);
 
+/* ---- geometric views on the device: a random affine warp per sample, the labels follow; two launches -------------------
+ * Rotation, isotropic scale, shear, translation and horizontal flip of a batch: pixels fp32 [B,3,S,S] bilinear, labels int64 [B,L,L]
+ * and per-pixel loss weights fp32 [B,L,L] nearest, all three under the SAME map.  Out-of-frame image taps take cfg->fill (normalised
+ * units; 0.0 is the mean colour), out-of-frame label cells take cfg->ignore_index and their weights 0.0.  The map goes from OUTPUT to
+ * SOURCE and is held as integers, so every index and every fraction is exact.  Row b of a parameter table int32
+ * [B][LC2IS_GEO_PARAM_WORDS]:
+ *   word LC2IS_GEO_FLAGS      bit 0 (LC2IS_GEO_WARP): the map is not the identity or the flip; bit 1 (LC2IS_GEO_FLIP): flipped
+ *   words LC2IS_GEO_M ..      m00 m01 m10 m11 in Q16 (LC2IS_GEO_ONE = 65536 = 1.0)
+ *   words LC2IS_GEO_T ..      tx ty in Q16, as a fraction of the side
+ *   words LC2IS_GEO_REC ..    the fp32 bit patterns of theta, s, phi, fx, fy as drawn: recorded for the reader, lc2is_geo_apply does not
+ *                             read them
+ *   words 12 .. 15            0
+ * The map, for output element (y, x) of a map of side n (n = S for pixels, n = L for label cells), all in int64:
+ *   u = 2x + 1 - n,  v = 2y + 1 - n,   U = m00 u + m01 v + 2 tx n,   V = m10 u + m11 v + 2 ty n
+ * Pixels:  X = U + (S - 1) 65536;  x0 = X >> 17 (floor);  fx = (X & 0x1FFFF) 2^-17;  Y, y0, fy likewise from V.  The taps are
+ *   (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1); a tap outside [0, S)^2 is fill_c.
+ *   out = lerp(lerp(p00, p01, fx), lerp(p10, p11, fx), fy),  lerp(a, b, f) = a + f (b - a)  (lc2is_aug_apply's form), in fp32.
+ *   When a fraction is 0 the near tap is SELECTED and the far tap is not read: a NaN next door does not spread, and the identity,
+ *   the flip, quarter turns and whole-pixel shifts are bit-exact copies of their source elements.
+ *   This is F.grid_sample(x, F.affine_grid(theta, align_corners=False), "bilinear", "zeros", align_corners=False) with
+ *   theta = [[m00, m01, 2 tx], [m10, m11, 2 ty]] / 65536 (and fill = 0).
+ * Label cells and weights:  xs = (U + L 65536) >> 17,  ys = (V + L 65536) >> 17  (the nearest cell centre, ties upwards); a cell
+ *   inside [0, L)^2 takes lab[ys][xs] and pw[ys][xs], a cell outside takes ignore_index and 0.0.
+ * Random numbers: h = the sample hash of lc2is_aug_params for (cfg's seed, *epoch, keys[b]) XOR LC2IS_GEO_STREAM, u24(k) as there: a
+ * GeometricAugment, a StrongAugment, a SampleMix and a TrainAugment with one seed share no draw; a sample's map depends on (seed,
+ * epoch, key) only, and a captured launch pair draws again on replay from the DEVICE epoch / keys.  Draws (a value is drawn whether
+ * its switch is on or not), each fp32 value fma(hi - lo, u24 * 2^-24, lo): the difference rounded to fp32, then ONE rounding (what
+ * aug_range's lo + (hi - lo) * t compiles to; written out here so that tx, ty can be restated exactly):
+ *   k=0  warp on iff u24 < warp_thr                 k=1  theta in [-rotate, rotate] radians
+ *   k=2  s in [scale_lo, scale_hi], uniform         k=3  phi in [-shear, shear] radians
+ *   k=4, 5  fx, fy in [-translate, translate]       k=6  flip on iff u24 < flip_thr, independent of k=0
+ * With warp on, in fp32:  M = (1/s) R(theta) H(phi),  R = [[cos, -sin], [sin, cos]],  H = [[1, tan phi], [0, 1]],
+ *   m.. = (int)rintf(M.. * 65536),  t. = (int)rintf(f. * 65536);  otherwise M = I, t = 0.  Flip then negates column 0 (m00, m10).
+ *   s > 1 magnifies.  With this M the content turns counter-clockwise: [[0, -1], [1, 0]] gives torch.rot90(x, 1, (-2, -1)).
+ * Limits of the config: 0 <= rotate <= pi, 0.25 <= scale_lo <= scale_hi <= 4, 0 <= shear <= pi / 4, 0 <= translate <= 0.5 (the fp32
+ * neighbours of pi and pi / 4 included), thresholds <= 2^24; they keep |m..| <= LC2IS_GEO_MAX_M = 8 * 65536. */
+#define LC2IS_GEO_STREAM 0x47454F31u /* "GEO1" */
+#define LC2IS_GEO_PARAM_WORDS 16
+#define LC2IS_GEO_FLAGS 0
+#define LC2IS_GEO_M 1
+#define LC2IS_GEO_T 5
+#define LC2IS_GEO_REC 7
+#define LC2IS_GEO_WARP 1
+#define LC2IS_GEO_FLIP 2
+#define LC2IS_GEO_ONE 65536
+#define LC2IS_GEO_MAX_M 524288
+#define LC2IS_GEO_MAX_T 65536
+#define LC2IS_GEO_MIN_SIDE 8
+typedef struct {
+  uint32_t seed_lo, seed_hi;      /* the 64-bit seed                                                   */
+  uint32_t warp_thr, flip_thr;    /* round(p * 2^24): on iff u24 < thr                                 */
+  float rotate;                   /* theta in [-rotate, rotate] RADIANS, rotate <= pi                  */
+  float scale_lo, scale_hi;       /* s: 0.25 <= scale_lo <= scale_hi <= 4                              */
+  float shear;                    /* phi in [-shear, shear] RADIANS, shear <= pi / 4                   */
+  float translate;                /* fx, fy in [-translate, translate] of the side, translate <= 0.5   */
+  float fill[3];                  /* out-of-frame colour per channel, NORMALISED units                 */
+  int64_t ignore_index;           /* out-of-frame label                                                */
+} lc2is_geo_config;
+
+/* geo_params_kernel, one thread per sample b < B: writes row b of params as defined above.  No atomics.
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (keys, epoch, cfg, params); LC2IS_ERR_SHAPE (B < 1, a config outside
+ * the limits above, keys not 8-byte, epoch / params not 4-byte aligned).
+ * replaces: the host-side draws of torchvision's RandomAffine.get_params / RandomHorizontalFlip and mmseg's RandomRotate (one
+ *   torch.empty(1).uniform_ or np.random call per value and image) and the 2 x 3 theta each image's draw is turned into. */
+int lc2is_geo_params(const int64_t* keys, int B, const int32_t* epoch, const lc2is_geo_config* cfg /* HOST */, int32_t* params,
+                     lc2is_stream_t stream);
+
+/* geo_apply_kernel, ONE launch for pixels, labels and weights: grid.y = B samples, grid.x = pixel blocks followed by label-cell
+ * blocks (256 lanes), the layout of mix_apply_kernel.  in_lab / in_pw may be NULL: that map is then neither read nor written (its
+ * out pointer is ignored); with both NULL there are no label-cell blocks (L is still checked).  Sample b, as row b of params says
+ * (only words 0 .. 6 are read):
+ *   flags == 0, whatever the other words hold: the COPY of the sample - pixels, labels and weights bit for bit (NaN payloads too).
+ *   a flag bit above bit 1, an |m..| > LC2IS_GEO_MAX_M or a |t.| > LC2IS_GEO_MAX_T: rendered as the copy as well.
+ *   otherwise (bit 0 or bit 1 set): the map of words 1 .. 6 as defined above.  The two bits are not told apart: a flip is the map
+ *   m = (-65536, 0, 0, 65536).
+ * Every 64-bit index is clamped into [-2, n] before it is narrowed and every tap is bounds-checked: whatever a row holds, nothing
+ * outside the inputs is read.
+ * Copy rows stream: a block moves 512 consecutive pixel quads of all three channels with 16-byte loads and stores, no index
+ * arithmetic (the later half of the sample's blocks has nothing to do).  Mapped rows: a block makes a 32 x 32 output tile; a lane
+ * makes 4 consecutive x of all three channels and writes three 16-byte stores.  A wave's patch is 32 columns x 8 rows (strong_apply's
+ * is 64 x 4): each of its store instructions still fills whole 128-byte lines, and its rotated footprint is squarer, so at 45
+ * degrees it spans about 28 source rows of 2 lines each where the 64 x 4 patch spans 48 rows of 2 - 3 lines.  The taps come from one
+ * of two places, chosen per block (block-uniform):
+ *   staged: the block forms the source bounding box of its tile from the tile's four corners (the map is affine, so the extreme
+ *     near taps belong to corners; + 1 for the far taps), clips it to the image and widens it to whole quads; when the box holds at
+ *     most 4096 words per channel (48 KB of LDS, three blocks per CU) it is staged once with 16-byte loads and every tap is an LDS
+ *     read.  Up to a 2 x zoom-out at any angle fits (45 degrees at scale 0.8: 60 x 64); at S <= 64 everything fits.
+ *   direct: a larger box (zooming far out: scale 0.25 reads 128 x 128) is not staged; the taps are predicated 4-byte gathers from
+ *     global memory.  The arithmetic is the same: both forms give the same bits.
+ * Label cells are one per lane (8-byte / 4-byte accesses) in every case.  The branches are block-uniform (one sample per grid.y).
+ * No atomics, no scratch; bitwise reproducible; a sample's output depends neither on B nor on its position in the batch.  Ideal
+ * traffic: one read and one write of [B,3,S,S] plus the label and weight maps.
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (in_px, params, cfg, out_px; out_lab with in_lab given; out_pw
+ * with in_pw given); LC2IS_ERR_SHAPE (B outside 1 .. 65535, S outside LC2IS_GEO_MIN_SIDE .. LC2IS_AUG_MAX_SIDE, S % 4, L < 1, S % L, a
+ * config outside the limits, pixels not 16-byte, labels not 8-byte, weights / params not 4-byte aligned, an output that overlaps
+ * its input).
+ * replaces: torchvision's RandomAffine / mmseg's RandomRotate on a device batch - F.affine_grid, F.grid_sample(bilinear) on the
+ *   pixels, F.grid_sample(nearest) on float copies of labels and weights, an in-frame mask and torch.where for the fill colour, the
+ *   ignore label and the zero weight: several full-size temporaries, and no exact definition at cell edges. */
+int lc2is_geo_apply(const float* in_px, const int64_t* in_lab, const float* in_pw, const int32_t* params,
+                    const lc2is_geo_config* cfg /* HOST */, int B, int S, int L, float* out_px, int64_t* out_lab, float* out_pw,
+                    lc2is_stream_t stream);
+
 /* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
  * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
  * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with

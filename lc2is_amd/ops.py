@@ -145,6 +145,8 @@ _ARGTYPES = {
     "lc2is_mix_apply": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
     "lc2is_strong_params": [_P, _I, _P, _P, _P, _P],
     "lc2is_strong_apply": [_P, _P, _P, _I, _I, _P, _P],
+    "lc2is_geo_params": [_P, _I, _P, _P, _P, _P],
+    "lc2is_geo_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -2688,6 +2690,117 @@ def strong_apply(x: torch.Tensor, params: torch.Tensor, cfg: StrongConfig, *, ou
     rc = _fn("lc2is_strong_apply")(_ptr(x), _ptr(params), C.addressof(cfg), B, S, _ptr(out), _stream())
     _lib.check(rc, f"strong_apply B={B} S={S}")
     return out
+
+
+# ---- geometric views (random affine warp; labels and weights follow) --------------------------------------------------
+GEO_PARAM_WORDS, GEO_STREAM = 16, 0x47454F31                                   # LC2IS_GEO_*
+GEO_FLAGS, GEO_M, GEO_T, GEO_REC = 0, 1, 5, 7
+GEO_WARP, GEO_FLIP = 1, 2
+GEO_ONE, GEO_MAX_M, GEO_MAX_T, GEO_MIN_SIDE = 65536, 524288, 65536, 8
+GEO_MAX_ROTATE, GEO_MAX_SHEAR = C.c_float(math.pi).value, C.c_float(math.pi / 4).value      # the fp32 neighbours of pi, pi / 4
+GEO_MIN_SCALE, GEO_MAX_SCALE, GEO_MAX_TRANSLATE = 0.25, 4.0, 0.5
+
+
+class GeoConfig(C.Structure):
+    """lc2is_geo_config (include/lc2is_hip.h): host struct, passed by value into both kernels."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("warp_thr", C.c_uint32), ("flip_thr", C.c_uint32),
+                ("rotate", C.c_float), ("scale_lo", C.c_float), ("scale_hi", C.c_float), ("shear", C.c_float),
+                ("translate", C.c_float), ("fill", C.c_float * 3), ("ignore_index", C.c_int64)]
+
+
+def _geo_config(cfg: GeoConfig, who: str) -> None:
+    """The limits of include/lc2is_hip.h (they keep every |m| <= GEO_MAX_M); a NaN fails its comparison."""
+    if max(cfg.warp_thr, cfg.flip_thr) > 1 << 24:
+        raise ValueError(f"lc2is_amd.{who}: thresholds must be at most 2^24, got {cfg.warp_thr}, {cfg.flip_thr}")
+    if not (0.0 <= cfg.rotate <= GEO_MAX_ROTATE and GEO_MIN_SCALE <= cfg.scale_lo <= cfg.scale_hi <= GEO_MAX_SCALE
+            and 0.0 <= cfg.shear <= GEO_MAX_SHEAR and 0.0 <= cfg.translate <= GEO_MAX_TRANSLATE):
+        raise ValueError(f"lc2is_amd.{who}: rotate {cfg.rotate} must be 0..pi, the scale range ({cfg.scale_lo}, {cfg.scale_hi}) ordered "
+                         f"inside [{GEO_MIN_SCALE}, {GEO_MAX_SCALE}], shear {cfg.shear} 0..pi/4 and translate {cfg.translate} "
+                         f"0..{GEO_MAX_TRANSLATE}")
+
+
+def geo_params(keys: torch.Tensor, epoch: torch.Tensor, cfg: GeoConfig, *, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Draw one affine map per sample (lc2is_geo_params): int32 [B, GEO_PARAM_WORDS] = flags (bit 0 warp, bit 1 flip), the output-to-
+    source matrix m00 m01 m10 m11 and the translation tx ty in Q16, the fp32 bit patterns of theta, s, phi, fx, fy as drawn; the
+    rest 0.  keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE int32 scalar.  Nothing but device
+    memory decides the result: a captured call draws again on replay."""
+    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
+    B = keys.numel()
+    if B < 1 or epoch.numel() != 1:
+        raise RuntimeError("lc2is_amd.geo_params: epoch must hold one int32 and keys at least one int64")
+    _geo_config(cfg, "geo_params")
+    if out is None:
+        out = torch.empty((B, GEO_PARAM_WORDS), dtype=torch.int32, device=keys.device)
+    _chk(out, torch.int32, "out")
+    if tuple(out.shape) != (B, GEO_PARAM_WORDS) or not out.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.geo_params: out must be contiguous int32 [{B}, {GEO_PARAM_WORDS}]")
+    rc = _fn("lc2is_geo_params")(_ptr(keys), B, _ptr(epoch), C.addressof(cfg), _ptr(out), _stream())
+    _lib.check(rc, f"geo_params B={B}")
+    return out
+
+
+def _geo_batch(batch, out):
+    """Everything geo_apply asks of its batch and outputs, before any device work; returns (B, S, L, out) with the missing outputs
+    allocated.  An entry of the batch that is None has None as its output."""
+    if not isinstance(batch, (tuple, list)) or len(batch) != 3:
+        raise TypeError("lc2is_amd.geo_apply: batch must be (pixel_values, labels or None, pixel_weight or None)")
+    px, lab, pw = batch
+    if px is None:
+        raise RuntimeError("lc2is_amd.geo_apply: pixel_values are required")
+    _chk(px, torch.float32, "pixel_values", 4); _chk(lab, torch.int64, "labels", 3); _chk(pw, torch.float32, "pixel_weight", 3)
+    B, S = px.shape[0], px.shape[2]
+    if B < 1 or tuple(px.shape) != (B, 3, S, S) or not px.is_contiguous() or px.data_ptr() % 16:
+        raise RuntimeError(f"lc2is_amd.geo_apply: pixel_values must be contiguous fp32 [B, 3, S, S] with a 16-byte base, got shape "
+                           f"{tuple(px.shape)}, strides {tuple(px.stride())}")
+    maps = [m for m in (lab, pw) if m is not None]
+    L = maps[0].shape[1] if maps else S
+    for m, name, align in ((lab, "labels", 8), (pw, "pixel_weight", 4)):
+        if m is not None and (tuple(m.shape) != (B, L, L) or not m.is_contiguous() or m.data_ptr() % align or m.device != px.device):
+            raise RuntimeError(f"lc2is_amd.geo_apply: {name} must be contiguous [{B}, L, L] on the pixels' device, labels and weights "
+                               f"of one L, got shape {tuple(m.shape)}, strides {tuple(m.stride())}")
+    if S < GEO_MIN_SIDE or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
+        raise ValueError(f"lc2is_amd.geo_apply: the size {S} must be a multiple of 4 and of the label size {L}, in "
+                         f"{GEO_MIN_SIDE}..{AUG_MAX_SIDE}")
+    if B > 65535:
+        raise ValueError(f"lc2is_amd.geo_apply: at most 65535 samples per call, got {B}")
+    if out is None:
+        out = (None, None, None)
+    if not isinstance(out, (tuple, list)) or len(out) != 3:
+        raise TypeError("lc2is_amd.geo_apply: out must be (pixel_values, labels or None, pixel_weight or None)")
+    outs = []
+    for o, i, dtype, nd, align, name in ((out[0], px, torch.float32, 4, 16, "out pixel_values"), (out[1], lab, torch.int64, 3, 8, "out labels"),
+                                         (out[2], pw, torch.float32, 3, 4, "out pixel_weight")):
+        if i is None:
+            outs.append(None)
+            continue
+        if o is None:
+            o = torch.empty_like(i)
+        _chk(o, dtype, name, nd)
+        if o.shape != i.shape or not o.is_contiguous() or o.data_ptr() % align or o.device != i.device:
+            raise RuntimeError(f"lc2is_amd.geo_apply: {name} must be contiguous {tuple(i.shape)} with a {align}-byte base on the input's device")
+        if _overlap(o, i):
+            raise RuntimeError(f"lc2is_amd.geo_apply: {name} may not overlap its input (a warp gathers: no in-place form)")
+        outs.append(o)
+    return B, S, L, tuple(outs)
+
+
+def geo_apply(batch, params: torch.Tensor, cfg: GeoConfig, *, out=None):
+    """One launch (lc2is_geo_apply): the affine warp of batch = (pixel_values fp32 [B, 3, S, S], labels int64 [B, L, L] or None,
+    pixel_weight fp32 [B, L, L] or None) as the rows of `params` (geo_params) say, all three under the same map: pixels bilinear with
+    cfg.fill out of frame, labels and weights nearest with cfg.ignore_index / 0.0 out of frame.  A row with no flag, or one out of
+    range, gives the sample bit for bit.  S % 4 == 0, S % L == 0, 8 <= S <= 4096.  Tensors must be contiguous (a batch slice is; a
+    strided or permuted view is refused, not copied); out: (pixels, labels, weights) to write into, none of which may overlap its
+    input.  Returns (pixels, labels, weights); an entry that was None stays None."""
+    B, S, L, (opx, olab, opw) = _geo_batch(batch, out)
+    _chk(params, torch.int32, "params")
+    _geo_config(cfg, "geo_apply")
+    if tuple(params.shape) != (B, GEO_PARAM_WORDS) or not params.is_contiguous():
+        raise RuntimeError(f"lc2is_amd.geo_apply: params must be contiguous int32 [{B}, {GEO_PARAM_WORDS}]")
+    px, lab, pw = batch
+    rc = _fn("lc2is_geo_apply")(_ptr(px), _ptr(lab), _ptr(pw), _ptr(params), C.addressof(cfg), B, S, L, _ptr(opx), _ptr(olab),
+                                _ptr(opw), _stream())
+    _lib.check(rc, f"geo_apply B={B} S={S} L={L}")
+    return opx, olab, opw
 
 
 def set_cu_budget(ncu: int) -> None:

@@ -45,7 +45,15 @@ launches, no host read; ``mixed`` is the helper)::
 ``(weak, labels_u, pw_u)`` first and call ``strong.view(mixed_inputs, keys, epoch)`` on the result - it takes any normalised fp32
 ``pixel_values``.
 
-Out of scope here: geometric strong augmentation (the labels would have to follow), pooling the confident-pixel counts across ranks, and models
+The geometric step (RandAugment-style rotate / scale / shear / translate of FixMatch, PseudoSeg, AEL) comes after the teacher has
+labelled the weak view: the student's pixels, the pseudo-labels and their weights are warped under ONE per-sample affine map
+(``lc2is_amd.data.GeometricAugment``, two launches, no host read); what the warp brings in from outside the frame is the mean
+colour, ``ignore_index`` and weight 0, so it costs no loss::
+
+    geo = GeometricAugment(rotate_deg=20.0, scale_range=(0.8, 1.25), seed=1234)
+    strong_view, labels_u, pw_u = geo.view(strong_view, labels_u, pw_u, keys, epoch)      # then combine / mix / step as above
+
+Out of scope here: warping score maps back (the inverse map, for a teacher that sees the warped image), pooling the confident-pixel counts across ranks, and models
 without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
 """
 from __future__ import annotations
