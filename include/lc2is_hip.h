@@ -1124,6 +1124,50 @@ int lc2is_geo_apply(const float* in_px, const int64_t* in_lab, const float* in_p
                     const lc2is_geo_config* cfg /* HOST */, int B, int S, int L, float* out_px, int64_t* out_lab, float* out_pw,
                     lc2is_stream_t stream);
 
+/* geo_scores_kernel, ONE launch: a teacher's low-resolution score map follows the student's geometric view (the soft-teacher step
+ * under a geometric view: the teacher saw the weak view, the student sees the warped one, and the per-pixel KL needs the teacher's
+ * scores at the student's grid positions), with an optional weight map at label resolution.  The FORWARD direction only: the same
+ * output-to-source map as lc2is_geo_apply.
+ *   in_scores / out_scores  fp32 [B][g][g][ld], i.e. [B*g*g, ld] channel-last as the head's scores are held; ALL ld columns are
+ *                           treated alike (padding columns are warped like the rest; their content is nobody's business)
+ *   params                  the table [B][LC2IS_GEO_PARAM_WORDS] of lc2is_geo_params; only words 0 .. 6 are read
+ *   in_tw / out_tw          fp32 [B][L][L], looked at only with want_tw != 0; in_tw may be NULL
+ * Rows are told apart exactly as lc2is_geo_apply tells them apart: flags == 0, a flag bit above bit 1, an |m..| > LC2IS_GEO_MAX_M
+ * or a |t.| > LC2IS_GEO_MAX_T give the COPY of the sample, bit for bit (NaN payloads too); otherwise the map of words 1 .. 6.
+ * Scores of a mapped row, output cell (y, x): the map above for a map of side n = g, all in int64:
+ *   u = 2x + 1 - g,  v = 2y + 1 - g,   U = m00 u + m01 v + 2 tx g,   V = m10 u + m11 v + 2 ty g
+ *   X = U + (g - 1) 65536;  Xc = min(max(X, 0), (g - 1) 2^17);  x0 = Xc >> 17;  fxi = Xc & 0x1FFFF;  fx = fxi 2^-17;
+ *   Y, Yc, y0, fyi, fy likewise from V.
+ *   The position is clamped BEFORE it is split into index and fraction: an out-of-frame cell selects the border cell (fraction
+ *   0) with no arithmetic, and every tap that is read lies inside the sample.  Taps and order are lc2is_geo_apply's pixel rule, per
+ *   column, in fp32:
+ *     top = fxi ? p00 + fx (p01 - p00) : p00;   bot = fxi ? p10 + fx (p11 - p10) : p10;   out = fyi ? top + fy (bot - top) : top
+ *   with p00 = in[y0][x0], p01 = in[y0][x0+1], p10 = in[y0+1][x0], p11 = in[y0+1][x0+1]; a far tap whose fraction is 0 is not read:
+ *   the identity, the flip, quarter and half turns and whole-cell shifts move bits, and a NaN next door does not spread.
+ *   This is F.grid_sample(x, F.affine_grid(theta, align_corners=False), "bilinear", padding_mode="border", align_corners=False)
+ *   with theta = [[m00, m01, 2 tx], [m10, m11, 2 ty]] / 65536 on the [B, ld, g, g] view of the scores.
+ *   Border, not a fill value: the head upsamples these scores bicubically, so a fill would leak into in-frame pixels next to the
+ *   edge; border values are plausible scores, and the mask below takes the out-of-frame pixels out of the loss.
+ * Weight map, want_tw != 0: lc2is_geo_apply's cell rule at side L: xs = (U + L 65536) >> 17, ys = (V + L 65536) >> 17 with U, V for
+ *   n = L; a cell inside [0, L)^2 takes in_tw[ys][xs], or 1.0f when in_tw is NULL (out_tw is then the IN-FRAME MASK); a cell outside
+ *   takes 0.0f.  A copy row copies in_tw, or writes ones.  With want_tw == 0 neither weight pointer is touched (L is not checked).
+ * Layout: grid.y = B samples, grid.x = score blocks followed by weight-cell blocks (256 lanes), the branches block-uniform (one
+ * sample per grid.y).  A score block of a mapped row owns a 4 x 4 patch of output cells, so that neighbouring cells share their taps
+ * in cache; a lane owns a float4 column group of a cell: four 16-byte loads at most and one 16-byte store along the channel axis,
+ * the lanes of a cell reading whole rows of 4 ld bytes.  A copy row streams: block k moves the 4 ld quads after quad 4 ld k of the
+ * sample with 16-byte loads and stores and no index arithmetic.  Weight cells are one per lane (4-byte accesses).  No LDS, no
+ * atomics, no scratch; bitwise reproducible; a sample's output depends neither on B nor on its position in the batch.  Every
+ * 64-bit index is range-checked before it is narrowed: whatever a row holds, nothing outside the inputs is read.  Ideal traffic:
+ * one read and one write of the scores plus the weight map.
+ * Errors, in this order, from the arguments alone: LC2IS_ERR_NULL (in_scores, params, out_scores; out_tw with want_tw);
+ * LC2IS_ERR_SHAPE (B outside 1 .. 65535, g outside 1 .. 512, ld outside 4 .. 1024, ld % 4; with want_tw: L < 1,
+ * L > LC2IS_AUG_MAX_SIDE, L % g; scores not 16-byte, weights / params not 4-byte aligned; an output that overlaps its input).
+ * replaces: scores.view(B, g, g, ld).permute(0, 3, 1, 2), a theta built from the table (on the host: a read-back that breaks graph
+ *   capture), F.affine_grid, F.grid_sample(bilinear, border), permute back and contiguous(); for the mask F.grid_sample(nearest) of
+ *   the weights or of ones and a torch.where - several temporaries of the scores' size, and no exact definition at cell edges. */
+int lc2is_geo_scores(const float* in_scores, const float* in_tw, const int32_t* params, int B, int g, int ld, int L, int want_tw,
+                     float* out_scores, float* out_tw, lc2is_stream_t stream);
+
 /* ---- online hard example mining (OHEM): the loss over the pixels the model currently gets wrong ----------------------
  * Rule, in loss space: a pixel is valid iff label != ignore_index && 0 <= label < C; l_i = lse_i - z_{i,y_i} (plain CE, fp32);
  * k = min(min_kept_total, n_valid - 1); L = the valid loss of rank k (0-based, descending); L_eff = fminf(L, loss_thresh) with

@@ -15,7 +15,9 @@
 //     per CU) and the taps are LDS reads; DIRECT form otherwise (zooming far out): 4-byte gathers from global memory.  Measured at
 //     B = 32, S = 512 (tools/probes/geo_staged): 10 degrees 108 -> 54 us, 45 degrees at scale 0.8 121 -> 58 us, same bits.
 //     No atomics, no scratch.
-// The exact definition is in include/lc2is_hip.h; tests/geo_ref.py restates it in numpy.
+//   * geo_scores_kernel: a teacher's low-resolution score map [B][g][g][ld] follows the view under the same table (the soft-teacher
+//     step), bilinear with border padding, and writes the weight map / in-frame mask at label resolution; described at the kernel.
+// The exact definition is in include/lc2is_hip.h; tests/geo_ref.py and tests/geo_scores_ref.py restate it in numpy.
 #include <math.h>
 #include "common.h"
 #include "aug_rng.h"
@@ -256,6 +258,95 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_apply_kernel(const float* __r
   for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane + (size_t)y * S + x) = o[c];
 }
 
+// The teacher's low-resolution score map under the same table: scores fp32 [B][G][G][4 Q] channel-last (head_scores' layout), bilinear
+// with BORDER padding (the position is clamped before it is split, so every tap lies inside the sample and no fill exists), and an
+// optional weight map fp32 [B][L][L] under geo_apply's cell rule (in_tw NULL: the in-frame mask).  One launch, one sample per
+// blockIdx.y, score blocks followed by weight-cell blocks, the branches block-uniform.  A score block owns a GS_PATCH x GS_PATCH patch
+// of output cells and a lane a float4 column group of a cell (16-byte loads and stores along the channel axis; the lanes of a cell
+// read whole rows of 16 Q bytes, and the cells of a patch share their taps in cache); a copy row streams the 16 Q quads that follow
+// blockIdx.x * 16 Q with no index arithmetic.  No LDS, no atomics, no scratch.
+constexpr int GS_PATCH = 4, GS_CELLS = GS_PATCH * GS_PATCH, GS_COPY = 4;   // GS_COPY: quads a lane of a copy row has in flight
+
+__global__ __launch_bounds__(GEO_THREADS) void geo_scores_kernel(const float* __restrict__ in_sc, const float* __restrict__ in_tw,
+                                                                  const int32_t* __restrict__ params, int G, int Q, int L,
+                                                                  int score_blocks, int patches_x, float* __restrict__ out_sc,
+                                                                  float* __restrict__ out_tw) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const GeoMap mp = geo_map(params + (size_t)b * GEO_P);
+
+  if ((int)blockIdx.x >= score_blocks) {   // ---- weight cells, one per lane (launched only when the weight map is wanted) ----
+    const int LL = L * L;
+    const int cell = ((int)blockIdx.x - score_blocks) * GEO_THREADS + tid;
+    if (cell >= LL) return;
+    const size_t base = (size_t)b * LL;
+    if (!mp.mapped) {   // block-uniform
+      out_tw[base + cell] = in_tw ? in_tw[base + cell] : 1.0f;
+      return;
+    }
+    int x;
+    const int y = aug_div(cell, L, __builtin_amdgcn_rcpf((float)L), x);
+    const long long u = 2 * x + 1 - L, v = 2 * y + 1 - L, n = L;
+    const long long xs = (mp.m00 * u + mp.m01 * v + 2 * mp.tx * n + n * 65536) >> 17;
+    const long long ys = (mp.m10 * u + mp.m11 * v + 2 * mp.ty * n + n * 65536) >> 17;
+    const bool inside = xs >= 0 && xs < n && ys >= 0 && ys < n;   // checked in 64 bits, then narrowed
+    float w = 0.0f;
+    if (inside) w = in_tw ? in_tw[base + (size_t)(geo_narrow(ys, L - 1) * L + geo_narrow(xs, L - 1))] : 1.0f;
+    out_tw[base + cell] = w;
+    return;
+  }
+
+  const int items = GS_CELLS * Q, total = G * G * Q;   // quads: of a block, of the sample (<= 2^26)
+  const f32x4_t* src = (const f32x4_t*)in_sc + (size_t)b * total;
+  f32x4_t* dst = (f32x4_t*)out_sc + (size_t)b * total;
+
+  if (!mp.mapped) {   // block-uniform: the block's share of the sample's quads, in order; the last blocks may have none
+    const int q0 = (int)blockIdx.x * items;   // < 2^27
+    for (int i0 = tid; i0 < items; i0 += GS_COPY * GEO_THREADS) {
+      f32x4_t v[GS_COPY];
+#pragma unroll
+      for (int e = 0; e < GS_COPY; ++e) {
+        const int i = i0 + e * GEO_THREADS;
+        if (i < items && q0 + i < total) v[e] = src[q0 + i];
+      }
+#pragma unroll
+      for (int e = 0; e < GS_COPY; ++e) {
+        const int i = i0 + e * GEO_THREADS;
+        if (i < items && q0 + i < total) dst[q0 + i] = v[e];
+      }
+    }
+    return;
+  }
+
+  // ---- the mapped patch: item i = (cell i / Q of the patch, column group i % Q) ----
+  int px;
+  const int py = aug_div((int)blockIdx.x, patches_x, __builtin_amdgcn_rcpf((float)patches_x), px);
+  const long long n = G, offx = 2 * mp.tx * n + (n - 1) * 65536, offy = 2 * mp.ty * n + (n - 1) * 65536, last = (n - 1) << 17;
+  const float rq = __builtin_amdgcn_rcpf((float)Q);
+  const int down = G * Q;
+  for (int i = tid; i < items; i += GEO_THREADS) {
+    int q;
+    const int c = aug_div(i, Q, rq, q);
+    const int x = px * GS_PATCH + (c & (GS_PATCH - 1)), y = py * GS_PATCH + c / GS_PATCH;
+    if (x >= G || y >= G) continue;
+    const long long u = 2 * x + 1 - G, v = 2 * y + 1 - G;
+    long long X = mp.m00 * u + mp.m01 * v + offx, Y = mp.m10 * u + mp.m11 * v + offy;
+    // clamped BEFORE the split: an out-of-frame position is the border cell with fraction 0, and a far tap that is read (its
+    // fraction is not 0, so the near index is at most G - 2) lies inside the sample too
+    X = X < 0 ? 0 : (X > last ? last : X);
+    Y = Y < 0 ? 0 : (Y > last ? last : Y);
+    const int x0 = geo_narrow(X >> 17, G - 1), y0 = geo_narrow(Y >> 17, G - 1);   // in [0, G - 1] by the clamp
+    const int fxi = (int)(X & 0x1FFFF), fyi = (int)(Y & 0x1FFFF);
+    const float fx = (float)fxi * (1.0f / 131072.0f), fy = (float)fyi * (1.0f / 131072.0f);
+    const bool hx = fxi != 0, hy = fyi != 0;
+    const f32x4_t* p = src + ((y0 * G + x0) * Q + q);
+    const f32x4_t p00 = p[0];
+    const f32x4_t p01 = hx ? p[Q] : p00, p10 = hy ? p[down] : p00, p11 = (hx && hy) ? p[down + Q] : p00;
+    const f32x4_t top = hx ? p00 + fx * (p01 - p00) : p00;
+    const f32x4_t bot = hx ? p10 + fx * (p11 - p10) : p10;
+    dst[(y * G + x) * Q + q] = hy ? top + fy * (bot - top) : top;
+  }
+}
+
 // [a, a + n) and [b, b + n) bytes share a byte
 bool geo_overlap(const void* a, const void* b, size_t n) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -302,5 +393,25 @@ extern "C" int lc2is_geo_apply(const float* in_px, const int64_t* in_lab, const 
   const int lab_blocks = (in_lab || in_pw) ? (int)((cells + GEO_THREADS - 1) / GEO_THREADS) : 0;
   hipLaunchKernelGGL(geo_apply_kernel<GEO_BOX_WORDS>, dim3(img_blocks + lab_blocks, B), dim3(GEO_THREADS), 0, stream, in_px, in_lab, in_pw, params,
                      *cfg, S, L, img_blocks, tiles_x, out_px, out_lab, out_pw);
+  return lc2is_check_launch();
+}
+
+extern "C" int lc2is_geo_scores(const float* in_scores, const float* in_tw, const int32_t* params, int B, int g, int ld, int L,
+                                int want_tw, float* out_scores, float* out_tw, lc2is_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!in_scores || !params || !out_scores || (want_tw && !out_tw)) return LC2IS_ERR_NULL;
+  if (!want_tw) in_tw = nullptr, out_tw = nullptr;   // neither weight pointer is looked at
+  if (B <= 0 || B > 65535 || g < 1 || g > 512 || ld < 4 || ld > 1024 || (ld & 3) ||
+      (want_tw && (L < 1 || L > LC2IS_AUG_MAX_SIDE || L % g)) || (((uintptr_t)in_scores | (uintptr_t)out_scores) & 15) ||
+      (((uintptr_t)in_tw | (uintptr_t)out_tw | (uintptr_t)params) & 3))
+    return LC2IS_ERR_SHAPE;
+  if (geo_overlap(out_scores, in_scores, (size_t)B * g * g * ld * sizeof(float)) ||
+      (want_tw && geo_overlap(out_tw, in_tw, (size_t)B * L * L * sizeof(float))))
+    return LC2IS_ERR_SHAPE;
+  // a mapped row: one block per 4 x 4 patch of cells; a copy row needs g * g / 16 blocks of 16 cells' quads, never more than that
+  const int patches_x = (g + GS_PATCH - 1) / GS_PATCH, score_blocks = patches_x * patches_x;
+  const int tw_blocks = want_tw ? (int)(((size_t)L * L + GEO_THREADS - 1) / GEO_THREADS) : 0;
+  hipLaunchKernelGGL(geo_scores_kernel, dim3(score_blocks + tw_blocks, B), dim3(GEO_THREADS), 0, stream, in_scores, in_tw, params, g,
+                     ld / 4, L, score_blocks, patches_x, out_scores, out_tw);
   return lc2is_check_launch();
 }

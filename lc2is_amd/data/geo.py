@@ -23,6 +23,13 @@ own: a ``GeometricAugment``, a ``StrongAugment``, a ``SampleMix`` and a ``TrainA
 does not depend on the batch, and nothing is read back, so the launch pair captures into a graph whose replays draw again from the
 device epoch / key tensors.  The exact definition is in include/lc2is_hip.h (lc2is_geo_params / lc2is_geo_apply); tests/geo_ref.py
 restates it in numpy.  There is no CPU path.
+
+For the soft teacher (``TrainStep.step_distill``) the teacher's low-resolution scores follow the student under the same table, in
+one more launch (lc2is_geo_scores; tests/geo_scores_ref.py): bilinear with border padding, with an in-frame mask at the labels' size
+that takes the cells from outside the frame out of the KL::
+
+    view, labels_g, pw_g, scores_g, mask = geo.view_distill(strong_view, labels, scores_t, keys, epoch)
+    step.step_distill(view, labels_g, scores_g, teacher_weight=mask)
 """
 from __future__ import annotations
 
@@ -45,7 +52,8 @@ class GeometricAugment:
     write into, none of which may overlap its input.  ``view(inputs, labels, pixel_weight, keys, epoch)`` returns
     ``({**inputs, "pixel_values": warped}, labels', pixel_weight')``.  ``rotate_deg`` (at most 180) and ``shear_deg`` (at most 45) are
     in degrees, ``scale_range`` lies inside [0.25, 4], ``translate`` (at most 0.5) is a share of the side.  ``last_params``: the
-    device table int32 [B, 16] of the last call (ops.geo_params), never read back here."""
+    device table int32 [B, 16] of the last call (ops.geo_params), never read back here.  ``warp_scores`` / ``view_distill``: a
+    teacher's low-resolution score map under the same table."""
 
     def __init__(self, prob: float = 1.0, rotate_deg: float = 20.0, scale_range=(0.8, 1.25), shear_deg: float = 0.0,
                  translate: float = 0.0, flip_prob: float = 0.0, fill=None, ignore_index: int = -100,
@@ -119,3 +127,83 @@ class GeometricAugment:
         every other entry of ``inputs`` is passed on as it is."""
         px, labels, pixel_weight = self((inputs["pixel_values"], labels, pixel_weight), keys, epoch, out=out)
         return {**inputs, "pixel_values": px}, labels, pixel_weight
+
+    @staticmethod
+    def _scores_grid(scores, B: int, teacher_weight, label_size, who: str) -> int:
+        """g of a score tensor fp32 [B*g*g, ld] for B samples, after the type and shape checks that need no device."""
+        for t, what in ((scores, "teacher scores"), (teacher_weight, "teacher_weight")):
+            if (t is not None or what == "teacher scores") and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise TypeError(f"lc2is_amd.data: {who} {what} must be a torch.float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if label_size is not None and (isinstance(label_size, bool) or not isinstance(label_size, int)):
+            raise TypeError(f"lc2is_amd.data: {who} label_size must be an int, got {label_size!r}")
+        if scores.dim() != 2 or scores.shape[0] < B or scores.shape[0] % B:
+            raise ValueError(f"lc2is_amd.data: {who} scores must be [B*g*g, ld] for B = {B} samples, got {tuple(scores.shape)}")
+        cells = scores.shape[0] // B
+        g = math.isqrt(cells)
+        if g * g != cells or g > ops.GEO_SCORES_MAX_G:
+            raise ValueError(f"lc2is_amd.data: {who} takes a square grid of at most {ops.GEO_SCORES_MAX_G} cells a side; {scores.shape[0]} "
+                             f"rows for {B} samples are {cells} cells each")
+        ld = scores.shape[1]
+        if ld < 4 or ld > ops.GEO_SCORES_MAX_LD or ld % 4:
+            raise ValueError(f"lc2is_amd.data: {who} scores need a pitch that is a multiple of 4 in 4..{ops.GEO_SCORES_MAX_LD}, got {ld}")
+        L = label_size
+        if teacher_weight is not None:
+            if teacher_weight.dim() != 3 or teacher_weight.shape[0] != B or teacher_weight.shape[1] != teacher_weight.shape[2]:
+                raise ValueError(f"lc2is_amd.data: {who} teacher_weight must be [{B}, L, L], got {tuple(teacher_weight.shape)}")
+            if L is not None and L != teacher_weight.shape[1]:
+                raise ValueError(f"lc2is_amd.data: {who} label_size {L} is not the teacher_weight's {teacher_weight.shape[1]}")
+            L = int(teacher_weight.shape[1])
+        if L is not None and (L < 1 or L > ops.AUG_MAX_SIDE or L % g):
+            raise ValueError(f"lc2is_amd.data: {who} needs a label size that is a multiple of g = {g} in 1..{ops.AUG_MAX_SIDE}, got {L}")
+        return g
+
+    def warp_scores(self, scores, teacher_weight=None, label_size=None, params=None, out=None):
+        """``(scores', teacher_weight' or None)``: a teacher's low-resolution scores fp32 [B*g*g, ld] (``model.head_scores`` of the
+        weak view) under the maps of the last call - the geometry the student's view was given - in one launch (``ops.geo_scores``):
+        bilinear with border padding, every column alike.  ``teacher_weight`` fp32 [B, L, L] follows as a ``pixel_weight`` does (0
+        out of frame); ``label_size=L`` without it asks for the in-frame mask; with neither the second result is None.  ``params``:
+        a table of ``ops.geo_params`` to use instead of ``last_params``; B is the table's, and g = isqrt(rows / B) must be exact.
+        ``out``: (scores, weight) to write into.  This is the forward direction only: the teacher saw the unwarped view."""
+        if params is None:
+            params = self.last_params
+        if params is None:
+            raise RuntimeError("lc2is_amd.data: GeometricAugment.warp_scores needs the table of a view: call the augmenter first, or "
+                               "pass params=")
+        if not torch.is_tensor(params) or params.dtype != torch.int32:
+            raise TypeError(f"lc2is_amd.data: GeometricAugment.warp_scores params must be an int32 tensor, got {getattr(params, 'dtype', type(params))}")
+        if params.dim() != 2 or params.shape[0] < 1 or params.shape[1] != ops.GEO_PARAM_WORDS:
+            raise ValueError(f"lc2is_amd.data: GeometricAugment.warp_scores params must be [B, {ops.GEO_PARAM_WORDS}], got {tuple(params.shape)}")
+        B = int(params.shape[0])
+        g = self._scores_grid(scores, B, teacher_weight, label_size, "GeometricAugment.warp_scores")
+        if not scores.is_cuda:
+            raise RuntimeError("lc2is_amd.data: GeometricAugment runs on a HIP device; there is no CPU path "
+                               "(tests/geo_scores_ref.py restates warp_scores in numpy, test-only)")
+        return ops.geo_scores(scores, params, B, g, teacher_weight=teacher_weight, label_size=label_size, out=out)
+
+    def view_distill(self, inputs: dict, labels, teacher_scores, keys, epoch, pixel_weight=None, teacher_weight=None):
+        """The soft-teacher step under a geometric view: ``(inputs', labels', pixel_weight', teacher_scores', teacher_weight')`` -
+        ``view`` and ``warp_scores`` under ONE table: three launches (params, apply, scores), no host read.  ``teacher_scores``:
+        the teacher's ``head_scores`` of the unwarped view, fp32 [B*g*g, ld].  ``teacher_weight'`` is always returned, at the
+        labels' size: the warped ``teacher_weight``, or the in-frame mask when none was given - what
+        ``TrainStep.step_distill(inputs', labels', teacher_scores', teacher_weight=teacher_weight')`` takes, so that the cells the
+        warp brought in from outside the frame cost no KL.  ``labels`` / ``pixel_weight`` may be None (and stay None), but one of
+        labels, pixel_weight and teacher_weight must give the label size."""
+        who = "GeometricAugment.view_distill"
+        px = inputs["pixel_values"]
+        sized = [t for t in (labels, pixel_weight, teacher_weight) if torch.is_tensor(t) and t.dim() == 3]
+        if not torch.is_tensor(px) or px.dim() != 4 or px.shape[0] < 1:
+            raise TypeError(f"lc2is_amd.data: {who} pixel_values must be a [B, 3, S, S] tensor")
+        if not sized:
+            raise ValueError(f"lc2is_amd.data: {who} needs labels, pixel_weight or teacher_weight [B, L, L] for the size of the mask")
+        L = int(sized[0].shape[1])
+        if any(t.shape[1] != L for t in sized):
+            raise ValueError(f"lc2is_amd.data: {who} labels, pixel_weight and teacher_weight must have one size")
+        B = int(px.shape[0])
+        g = self._scores_grid(teacher_scores, B, teacher_weight, L, who)
+        if not teacher_scores.is_cuda or not px.is_cuda:
+            raise RuntimeError("lc2is_amd.data: GeometricAugment runs on a HIP device; there is no CPU path "
+                               "(tests/geo_ref.py and tests/geo_scores_ref.py restate it in numpy, test-only)")
+        _, _, outs = ops._geo_scores_batch(teacher_scores, B, g, teacher_weight, L, None)   # layout, alignment: before the first launch
+        inputs_g, labels_g, pw_g = self.view(inputs, labels, pixel_weight, keys, epoch)
+        scores_g, tw_g = self.warp_scores(teacher_scores, teacher_weight, L, out=outs)
+        return inputs_g, labels_g, pw_g, scores_g, tw_g

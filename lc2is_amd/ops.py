@@ -147,6 +147,7 @@ _ARGTYPES = {
     "lc2is_strong_apply": [_P, _P, _P, _I, _I, _P, _P],
     "lc2is_geo_params": [_P, _I, _P, _P, _P, _P],
     "lc2is_geo_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "lc2is_geo_scores": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "lc2is_swin_attn_fwd": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "lc2is_swin_bias_table_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lc2is_swin_attn_bwd_workspace_bytes": [_I, _I, _I],
@@ -2801,6 +2802,80 @@ def geo_apply(batch, params: torch.Tensor, cfg: GeoConfig, *, out=None):
                                 _ptr(opw), _stream())
     _lib.check(rc, f"geo_apply B={B} S={S} L={L}")
     return opx, olab, opw
+
+
+GEO_SCORES_MAX_G, GEO_SCORES_MAX_LD = 512, 1024                               # lc2is_geo_scores' limits
+
+
+def _geo_scores_batch(scores, B, g, teacher_weight, label_size, out):
+    """Everything geo_scores asks of its operands and outputs, before any device work (as _geo_batch for geo_apply); returns
+    (ld, L or None, (scores', weight' or None)) with the missing outputs allocated."""
+    for v, what in ((B, "B"), (g, "g"), (label_size, "label_size")):
+        if (v is not None or what != "label_size") and (isinstance(v, bool) or not isinstance(v, int)):
+            raise TypeError(f"lc2is_amd.geo_scores: {what} must be an int, got {v!r}")
+    if out is None:
+        out = (None, None)
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise TypeError("lc2is_amd.geo_scores: out must be (scores or None, weight or None)")
+    for t, what in ((scores, "scores"), (teacher_weight, "teacher_weight"), (out[0], "out scores"), (out[1], "out weight")):
+        if (t is not None or what == "scores") and not torch.is_tensor(t):
+            raise TypeError(f"lc2is_amd.geo_scores: {what} must be a tensor, got {type(t).__name__}")
+    _chk(scores, torch.float32, "scores", 2); _chk(teacher_weight, torch.float32, "teacher_weight", 3)
+    ld = scores.shape[1]
+    if not 1 <= B <= 65535 or not 1 <= g <= GEO_SCORES_MAX_G or ld < 4 or ld > GEO_SCORES_MAX_LD or ld % 4:
+        raise ValueError(f"lc2is_amd.geo_scores: B {B} must be 1..65535, g {g} 1..{GEO_SCORES_MAX_G} and the pitch {ld} a multiple of 4 in "
+                         f"4..{GEO_SCORES_MAX_LD}")
+    if scores.shape[0] != B * g * g or not scores.is_contiguous() or scores.data_ptr() % 16:
+        raise RuntimeError(f"lc2is_amd.geo_scores: scores must be contiguous fp32 [{B}*{g}*{g}, ld] with a 16-byte base, got shape "
+                           f"{tuple(scores.shape)}, strides {tuple(scores.stride())}")
+    L = label_size
+    if teacher_weight is not None:
+        Lw = teacher_weight.shape[1]
+        if tuple(teacher_weight.shape) != (B, Lw, Lw) or not teacher_weight.is_contiguous() or teacher_weight.data_ptr() % 4 or \
+                teacher_weight.device != scores.device:
+            raise RuntimeError(f"lc2is_amd.geo_scores: teacher_weight must be contiguous fp32 [{B}, L, L] on the scores' device, got shape "
+                               f"{tuple(teacher_weight.shape)}, strides {tuple(teacher_weight.stride())}")
+        if L is not None and L != Lw:
+            raise ValueError(f"lc2is_amd.geo_scores: label_size {L} is not the teacher_weight's {Lw}")
+        L = Lw
+    if L is not None and (L < 1 or L > AUG_MAX_SIDE or L % g):
+        raise ValueError(f"lc2is_amd.geo_scores: the label size {L} must be a multiple of g = {g} in 1..{AUG_MAX_SIDE}")
+    if L is None and out[1] is not None:
+        raise ValueError("lc2is_amd.geo_scores: an out weight without teacher_weight or label_size: no weight map is made")
+    outs = []
+    for o, shape, like, align, name in ((out[0], tuple(scores.shape), scores, 16, "out scores"),
+                                        (out[1], None if L is None else (B, L, L), teacher_weight, 4, "out weight")):
+        if shape is None:
+            outs.append(None)
+            continue
+        if o is None:
+            o = torch.empty(shape, dtype=torch.float32, device=scores.device)
+        _chk(o, torch.float32, name, len(shape))
+        if tuple(o.shape) != shape or not o.is_contiguous() or o.data_ptr() % align or o.device != scores.device:
+            raise RuntimeError(f"lc2is_amd.geo_scores: {name} must be contiguous fp32 {shape} with a {align}-byte base on the scores' device")
+        if _overlap(o, like):
+            raise RuntimeError(f"lc2is_amd.geo_scores: {name} may not overlap its input (a warp gathers: no in-place form)")
+        outs.append(o)
+    return ld, L, tuple(outs)
+
+
+def geo_scores(scores: torch.Tensor, params: torch.Tensor, B: int, g: int, *, teacher_weight: torch.Tensor | None = None,
+               label_size: int | None = None, out=None):
+    """One launch (lc2is_geo_scores): a teacher's low-resolution scores fp32 [B*g*g, ld] (model.head_scores' layout, every column
+    alike) under the rows of `params` (geo_params) - the map geo_apply gave the student's pixels - bilinear with BORDER padding:
+    F.grid_sample(padding_mode="border", align_corners=False) of the recorded matrix on the [B, ld, g, g] view.  A row with no flag,
+    or one out of range, gives the sample bit for bit.  teacher_weight fp32 [B, L, L] follows under geo_apply's cell rule (0.0 out
+    of frame); label_size=L without it asks for the in-frame mask (1.0 / 0.0) at that size; with neither no weight map is made.
+    g <= 512, ld % 4 == 0 in 4..1024, L % g == 0.  Tensors must be contiguous (refused, not copied); out: (scores, weight) to write
+    into, neither of which may overlap its input.  Returns (scores', weight' or None)."""
+    ld, L, (osc, otw) = _geo_scores_batch(scores, B, g, teacher_weight, label_size, out)
+    _chk(params, torch.int32, "params")
+    if tuple(params.shape) != (B, GEO_PARAM_WORDS) or not params.is_contiguous() or params.device != scores.device:
+        raise RuntimeError(f"lc2is_amd.geo_scores: params must be contiguous int32 [{B}, {GEO_PARAM_WORDS}] on the scores' device")
+    rc = _fn("lc2is_geo_scores")(_ptr(scores), _ptr(teacher_weight), _ptr(params), B, g, ld, L or 0, int(L is not None), _ptr(osc),
+                                 _ptr(otw), _stream())
+    _lib.check(rc, f"geo_scores B={B} g={g} ld={ld} L={L}")
+    return osc, otw
 
 
 def set_cu_budget(ncu: int) -> None:

@@ -53,7 +53,20 @@ colour, ``ignore_index`` and weight 0, so it costs no loss::
     geo = GeometricAugment(rotate_deg=20.0, scale_range=(0.8, 1.25), seed=1234)
     strong_view, labels_u, pw_u = geo.view(strong_view, labels_u, pw_u, keys, epoch)      # then combine / mix / step as above
 
-Out of scope here: warping score maps back (the inverse map, for a teacher that sees the warped image), pooling the confident-pixel counts across ranks, and models
+The soft teacher under the same step: the teacher sees the weak view, the student the warped one, and the teacher's low-resolution
+scores follow the student (``geo.view_distill``: params, apply and ``ops.geo_scores``, three launches, no host read; the scores are
+sampled bilinearly with border padding, every column alike).  The fifth result is the in-frame mask at the labels' size (or the
+warped ``teacher_weight`` when one is given): passed on as ``teacher_weight=`` it takes the cells the warp brought in from outside
+the frame out of the KL, as ``ignore_index`` takes them out of the cross-entropy::
+
+    with step.ema_weights():
+        scores_t = model.head_scores(weak_view)                # of the UNWARPED view
+    view, labels_g, _, scores_g, mask = geo.view_distill(strong_view, labels, scores_t, keys, epoch)
+    step.step_distill(view, labels_g, scores_g, teacher_weight=mask)
+
+(``geo.warp_scores(scores_t, label_size=L)`` alone warps under the table of the last ``geo.view``.)
+
+Out of scope here: the inverse map of a score field (for a teacher that sees the warped image: its shift can pass the table's limit), pooling the confident-pixel counts across ranks, and models
 without ``predict_confidence`` (``AuxiliaryLoss``, ``DenseClip``, ``ContrastiveModel``, more than 192 classes).
 """
 from __future__ import annotations

@@ -13,9 +13,9 @@ CSRC = ROOT / "lc2is_amd" / "csrc"
 HOT = ("gemm_nt_pp_kernel", "gemm_nt_w384_kernel", "gemm_nt_rows_kernel", "gemm_nt_dma_kernel", "gemm_tn_grouped", "attn_fwd_kernel<64", "attn_fwd_kernel<96",
        "attn_bwd_dq2_kernel<64", "attn_bwd_dkdv_kernel<64", "attn_bwd_dq2_kernel<96", "attn_bwd_dkdv_kernel<96",
        "head_ce_grp_kernel", "head_focal_grp_kernel", "head_sigmoid_grp_kernel", "head_finish_kernel", "head_conf_grp_kernel", "head_ce_pw_grp_kernel", "head_kd_grp_kernel", "ln_fwd_kernel", "ln_bwd_kernel", "sgd_kernel",
-       "strong_params_kernel", "strong_apply_kernel", "geo_params_kernel", "geo_apply_kernel")
+       "strong_params_kernel", "strong_apply_kernel", "geo_params_kernel", "geo_apply_kernel", "geo_scores_kernel")
 # (geo.hip as built today: geo_params_kernel 30 VGPRs, no LDS; geo_apply_kernel<4096> 56 VGPRs, 48 KB of LDS for the staged source box =
-# three blocks of 256 lanes per CU, 3 waves per SIMD; neither uses scratch)
+# three blocks of 256 lanes per CU, 3 waves per SIMD; geo_scores_kernel 58 VGPRs, no LDS, 8 waves per SIMD; none uses scratch)
 # known, accepted (listed so that a NEW spill is a failure): 12 bytes (one 64-bit address + one dword, stored once in front of the row
 # loop) in the 128-register LayerNorm backward at C = 768 — HBM-bound at 5.4 TB/s; compiling it for 3 waves per SIMD instead removes the
 # spill and measured slower (round 2), and one base pointer per stream instead of fp32 / bf16 pairs made hipcc demote the row arrays to
