@@ -1,6 +1,7 @@
-// The counter-based RNG of the data-path kernels (augment.hip, mix.hip, strong.hip), their exact small-quotient division and the
-// composition of colour maps (aug_left_mul).  Every random number is a pure function of (seed, epoch, key, draw number); the
-// definition is in include/lc2is_hip.h (lc2is_aug_params) and tests/augment_ref.py restates it in numpy, bit for bit.
+// The counter-based RNG of the data-path kernels (augment.hip, mix.hip, strong.hip, geo.hip), its two uniform ranges, the exact
+// small-quotient division and the builders of colour maps (aug_left_mul and the saturation / hue / grey steps on top of it).  Every
+// random number is a pure function of (seed, epoch, key, draw number); the definition is in include/lc2is_hip.h (lc2is_aug_params)
+// and tests/augment_ref.py restates it in numpy, bit for bit.  What the kernels of a view share beyond that is in view_common.h.
 #pragma once
 #include "common.h"
 
@@ -14,8 +15,13 @@ __device__ __forceinline__ unsigned aug_key(unsigned seed_lo, unsigned seed_hi, 
   return mix32(h ^ ((unsigned)epoch * AUG_GOLD + 0x85EBCA6Bu));
 }
 __device__ __forceinline__ unsigned aug_u24(unsigned h, unsigned k) { return mix32(h + k * AUG_GOLD) >> 8; }
+// lo + (hi - lo) * t as a product and a sum (TWO roundings as written): the colour draws, restated within a tolerance, not bit for bit
 __device__ __forceinline__ float aug_range(unsigned u24, float lo, float hi) {
   return lo + (hi - lo) * ((float)u24 * (1.0f / 16777216.0f));
+}
+// the same with ONE rounding after the difference (an fma): sigma and the geometric draws, whose restatements form the same fp32 number
+__device__ __forceinline__ float aug_range1(unsigned u24, float lo, float hi) {
+  return __builtin_fmaf(hi - lo, (float)u24 * (1.0f / 16777216.0f), lo);
 }
 
 // n / d and the remainder for 0 <= n < 2^31, 1 <= d < 2^24, n / d <= 4096, rcp_d = v_rcp_f32(d) (1 ulp): the fp32 estimate is off
@@ -42,6 +48,24 @@ __device__ __forceinline__ void aug_left_mul(const float (&A)[9], float (&M)[9],
   for (int e = 0; e < 9; ++e) M[e] = N[e];
 #pragma unroll
   for (int e = 0; e < 3; ++e) o[e] = p[e];
+}
+
+// The colour steps both parameter kernels fold into rgb' = M rgb + o.  Saturation: blend with the 0.299 / 0.587 / 0.114 grey by sa
+__device__ __forceinline__ void aug_saturation(float sa, float (&M)[9], float (&o)[3]) {
+  const float g0 = (1.f - sa) * 0.299f, g1 = (1.f - sa) * 0.587f, g2 = (1.f - sa) * 0.114f;
+  const float A[9] = {sa + g0, g1, g2, g0, sa + g1, g2, g0, g1, sa + g2};
+  aug_left_mul(A, M, o);
+}
+// hue: rotation about the grey axis by the angle whose cosine and sine are cs, sn
+__device__ __forceinline__ void aug_hue(float cs, float sn, float (&M)[9], float (&o)[3]) {
+  const float d = cs + (1.f - cs) * (1.f / 3.f), p = (1.f - cs) * (1.f / 3.f), q = sn * 0.57735026918962576f;
+  const float A[9] = {d, p - q, p + q, p + q, d, p - q, p - q, p + q, d};
+  aug_left_mul(A, M, o);
+}
+// grey: every channel becomes the luma
+__device__ __forceinline__ void aug_grey(float (&M)[9], float (&o)[3]) {
+  const float A[9] = {0.299f, 0.587f, 0.114f, 0.299f, 0.587f, 0.114f, 0.299f, 0.587f, 0.114f};
+  aug_left_mul(A, M, o);
 }
 
 }  // namespace

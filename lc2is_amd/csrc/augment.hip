@@ -11,9 +11,11 @@
 //     per sample counts the label cells aug_apply would write for each candidate origin and replaces the row's (top, left).
 //   * label_hist_kernel: per-image class counts of the pool's label maps, for class weights.  Both count with label_hist.h.
 // The exact definition is in include/lc2is_hip.h; tests/augment_ref.py and tests/catcrop_ref.py restate it in numpy (integers bit
-// for bit).  The counter RNG (aug_key, aug_u24, aug_range), aug_div and aug_left_mul live in aug_rng.h, shared with mix.hip and strong.hip.
+// for bit).  The counter RNG, aug_div and the colour steps live in aug_rng.h; the colour map's load and apply and the label cell's rule
+// (aug_cell_pos, aug_cell_src), which the apply and the crop-select kernel share, in view_common.h.
 #include "common.h"
 #include "aug_rng.h"
+#include "view_common.h"
 #include "label_hist.h"
 #include "lc2is_hip.h"
 
@@ -67,17 +69,11 @@ __global__ __launch_bounds__(64) void aug_params_kernel(const int64_t* __restric
     for (int e = 0; e < 3; ++e) o[e] *= c;
   }
   if (aug_u24(h, 8) < cfg.photo_thr[2]) {
-    const float sa = aug_range(aug_u24(h, 9), cfg.saturation_lo, cfg.saturation_hi);
-    const float g0 = (1.f - sa) * 0.299f, g1 = (1.f - sa) * 0.587f, g2 = (1.f - sa) * 0.114f;
-    const float A[9] = {sa + g0, g1, g2, g0, sa + g1, g2, g0, g1, sa + g2};
-    aug_left_mul(A, M, o);
+    aug_saturation(aug_range(aug_u24(h, 9), cfg.saturation_lo, cfg.saturation_hi), M, o);
   }
   if (aug_u24(h, 10) < cfg.photo_thr[3]) {
     const float a = aug_range(aug_u24(h, 11), -cfg.hue_delta, cfg.hue_delta);
-    const float cs = cosf(a), sn = sinf(a);
-    const float d = cs + (1.f - cs) * (1.f / 3.f), p = (1.f - cs) * (1.f / 3.f), q = sn * 0.57735026918962576f;
-    const float A[9] = {d, p - q, p + q, p + q, d, p - q, p - q, p + q, d};
-    aug_left_mul(A, M, o);
+    aug_hue(cosf(a), sinf(a), M, o);
   }
 #pragma unroll
   for (int e = 0; e < 9; ++e) row[LC2IS_AUG_M + e] = __builtin_bit_cast(int, M[e]);
@@ -137,13 +133,10 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const unsigned char* __r
     if (cell >= L * L) return;
     int cj;
     const int ci = aug_div(cell, L, __builtin_amdgcn_rcpf((float)L), cj);
-    const int q = S / L;
-    const int i = ci * q + (q >> 1), j = cj * q + (q >> 1);
-    const int yr = (int)((unsigned)s.top + (unsigned)i), xr = (int)((unsigned)s.left + (unsigned)(s.flip ? S - 1 - j : j));
+    int yr, xr, ys, xs;
     long v = pad_label;
-    if (s.valid && (unsigned)yr < (unsigned)s.nh && (unsigned)xr < (unsigned)s.nw) {
-      int rem;
-      const int ys = aug_div((2 * yr + 1) * s.H, dy, rdy, rem), xs = aug_div((2 * xr + 1) * s.W, dx, rdx, rem);
+    if (aug_cell_pos(s.valid, ci, cj, S / L, S, s.top, s.left, s.flip, s.nh, s.nw, yr, xr)) {
+      aug_cell_src(yr, xr, s.H, s.W, dy, dx, rdy, rdx, ys, xs);
       v = lab[s.lab_off + (long long)ys * s.W + xs];
     }
     out_lab[((size_t)b * L + ci) * L + cj] = v;
@@ -194,11 +187,7 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const unsigned char* __r
     t0[k] = aug_load8(r0 + 3 * x0);
     t1[k] = aug_load8(r1 + 3 * x0);
   }
-  float M[9], o[3];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) M[e] = __builtin_bit_cast(float, prow[LC2IS_AUG_M + e]);
-#pragma unroll
-  for (int e = 0; e < 3; ++e) o[e] = __builtin_bit_cast(float, prow[LC2IS_AUG_O + e]);
+  const ColourMap km = colour_load(prow, LC2IS_AUG_M);
 
   f32x4_t out[3];
 #pragma unroll
@@ -212,9 +201,7 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const unsigned char* __r
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float v = M[3 * c] * a[0] + M[3 * c + 1] * a[1] + M[3 * c + 2] * a[2] + o[c];
-      v = fminf(fmaxf(v, 0.f), 255.f);
-      v = (v * (1.0f / 255.0f) - norm.mean[c]) * norm.inv_std[c];
+      const float v = (colour_apply(km, a, c) * (1.0f / 255.0f) - norm.mean[c]) * norm.inv_std[c];
       out[c][k] = in[k] ? v : 0.f;
     }
   }
@@ -245,7 +232,7 @@ __device__ __forceinline__ LabSample lab_sample(const lc2is_aug_image* __restric
 }
 
 // One block per sample walks the candidates in order and leaves at the first accepted one.  Per candidate: every lane gathers
-// LH_UNROLL label cells per round (the coordinates of aug_apply_kernel's label branch, flip included), the waves count them in
+// LH_UNROLL label cells per round (aug_cell_pos / aug_cell_src: the cells aug_apply_kernel's label branch writes), the waves count them in
 // their LDS rows, 256 lanes add the rows in wave order and four waves reduce n = sum, m = max, d = classes present; the verdict
 // d > 1 && m * 1024 < ratio1024 * n is block-uniform.  Lane 0 writes the chosen (top, left) into the row and {t*, n, m, d} to info.
 __global__ __launch_bounds__(LH_THREADS) void aug_crop_select_kernel(const unsigned char* __restrict__ lab, size_t lab_bytes,
@@ -292,13 +279,12 @@ __global__ __launch_bounds__(LH_THREADS) void aug_crop_select_kernel(const unsig
         cell = in ? cell : 0;
         int cj;
         const int ci = aug_div(cell, L, rL, cj);
-        const int i = ci * q + (q >> 1), j = cj * q + (q >> 1);
-        const int yr = (int)((unsigned)top + (unsigned)i), xr = (int)((unsigned)left + (unsigned)(flip ? S - 1 - j : j));
-        in = in && (unsigned)yr < (unsigned)nh && (unsigned)xr < (unsigned)nw;   // outside: padding, not counted
+        int yr, xr;
+        in = aug_cell_pos(in, ci, cj, q, S, top, left, flip, nh, nw, yr, xr);   // outside: padding, not counted
         v[e] = 0u;
         if (in) {
-          int rem;
-          const int ys = aug_div((2 * yr + 1) * H, dy, rdy, rem), xs = aug_div((2 * xr + 1) * W, dx, rdx, rem);
+          int ys, xs;
+          aug_cell_src(yr, xr, H, W, dy, dx, rdy, rdx, ys, xs);
           v[e] = src[(long long)ys * W + xs];
         }
         counted[e] = in && (int)v[e] != ignore_label;

@@ -235,6 +235,12 @@ int set_dyn_lds(int bytes) {
   return LC2IS_OK;
 }
 
+// [a, a + na) and [b, b + nb) bytes share a byte (a NULL range shares none): how a launcher refuses an output that aliases an input
+static inline bool lc2is_bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a && b && x < y + nb && y < x + na;
+}
+
 static inline int lc2is_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? LC2IS_OK : LC2IS_ERR_LAUNCH;

@@ -17,10 +17,13 @@
 //     No atomics, no scratch.
 //   * geo_scores_kernel: a teacher's low-resolution score map [B][g][g][ld] follows the view under the same table (the soft-teacher
 //     step), bilinear with border padding, and writes the weight map / in-frame mask at label resolution; described at the kernel.
-// The exact definition is in include/lc2is_hip.h; tests/geo_ref.py and tests/geo_scores_ref.py restate it in numpy.
+// The exact definition is in include/lc2is_hip.h; tests/geo_ref.py and tests/geo_scores_ref.py restate it in numpy.  The draws' range
+// (aug_range1) lives in aug_rng.h; the table row (geo_map), the cell rule (geo_cell), the position split and guarded blend (geo_split,
+// geo_lerp) and the streamed copy live in view_common.h; the launchers' overlap predicate in common.h.
 #include <math.h>
 #include "common.h"
 #include "aug_rng.h"
+#include "view_common.h"
 #include "lc2is_hip.h"
 
 namespace {
@@ -33,11 +36,6 @@ constexpr int GEO_BOX_WORDS = 4096;                // the staged source box per 
 static_assert(GEO_TW * GEO_TH / 4 == GEO_THREADS && GEO_BOX_WORDS % (4 * GEO_THREADS) == 0 && LC2IS_GEO_REC + 5 <= GEO_P && LC2IS_GEO_M + 4 == LC2IS_GEO_T &&
               LC2IS_GEO_T + 2 == LC2IS_GEO_REC, "one quad per lane; parameter row layout");
 
-// lo + (hi - lo) * t with ONE rounding after the difference (include/lc2is_hip.h): restated exactly by tests/geo_ref.py
-__device__ __forceinline__ float geo_range(unsigned u24, float lo, float hi) {
-  return __builtin_fmaf(hi - lo, (float)u24 * (1.0f / 16777216.0f), lo);
-}
-
 __global__ __launch_bounds__(64) void geo_params_kernel(const int64_t* __restrict__ keys, int B, const int32_t* __restrict__ epoch,
                                                          const lc2is_geo_config cfg, int32_t* __restrict__ params) {
   const int b = blockIdx.x * 64 + threadIdx.x;
@@ -45,11 +43,11 @@ __global__ __launch_bounds__(64) void geo_params_kernel(const int64_t* __restric
   int32_t* row = params + (size_t)b * GEO_P;
   const unsigned h = aug_key(cfg.seed_lo, cfg.seed_hi, *epoch, (long long)keys[b]) ^ LC2IS_GEO_STREAM;
   const bool warp = aug_u24(h, 0) < cfg.warp_thr, flip = aug_u24(h, 6) < cfg.flip_thr;
-  const float theta = geo_range(aug_u24(h, 1), -cfg.rotate, cfg.rotate);
-  const float s = geo_range(aug_u24(h, 2), cfg.scale_lo, cfg.scale_hi);
-  const float phi = geo_range(aug_u24(h, 3), -cfg.shear, cfg.shear);
-  const float fx = geo_range(aug_u24(h, 4), -cfg.translate, cfg.translate);
-  const float fy = geo_range(aug_u24(h, 5), -cfg.translate, cfg.translate);
+  const float theta = aug_range1(aug_u24(h, 1), -cfg.rotate, cfg.rotate);
+  const float s = aug_range1(aug_u24(h, 2), cfg.scale_lo, cfg.scale_hi);
+  const float phi = aug_range1(aug_u24(h, 3), -cfg.shear, cfg.shear);
+  const float fx = aug_range1(aug_u24(h, 4), -cfg.translate, cfg.translate);
+  const float fy = aug_range1(aug_u24(h, 5), -cfg.translate, cfg.translate);
   int m00 = LC2IS_GEO_ONE, m01 = 0, m10 = 0, m11 = LC2IS_GEO_ONE, tx = 0, ty = 0;
   if (warp) {   // M = (1/s) R(theta) H(phi)
     const float cs = cosf(theta), sn = sinf(theta), tn = tanf(phi), inv = 65536.0f / s;
@@ -73,37 +71,14 @@ __global__ __launch_bounds__(64) void geo_params_kernel(const int64_t* __restric
   for (int e = LC2IS_GEO_REC + 5; e < GEO_P; ++e) row[e] = 0;
 }
 
-struct GeoMap {   // block-uniform: one sample per blockIdx.y
-  bool mapped;    // false: the copy
-  long long m00, m01, m10, m11, tx, ty;
-};
-__device__ __forceinline__ GeoMap geo_map(const int32_t* __restrict__ prow) {
-  GeoMap g;
-  const int flags = prow[LC2IS_GEO_FLAGS];
-  bool ok = flags != 0 && !(flags & ~(LC2IS_GEO_WARP | LC2IS_GEO_FLIP));
-  int w[6];
-#pragma unroll
-  for (int e = 0; e < 6; ++e) w[e] = prow[LC2IS_GEO_M + e];
-  // (-MAX <= v && v <= MAX, not abs: INT32_MIN has no absolute value)
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ok = ok && w[e] >= -LC2IS_GEO_MAX_M && w[e] <= LC2IS_GEO_MAX_M;
-#pragma unroll
-  for (int e = 4; e < 6; ++e) ok = ok && w[e] >= -LC2IS_GEO_MAX_T && w[e] <= LC2IS_GEO_MAX_T;
-  g.mapped = ok;
-  g.m00 = w[0]; g.m01 = w[1]; g.m10 = w[2]; g.m11 = w[3]; g.tx = w[4]; g.ty = w[5];
-  return g;
-}
-// A 64-bit source index, range-checked before it is narrowed: every value below -2 or above n behaves as -2 / n (all taps outside).
-__device__ __forceinline__ int geo_narrow(long long i, int n) { return (int)(i < -2 ? -2ll : (i > (long long)n ? (long long)n : i)); }
-
 // One output pixel of all three channels.  X, Y: the source position in units of 2^-17 pixel (|X|, |Y| < 2^36 for a valid row).  The
 // taps are taken from base[c * cstride + (y - by) * w + (x - bx)]: the image itself (base = the sample, w = S, bx = by = 0) or the
 // staged box in LDS.  Every call site is inlined with its own address space.
 __device__ __forceinline__ void geo_pixel(const float* base, size_t cstride, int w, int bx, int by, int S, long long X, long long Y,
                                           const lc2is_geo_config& cfg, float (&out)[3]) {
-  const int x0 = geo_narrow(X >> 17, S), y0 = geo_narrow(Y >> 17, S);
-  const int fxi = (int)(X & 0x1FFFF), fyi = (int)(Y & 0x1FFFF);
-  const float fx = (float)fxi * (1.0f / 131072.0f), fy = (float)fyi * (1.0f / 131072.0f);
+  int fxi, fyi;
+  float fx, fy;
+  const int x0 = geo_narrow(geo_split(X, fxi, fx), S), y0 = geo_narrow(geo_split(Y, fyi, fy), S);
   // a far tap is needed only where its fraction is not 0; every tap that is read lies inside [0, S)^2 (and so inside the box)
   const bool r0 = (unsigned)y0 < (unsigned)S, r1 = fyi != 0 && (unsigned)(y0 + 1) < (unsigned)S;
   const bool c0 = (unsigned)x0 < (unsigned)S, c1 = fxi != 0 && (unsigned)(x0 + 1) < (unsigned)S;
@@ -114,9 +89,7 @@ __device__ __forceinline__ void geo_pixel(const float* base, size_t cstride, int
     const float f = cfg.fill[c];
     const float p00 = (r0 && c0) ? p[o00] : f, p01 = (r0 && c1) ? p[o00 + 1] : f;
     const float p10 = (r1 && c0) ? p[o00 + w] : f, p11 = (r1 && c1) ? p[o00 + w + 1] : f;
-    const float top = fxi ? p00 + fx * (p01 - p00) : p00;
-    const float bot = fxi ? p10 + fx * (p11 - p10) : p10;
-    out[c] = fyi ? top + fy * (bot - top) : top;
+    out[c] = geo_lerp(p00, p01, p10, p11, fxi != 0, fyi != 0, fx, fy);
   }
 }
 
@@ -141,12 +114,8 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_apply_kernel(const float* __r
       if (in_pw) out_pw[base + cell] = in_pw[base + cell];
       return;
     }
-    int x;
-    const int y = aug_div(cell, L, __builtin_amdgcn_rcpf((float)L), x);
-    const long long u = 2 * x + 1 - L, v = 2 * y + 1 - L, n = L;
-    const long long xs = (g.m00 * u + g.m01 * v + 2 * g.tx * n + n * 65536) >> 17;
-    const long long ys = (g.m10 * u + g.m11 * v + 2 * g.ty * n + n * 65536) >> 17;
-    const bool inside = xs >= 0 && xs < n && ys >= 0 && ys < n;   // checked in 64 bits, then narrowed
+    long long xs, ys;
+    const bool inside = geo_cell(g, cell, L, xs, ys);   // checked in 64 bits, then narrowed
     const size_t from = base + (inside ? (size_t)((int)ys * L + (int)xs) : 0);
     if (in_lab) out_lab[base + cell] = inside ? in_lab[from] : cfg.ignore_index;
     if (in_pw) out_pw[base + cell] = inside ? in_pw[from] : 0.0f;
@@ -158,25 +127,9 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_apply_kernel(const float* __r
   float* dst = out_px + (size_t)b * 3 * plane;
 
   if (!g.mapped) {   // block-uniform: stream GEO_COPY_QUADS consecutive quads of the plane, all 3 channels; the later blocks have none
-    const int total = S * (S >> 2);
-    const int q0 = (int)blockIdx.x * GEO_COPY_QUADS + tid;
-    f32x4_t v[GEO_COPY_QUADS / GEO_THREADS][3];
-#pragma unroll
-    for (int e = 0; e < GEO_COPY_QUADS / GEO_THREADS; ++e) {
-      const int q = q0 + e * GEO_THREADS;
-      if (q < total) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[e][c] = *(const f32x4_t*)(src + c * plane + 4 * (size_t)q);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < GEO_COPY_QUADS / GEO_THREADS; ++e) {
-      const int q = q0 + e * GEO_THREADS;
-      if (q < total) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane + 4 * (size_t)q) = v[e][c];
-      }
-    }
+    const int total = S * (S >> 2), q0 = (int)blockIdx.x * GEO_COPY_QUADS + tid;
+    const auto v = view_load_quads<GEO_COPY_QUADS / GEO_THREADS, GEO_THREADS>(src, plane, total, q0);
+    view_store_quads<GEO_COPY_QUADS / GEO_THREADS, GEO_THREADS>(dst, plane, total, q0, v);
     return;
   }
 
@@ -283,14 +236,10 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_scores_kernel(const float* __
       out_tw[base + cell] = in_tw ? in_tw[base + cell] : 1.0f;
       return;
     }
-    int x;
-    const int y = aug_div(cell, L, __builtin_amdgcn_rcpf((float)L), x);
-    const long long u = 2 * x + 1 - L, v = 2 * y + 1 - L, n = L;
-    const long long xs = (mp.m00 * u + mp.m01 * v + 2 * mp.tx * n + n * 65536) >> 17;
-    const long long ys = (mp.m10 * u + mp.m11 * v + 2 * mp.ty * n + n * 65536) >> 17;
-    const bool inside = xs >= 0 && xs < n && ys >= 0 && ys < n;   // checked in 64 bits, then narrowed
+    long long xs, ys;
     float w = 0.0f;
-    if (inside) w = in_tw ? in_tw[base + (size_t)(geo_narrow(ys, L - 1) * L + geo_narrow(xs, L - 1))] : 1.0f;
+    if (geo_cell(mp, cell, L, xs, ys))   // checked in 64 bits, then narrowed
+      w = in_tw ? in_tw[base + (size_t)(geo_narrow(ys, L - 1) * L + geo_narrow(xs, L - 1))] : 1.0f;
     out_tw[base + cell] = w;
     return;
   }
@@ -334,24 +283,18 @@ __global__ __launch_bounds__(GEO_THREADS) void geo_scores_kernel(const float* __
     // fraction is not 0, so the near index is at most G - 2) lies inside the sample too
     X = X < 0 ? 0 : (X > last ? last : X);
     Y = Y < 0 ? 0 : (Y > last ? last : Y);
-    const int x0 = geo_narrow(X >> 17, G - 1), y0 = geo_narrow(Y >> 17, G - 1);   // in [0, G - 1] by the clamp
-    const int fxi = (int)(X & 0x1FFFF), fyi = (int)(Y & 0x1FFFF);
-    const float fx = (float)fxi * (1.0f / 131072.0f), fy = (float)fyi * (1.0f / 131072.0f);
+    int fxi, fyi;
+    float fx, fy;
+    const int x0 = geo_narrow(geo_split(X, fxi, fx), G - 1), y0 = geo_narrow(geo_split(Y, fyi, fy), G - 1);   // in [0, G - 1] by the clamp
     const bool hx = fxi != 0, hy = fyi != 0;
     const f32x4_t* p = src + ((y0 * G + x0) * Q + q);
     const f32x4_t p00 = p[0];
     const f32x4_t p01 = hx ? p[Q] : p00, p10 = hy ? p[down] : p00, p11 = (hx && hy) ? p[down + Q] : p00;
-    const f32x4_t top = hx ? p00 + fx * (p01 - p00) : p00;
-    const f32x4_t bot = hx ? p10 + fx * (p11 - p10) : p10;
-    dst[(y * G + x) * Q + q] = hy ? top + fy * (bot - top) : top;
+    dst[(y * G + x) * Q + q] = geo_lerp(p00, p01, p10, p11, hx, hy, fx, fy);
   }
 }
 
-// [a, a + n) and [b, b + n) bytes share a byte
-bool geo_overlap(const void* a, const void* b, size_t n) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + n && y < x + n;
-}
+bool geo_overlap(const void* a, const void* b, size_t n) { return lc2is_bytes_overlap(a, n, b, n); }   // an output and its input, one size
 
 // the limits of include/lc2is_hip.h; a NaN fails every comparison and is refused
 bool geo_config_ok(const lc2is_geo_config* c) {
@@ -384,8 +327,8 @@ extern "C" int lc2is_geo_apply(const float* in_px, const int64_t* in_lab, const 
       (((uintptr_t)in_px | (uintptr_t)out_px) & 15) || (((uintptr_t)in_lab | (uintptr_t)out_lab) & 7) ||
       (((uintptr_t)in_pw | (uintptr_t)out_pw | (uintptr_t)params) & 3))
     return LC2IS_ERR_SHAPE;
-  const size_t cells = (size_t)L * L;
-  if (geo_overlap(out_px, in_px, (size_t)B * 3 * S * S * sizeof(float)) || geo_overlap(out_lab, in_lab, B * cells * 8) ||
+  const size_t cells = (size_t)L * L, px = (size_t)B * 3 * S * S * sizeof(float);
+  if (geo_overlap(out_px, in_px, px) || geo_overlap(out_lab, in_lab, B * cells * 8) ||
       geo_overlap(out_pw, in_pw, B * cells * 4))
     return LC2IS_ERR_SHAPE;
   // the tiles of a mapped row; a copy row needs S * S / 2048 blocks of quads, never more than that
@@ -405,8 +348,8 @@ extern "C" int lc2is_geo_scores(const float* in_scores, const float* in_tw, cons
       (want_tw && (L < 1 || L > LC2IS_AUG_MAX_SIDE || L % g)) || (((uintptr_t)in_scores | (uintptr_t)out_scores) & 15) ||
       (((uintptr_t)in_tw | (uintptr_t)out_tw | (uintptr_t)params) & 3))
     return LC2IS_ERR_SHAPE;
-  if (geo_overlap(out_scores, in_scores, (size_t)B * g * g * ld * sizeof(float)) ||
-      (want_tw && geo_overlap(out_tw, in_tw, (size_t)B * L * L * sizeof(float))))
+  const size_t sc = (size_t)B * g * g * ld * sizeof(float), tw = (size_t)B * L * L * sizeof(float);
+  if (geo_overlap(out_scores, in_scores, sc) || (want_tw && geo_overlap(out_tw, in_tw, tw)))
     return LC2IS_ERR_SHAPE;
   // a mapped row: one block per 4 x 4 patch of cells; a copy row needs g * g / 16 blocks of 16 cells' quads, never more than that
   const int patches_x = (g + GS_PATCH - 1) / GS_PATCH, score_blocks = patches_x * patches_x;

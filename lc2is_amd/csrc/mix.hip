@@ -8,6 +8,7 @@
 //     aug_apply_kernel).  HBM-bound: 3 * 16-byte loads of the CHOSEN side and 3 * 16-byte stores per lane; the mask is one source
 //     label (8 bytes, shared by the r rows of a cell and cached) and one bitmap word from LDS per pixel quad.
 // The exact definition is in include/lc2is_hip.h; tests/mix_ref.py restates it in numpy (every output is a select: bit for bit).
+// The RNG and aug_div live in aug_rng.h; the launcher's overlap predicate (lc2is_bytes_overlap) in common.h.
 #include "common.h"
 #include "aug_rng.h"
 #include "lc2is_hip.h"
@@ -240,12 +241,6 @@ __global__ __launch_bounds__(256) void mix_apply_kernel(const float* __restrict_
   }
 }
 
-// [a, a + na) and [b, b + nb) bytes share a byte
-bool mix_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" int lc2is_mix_select(const int64_t* src_lab, int Bs, const int64_t* src_index, const int64_t* keys, int B,
@@ -274,9 +269,9 @@ extern "C" int lc2is_mix_apply(const float* dst_px, const int64_t* dst_lab, cons
       (((uintptr_t)dst_pw | (uintptr_t)src_pw | (uintptr_t)out_pw | (uintptr_t)plan) & 3))
     return LC2IS_ERR_SHAPE;
   const size_t px = (size_t)3 * S * S * sizeof(float), cells = (size_t)L * L;
-  if (mix_overlap(out_px, B * px, dst_px, B * px) || mix_overlap(out_px, B * px, src_px, Bs * px) ||
-      mix_overlap(out_lab, B * cells * 8, dst_lab, B * cells * 8) || mix_overlap(out_lab, B * cells * 8, src_lab, Bs * cells * 8) ||
-      mix_overlap(out_pw, B * cells * 4, dst_pw, B * cells * 4) || mix_overlap(out_pw, B * cells * 4, src_pw, Bs * cells * 4))
+  if (lc2is_bytes_overlap(out_px, B * px, dst_px, B * px) || lc2is_bytes_overlap(out_px, B * px, src_px, Bs * px) ||
+      lc2is_bytes_overlap(out_lab, B * cells * 8, dst_lab, B * cells * 8) || lc2is_bytes_overlap(out_lab, B * cells * 8, src_lab, Bs * cells * 8) ||
+      lc2is_bytes_overlap(out_pw, B * cells * 4, dst_pw, B * cells * 4) || lc2is_bytes_overlap(out_pw, B * cells * 4, src_pw, Bs * cells * 4))
     return LC2IS_ERR_SHAPE;
   const int img_blocks = (S * (S >> 2) + 255) / 256, lab_blocks = (int)((cells + 255) / 256);
   const dim3 grid(img_blocks + lab_blocks, B), block(256);

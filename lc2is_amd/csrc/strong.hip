@@ -11,9 +11,11 @@
 //     radius, so the window lives in registers (no scratch) and taps past R are never touched.  LDS: 45 KB tile + 12 KB row-pass
 //     buffer = 57 KB, two blocks per CU.  The staged row stride of 80 words leaves a 16-byte LDS read two-way conflicted between
 //     neighbouring rows at worst; the LDS is not the limit (about 25 16-byte reads per 32 bytes of HBM traffic at R = 8).
-// The exact definition is in include/lc2is_hip.h; tests/strong_ref.py restates it in numpy.
+// The exact definition is in include/lc2is_hip.h; tests/strong_ref.py restates it in numpy.  The colour steps and sigma's one-rounding
+// range live in aug_rng.h; the colour map's load and apply and the no-blur path's streamed copy in view_common.h.
 #include "common.h"
 #include "aug_rng.h"
+#include "view_common.h"
 #include "lc2is_hip.h"
 
 namespace {
@@ -48,25 +50,13 @@ __global__ __launch_bounds__(64) void strong_params_kernel(const int64_t* __rest
     for (int e = 0; e < 3; ++e) o[e] = (o[e] + d) * c;
 #pragma unroll
     for (int e = 0; e < 9; ++e) M[e] *= c;
-    {
-      const float g0 = (1.f - sa) * 0.299f, g1 = (1.f - sa) * 0.587f, g2 = (1.f - sa) * 0.114f;
-      const float A[9] = {sa + g0, g1, g2, g0, sa + g1, g2, g0, g1, sa + g2};
-      aug_left_mul(A, M, o);
-    }
-    {
-      const float cs = cosf(a), sn = sinf(a);
-      const float dd = cs + (1.f - cs) * (1.f / 3.f), p = (1.f - cs) * (1.f / 3.f), q = sn * 0.57735026918962576f;
-      const float A[9] = {dd, p - q, p + q, p + q, dd, p - q, p - q, p + q, dd};
-      aug_left_mul(A, M, o);
-    }
+    aug_saturation(sa, M, o);
+    aug_hue(cosf(a), sinf(a), M, o);
   }
-  if (grey) {
-    const float A[9] = {0.299f, 0.587f, 0.114f, 0.299f, 0.587f, 0.114f, 0.299f, 0.587f, 0.114f};
-    aug_left_mul(A, M, o);
-  }
+  if (grey) aug_grey(M, o);
 
   // sigma with ONE rounding (the restatement forms the same fp32 number, so R agrees exactly), R and the normalised taps
-  const float sigma = __builtin_fmaf(cfg.sigma_hi - cfg.sigma_lo, (float)aug_u24(h, 7) * (1.0f / 16777216.0f), cfg.sigma_lo);
+  const float sigma = aug_range1(aug_u24(h, 7), cfg.sigma_lo, cfg.sigma_hi);
   int R = (int)ceilf(4.f * sigma);
   R = R < 0 ? 0 : (R > ST_RMAX ? ST_RMAX : R);
   const float s2 = -1.f / (2.f * sigma * sigma);
@@ -91,29 +81,15 @@ __global__ __launch_bounds__(64) void strong_params_kernel(const int64_t* __rest
   for (int e = LC2IS_STRONG_W + ST_RMAX + 1; e < ST_P; ++e) row[e] = 0;
 }
 
-struct StrongColour {   // block-uniform
-  float M[9], o[3];
-};
-__device__ __forceinline__ StrongColour strong_colour(const int32_t* __restrict__ prow) {
-  StrongColour k;
-#pragma unroll
-  for (int e = 0; e < 9; ++e) k.M[e] = __builtin_bit_cast(float, prow[LC2IS_STRONG_M + e]);
-#pragma unroll
-  for (int e = 0; e < 3; ++e) k.o[e] = __builtin_bit_cast(float, prow[LC2IS_STRONG_O + e]);
-  return k;
-}
 // normalised rgb of 4 pixels -> v' = clamp(M v + o, 0, 255) on the 0..255 scale
-__device__ __forceinline__ void strong_map(f32x4_t (&v)[3], const StrongColour& k, const lc2is_strong_config& cfg) {
+__device__ __forceinline__ void strong_map(f32x4_t (&v)[3], const ColourMap& k, const lc2is_strong_config& cfg) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float a[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) a[c] = 255.f * (v[c][e] * cfg.std[c] + cfg.mean[c]);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float u = k.M[3 * c] * a[0] + k.M[3 * c + 1] * a[1] + k.M[3 * c + 2] * a[2] + k.o[c];
-      v[c][e] = fminf(fmaxf(u, 0.f), 255.f);
-    }
+    for (int c = 0; c < 3; ++c) v[c][e] = colour_apply(k, a, c);
   }
 }
 __device__ __forceinline__ f32x4_t strong_renorm(f32x4_t v, int c, const lc2is_strong_config& cfg) {
@@ -139,7 +115,7 @@ __device__ __forceinline__ void strong_blur_tile(const float* __restrict__ in, f
   const int rows_st = rows + 2 * R, gw = (cols + 2 * HR) >> 2, ow = cols >> 2;   // staged row r is image y = ty0 - R + r
   const float rgw = __builtin_amdgcn_rcpf((float)gw), row_ = __builtin_amdgcn_rcpf((float)ow);
   const size_t plane = (size_t)S * S;
-  const StrongColour k = strong_colour(prow);
+  const ColourMap k = colour_load(prow, LC2IS_STRONG_M);
   float w[R + 1];
 #pragma unroll
   for (int e = 0; e <= R; ++e) w[e] = __builtin_bit_cast(float, prow[LC2IS_STRONG_W + e]);
@@ -244,17 +220,10 @@ __global__ __launch_bounds__(ST_THREADS) void strong_apply_kernel(const float* _
   if (!blur) {   // block-uniform: stream ST_QUADS consecutive quads of the plane, all 3 channels
     const int total = S * (S >> 2);
     const int q0 = (int)blockIdx.x * ST_QUADS + tid;
-    f32x4_t v[ST_QUADS / ST_THREADS][3];
-#pragma unroll
-    for (int u = 0; u < ST_QUADS / ST_THREADS; ++u) {
-      const int q = q0 + u * ST_THREADS;
-      if (q < total) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[u][c] = *(const f32x4_t*)(src + c * plane + 4 * (size_t)q);
-      }
-    }
+    auto r = view_load_quads<ST_QUADS / ST_THREADS, ST_THREADS>(src, plane, total, q0);
+    auto& v = r.v;
     if (colour) {
-      const StrongColour k = strong_colour(prow);
+      const ColourMap k = colour_load(prow, LC2IS_STRONG_M);
 #pragma unroll
       for (int u = 0; u < ST_QUADS / ST_THREADS; ++u) {
         if (q0 + u * ST_THREADS < total) {
@@ -264,14 +233,7 @@ __global__ __launch_bounds__(ST_THREADS) void strong_apply_kernel(const float* _
         }
       }
     }
-#pragma unroll
-    for (int u = 0; u < ST_QUADS / ST_THREADS; ++u) {
-      const int q = q0 + u * ST_THREADS;
-      if (q < total) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(f32x4_t*)(dst + c * plane + 4 * (size_t)q) = v[u][c];
-      }
-    }
+    view_store_quads<ST_QUADS / ST_THREADS, ST_THREADS>(dst, plane, total, q0, r);
     return;
   }
 
@@ -313,8 +275,7 @@ extern "C" int lc2is_strong_apply(const float* in, const int32_t* params, const 
       ((uintptr_t)params & 3))
     return LC2IS_ERR_SHAPE;
   const size_t bytes = (size_t)B * 3 * S * S * sizeof(float);
-  const uintptr_t x = (uintptr_t)in, y = (uintptr_t)out;
-  if (x < y + bytes && y < x + bytes) return LC2IS_ERR_SHAPE;   // the blur reads a halo: not in place
+  if (lc2is_bytes_overlap(out, bytes, in, bytes)) return LC2IS_ERR_SHAPE;   // the blur reads a halo: not in place
   const int tiles_x = (S + ST_TW - 1) / ST_TW, tiles_y = (S + ST_TH - 1) / ST_TH;
   hipLaunchKernelGGL(strong_apply_kernel, dim3(tiles_x * tiles_y, B), dim3(ST_THREADS), 0, stream, in, params, *cfg, S, tiles_x, out);
   return lc2is_check_launch();

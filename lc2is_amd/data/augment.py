@@ -49,6 +49,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ._shared import _epoch, _indices, _mean_std, _need_cuda, _seed_words, _threshold, _upload
 from .preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
 
 ALIGN = 256                      # every image / label map starts on a multiple of this in its buffer
@@ -74,14 +75,6 @@ def pack_offsets(shapes, img_start: int = 0, lab_start: int = 0):
     return img_offs, lab_offs, io, lo
 
 
-def _need_cuda(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("lc2is_amd.data: augmentation runs on a HIP device; there is no CPU path "
-                           "(tests/augment_ref.py restates it in numpy, test-only)")
-    return device
-
-
 def _as_u8(a, what: str) -> torch.Tensor:
     if isinstance(a, np.ndarray):
         if a.dtype != np.uint8:
@@ -96,11 +89,6 @@ def _desc_rows(shapes, img_offs, lab_offs) -> torch.Tensor:
     """lc2is_aug_image rows as int64 [n, 3]: img_off, lab_off, H | W << 32."""
     return torch.tensor([[io, lo, h | (w << 32)] for (h, w), io, lo in zip(shapes, img_offs, lab_offs)],
                         dtype=torch.int64).reshape(-1, 3)
-
-
-def _upload(t: torch.Tensor, device) -> torch.Tensor:
-    """Host tensor -> device through pinned memory, asynchronously (no host synchronisation)."""
-    return t.pin_memory().to(device, non_blocking=True)
 
 
 class DeviceImagePool:
@@ -221,12 +209,6 @@ class DeviceImagePool:
         return self._desc
 
 
-def _threshold(p: float, what: str) -> int:
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"lc2is_amd.data: {what} must be a probability, got {p}")
-    return int(round(p * (1 << 24)))
-
-
 def class_weights(counts: torch.Tensor, n_classes: int = 151, ignore_index: int | None = 0, mode: str = "median_freq",
                   dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Class weights fp32 [n_classes] for ``CrossEntropyLoss(weight=)`` / ``TrainStep(criterion=)`` from per-image class counts
@@ -284,9 +266,9 @@ class TrainAugment:
         lo, hi = (int(round(float(r) * 1024)) for r in ratio_range)
         if not 1 <= lo <= hi <= 1 << 20 or not 1 <= int(base_size) <= 65536:
             raise ValueError(f"lc2is_amd.data: bad base_size {base_size} / ratio_range {tuple(ratio_range)}")
-        if len(image_mean) != 3 or len(image_std) != 3 or min(image_std) <= 0:
-            raise ValueError("lc2is_amd.data: image_mean / image_std must hold three values, std positive")
-        self.crop_size, self.label_size, self.pad_label, self.seed = S, L, int(pad_label), int(seed) & (2 ** 64 - 1)
+        _mean_std(image_mean, image_std)
+        self.crop_size, self.label_size, self.pad_label = S, L, int(pad_label)
+        self.seed, seed_lo, seed_hi = _seed_words(int(seed))
         ignore = cat_ignore_label
         if isinstance(ignore, str) and ignore == _PAD_LABEL:      # defaulted: only a crop rule that is on needs it in range
             ignore = int(pad_label) if cat_max_ratio is not None or 0 <= int(pad_label) <= 255 else None
@@ -312,7 +294,7 @@ class TrainAugment:
         if photometric is False:
             probs = (0.0,) * 4
         c = self.config = ops.AugConfig()
-        c.seed_lo, c.seed_hi = self.seed & 0xffffffff, self.seed >> 32
+        c.seed_lo, c.seed_hi = seed_lo, seed_hi
         c.crop_size, c.base_size, c.ratio_lo1024, c.ratio_hi1024 = S, int(base_size), lo, hi
         c.flip_thr = _threshold(float(flip_prob), "flip_prob")
         for i, p in enumerate(probs):
@@ -328,21 +310,7 @@ class TrainAugment:
         self._stage = self._stage_free = None
 
     # ---- the launches ----
-    @staticmethod
-    def _indices(indices, device) -> torch.Tensor:
-        if torch.is_tensor(indices) and indices.is_cuda:
-            if indices.dtype != torch.int64 or indices.dim() != 1:
-                raise TypeError("lc2is_amd.data: device indices must be a 1-D int64 tensor")
-            return indices.contiguous()
-        return _upload(torch.as_tensor(indices, dtype=torch.int64).reshape(-1), device)
-
-    @staticmethod
-    def _epoch(epoch, device) -> torch.Tensor:
-        if torch.is_tensor(epoch) and epoch.is_cuda:
-            if epoch.dtype != torch.int32 or epoch.numel() != 1:
-                raise TypeError("lc2is_amd.data: a device epoch must be one int32")
-            return epoch
-        return _upload(torch.tensor([int(epoch)], dtype=torch.int32), device)
+    _indices, _epoch = staticmethod(_indices), staticmethod(_epoch)      # (the key / epoch upload of _shared, under its old names)
 
     def params(self, pool: DeviceImagePool, indices, epoch, *, keys=None, out: torch.Tensor | None = None) -> torch.Tensor:
         """The parameter table int32 [B, 20] of the samples `indices` of the pool in `epoch` (ops.aug_params).  keys: the dataset

@@ -38,9 +38,9 @@ import math
 import torch
 
 from .. import ops
-from .augment import TrainAugment, _need_cuda, _threshold
+from ._shared import (_epoch, _int, _keys_for, _mean_std, _number, _pair, _pixel_shape, _require_device, _seed_words, _tensor_type,
+                      _threshold)
 from .preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
-from .strong import _number, _pair
 
 
 class GeometricAugment:
@@ -67,22 +67,18 @@ class GeometricAugment:
                              f"{translate} 0..{ops.GEO_MAX_TRANSLATE}")
         if not ops.GEO_MIN_SCALE <= scale[0] <= scale[1] <= ops.GEO_MAX_SCALE:
             raise ValueError(f"lc2is_amd.data: scale_range must be ordered inside [{ops.GEO_MIN_SCALE}, {ops.GEO_MAX_SCALE}], got {scale}")
-        if len(image_mean) != 3 or len(image_std) != 3 or min(image_std) <= 0:
-            raise ValueError("lc2is_amd.data: image_mean / image_std must hold three values, std positive")
+        _mean_std(image_mean, image_std)
         if fill is not None:
             if not isinstance(fill, (tuple, list)) or len(fill) != 3:
                 raise TypeError(f"lc2is_amd.data: fill must be None or an (r, g, b) triple on the 0..255 scale, got {fill!r}")
             fill = [_number(v, "fill") for v in fill]
             if min(fill) < 0.0 or max(fill) > 255.0:
                 raise ValueError(f"lc2is_amd.data: fill must lie in 0..255, got {fill}")
-        for v, what in ((ignore_index, "ignore_index"), (seed, "seed")):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise TypeError(f"lc2is_amd.data: {what} must be an int, got {v!r}")
+        _int(ignore_index, "ignore_index"), _int(seed, "seed")
         if not -2 ** 63 <= ignore_index < 2 ** 63:
             raise ValueError(f"lc2is_amd.data: ignore_index must fit int64, got {ignore_index}")
-        self.seed = seed & (2 ** 64 - 1)
         c = self.config = ops.GeoConfig()
-        c.seed_lo, c.seed_hi = self.seed & 0xffffffff, self.seed >> 32
+        self.seed, c.seed_lo, c.seed_hi = _seed_words(seed)
         c.warp_thr, c.flip_thr = warp_thr, flip_thr
         c.rotate, c.shear, c.translate = math.radians(rotate), math.radians(shear), shift
         c.scale_lo, c.scale_hi = scale
@@ -97,27 +93,17 @@ class GeometricAugment:
             raise TypeError("lc2is_amd.data: GeometricAugment batch must be (pixel_values, labels or None, pixel_weight or None)")
         x, lab, pw = batch
         for t, dtype, what in ((x, torch.float32, "pixel_values"), (lab, torch.int64, "labels"), (pw, torch.float32, "pixel_weight")):
-            if (t is not None or what == "pixel_values") and (not torch.is_tensor(t) or t.dtype != dtype):
-                raise TypeError(f"lc2is_amd.data: GeometricAugment {what} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
-        if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-            raise ValueError(f"lc2is_amd.data: GeometricAugment pixel_values must be [B, 3, S, S], got {tuple(x.shape)}")
-        B, S = int(x.shape[0]), int(x.shape[2])
-        if S < ops.GEO_MIN_SIDE or S > ops.AUG_MAX_SIDE or S % 4:
-            raise ValueError(f"lc2is_amd.data: GeometricAugment needs S a multiple of 4 in {ops.GEO_MIN_SIDE}..{ops.AUG_MAX_SIDE}, got {S}")
+            _tensor_type("GeometricAugment", t, dtype, what, optional=what != "pixel_values")
+        B, S = _pixel_shape("GeometricAugment", x, ops.GEO_MIN_SIDE, ops.AUG_MAX_SIDE)
         for t, what in ((lab, "labels"), (pw, "pixel_weight")):
             if t is not None and (t.dim() != 3 or t.shape[0] != B or t.shape[1] != t.shape[2] or t.shape[1] < 1 or S % t.shape[1]):
                 raise ValueError(f"lc2is_amd.data: GeometricAugment {what} must be [{B}, L, L] with L dividing {S}, got {tuple(t.shape)}")
         if lab is not None and pw is not None and lab.shape != pw.shape:
             raise ValueError(f"lc2is_amd.data: GeometricAugment labels {tuple(lab.shape)} and pixel_weight {tuple(pw.shape)} differ")
-        if not x.is_cuda:
-            raise RuntimeError("lc2is_amd.data: GeometricAugment runs on a HIP device; there is no CPU path "
-                               "(tests/geo_ref.py restates it in numpy, test-only)")
-        dev = _need_cuda(x.device)
+        dev = _require_device("GeometricAugment", "tests/geo_ref.py restates it in numpy", x)
         _, _, _, out = ops._geo_batch(batch, out)               # layout, alignment and overlap, before the first launch
-        keys = TrainAugment._indices(keys, dev)
-        if keys.numel() != B:
-            raise ValueError(f"lc2is_amd.data: GeometricAugment got {keys.numel()} keys for {B} samples")
-        params = ops.geo_params(keys, TrainAugment._epoch(epoch, dev), self.config)
+        keys = _keys_for("GeometricAugment", keys, dev, B)
+        params = ops.geo_params(keys, _epoch(epoch, dev), self.config)
         out = ops.geo_apply(batch, params, self.config, out=out)
         self.last_params = params
         return out
@@ -131,11 +117,10 @@ class GeometricAugment:
     @staticmethod
     def _scores_grid(scores, B: int, teacher_weight, label_size, who: str) -> int:
         """g of a score tensor fp32 [B*g*g, ld] for B samples, after the type and shape checks that need no device."""
-        for t, what in ((scores, "teacher scores"), (teacher_weight, "teacher_weight")):
-            if (t is not None or what == "teacher scores") and (not torch.is_tensor(t) or t.dtype != torch.float32):
-                raise TypeError(f"lc2is_amd.data: {who} {what} must be a torch.float32 tensor, got {getattr(t, 'dtype', type(t))}")
-        if label_size is not None and (isinstance(label_size, bool) or not isinstance(label_size, int)):
-            raise TypeError(f"lc2is_amd.data: {who} label_size must be an int, got {label_size!r}")
+        _tensor_type(who, scores, torch.float32, "teacher scores")
+        _tensor_type(who, teacher_weight, torch.float32, "teacher_weight", optional=True)
+        if label_size is not None:
+            _int(label_size, f"{who} label_size")
         if scores.dim() != 2 or scores.shape[0] < B or scores.shape[0] % B:
             raise ValueError(f"lc2is_amd.data: {who} scores must be [B*g*g, ld] for B = {B} samples, got {tuple(scores.shape)}")
         cells = scores.shape[0] // B
@@ -169,8 +154,7 @@ class GeometricAugment:
         if params is None:
             raise RuntimeError("lc2is_amd.data: GeometricAugment.warp_scores needs the table of a view: call the augmenter first, or "
                                "pass params=")
-        if not torch.is_tensor(params) or params.dtype != torch.int32:
-            raise TypeError(f"lc2is_amd.data: GeometricAugment.warp_scores params must be an int32 tensor, got {getattr(params, 'dtype', type(params))}")
+        _tensor_type("GeometricAugment.warp_scores", params, torch.int32, "params")
         if params.dim() != 2 or params.shape[0] < 1 or params.shape[1] != ops.GEO_PARAM_WORDS:
             raise ValueError(f"lc2is_amd.data: GeometricAugment.warp_scores params must be [B, {ops.GEO_PARAM_WORDS}], got {tuple(params.shape)}")
         B = int(params.shape[0])

@@ -26,15 +26,9 @@ from __future__ import annotations
 import torch
 
 from .. import ops
-from .augment import TrainAugment, _need_cuda
+from ._shared import _epoch, _int, _keys_for, _require_device, _seed_words, _tensor_type
 
 _MODES = {"none": ops.MIX_NONE, "classmix": ops.MIX_CLASSMIX, "cutmix": ops.MIX_CUTMIX}
-
-
-def _int(v, what: str) -> int:
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"lc2is_amd.data: {what} must be an int, got {v!r}")
-    return v
 
 
 class SampleMix:
@@ -60,9 +54,10 @@ class SampleMix:
             raise ValueError(f"lc2is_amd.data: box_area must be an ordered pair of area shares in (0, 1] (at least 1/1024), got {tuple(box_area)}")
         self.mode, self.n_classes, self.ignore_index = mode, n_classes, _int(ignore_index, "ignore_index")
         self.exclude_label = None if exclude_label is None else _int(exclude_label, "exclude_label")
-        self.box_area, self.seed = (lo, hi), int(seed) & (2 ** 64 - 1)
+        self.box_area = (lo, hi)
         c = self.config = ops.MixConfig()
-        c.seed_lo, c.seed_hi, c.mode, c.n_classes = self.seed & 0xffffffff, self.seed >> 32, _MODES[mode], n_classes
+        self.seed, c.seed_lo, c.seed_hi = _seed_words(int(seed))
+        c.mode, c.n_classes = _MODES[mode], n_classes
         c.ignore_index, c.exclude_label = self.ignore_index, -1 if self.exclude_label is None else self.exclude_label
         c.area_lo1024, c.area_hi1024 = int(round(lo * 1024)), int(round(hi * 1024))
         self.last_info = None
@@ -74,10 +69,7 @@ class SampleMix:
             raise TypeError(f"lc2is_amd.data: SampleMix {name} must be (pixel_values, labels, pixel_weight or None)")
         px, lab, pw = batch
         for t, dtype, what in ((px, torch.float32, "pixel_values"), (lab, torch.int64, "labels"), (pw, torch.float32, "pixel_weight")):
-            if t is None and what == "pixel_weight":
-                continue
-            if not torch.is_tensor(t) or t.dtype != dtype:
-                raise TypeError(f"lc2is_amd.data: SampleMix {name} {what} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+            _tensor_type(f"SampleMix {name}", t, dtype, what, optional=what == "pixel_weight")
         if px.dim() != 4 or px.shape[1] != 3 or px.shape[2] != px.shape[3] or lab.dim() != 3 or lab.shape[1] != lab.shape[2] or \
                 lab.shape[0] != px.shape[0] or px.shape[0] < 1 or (pw is not None and pw.shape != lab.shape):
             raise ValueError(f"lc2is_amd.data: SampleMix {name} must be pixel_values [n, 3, S, S], labels [n, L, L] and pixel_weight "
@@ -92,18 +84,11 @@ class SampleMix:
         _, S2, L2 = self._batch(src, "src")
         if (S2, L2) != (S, L):
             raise ValueError(f"lc2is_amd.data: SampleMix dst is {S} px / {L} cells a side, src {S2} / {L2}")
-        if not dst[0].is_cuda or not src[0].is_cuda:
-            raise RuntimeError("lc2is_amd.data: SampleMix runs on a HIP device; there is no CPU path "
-                               "(tests/mix_ref.py restates it in numpy, test-only)")
-        dev = _need_cuda(dst[0].device)
-        keys = TrainAugment._indices(keys, dev)
-        if keys.numel() != B:
-            raise ValueError(f"lc2is_amd.data: SampleMix got {keys.numel()} keys for {B} destination samples")
+        dev = _require_device("SampleMix", "tests/mix_ref.py restates it in numpy", dst[0], src[0])   # (mix_apply checks layout and overlap)
+        keys = _keys_for("SampleMix", keys, dev, B, of="destination samples")
         if src_index is not None:
-            src_index = TrainAugment._indices(src_index, dev)
-            if src_index.numel() != B:
-                raise ValueError(f"lc2is_amd.data: SampleMix got {src_index.numel()} source rows for {B} destination samples")
-        plan, info = ops.mix_select(src[1], keys, TrainAugment._epoch(epoch, dev), self.config, src_index=src_index)
+            src_index = _keys_for("SampleMix", src_index, dev, B, "source rows", "destination samples")
+        plan, info = ops.mix_select(src[1], keys, _epoch(epoch, dev), self.config, src_index=src_index)
         px, lab, pw = ops.mix_apply(tuple(dst), tuple(src), plan, out=out)
         self.last_info = info
         return px, lab, pw, info

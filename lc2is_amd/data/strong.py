@@ -31,25 +31,9 @@ import math
 import torch
 
 from .. import ops
-from .augment import TrainAugment, _need_cuda, _threshold
+from ._shared import (_epoch, _int, _keys_for, _mean_std, _number, _pair, _pixel_shape, _require_device, _seed_words, _tensor_type,
+                      _threshold)
 from .preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
-
-
-def _number(v, what: str) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise TypeError(f"lc2is_amd.data: {what} must be a number, got {v!r}")
-    if not math.isfinite(v):
-        raise ValueError(f"lc2is_amd.data: {what} must be finite, got {v!r}")
-    return float(v)
-
-
-def _pair(v, what: str) -> tuple[float, float]:
-    if not isinstance(v, (tuple, list)) or len(v) != 2:
-        raise TypeError(f"lc2is_amd.data: {what} must be a (lo, hi) pair, got {v!r}")
-    lo, hi = _number(v[0], what), _number(v[1], what)
-    if lo > hi:
-        raise ValueError(f"lc2is_amd.data: {what} must be ordered, got {tuple(v)}")
-    return lo, hi
 
 
 class StrongAugment:
@@ -75,13 +59,9 @@ class StrongAugment:
         if not 0.0 < sigma[0] <= sigma[1] <= ops.STRONG_MAX_SIGMA:
             raise ValueError(f"lc2is_amd.data: sigma_range must be ordered inside (0, {ops.STRONG_MAX_SIGMA}] (the blur's radius is at "
                              f"most {ops.STRONG_MAX_RADIUS}), got {sigma}")
-        if len(image_mean) != 3 or len(image_std) != 3 or min(image_std) <= 0:
-            raise ValueError("lc2is_amd.data: image_mean / image_std must hold three values, std positive")
-        if isinstance(seed, bool) or not isinstance(seed, int):
-            raise TypeError(f"lc2is_amd.data: seed must be an int, got {seed!r}")
-        self.seed = seed & (2 ** 64 - 1)
+        _mean_std(image_mean, image_std)
         c = self.config = ops.StrongConfig()
-        c.seed_lo, c.seed_hi = self.seed & 0xffffffff, self.seed >> 32
+        self.seed, c.seed_lo, c.seed_hi = _seed_words(_int(seed, "seed"))
         c.jitter_thr, c.gray_thr, c.blur_thr = probs
         c.brightness_delta, c.hue_delta = float(brightness_delta), math.radians(float(hue_delta))
         (c.contrast_lo, c.contrast_hi), (c.saturation_lo, c.saturation_hi), (c.sigma_lo, c.sigma_hi) = contrast, saturation, sigma
@@ -91,22 +71,12 @@ class StrongAugment:
 
     def __call__(self, pixel_values, keys, epoch, out: torch.Tensor | None = None) -> torch.Tensor:
         x = pixel_values
-        if not torch.is_tensor(x) or x.dtype != torch.float32:
-            raise TypeError(f"lc2is_amd.data: StrongAugment pixel_values must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
-        if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-            raise ValueError(f"lc2is_amd.data: StrongAugment pixel_values must be [B, 3, S, S], got {tuple(x.shape)}")
-        B, S = int(x.shape[0]), int(x.shape[2])
-        if S < ops.STRONG_MIN_SIDE or S > ops.AUG_MAX_SIDE or S % 4:
-            raise ValueError(f"lc2is_amd.data: StrongAugment needs S a multiple of 4 in {ops.STRONG_MIN_SIDE}..{ops.AUG_MAX_SIDE}, got {S}")
-        if not x.is_cuda:
-            raise RuntimeError("lc2is_amd.data: StrongAugment runs on a HIP device; there is no CPU path "
-                               "(tests/strong_ref.py restates it in numpy, test-only)")
-        dev = _need_cuda(x.device)
+        _tensor_type("StrongAugment", x, torch.float32, "pixel_values")
+        B, _ = _pixel_shape("StrongAugment", x, ops.STRONG_MIN_SIDE, ops.AUG_MAX_SIDE)
+        dev = _require_device("StrongAugment", "tests/strong_ref.py restates it in numpy", x)
         _, _, out = ops._strong_batch(x, out)                 # layout, alignment and overlap, before the first launch
-        keys = TrainAugment._indices(keys, dev)
-        if keys.numel() != B:
-            raise ValueError(f"lc2is_amd.data: StrongAugment got {keys.numel()} keys for {B} samples")
-        params = ops.strong_params(keys, TrainAugment._epoch(epoch, dev), self.config)
+        keys = _keys_for("StrongAugment", keys, dev, B)
+        params = ops.strong_params(keys, _epoch(epoch, dev), self.config)
         out = ops.strong_apply(x, params, self.config, out=out)
         self.last_params = params
         return out

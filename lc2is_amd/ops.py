@@ -243,6 +243,69 @@ def _chk_ld8(who: str, t: torch.Tensor, name: str):
                            f"got {t.stride(0)}")
 
 
+# ---- the device data views (aug_*, mix_*, strong_*, geo_*): what their wrappers ask of an operand, each rule once ----
+def _overlap(a: torch.Tensor, b: torch.Tensor | None) -> bool:
+    """The byte ranges of two tensors share a byte (lc2is_bytes_overlap of csrc/common.h)."""
+    a0, b0 = a.data_ptr(), 0 if b is None else b.data_ptr()
+    return b is not None and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _view_table(who: str, t, name: str, B: int, words: int, dev=None, new_on=None) -> torch.Tensor:
+    """A parameter, plan or info table: contiguous int32 [B, words], on ``dev`` where one is named; None is allocated on ``new_on``."""
+    if t is None and new_on is not None:
+        t = torch.empty((B, words), dtype=torch.int32, device=new_on)
+    _chk(t, torch.int32, name)
+    if tuple(t.shape) != (B, words) or not t.is_contiguous() or (dev is not None and t.device != dev):
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous int32 [{B}, {words}]" + ("" if dev is None else f" on {dev}"))
+    return t
+
+
+def _view_keys(who: str, keys, epoch, B: int | None = None) -> int:
+    """epoch: one int32 on the device; keys: one int64 per sample (B None: the keys give B, at least one).  Returns B."""
+    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
+    n = keys.numel() if B is None else B
+    if n < 1 or epoch.numel() != 1 or (keys is not None and keys.numel() != n):
+        raise RuntimeError(f"lc2is_amd.{who}: epoch must hold one int32 and keys one int64 per sample, at least one")
+    return n
+
+
+def _view_pixels(who: str, x, name: str, align: int = 16):
+    """A pixel batch: fp32 [B, 3, S, S], contiguous, with an ``align``-byte base; returns (B, S).  The side rule is _view_side's."""
+    _chk(x, torch.float32, name, 4)
+    B, S = x.shape[0], x.shape[2]
+    if B < 1 or tuple(x.shape) != (B, 3, S, S) or not x.is_contiguous() or x.data_ptr() % align:
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous fp32 [B, 3, S, S] with a {align}-byte base, got {tuple(x.shape)}, strides {tuple(x.stride())}")
+    return B, S
+
+
+def _view_side(who: str, B: int, S: int, L: int | None, min_side: int) -> None:
+    """S a multiple of 4 (and of the label size L, where there is one) in min_side..AUG_MAX_SIDE; at most 65535 samples (one per blockIdx.y)."""
+    if S < min_side or S > AUG_MAX_SIDE or S % 4 or (L is not None and (L < 1 or S % L)):
+        raise ValueError(f"lc2is_amd.{who}: the size {S} must be a multiple of 4" + ("" if L is None else f" and of the label size {L}") + f", in {min_side}..{AUG_MAX_SIDE}")
+    if not 1 <= B <= 65535:
+        raise ValueError(f"lc2is_amd.{who}: 1..65535 samples per call, got {B}")
+
+
+def _view_cells(who: str, m, name: str, dtype, B: int, L: int, dev=None) -> None:
+    """A label (int64) or weight (fp32) map on the cells: contiguous [B, L, L] with an aligned base, on ``dev`` where one is named."""
+    _chk(m, dtype, name, 3)
+    if m is not None and (tuple(m.shape) != (B, L, L) or not m.is_contiguous() or m.data_ptr() % m.element_size() or (dev is not None and m.device != dev)):
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous {dtype} [{B}, L, L], labels and weights of one L" +
+                           ("" if dev is None else " on the first operand's device") + f", got {tuple(m.shape)}, strides {tuple(m.stride())}")
+
+
+def _view_out(who: str, o, name: str, shape, dtype, new_on, align: int = 1, inputs=(), refusal: str = "", dev=None) -> torch.Tensor:
+    """None is allocated on ``new_on``; else contiguous ``shape``, ``align``-byte base (on ``dev`` if named), no byte shared with ``inputs``."""
+    if o is None:
+        o = torch.empty(shape, dtype=dtype, device=new_on)
+    _chk(o, dtype, name, len(shape))
+    if tuple(o.shape) != tuple(shape) or not o.is_contiguous() or o.data_ptr() % align or (dev is not None and o.device != dev):
+        raise RuntimeError(f"lc2is_amd.{who}: {name} must be contiguous {dtype} {tuple(shape)}, {align}-byte base" + ("" if dev is None else ", on the input's device"))
+    if any(_overlap(o, i) for i in inputs):
+        raise RuntimeError(f"lc2is_amd.{who}: {name} {refusal}")
+    return o
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
@@ -2435,15 +2498,8 @@ def aug_params(slots: torch.Tensor, epoch: torch.Tensor, desc: torch.Tensor, cfg
     desc; keys int64 [B] or None: the dataset indices the random numbers are a function of (None: the slots); epoch: DEVICE int32
     scalar.  Nothing but device memory decides the result, so a captured call draws again on replay."""
     _aug_tables(desc, slots, "aug_params")
-    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
-    B = slots.numel()
-    if epoch.numel() != 1 or (keys is not None and keys.numel() != B):
-        raise RuntimeError("lc2is_amd.aug_params: epoch must hold one int32 and keys one int64 per sample")
-    if out is None:
-        out = torch.empty((B, AUG_PARAM_WORDS), dtype=torch.int32, device=slots.device)
-    _chk(out, torch.int32, "out")
-    if tuple(out.shape) != (B, AUG_PARAM_WORDS) or not out.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.aug_params: out must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    B = _view_keys("aug_params", keys, epoch, slots.numel())
+    out = _view_table("aug_params", out, "out", B, AUG_PARAM_WORDS, new_on=slots.device)
     rc = _fn("lc2is_aug_params")(_ptr(slots), _ptr(keys), B, _ptr(epoch), _ptr(desc), desc.shape[0], C.addressof(cfg), _ptr(out),
                                  _stream())
     _lib.check(rc, f"aug_params B={B}")
@@ -2456,19 +2512,13 @@ def aug_apply(img: torch.Tensor, lab: torch.Tensor, desc: torch.Tensor, slots: t
     the pool's uint8 HWC pixels -> fp32 [B, 3, S, S], and the nearest-exact labels of the same geometry at the centres of the
     (S / L)^2 cells -> int64 [B, L, L].  img / lab: the pool's packed uint8 buffers; desc / slots as in aug_params; params its table."""
     _aug_tables(desc, slots, "aug_apply")
-    _chk(img, torch.uint8, "img", 1); _chk(lab, torch.uint8, "lab", 1); _chk(params, torch.int32, "params")
+    _chk(img, torch.uint8, "img", 1); _chk(lab, torch.uint8, "lab", 1)
     B = slots.numel()
-    if tuple(params.shape) != (B, AUG_PARAM_WORDS) or not params.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.aug_apply: params must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    _view_table("aug_apply", params, "params", B, AUG_PARAM_WORDS)
     if S < 1 or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
         raise ValueError(f"lc2is_amd.aug_apply: crop size {S} must be a multiple of 4 and of the label size {L}, at most {AUG_MAX_SIDE}")
-    if out_img is None:
-        out_img = torch.empty((B, 3, S, S), dtype=torch.float32, device=img.device)
-    if out_lab is None:
-        out_lab = torch.empty((B, L, L), dtype=torch.int64, device=img.device)
-    _chk(out_img, torch.float32, "out_img", 4); _chk(out_lab, torch.int64, "out_lab", 3)
-    if tuple(out_img.shape) != (B, 3, S, S) or tuple(out_lab.shape) != (B, L, L) or not (out_img.is_contiguous() and out_lab.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.aug_apply: outputs must be contiguous [{B}, 3, {S}, {S}] fp32 and [{B}, {L}, {L}] int64")
+    out_img = _view_out("aug_apply", out_img, "out_img", (B, 3, S, S), torch.float32, img.device)
+    out_lab = _view_out("aug_apply", out_lab, "out_lab", (B, L, L), torch.int64, img.device)
     rc = _fn("lc2is_aug_apply")(_ptr(img), img.numel(), _ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), _ptr(params),
                                 B, S, L, C.addressof(norm), int(pad_label), _ptr(out_img), _ptr(out_lab), _stream())
     _lib.check(rc, f"aug_apply B={B} S={S} L={L}")
@@ -2486,23 +2536,15 @@ def aug_crop_select(lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, 
     none accepted; {-1, 0, 0, 0}: a row out of range, left untouched).  lab: the pool's packed label buffer; desc / slots / keys /
     epoch / cfg as in aug_params.  Nothing but device memory decides the result."""
     _aug_tables(desc, slots, "aug_crop_select")
-    _chk(lab, torch.uint8, "lab", 1); _chk(params, torch.int32, "params")
-    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
-    B, S, L = slots.numel(), int(cfg.crop_size), int(L)
-    if epoch.numel() != 1 or (keys is not None and keys.numel() != B):
-        raise RuntimeError("lc2is_amd.aug_crop_select: epoch must hold one int32 and keys one int64 per sample")
-    if tuple(params.shape) != (B, AUG_PARAM_WORDS) or not params.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.aug_crop_select: params must be contiguous int32 [{B}, {AUG_PARAM_WORDS}]")
+    _chk(lab, torch.uint8, "lab", 1)
+    B, S, L = _view_keys("aug_crop_select", keys, epoch, slots.numel()), int(cfg.crop_size), int(L)
+    _view_table("aug_crop_select", params, "params", B, AUG_PARAM_WORDS)
     if S < 1 or S > AUG_MAX_SIDE or L < 1 or S % L:
         raise ValueError(f"lc2is_amd.aug_crop_select: crop size {S} must be a multiple of the label size {L}, at most {AUG_MAX_SIDE}")
     if not 1 <= int(ratio1024) <= 1023 or not -1 <= int(ignore_label) <= 255 or not 1 <= int(tries) <= AUG_MAX_TRIES:
         raise ValueError(f"lc2is_amd.aug_crop_select: ratio1024 {ratio1024} must be 1..1023, ignore_label {ignore_label} -1..255 and "
                          f"tries {tries} 1..{AUG_MAX_TRIES}")
-    if info is None:
-        info = torch.empty((B, 4), dtype=torch.int32, device=slots.device)
-    _chk(info, torch.int32, "info")
-    if tuple(info.shape) != (B, 4) or not info.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.aug_crop_select: info must be contiguous int32 [{B}, 4]")
+    info = _view_table("aug_crop_select", info, "info", B, 4, new_on=slots.device)
     rc = _fn("lc2is_aug_crop_select")(_ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), _ptr(keys), B, _ptr(epoch),
                                       C.addressof(cfg), _ptr(params), L, int(ratio1024), int(ignore_label), int(tries), _ptr(info),
                                       _stream())
@@ -2516,11 +2558,7 @@ def label_histogram(lab: torch.Tensor, desc: torch.Tensor, slots: torch.Tensor, 
     _aug_tables(desc, slots, "label_histogram")
     _chk(lab, torch.uint8, "lab", 1)
     B = slots.numel()
-    if out is None:
-        out = torch.empty((B, LABEL_BINS), dtype=torch.int32, device=slots.device)
-    _chk(out, torch.int32, "out")
-    if tuple(out.shape) != (B, LABEL_BINS) or not out.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.label_histogram: out must be contiguous int32 [{B}, {LABEL_BINS}]")
+    out = _view_table("label_histogram", out, "out", B, LABEL_BINS, new_on=slots.device)
     rc = _fn("lc2is_label_histogram")(_ptr(lab), lab.numel(), _ptr(desc), desc.shape[0], _ptr(slots), B, _ptr(out), _stream())
     _lib.check(rc, f"label_histogram B={B}")
     return out
@@ -2538,20 +2576,12 @@ class MixConfig(C.Structure):
 
 
 def _mix_batch(px, lab, pw, name):
-    _chk(px, torch.float32, f"{name} pixels", 4); _chk(lab, torch.int64, f"{name} labels", 3); _chk(pw, torch.float32, f"{name} weights", 3)
-    n, S, L = px.shape[0], px.shape[2], lab.shape[1]
-    if n < 1 or tuple(px.shape) != (n, 3, S, S) or tuple(lab.shape) != (n, L, L) or (pw is not None and pw.shape != lab.shape) \
-            or not (px.is_contiguous() and lab.is_contiguous() and (pw is None or pw.is_contiguous())):
-        raise RuntimeError(f"lc2is_amd.mix_apply: the {name} batch must be contiguous pixels [n, 3, S, S], labels [n, L, L] and "
-                           "weights [n, L, L] or None")
+    n, S = _view_pixels("mix_apply", px, f"{name} pixels", align=4)
+    _chk(lab, torch.int64, f"{name} labels", 3)
+    L = lab.shape[1]
+    _view_cells("mix_apply", lab, f"{name} labels", torch.int64, n, L)
+    _view_cells("mix_apply", pw, f"{name} weights", torch.float32, n, L)
     return n, S, L
-
-
-def _overlap(a: torch.Tensor, b: torch.Tensor | None) -> bool:
-    if b is None:
-        return False
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
 def mix_select(src_lab: torch.Tensor, keys: torch.Tensor, epoch: torch.Tensor, cfg: MixConfig, *,
@@ -2561,26 +2591,19 @@ def mix_select(src_lab: torch.Tensor, keys: torch.Tensor, epoch: torch.Tensor, c
     masked cells, L * L ({-1, 0, 0, 0}: the source row lies outside the source batch; that sample keeps its destination).  src_lab
     int64 [Bs, L, L]: the source batch's label maps; keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE
     int32 scalar; src_index int64 [B] or None (row b).  Nothing but device memory decides the result: a captured call draws again."""
-    _chk(src_lab, torch.int64, "src_lab", 3); _chk(keys, torch.int64, "keys", 1); _chk(src_index, torch.int64, "src_index", 1)
-    _chk(epoch, torch.int32, "epoch", None)
-    Bs, L, B = src_lab.shape[0], src_lab.shape[1], keys.numel()
-    if Bs < 1 or B < 1 or src_lab.shape[2] != L or not src_lab.is_contiguous() or epoch.numel() != 1 or \
-            (src_index is not None and src_index.numel() != B):
-        raise RuntimeError("lc2is_amd.mix_select: src_lab must be contiguous int64 [Bs, L, L], epoch one int32, keys and src_index "
-                           "one int64 per output sample")
+    _chk(src_lab, torch.int64, "src_lab", 3); _chk(src_index, torch.int64, "src_index", 1)
+    B = _view_keys("mix_select", keys, epoch)
+    Bs, L = src_lab.shape[0], src_lab.shape[1]
+    if Bs < 1 or src_lab.shape[2] != L or not src_lab.is_contiguous() or (src_index is not None and src_index.numel() != B):
+        raise RuntimeError("lc2is_amd.mix_select: src_lab must be contiguous int64 [Bs, L, L] and src_index one int64 per output sample")
     if not 1 <= L <= AUG_MAX_SIDE:
         raise ValueError(f"lc2is_amd.mix_select: label size {L} must be 1..{AUG_MAX_SIDE}")
     if cfg.mode not in (MIX_NONE, MIX_CLASSMIX, MIX_CUTMIX) or not 1 <= cfg.n_classes <= MIX_MAX_CLASSES or \
             not 1 <= cfg.area_lo1024 <= cfg.area_hi1024 <= 1024:
         raise ValueError(f"lc2is_amd.mix_select: mode {cfg.mode} must be MIX_NONE / MIX_CLASSMIX / MIX_CUTMIX, n_classes {cfg.n_classes} "
                          f"1..{MIX_MAX_CLASSES} and the area range ({cfg.area_lo1024}, {cfg.area_hi1024}) ordered inside 1..1024")
-    if plan is None:
-        plan = torch.empty((B, MIX_PLAN_WORDS), dtype=torch.int32, device=keys.device)
-    if info is None:
-        info = torch.empty((B, 4), dtype=torch.int32, device=keys.device)
-    _chk(plan, torch.int32, "plan"); _chk(info, torch.int32, "info")
-    if tuple(plan.shape) != (B, MIX_PLAN_WORDS) or tuple(info.shape) != (B, 4) or not (plan.is_contiguous() and info.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.mix_select: plan / info must be contiguous int32 [{B}, {MIX_PLAN_WORDS}] / [{B}, 4]")
+    plan = _view_table("mix_select", plan, "plan", B, MIX_PLAN_WORDS, new_on=keys.device)
+    info = _view_table("mix_select", info, "info", B, 4, new_on=keys.device)
     rc = _fn("lc2is_mix_select")(_ptr(src_lab), Bs, _ptr(src_index), _ptr(keys), B, _ptr(epoch), C.addressof(cfg), L, _ptr(plan),
                                  _ptr(info), _stream())
     _lib.check(rc, f"mix_select B={B} Bs={Bs} L={L}")
@@ -2598,22 +2621,13 @@ def mix_apply(dst, src, plan: torch.Tensor, out=None):
     Bs, S2, L2 = _mix_batch(spx, slab, spw, "source")
     if (S2, L2) != (S, L):
         raise RuntimeError(f"lc2is_amd.mix_apply: the destination is {S} px / {L} cells a side, the source {S2} / {L2}")
-    if S < 4 or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
-        raise ValueError(f"lc2is_amd.mix_apply: the size {S} must be a multiple of 4 and of the label size {L}, at most {AUG_MAX_SIDE}")
-    if not 1 <= B <= 65535:
-        raise ValueError(f"lc2is_amd.mix_apply: at most 65535 samples per call, got {B}")
-    _chk(plan, torch.int32, "plan")
-    if tuple(plan.shape) != (B, MIX_PLAN_WORDS) or not plan.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.mix_apply: plan must be contiguous int32 [{B}, {MIX_PLAN_WORDS}]")
-    if out is None:
-        out = (torch.empty_like(dpx), torch.empty_like(dlab), torch.empty(dlab.shape, dtype=torch.float32, device=dlab.device))
-    opx, olab, opw = out
-    _chk(opx, torch.float32, "out pixels", 4); _chk(olab, torch.int64, "out labels", 3); _chk(opw, torch.float32, "out weights", 3)
-    if opx.shape != dpx.shape or olab.shape != dlab.shape or opw.shape != dlab.shape or \
-            not (opx.is_contiguous() and olab.is_contiguous() and opw.is_contiguous()):
-        raise RuntimeError(f"lc2is_amd.mix_apply: outputs must be contiguous [{B}, 3, {S}, {S}] fp32, [{B}, {L}, {L}] int64 and fp32")
-    if any(_overlap(o, i) for o, ins in ((opx, (dpx, spx)), (olab, (dlab, slab)), (opw, (dpw, spw))) for i in ins):
-        raise RuntimeError("lc2is_amd.mix_apply: an output may not alias an input (the source batch may be the destination batch)")
+    _view_side("mix_apply", B, S, L, 4)
+    _view_table("mix_apply", plan, "plan", B, MIX_PLAN_WORDS)
+    why = "may not alias an input (the source batch may be the destination batch)"
+    opx, olab, opw = out or (None, None, None)
+    opx = _view_out("mix_apply", opx, "out pixels", dpx.shape, torch.float32, dpx.device, inputs=(dpx, spx), refusal=why)
+    olab = _view_out("mix_apply", olab, "out labels", dlab.shape, torch.int64, dlab.device, inputs=(dlab, slab), refusal=why)
+    opw = _view_out("mix_apply", opw, "out weights", dlab.shape, torch.float32, dlab.device, inputs=(dpw, spw), refusal=why)
     rc = _fn("lc2is_mix_apply")(_ptr(dpx), _ptr(dlab), _ptr(dpw), _ptr(spx), _ptr(slab), _ptr(spw), Bs, _ptr(plan), B, S, L,
                                 _ptr(opx), _ptr(olab), _ptr(opw), _stream())
     _lib.check(rc, f"mix_apply B={B} Bs={Bs} S={S} L={L}")
@@ -2640,18 +2654,11 @@ def strong_params(keys: torch.Tensor, epoch: torch.Tensor, cfg: StrongConfig, *,
     bit 1 grey, bit 2 blur), the blur radius R, then fp32 bit patterns: sigma, the colour matrix M[3][3] and offset o[3], the blur taps
     w[0..8]; the rest 0.  keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE int32 scalar.  Nothing but
     device memory decides the result: a captured call draws again on replay."""
-    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
-    B = keys.numel()
-    if B < 1 or epoch.numel() != 1:
-        raise RuntimeError("lc2is_amd.strong_params: epoch must hold one int32 and keys at least one int64")
+    B = _view_keys("strong_params", keys, epoch)
     if max(cfg.jitter_thr, cfg.gray_thr, cfg.blur_thr) > 1 << 24 or not 0.0 < cfg.sigma_lo <= cfg.sigma_hi <= STRONG_MAX_SIGMA:
         raise ValueError(f"lc2is_amd.strong_params: thresholds must be at most 2^24 and the sigma range ({cfg.sigma_lo}, {cfg.sigma_hi}) "
                          f"ordered inside (0, {STRONG_MAX_SIGMA}]")
-    if out is None:
-        out = torch.empty((B, STRONG_PARAM_WORDS), dtype=torch.int32, device=keys.device)
-    _chk(out, torch.int32, "out")
-    if tuple(out.shape) != (B, STRONG_PARAM_WORDS) or not out.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.strong_params: out must be contiguous int32 [{B}, {STRONG_PARAM_WORDS}]")
+    out = _view_table("strong_params", out, "out", B, STRONG_PARAM_WORDS, new_on=keys.device)
     rc = _fn("lc2is_strong_params")(_ptr(keys), B, _ptr(epoch), C.addressof(cfg), _ptr(out), _stream())
     _lib.check(rc, f"strong_params B={B}")
     return out
@@ -2659,22 +2666,9 @@ def strong_params(keys: torch.Tensor, epoch: torch.Tensor, cfg: StrongConfig, *,
 
 def _strong_batch(x: torch.Tensor, out: torch.Tensor | None):
     """Everything strong_apply asks of its input and output, before any device work; returns (B, S, out), out allocated if None."""
-    _chk(x, torch.float32, "pixel_values", 4)
-    B, S = x.shape[0], x.shape[2]
-    if B < 1 or tuple(x.shape) != (B, 3, S, S) or not x.is_contiguous() or x.data_ptr() % 16:
-        raise RuntimeError(f"lc2is_amd.strong_apply: pixel_values must be contiguous fp32 [B, 3, S, S] with a 16-byte base, got shape "
-                           f"{tuple(x.shape)}, strides {tuple(x.stride())}")
-    if S < STRONG_MIN_SIDE or S > AUG_MAX_SIDE or S % 4:
-        raise ValueError(f"lc2is_amd.strong_apply: the size {S} must be a multiple of 4 in {STRONG_MIN_SIDE}..{AUG_MAX_SIDE}")
-    if B > 65535:
-        raise ValueError(f"lc2is_amd.strong_apply: at most 65535 samples per call, got {B}")
-    if out is None:
-        out = torch.empty_like(x)
-    _chk(out, torch.float32, "out", 4)
-    if out.shape != x.shape or not out.is_contiguous() or out.data_ptr() % 16:
-        raise RuntimeError(f"lc2is_amd.strong_apply: out must be contiguous fp32 [{B}, 3, {S}, {S}] with a 16-byte base")
-    if _overlap(out, x):
-        raise RuntimeError("lc2is_amd.strong_apply: out may not overlap the input (the blur reads a halo: no in-place form)")
+    B, S = _view_pixels("strong_apply", x, "pixel_values")
+    _view_side("strong_apply", B, S, None, STRONG_MIN_SIDE)
+    out = _view_out("strong_apply", out, "out", x.shape, torch.float32, x.device, 16, (x,), "may not overlap the input (the blur reads a halo: no in-place form)")
     return B, S, out
 
 
@@ -2684,10 +2678,8 @@ def strong_apply(x: torch.Tensor, params: torch.Tensor, cfg: StrongConfig, *, ou
     a row with no flag gives the input bit for bit.  S % 4 == 0, 12 <= S <= 4096.  x must be contiguous with a 16-byte base (a batch
     slice x[i:j] is; a strided or permuted view is refused, not copied); out: a tensor to write into, which may not overlap x (the
     blur reads a halo)."""
-    _chk(params, torch.int32, "params")
     B, S, out = _strong_batch(x, out)
-    if tuple(params.shape) != (B, STRONG_PARAM_WORDS) or not params.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.strong_apply: params must be contiguous int32 [{B}, {STRONG_PARAM_WORDS}]")
+    _view_table("strong_apply", params, "params", B, STRONG_PARAM_WORDS)
     rc = _fn("lc2is_strong_apply")(_ptr(x), _ptr(params), C.addressof(cfg), B, S, _ptr(out), _stream())
     _lib.check(rc, f"strong_apply B={B} S={S}")
     return out
@@ -2700,6 +2692,7 @@ GEO_WARP, GEO_FLIP = 1, 2
 GEO_ONE, GEO_MAX_M, GEO_MAX_T, GEO_MIN_SIDE = 65536, 524288, 65536, 8
 GEO_MAX_ROTATE, GEO_MAX_SHEAR = C.c_float(math.pi).value, C.c_float(math.pi / 4).value      # the fp32 neighbours of pi, pi / 4
 GEO_MIN_SCALE, GEO_MAX_SCALE, GEO_MAX_TRANSLATE = 0.25, 4.0, 0.5
+_GATHERS = "may not overlap its input (a warp gathers: no in-place form)"
 
 
 class GeoConfig(C.Structure):
@@ -2725,16 +2718,9 @@ def geo_params(keys: torch.Tensor, epoch: torch.Tensor, cfg: GeoConfig, *, out: 
     source matrix m00 m01 m10 m11 and the translation tx ty in Q16, the fp32 bit patterns of theta, s, phi, fx, fy as drawn; the
     rest 0.  keys int64 [B]: the indices the random numbers are a function of; epoch: DEVICE int32 scalar.  Nothing but device
     memory decides the result: a captured call draws again on replay."""
-    _chk(keys, torch.int64, "keys", 1); _chk(epoch, torch.int32, "epoch", None)
-    B = keys.numel()
-    if B < 1 or epoch.numel() != 1:
-        raise RuntimeError("lc2is_amd.geo_params: epoch must hold one int32 and keys at least one int64")
+    B = _view_keys("geo_params", keys, epoch)
     _geo_config(cfg, "geo_params")
-    if out is None:
-        out = torch.empty((B, GEO_PARAM_WORDS), dtype=torch.int32, device=keys.device)
-    _chk(out, torch.int32, "out")
-    if tuple(out.shape) != (B, GEO_PARAM_WORDS) or not out.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.geo_params: out must be contiguous int32 [{B}, {GEO_PARAM_WORDS}]")
+    out = _view_table("geo_params", out, "out", B, GEO_PARAM_WORDS, new_on=keys.device)
     rc = _fn("lc2is_geo_params")(_ptr(keys), B, _ptr(epoch), C.addressof(cfg), _ptr(out), _stream())
     _lib.check(rc, f"geo_params B={B}")
     return out
@@ -2749,40 +2735,19 @@ def _geo_batch(batch, out):
     if px is None:
         raise RuntimeError("lc2is_amd.geo_apply: pixel_values are required")
     _chk(px, torch.float32, "pixel_values", 4); _chk(lab, torch.int64, "labels", 3); _chk(pw, torch.float32, "pixel_weight", 3)
-    B, S = px.shape[0], px.shape[2]
-    if B < 1 or tuple(px.shape) != (B, 3, S, S) or not px.is_contiguous() or px.data_ptr() % 16:
-        raise RuntimeError(f"lc2is_amd.geo_apply: pixel_values must be contiguous fp32 [B, 3, S, S] with a 16-byte base, got shape "
-                           f"{tuple(px.shape)}, strides {tuple(px.stride())}")
-    maps = [m for m in (lab, pw) if m is not None]
-    L = maps[0].shape[1] if maps else S
-    for m, name, align in ((lab, "labels", 8), (pw, "pixel_weight", 4)):
-        if m is not None and (tuple(m.shape) != (B, L, L) or not m.is_contiguous() or m.data_ptr() % align or m.device != px.device):
-            raise RuntimeError(f"lc2is_amd.geo_apply: {name} must be contiguous [{B}, L, L] on the pixels' device, labels and weights "
-                               f"of one L, got shape {tuple(m.shape)}, strides {tuple(m.stride())}")
-    if S < GEO_MIN_SIDE or S > AUG_MAX_SIDE or S % 4 or L < 1 or S % L:
-        raise ValueError(f"lc2is_amd.geo_apply: the size {S} must be a multiple of 4 and of the label size {L}, in "
-                         f"{GEO_MIN_SIDE}..{AUG_MAX_SIDE}")
-    if B > 65535:
-        raise ValueError(f"lc2is_amd.geo_apply: at most 65535 samples per call, got {B}")
+    B, S = _view_pixels("geo_apply", px, "pixel_values")
+    L = next((m.shape[1] for m in (lab, pw) if m is not None), S)
+    _view_cells("geo_apply", lab, "labels", torch.int64, B, L, px.device)
+    _view_cells("geo_apply", pw, "pixel_weight", torch.float32, B, L, px.device)
+    _view_side("geo_apply", B, S, L, GEO_MIN_SIDE)
     if out is None:
         out = (None, None, None)
     if not isinstance(out, (tuple, list)) or len(out) != 3:
         raise TypeError("lc2is_amd.geo_apply: out must be (pixel_values, labels or None, pixel_weight or None)")
-    outs = []
-    for o, i, dtype, nd, align, name in ((out[0], px, torch.float32, 4, 16, "out pixel_values"), (out[1], lab, torch.int64, 3, 8, "out labels"),
-                                         (out[2], pw, torch.float32, 3, 4, "out pixel_weight")):
-        if i is None:
-            outs.append(None)
-            continue
-        if o is None:
-            o = torch.empty_like(i)
-        _chk(o, dtype, name, nd)
-        if o.shape != i.shape or not o.is_contiguous() or o.data_ptr() % align or o.device != i.device:
-            raise RuntimeError(f"lc2is_amd.geo_apply: {name} must be contiguous {tuple(i.shape)} with a {align}-byte base on the input's device")
-        if _overlap(o, i):
-            raise RuntimeError(f"lc2is_amd.geo_apply: {name} may not overlap its input (a warp gathers: no in-place form)")
-        outs.append(o)
-    return B, S, L, tuple(outs)
+    outs = tuple(None if i is None else _view_out("geo_apply", o, name, i.shape, i.dtype, i.device, align, (i,), _GATHERS, dev=i.device)
+                 for o, i, align, name in ((out[0], px, 16, "out pixel_values"), (out[1], lab, 8, "out labels"),
+                                           (out[2], pw, 4, "out pixel_weight")))
+    return B, S, L, outs
 
 
 def geo_apply(batch, params: torch.Tensor, cfg: GeoConfig, *, out=None):
@@ -2793,10 +2758,8 @@ def geo_apply(batch, params: torch.Tensor, cfg: GeoConfig, *, out=None):
     strided or permuted view is refused, not copied); out: (pixels, labels, weights) to write into, none of which may overlap its
     input.  Returns (pixels, labels, weights); an entry that was None stays None."""
     B, S, L, (opx, olab, opw) = _geo_batch(batch, out)
-    _chk(params, torch.int32, "params")
     _geo_config(cfg, "geo_apply")
-    if tuple(params.shape) != (B, GEO_PARAM_WORDS) or not params.is_contiguous():
-        raise RuntimeError(f"lc2is_amd.geo_apply: params must be contiguous int32 [{B}, {GEO_PARAM_WORDS}]")
+    _view_table("geo_apply", params, "params", B, GEO_PARAM_WORDS)
     px, lab, pw = batch
     rc = _fn("lc2is_geo_apply")(_ptr(px), _ptr(lab), _ptr(pw), _ptr(params), C.addressof(cfg), B, S, L, _ptr(opx), _ptr(olab),
                                 _ptr(opw), _stream())
@@ -2831,10 +2794,7 @@ def _geo_scores_batch(scores, B, g, teacher_weight, label_size, out):
     L = label_size
     if teacher_weight is not None:
         Lw = teacher_weight.shape[1]
-        if tuple(teacher_weight.shape) != (B, Lw, Lw) or not teacher_weight.is_contiguous() or teacher_weight.data_ptr() % 4 or \
-                teacher_weight.device != scores.device:
-            raise RuntimeError(f"lc2is_amd.geo_scores: teacher_weight must be contiguous fp32 [{B}, L, L] on the scores' device, got shape "
-                               f"{tuple(teacher_weight.shape)}, strides {tuple(teacher_weight.stride())}")
+        _view_cells("geo_scores", teacher_weight, "teacher_weight", torch.float32, B, Lw, scores.device)
         if L is not None and L != Lw:
             raise ValueError(f"lc2is_amd.geo_scores: label_size {L} is not the teacher_weight's {Lw}")
         L = Lw
@@ -2842,21 +2802,10 @@ def _geo_scores_batch(scores, B, g, teacher_weight, label_size, out):
         raise ValueError(f"lc2is_amd.geo_scores: the label size {L} must be a multiple of g = {g} in 1..{AUG_MAX_SIDE}")
     if L is None and out[1] is not None:
         raise ValueError("lc2is_amd.geo_scores: an out weight without teacher_weight or label_size: no weight map is made")
-    outs = []
-    for o, shape, like, align, name in ((out[0], tuple(scores.shape), scores, 16, "out scores"),
-                                        (out[1], None if L is None else (B, L, L), teacher_weight, 4, "out weight")):
-        if shape is None:
-            outs.append(None)
-            continue
-        if o is None:
-            o = torch.empty(shape, dtype=torch.float32, device=scores.device)
-        _chk(o, torch.float32, name, len(shape))
-        if tuple(o.shape) != shape or not o.is_contiguous() or o.data_ptr() % align or o.device != scores.device:
-            raise RuntimeError(f"lc2is_amd.geo_scores: {name} must be contiguous fp32 {shape} with a {align}-byte base on the scores' device")
-        if _overlap(o, like):
-            raise RuntimeError(f"lc2is_amd.geo_scores: {name} may not overlap its input (a warp gathers: no in-place form)")
-        outs.append(o)
-    return ld, L, tuple(outs)
+    osc = _view_out("geo_scores", out[0], "out scores", scores.shape, torch.float32, scores.device, 16, (scores,), _GATHERS, dev=scores.device)
+    otw = None if L is None else _view_out("geo_scores", out[1], "out weight", (B, L, L), torch.float32, scores.device, 4,
+                                           (teacher_weight,), _GATHERS, dev=scores.device)
+    return ld, L, (osc, otw)
 
 
 def geo_scores(scores: torch.Tensor, params: torch.Tensor, B: int, g: int, *, teacher_weight: torch.Tensor | None = None,
@@ -2869,9 +2818,7 @@ def geo_scores(scores: torch.Tensor, params: torch.Tensor, B: int, g: int, *, te
     g <= 512, ld % 4 == 0 in 4..1024, L % g == 0.  Tensors must be contiguous (refused, not copied); out: (scores, weight) to write
     into, neither of which may overlap its input.  Returns (scores', weight' or None)."""
     ld, L, (osc, otw) = _geo_scores_batch(scores, B, g, teacher_weight, label_size, out)
-    _chk(params, torch.int32, "params")
-    if tuple(params.shape) != (B, GEO_PARAM_WORDS) or not params.is_contiguous() or params.device != scores.device:
-        raise RuntimeError(f"lc2is_amd.geo_scores: params must be contiguous int32 [{B}, {GEO_PARAM_WORDS}] on the scores' device")
+    _view_table("geo_scores", params, "params", B, GEO_PARAM_WORDS, dev=scores.device)
     rc = _fn("lc2is_geo_scores")(_ptr(scores), _ptr(teacher_weight), _ptr(params), B, g, ld, L or 0, int(L is not None), _ptr(osc),
                                  _ptr(otw), _stream())
     _lib.check(rc, f"geo_scores B={B} g={g} ld={ld} L={L}")
