@@ -16,26 +16,11 @@ from .. import ops
 from .base import require_cuda
 
 
-class _CEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, ignore_index):
-        lg = logits.float().contiguous()
-        lb = labels.contiguous()
-        loss2, lse = ops.ce_nchw_fwd(lg, lb, ignore_index)
-        ctx.saved = (lg, lb, lse, loss2, ignore_index)
-        return loss2[0] / loss2[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        lg, lb, lse, loss2, ignore_index = ctx.saved
-        scale = (g / loss2[1]).reshape(1).float().contiguous()  # device scalar: upstream grad / counted pixels
-        return ops.ce_nchw_bwd(lg, lb, lse, scale, 1.0, ignore_index), None, None
-
-
 class _PixelLossFn(torch.autograd.Function):
     """A per-pixel criterion on NCHW logits with 'mean' / 'sum' / 'none': ``fwd`` / ``bwd`` are its pair of ops, ``kw`` their
     keywords.  ``has_lse``: ``fwd`` returns (loss2, lse[, per-pixel]) and ``bwd`` takes the lse after the labels (the softmax
-    losses); otherwise loss2 or (loss2, per-pixel) and no lse (the sigmoid losses).  The default cross-entropy stays on _CEFn."""
+    losses); otherwise loss2 or (loss2, per-pixel) and no lse (the sigmoid losses).  The default cross-entropy goes through here
+    too: with no weight and no smoothing the C side launches the plain kernels."""
 
     @staticmethod
     def forward(ctx, logits, labels, ignore_index, reduction, fwd, bwd, has_lse, kw):
@@ -86,8 +71,6 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         self._check_nchw(input, target, "CrossEntropyLoss")
-        if self.weight is None and self.label_smoothing == 0.0 and self.reduction == "mean":
-            return _CEFn.apply(input, target, self.ignore_index)
         return _PixelLossFn.apply(input, target, self.ignore_index, self.reduction, ops.ce_nchw_fwd, ops.ce_nchw_bwd, True,
                                   dict(class_weight=self.weight, label_smoothing=self.label_smoothing))
 

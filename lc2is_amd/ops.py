@@ -1252,6 +1252,24 @@ def _chk_grad_px(who: str, grad_px, B: int, H: int, W: int) -> None:
             raise RuntimeError(f"lc2is_amd.{who}: grad_px must be contiguous [{B},{H},{W}]")
 
 
+def _chk_nchw_bwd(logits, labels, lse, grad_scale_dev) -> None:
+    """The dtype checks every ``*_nchw_bwd`` opens with (``lse``: None for the sigmoid losses, which save none)."""
+    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
+    _chk(lse, torch.float32, "lse", 3); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+
+
+def _nchw_fwd_alloc(logits, B: int, H: int, W: int, per_pixel: bool, lse: bool = True):
+    """What an ordered ``*_nchw_fwd`` allocates: loss[2] (overwritten: block partials summed in a fixed order), the partials
+    workspace (per call, like head_upsample_ce's slabs) and its byte count, lse [B,H,W] or None, the per-pixel map or None."""
+    dev = logits.device
+    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lse_map = torch.empty((B, H, W), dtype=torch.float32, device=dev) if lse else None
+    lpx = torch.empty((B, H, W), dtype=torch.float32, device=dev) if per_pixel else None
+    return loss, ws, nbytes, lse_map, lpx
+
+
 def _ce_options(class_weight, label_smoothing: float, C: int, dev):
     """Validate F.cross_entropy's weight / label_smoothing for a C-class call; True when either is set."""
     if not 0.0 <= label_smoothing <= 1.0:
@@ -1652,8 +1670,7 @@ def ce_dice_nchw_fwd(logits, labels, ignore_index: int = -100, *, ce_weight: flo
 
 def ce_dice_nchw_bwd(logits, labels, lse, coef, grad_scale_dev, grad_scale: float = 1.0, ignore_index: int = -100):
     """dlogits = grad_scale * grad_scale_dev (device scalar or None) * d loss / d logits, from ``ce_dice_nchw_fwd``'s lse and coef."""
-    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
-    _chk(lse, torch.float32, "lse", 3); _chk(coef, torch.float32, "coef", 1); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    _chk_nchw_bwd(logits, labels, lse, grad_scale_dev); _chk(coef, torch.float32, "coef", 1)
     B, Cc, H, W = _nchw_front("ce_dice_nchw_bwd", logits, labels, bwd=True, lse=(lse,))
     if not 1 <= Cc <= DICE_CMAX or coef.numel() != 2 * ((Cc + 3) // 4 * 4) + 4:
         raise RuntimeError(f"lc2is_amd.ce_dice_nchw_bwd: coef must be ce_dice_nchw_fwd's block for C={Cc} (C <= {DICE_CMAX})")
@@ -1704,13 +1721,8 @@ def focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=Non
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     gamma, poly_eps = focal_options(gamma, poly_eps)
     B, Cc, H, W = _nchw_front("focal_nchw_fwd", logits, labels)
-    dev = logits.device
-    _focal_weight(class_weight, Cc, dev)
-    lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    loss = torch.empty(2, dtype=torch.float32, device=dev)   # overwritten: block partials summed in a fixed order
-    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    lpx = torch.empty((B, H, W), dtype=torch.float32, device=dev) if per_pixel else None
+    _focal_weight(class_weight, Cc, logits.device)
+    loss, ws, nbytes, lse, lpx = _nchw_fwd_alloc(logits, B, H, W, per_pixel)
     _lib.check(_fn("lc2is_focal_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W, ignore_index,
                                            _ptr(class_weight), gamma, poly_eps, _ptr(ws), nbytes, _stream()), "focal_nchw_fwd")
     return (loss, lse, lpx) if per_pixel else (loss, lse)
@@ -1720,8 +1732,7 @@ def focal_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float = 1.0,
                    gamma: float = 2.0, poly_eps: float = 0.0, grad_px=None):
     """dlogits = grad_scale * grad_scale_dev (device scalar or None) * grad_px (per pixel, [B,H,W] fp32, optional) * dl_i/dlogits,
     from ``focal_nchw_fwd``'s lse."""
-    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
-    _chk(lse, torch.float32, "lse", 3); _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    _chk_nchw_bwd(logits, labels, lse, grad_scale_dev)
     gamma, poly_eps = focal_options(gamma, poly_eps)
     B, Cc, H, W = _nchw_front("focal_nchw_bwd", logits, labels, bwd=True, lse=(lse,))
     _focal_weight(class_weight, Cc, logits.device)
@@ -1786,12 +1797,8 @@ def sigmoid_focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_we
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
     gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
     B, Cc, H, W = _nchw_front("sigmoid_focal_nchw_fwd", logits, labels)
-    dev = logits.device
-    _focal_weight(class_weight, Cc, dev)
-    loss = torch.empty(2, dtype=torch.float32, device=dev)   # overwritten: block partials summed in a fixed order
-    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    lpx = torch.empty((B, H, W), dtype=torch.float32, device=dev) if per_pixel else None
+    _focal_weight(class_weight, Cc, logits.device)
+    loss, ws, nbytes, _, lpx = _nchw_fwd_alloc(logits, B, H, W, per_pixel, lse=False)
     _lib.check(_fn("lc2is_sigmoid_focal_nchw_fwd")(_ptr(logits), _ptr(labels), _ptr(loss), _ptr(lpx), B, Cc, H * W, ignore_index,
                                                    _ptr(class_weight), gamma, alpha, class_scale, _ptr(ws), nbytes, _stream()),
                "sigmoid_focal_nchw_fwd")
@@ -1801,8 +1808,7 @@ def sigmoid_focal_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_we
 def sigmoid_focal_nchw_bwd(logits, labels, grad_scale_dev, grad_scale: float = 1.0, ignore_index: int = -100, *, class_weight=None,
                            gamma: float = 2.0, alpha=0.25, class_scale: float = 1.0, grad_px=None):
     """dlogits = grad_scale * grad_scale_dev (device scalar or None) * grad_px (per pixel, [B,H,W] fp32, optional) * dl_i/dlogits."""
-    _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
-    _chk(grad_scale_dev, torch.float32, "grad_scale_dev", 1)
+    _chk_nchw_bwd(logits, labels, None, grad_scale_dev)
     gamma, alpha, class_scale = _sigmoid_args(gamma, alpha, class_scale)
     B, Cc, H, W = _nchw_front("sigmoid_focal_nchw_bwd", logits, labels, bwd=True)
     _focal_weight(class_weight, Cc, logits.device)
@@ -1819,15 +1825,9 @@ def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, 
     """Returns (loss_sum[2], lse [B,H,W]) — loss_sum = (sum of per-pixel losses, sum of w_y over the counted pixels) — and,
     with per_pixel=True, a third tensor: the per-pixel losses [B,H,W] (reduction="none"; 0 where not counted)."""
     _chk(logits, torch.float32, "logits", 4); _chk(labels, torch.int64, "labels", 3)
-    if not logits.is_contiguous() or not labels.is_contiguous():
-        raise RuntimeError("lc2is_amd.ce_nchw_fwd: logits/labels must be contiguous")
-    B, Cc, H, W = logits.shape
+    B, Cc, H, W = _nchw_front("ce_nchw_fwd", logits, labels)
     _ce_options(class_weight, label_smoothing, Cc, logits.device)   # (validation; the C side picks the kernel variant)
-    lse = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
-    loss = torch.empty(2, dtype=torch.float32, device=logits.device)   # overwritten: block partials summed in a fixed order
-    nbytes = _fn("lc2is_ce_nchw_fwd_workspace_bytes")(B, H * W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)   # (per call, like head_upsample_ce's slabs)
-    lpx = torch.empty((B, H, W), dtype=torch.float32, device=logits.device) if per_pixel else None
+    loss, ws, nbytes, lse, lpx = _nchw_fwd_alloc(logits, B, H, W, per_pixel)
     _lib.check(_fn("lc2is_ce_nchw_fwd_ordered")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(loss), _ptr(lpx), B, Cc, H * W,
                                                 ignore_index, _ptr(class_weight), label_smoothing, _ptr(ws), nbytes,
                                                 _stream()), "ce_nchw_fwd")
@@ -1836,15 +1836,13 @@ def ce_nchw_fwd(logits, labels, ignore_index: int = -100, *, class_weight=None, 
 
 def ce_nchw_bwd(logits, labels, lse, grad_scale_dev, grad_scale: float, ignore_index: int = -100, *, class_weight=None,
                 label_smoothing: float = 0.0, grad_px=None):
-    """dlogits = grad_scale * grad_scale_dev * grad_px (per pixel, [B,H,W] fp32, optional) * dloss_i/dlogits."""
-    B, Cc, H, W = logits.shape
-    opts = _ce_options(class_weight, label_smoothing, Cc, logits.device)
-    d = torch.empty_like(logits)
-    if not (opts or grad_px is not None):
-        _lib.check(_fn("lc2is_ce_nchw_bwd")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
-                                            _ptr(d), B, Cc, H * W, ignore_index, _stream()), "ce_nchw_bwd")
-        return d
+    """dlogits = grad_scale * grad_scale_dev * grad_px (per pixel, [B,H,W] fp32, optional) * dloss_i/dlogits, from
+    ``ce_nchw_fwd``'s lse.  With every option unset the C side launches the plain kernel."""
+    _chk_nchw_bwd(logits, labels, lse, grad_scale_dev)
+    B, Cc, H, W = _nchw_front("ce_nchw_bwd", logits, labels, bwd=True, lse=(lse,))
+    _ce_options(class_weight, label_smoothing, Cc, logits.device)
     _chk_grad_px("ce_nchw_bwd", grad_px, B, H, W)
+    d = torch.empty_like(logits)
     _lib.check(_fn("lc2is_ce_nchw_bwd_opts")(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(grad_scale_dev), grad_scale,
                                              _ptr(grad_px), _ptr(d), B, Cc, H * W, ignore_index, _ptr(class_weight),
                                              label_smoothing, _stream()), "ce_nchw_bwd")

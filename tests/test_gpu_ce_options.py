@@ -90,24 +90,26 @@ def test_head_upsample_ce_options_refused_on_the_atomic_path(dev):
         ops.head_upsample_ce(lo, labels, B, h, h, C, 4, ops.INTERP_BILINEAR, class_weight=torch.ones(C + 1, device=dev))
 
 
-@pytest.mark.parametrize("weighted,eps", [(True, 0.0), (False, 0.2), (True, 0.2)])
-def test_ce_nchw_options_vs_torch(dev, weighted, eps):
+def _ce_nchw_vs_torch(dev, shape, weighted, eps, over=0, count_tol=1e-5):
+    """ops.ce_nchw_fwd / ce_nchw_bwd at one shape.  Labels are drawn from [0, C + over): those >= C are not counted (the reference
+    ignores them)."""
     from lc2is_amd import ops
-    B, C, H, W = 2, 151, 24, 20
+    B, C, H, W = shape
     g = torch.Generator().manual_seed(3)
     x = torch.randn(B, C, H, W, generator=g) * 2
-    labels = torch.randint(0, C, (B, H, W), generator=g)
-    labels[:, ::4] = IGN
+    dev_labels = torch.randint(0, C + over, (B, H, W), generator=g)
+    dev_labels[:, ::4] = IGN
+    labels = torch.where(dev_labels < C, dev_labels, torch.full_like(dev_labels, IGN))
     w64 = _weights(C, 2) if weighted else None
     kw = dict(class_weight=None if w64 is None else w64.float().to(dev), label_smoothing=eps)
-    xd, ld = x.to(dev), labels.to(dev)
+    xd, ld = x.to(dev), dev_labels.to(dev)
     loss2, lse, lpx = ops.ce_nchw_fwd(xd, ld, IGN, per_pixel=True, **kw)
     x64 = x.double().requires_grad_(True)
     ref = F.cross_entropy(x64, labels, weight=w64, label_smoothing=eps, reduction="none")
     assert _rel(lpx, ref.detach()) <= 1e-5
     assert abs(loss2[0].item() - ref.sum().item()) <= 1e-5 * abs(ref.sum().item())
     wsum = (w64[labels[labels != IGN]].sum() if weighted else (labels != IGN).sum()).item()
-    assert abs(loss2[1].item() - wsum) <= 1e-5 * wsum
+    assert abs(loss2[1].item() - wsum) <= count_tol * wsum
     gpx = torch.rand(B, H, W, generator=g, dtype=torch.float64) + 0.5   # non-uniform upstream gradient
     ref.backward(gpx)
     d = ops.ce_nchw_bwd(xd, ld, lse, None, 1.0, IGN, grad_px=gpx.float().to(dev), **kw)
@@ -117,6 +119,49 @@ def test_ce_nchw_options_vs_torch(dev, weighted, eps):
     F.cross_entropy(x64, labels, weight=w64, label_smoothing=eps, reduction="sum").backward(torch.tensor(0.5, dtype=torch.float64))
     d2 = ops.ce_nchw_bwd(xd, ld, lse, torch.full((1,), 0.25, device=dev), 2.0, IGN, **kw)
     assert _rel(d2, x64.grad) <= 1e-5
+
+
+@pytest.mark.parametrize("weighted,eps", [(True, 0.0), (False, 0.2), (True, 0.2)])
+def test_ce_nchw_options_vs_torch(dev, weighted, eps):
+    _ce_nchw_vs_torch(dev, (2, 151, 24, 20), weighted, eps)
+
+
+@pytest.mark.parametrize("weighted,eps", [(False, 0.0), (True, 0.2)], ids=["plain", "opts"])
+def test_ce_nchw_past_the_grid_cap(dev, weighted, eps):
+    """2 099 601 pixels: more than 8192 blocks of 256, and no multiple of 256 or 64 — the strided walk of the forward and of the
+    backward, both kernel variants.  The sums to the bounds of test_ce_nchw_fwd_sums_are_ordered (1e-5 / 1e-6 relative)."""
+    _ce_nchw_vs_torch(dev, (1, 2, 1449, 1449), weighted, eps, over=2, count_tol=1e-6)
+
+
+@pytest.mark.parametrize("weighted,eps", [(False, 0.0), (True, 0.2)], ids=["plain", "opts"])
+def test_ce_nchw_one_class(dev, weighted, eps):
+    """C = 1: the softmax is 1, so every loss and every gradient is 0 in exact arithmetic and a relative error has no meaning.  In
+    fp32 the terms that cancel (w lse against w z; (1 - eps) w + eps w against itself) are each rounded, so the bound is the 1e-5 of
+    the NCHW tests relative to the size of those terms: w |z| for a loss, w g for a gradient.  lse and the count as usual."""
+    from lc2is_amd import ops
+    B, C, H, W = 1, 1, 5, 7
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(B, C, H, W, generator=g) * 2
+    labels = torch.randint(0, C + 2, (B, H, W), generator=g)
+    labels[:, ::4] = IGN
+    valid = labels == 0
+    w64 = _weights(C, 2) if weighted else torch.ones(1, dtype=torch.float64)
+    kw = dict(class_weight=w64.float().to(dev) if weighted else None, label_smoothing=eps)
+    xd, ld = x.to(dev), labels.to(dev)
+    loss2, lse, lpx = ops.ce_nchw_fwd(xd, ld, IGN, per_pixel=True, **kw)
+    assert _rel(lse, x[:, 0]) <= 1e-5
+    assert abs(loss2[1].item() - w64[0].item() * int(valid.sum())) <= 1e-5 * w64[0].item() * int(valid.sum())
+    size = (w64[0] * x[:, 0].double().abs()) * valid
+    ref_labels = torch.where(valid, labels, torch.full_like(labels, IGN))
+    ref = F.cross_entropy(x.double(), ref_labels, weight=w64 if weighted else None, label_smoothing=eps, reduction="none")
+    assert _rel(lse, torch.logsumexp(x.double(), 1)) <= 1e-5                   # fp64 torch is finite here: lse = z, losses ~ 0
+    assert (lpx.double().cpu() - ref).abs().max().item() <= 1e-5 * size.max().item()
+    assert lpx.double().abs().max().item() <= 1e-5 * size.max().item() and not lpx.cpu()[~valid].any()
+    assert abs(loss2[0].item()) <= 1e-5 * size.sum().item()
+    gpx = torch.rand(B, H, W, generator=g) + 0.5
+    for d, gmax in ((ops.ce_nchw_bwd(xd, ld, lse, None, 1.0, IGN, grad_px=gpx.to(dev), **kw), gpx.max().item()),
+                    (ops.ce_nchw_bwd(xd, ld, lse, torch.full((1,), 0.25, device=dev), 2.0, IGN, **kw), 0.5)):
+        assert d.abs().max().item() <= 1e-5 * w64[0].item() * gmax and not d.cpu()[:, 0][~valid].any()
 
 
 @pytest.mark.parametrize("reduction", ["mean", "sum", "none"])

@@ -175,9 +175,29 @@ def test_dice_weight_zero_is_the_mean_ce_head(dev, mode, S, C, h, w):
 @pytest.mark.parametrize("cw,dw", WEIGHTS)
 @pytest.mark.parametrize("C", [10, 151])
 def test_dice_cross_entropy_module_on_nchw_logits(dev, C, cw, dw, present_only, smooth):
+    _dice_nchw_vs_fp64(dev, (2, C, 20, 28), cw, dw, present_only, smooth)
+
+
+@pytest.mark.parametrize("present_only,smooth", [(True, 1.0), (False, 0.0)])
+@pytest.mark.parametrize("C", [5, 192])
+def test_dice_nchw_edge_class_counts(dev, C, present_only, smooth):
+    """C = 5: the rows of the statistics slab and of the coefficient block are padded to cq = 8; C = 192: the class limit."""
+    _dice_nchw_vs_fp64(dev, (1, C, 9, 7), 1.0, 3.0, present_only, smooth)
+
+
+def test_dice_nchw_past_the_grid_cap(dev):
+    """525 625 pixels: more than the 2048 blocks of the statistics pass, and no multiple of 256 or 64 — its block-uniform strided
+    loop, the coefficient pass over 2048 slabs, and the backward's walk.  The CE mean (the loss sum over the exact count) also to the
+    1e-5 of test_ce_nchw_fwd_sums_are_ordered at this size."""
+    loss4, out = _dice_nchw_vs_fp64(dev, (1, 3, 725, 725), 1.0, 3.0, False, 1.0, ld=3)
+    assert abs(loss4[1].item() - out["ce"].item()) <= 1e-5 * abs(out["ce"].item())
+
+
+def _dice_nchw_vs_fp64(dev, shape, cw, dw, present_only, smooth, ld=192):
+    """``ld``: the width the gradient is padded to for _check (192 as the head's; C where the map is large)."""
     import lc2is_amd.nn as N
     from lc2is_amd import ops
-    B, H, W = 2, 20, 28
+    B, C, H, W = shape
     g = torch.Generator().manual_seed(C)
     x = torch.randn(B, C, H, W, generator=g) * 2
     labels = torch.randint(0, C + 3, (B, H, W), generator=g)
@@ -193,7 +213,7 @@ def test_dice_cross_entropy_module_on_nchw_logits(dev, C, cw, dw, present_only, 
     assert torch.equal(loss.detach(), loss4[0])
     stats = torch.zeros(3, 192, device=dev)
     stats[:, :C] = torch.stack([I, P, T])
-    pad = torch.zeros(B * H * W, 192, device=dev)
+    pad = torch.zeros(B * H * W, ld, device=dev)
     pad[:, :C] = xd.grad.permute(0, 2, 3, 1).reshape(-1, C) / 1.5
     _check(loss4, stats, pad, out, grad.permute(0, 2, 3, 1).reshape(-1, C), C, f"nchw C={C} cw={cw} dw={dw} po={present_only} s={smooth}")
     # the launchers directly: host scalar times device scalar
@@ -207,6 +227,7 @@ def test_dice_cross_entropy_module_on_nchw_logits(dev, C, cw, dw, present_only, 
     l0 = crit(x0, none)
     l0.backward()
     assert l0.item() == 0.0 and crit.last_stats[3].tolist() == [0.0, 0.0, 0.0, 0.0] and not x0.grad.any()
+    return loss4, out
 
 
 def _tiny(dev):

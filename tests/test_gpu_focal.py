@@ -125,11 +125,12 @@ def test_bitwise_reproducible(dev, mode, S):
 
 
 # ---- 5. the NCHW kernels and the module ----
-def _nchw_case():
-    B, C, H, W = 2, 151, 24, 20
+def _nchw_case(shape=(2, 151, 24, 20), over=0):
+    """Labels from [0, C + over): those >= C are not counted."""
+    B, C, H, W = shape
     g = torch.Generator().manual_seed(3)
     x = torch.randn(B, C, H, W, generator=g) * 2
-    labels = torch.randint(0, C, (B, H, W), generator=g)
+    labels = torch.randint(0, C + over, (B, H, W), generator=g)
     labels[:, ::4] = IGN
     gpx = torch.rand(B, H, W, generator=g, dtype=torch.float64) + 0.5   # non-uniform upstream gradient
     return x, labels, gpx
@@ -137,9 +138,38 @@ def _nchw_case():
 
 @pytest.mark.parametrize("gamma,eps", R.PARAMS)
 def test_focal_nchw_kernels_vs_fp64(dev, gamma, eps):
+    _focal_nchw_vs_fp64(dev, _nchw_case(), gamma, eps)
+
+
+def test_focal_nchw_past_the_grid_cap(dev):
+    """2 099 601 pixels: more than 8192 blocks of 256, and no multiple of 256 or 64 — the strided walk of the forward and of the
+    backward.  The count to the 1e-6 of test_ce_nchw_fwd_sums_are_ordered at this size."""
+    _focal_nchw_vs_fp64(dev, _nchw_case((1, 2, 1449, 1449), over=2), 1.5, 2, wsum_tol=1e-6)
+
+
+@pytest.mark.parametrize("gamma,eps", [(2, 0), (0, 1)])
+def test_focal_nchw_one_class(dev, gamma, eps):
+    """C = 1: p = 1 and q = 0, so every loss and every gradient is 0 in exact arithmetic and a relative error has no meaning (the
+    fp64 reference forms 0 * inf).  The bound is the 1e-5 of the NCHW tests relative to the size of the factors: w for a loss, w g
+    for a gradient.  lse and the weighted count as usual."""
     from lc2is_amd import ops
-    x, labels, gpx = _nchw_case()
-    w64 = R.weights(151, 2)
+    x, labels, gpx = _nchw_case((1, 1, 5, 7), over=2)
+    valid = labels == 0
+    w = R.weights(1, 2)[0].item()
+    kw = dict(class_weight=R.weights(1, 2).float().to(dev), gamma=gamma, poly_eps=eps)
+    xd, ld = x.to(dev), labels.to(dev)
+    loss2, lse, lpx = ops.focal_nchw_fwd(xd, ld, IGN, per_pixel=True, **kw)
+    assert _rel(lse, x[:, 0]) <= 1e-5 and abs(loss2[1].item() - w * int(valid.sum())) <= 1e-5 * w * int(valid.sum())
+    assert lpx.abs().max().item() <= 1e-5 * w and abs(loss2[0].item()) <= 1e-5 * w * int(valid.sum())
+    for d, gmax in ((ops.focal_nchw_bwd(xd, ld, lse, None, 1.0, IGN, grad_px=gpx.float().to(dev), **kw), gpx.max().item()),
+                    (ops.focal_nchw_bwd(xd, ld, lse, torch.full((1,), 0.25, device=dev), 2.0, IGN, **kw), 0.5)):
+        assert d.abs().max().item() <= 1e-5 * w * gmax and not d.cpu()[:, 0][~valid].any()
+
+
+def _focal_nchw_vs_fp64(dev, case, gamma, eps, wsum_tol=1e-5):
+    from lc2is_amd import ops
+    x, labels, gpx = case
+    w64 = R.weights(x.shape[1], 2)
     kw = dict(class_weight=w64.float().to(dev), gamma=gamma, poly_eps=eps)
     xd, ld = x.to(dev), labels.to(dev)
     loss2, lse, lpx = ops.focal_nchw_fwd(xd, ld, IGN, per_pixel=True, **kw)
@@ -156,7 +186,7 @@ def test_focal_nchw_kernels_vs_fp64(dev, gamma, eps):
     d2 = ops.focal_nchw_bwd(xd, ld, lse, torch.full((1,), 0.25, device=dev), 2.0, IGN, **kw)   # device scalar times host scalar
     fig["grad_scalar"] = _rel(d2, x64.grad)
     print("focal figures nchw", (gamma, eps), fig)
-    assert all(v <= 1e-5 for v in fig.values()), fig
+    assert all(v <= 1e-5 for v in fig.values()) and fig["wsum"] <= wsum_tol, fig
     loss2b, _ = ops.focal_nchw_fwd(xd, ld, IGN, **kw)
     assert torch.equal(loss2b, loss2)
 

@@ -240,6 +240,33 @@ def test_swin_attn_refuses(dev, no_launch):
            outputs=("dbias", "dqkv"), defines=("qkv",))
 
 
+def test_ce_nchw_refuses(dev, no_launch):
+    """ops.ce_nchw_fwd / ce_nchw_bwd index labels, lse and grad_px by B, H, W of the logits alone: a tensor that is short is read
+    out of bounds.  Each bad operand is refused before any launch (the well-formed call reaches the launcher)."""
+    ops = no_launch
+    B, C, H, W = 1, 3, 4, 5
+    z = torch.zeros(B, C, H, W, device=dev)
+    lab = torch.zeros(B, H, W, dtype=torch.int64, device=dev)
+    lse = torch.zeros(B, H, W, device=dev)
+    short = torch.zeros(B, H, W - 1, device=dev)
+    strided = torch.zeros(B, H, 2 * W, device=dev)[..., :W]          # the right shape, rows 2 W apart
+    fwd_bad = dict(labels_short=(z, lab[..., :W - 1].contiguous()), labels_int32=(z, lab.int()),
+                   logits_not_contiguous=(torch.zeros(B, C, H, 2 * W, device=dev)[..., :W], lab))
+    for what, (logits, labels) in fwd_bad.items():
+        with pytest.raises(RuntimeError, match=r"lc2is_amd"):
+            ops.ce_nchw_fwd(logits, labels)
+    bwd_bad = dict(labels_short=dict(labels=lab[..., :W - 1].contiguous()), lse_short=dict(lse=short),
+                   lse_not_contiguous=dict(lse=strided), grad_px_short=dict(grad_px=short))
+    for what, swap in bwd_bad.items():
+        a = {**dict(labels=lab, lse=lse, grad_px=None), **swap}
+        with pytest.raises(RuntimeError, match=r"lc2is_amd"):
+            ops.ce_nchw_bwd(z, a["labels"], a["lse"], None, 1.0, grad_px=a["grad_px"])
+    with pytest.raises(AssertionError, match="about to be launched"):
+        ops.ce_nchw_fwd(z, lab)
+    with pytest.raises(AssertionError, match="about to be launched"):
+        ops.ce_nchw_bwd(z, lab, lse, None, 1.0, grad_px=lse)
+
+
 def test_module_shaped_calls_are_not_refused(dev):
     """What nn/hier.py, nn/ftn.py, nn/decoder.py and nn/swin.py pass — column slices of packed buffers, outputs inside padded ones —
     goes through the real entry points."""

@@ -137,11 +137,12 @@ def test_bitwise_reproducible(dev, mode, S):
 
 
 # ---- 5. the NCHW kernels and the modules ----
-def _nchw_case():
-    B, C, H, W = 2, 151, 24, 20
+def _nchw_case(shape=(2, 151, 24, 20), over=0):
+    """Labels from [0, C + over): those >= C are not counted."""
+    B, C, H, W = shape
     g = torch.Generator().manual_seed(3)
     x = torch.randn(B, C, H, W, generator=g) * 2
-    labels = torch.randint(0, C, (B, H, W), generator=g)
+    labels = torch.randint(0, C + over, (B, H, W), generator=g)
     labels[:, ::4] = IGN
     gpx = torch.rand(B, H, W, generator=g, dtype=torch.float64) + 0.5   # non-uniform upstream gradient
     return x, labels, gpx
@@ -149,9 +150,21 @@ def _nchw_case():
 
 @pytest.mark.parametrize("gamma,alpha", R.PARAMS)
 def test_sigmoid_focal_nchw_kernels_vs_fp64(dev, gamma, alpha):
+    _sigmoid_nchw_vs_fp64(dev, _nchw_case(), gamma, alpha)
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 1449, 1449), (1, 1, 5, 7)], ids=["grid_capped", "one_class"])
+@pytest.mark.parametrize("gamma,alpha", [(2, 0.25), (0, None)])
+def test_sigmoid_focal_nchw_edge_shapes(dev, shape, gamma, alpha):
+    """2 099 601 pixels — more than 8192 blocks of 256, and no multiple of 256 or 64: the strided walk of the forward and of the
+    backward — and C = 1; both element variants (gamma != 0 / == 0).  The count is exact, as at every shape."""
+    _sigmoid_nchw_vs_fp64(dev, _nchw_case(shape, over=2), gamma, alpha)
+
+
+def _sigmoid_nchw_vs_fp64(dev, case, gamma, alpha):
     from lc2is_amd import ops
-    x, labels, gpx = _nchw_case()
-    w64 = R.weights(151, 2)
+    x, labels, gpx = case
+    w64 = R.weights(x.shape[1], 2)
     cs = 0.5
     kw = dict(class_weight=w64.float().to(dev), gamma=gamma, alpha=alpha, class_scale=cs)
     xd, ld = x.to(dev), labels.to(dev)

@@ -7,6 +7,8 @@
   python tools/head_path_digest.py --root TREE              (one HIP device)
       runs the model site, the tail site, TrainStep and the NCHW criteria for fixed seeds and prints a sha256 of the raw bytes of
       each loss, gradient and published statistic (raw bytes: NaN-safe).
+  python tools/head_path_digest.py --root TREE --nchw       (one HIP device)
+      the NCHW criteria alone, at more shapes: one block, ragged blocks, past the grid caps, C = 1, C = 192.
 
 ``--root`` is the tree whose ``lc2is_amd`` is imported (default: the tree this file is in); set LC2IS_LIB to share one built
 library between trees.  ``--out FILE`` writes the lines there; the last line of stdout is always "sha256 <hash> <n> lines".
@@ -184,26 +186,61 @@ def digest(N, torch, emit):
         pub = [getattr(crit, a, None) for a in ("last_labels", "last_info")] + list(getattr(crit, "last_stats", None) or ())
         emit(f"TrainStep {name} | loss={_sha(torch, *losses)} arena={_sha(torch, ts.arena.flat)} published={_sha(torch, *pub)} "
              f"seg_counts={_sha(torch, ts.seg_counts if extra else None)}")
-    g = torch.Generator().manual_seed(19)
-    z = (torch.randn(2, 10, 12, 9, generator=g) * 3).to(dev)
-    lab = _labels(torch, 2, 12, 9, 10, 23).to(dev)
-    w10 = (0.5 + torch.rand(10, generator=g)).to(dev)
-    gpx = torch.randn(2, 12, 9, generator=g).to(dev)
-    for name, make in (("CrossEntropyLoss", lambda r: N.CrossEntropyLoss(reduction=r)),
-                       ("CrossEntropyLoss(weight, smoothing)", lambda r: N.CrossEntropyLoss(weight=w10, label_smoothing=0.1, reduction=r)),
-                       ("FocalLoss(weight)", lambda r: N.FocalLoss(2.0, 1.0, weight=w10, reduction=r)),
-                       ("SigmoidFocalLoss(weight)", lambda r: N.SigmoidFocalLoss(2.0, 0.25, weight=w10, reduction=r)),
-                       ("SigmoidFocalLoss(pixels)", lambda r: N.SigmoidFocalLoss(0.0, None, normalize="pixels", reduction=r)),
-                       ("DiceCrossEntropyLoss", lambda r: N.DiceCrossEntropyLoss(reduction=r))):
-        for reduction in ("mean", "sum", "none"):
-            if name.startswith("Dice") and reduction != "mean":
-                continue
-            for ignored in (False, True):
-                x = z.clone().requires_grad_(True)
-                target = torch.full_like(lab, IGN) if ignored else lab
-                loss = make(reduction)(x, target)
-                loss.backward(gpx if reduction == "none" else None)
-                emit(f"nchw {name} {reduction} all-ignored={int(ignored)} | loss={_sha(torch, loss)} dlogits={_sha(torch, x.grad)}")
+    digest_nchw(N, torch, emit)
+
+
+# one block; several ragged blocks; past the grid cap of the per-pixel kernels (8192 blocks) and of the Dice statistics (2048); C = 1;
+# the Dice class limit (Dice only)
+NCHW_SHAPES = ((2, 10, 12, 9), (2, 151, 24, 20), (1, 2, 1449, 1449), (1, 3, 725, 725), (1, 1, 5, 7), (1, 192, 9, 7))
+
+
+def digest_nchw(N, torch, emit):
+    """The criteria on materialised NCHW logits: every module and reduction, then each ``ops.*_nchw_bwd`` called directly with a
+    device scalar (0.25) times a host scale (2.0)."""
+    from lc2is_amd import ops
+    dev = torch.device("cuda", 0)
+    for B, C, H, W in NCHW_SHAPES:
+        g = torch.Generator().manual_seed(19)
+        z = (torch.randn(B, C, H, W, generator=g) * 3).to(dev)
+        lab = _labels(torch, B, H, W, C, 23).to(dev)
+        wc = (0.5 + torch.rand(C, generator=g)).to(dev)
+        gpx = torch.randn(B, H, W, generator=g).to(dev)
+        shape = f"{B}x{C}x{H}x{W}"
+        modules = (("CrossEntropyLoss", lambda r: N.CrossEntropyLoss(reduction=r)),
+                   ("CrossEntropyLoss(weight, smoothing)", lambda r: N.CrossEntropyLoss(weight=wc, label_smoothing=0.1, reduction=r)),
+                   ("FocalLoss(weight)", lambda r: N.FocalLoss(2.0, 1.0, weight=wc, reduction=r)),
+                   ("SigmoidFocalLoss(weight)", lambda r: N.SigmoidFocalLoss(2.0, 0.25, weight=wc, reduction=r)),
+                   ("SigmoidFocalLoss(pixels)", lambda r: N.SigmoidFocalLoss(0.0, None, normalize="pixels", reduction=r)),
+                   ("OhemCrossEntropyLoss(weight)", lambda r: N.OhemCrossEntropyLoss(0.7, 8, weight=wc, reduction=r)),
+                   ("DiceCrossEntropyLoss", lambda r: N.DiceCrossEntropyLoss(reduction=r)))
+        for name, make in modules[6 if C == 192 else 0:]:
+            for reduction in ("mean", "sum", "none"):
+                if (name.startswith("Dice") and reduction != "mean") or (name.startswith("Ohem") and reduction == "none"):
+                    continue
+                for ignored in (False, True):
+                    x = z.clone().requires_grad_(True)
+                    target = torch.full_like(lab, IGN) if ignored else lab
+                    loss = make(reduction)(x, target)
+                    loss.backward(gpx if reduction == "none" else None)
+                    emit(f"nchw {shape} {name} {reduction} all-ignored={int(ignored)} | loss={_sha(torch, loss)} "
+                         f"dlogits={_sha(torch, x.grad)}")
+        quarter = torch.full((1,), 0.25, device=dev)
+        loss4, stats, lse, coef = ops.ce_dice_nchw_fwd(z, lab, IGN)
+        direct = [("ce_dice", (loss4, stats, coef), ops.ce_dice_nchw_bwd(z, lab, lse, coef, quarter, 2.0, IGN))]
+        if C != 192:
+            kw = dict(class_weight=wc, label_smoothing=0.1)
+            loss2, lse = ops.ce_nchw_fwd(z, lab, IGN)
+            direct.append(("ce", (loss2, lse), ops.ce_nchw_bwd(z, lab, lse, quarter, 2.0, IGN)))
+            loss2, lse = ops.ce_nchw_fwd(z, lab, IGN, **kw)
+            direct.append(("ce(weight, smoothing)", (loss2, lse), ops.ce_nchw_bwd(z, lab, lse, quarter, 2.0, IGN, **kw)))
+            kw = dict(class_weight=wc, gamma=2.0, poly_eps=1.0)
+            loss2, lse = ops.focal_nchw_fwd(z, lab, IGN, **kw)
+            direct.append(("focal", (loss2, lse), ops.focal_nchw_bwd(z, lab, lse, quarter, 2.0, IGN, grad_px=gpx, **kw)))
+            kw = dict(class_weight=wc, gamma=2.0, alpha=0.25, class_scale=1.0 / C)
+            loss2 = ops.sigmoid_focal_nchw_fwd(z, lab, IGN, **kw)
+            direct.append(("sigmoid_focal", (loss2,), ops.sigmoid_focal_nchw_bwd(z, lab, quarter, 2.0, IGN, **kw)))
+        for name, fwd, d in direct:
+            emit(f"nchw {shape} ops.{name}_nchw fwd+bwd scale=0.25*2.0 | fwd={_sha(torch, *fwd)} dlogits={_sha(torch, d)}")
     torch.cuda.synchronize()
 
 
@@ -211,6 +248,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root", default=str(HERE))
     ap.add_argument("--validate", action="store_true")
+    ap.add_argument("--nchw", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, str(Path(a.root).resolve()))
@@ -227,7 +265,7 @@ def main():
         n += 1
         print(line, file=out or sys.stdout)
 
-    (validate if a.validate else digest)(N, torch, emit)
+    (validate if a.validate else digest_nchw if a.nchw else digest)(N, torch, emit)
     if out:
         out.close()
     print(f"sha256 {h.hexdigest()} {n} lines")
